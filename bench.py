@@ -7,7 +7,15 @@ Metric: Mray/s (fwd+bwd) on the Cornell box of /root/reference/src/render.cpp:26
 eye to its end, gradients accumulated and reduced.  ray = one raycast (camera ray included),
 exactly what the reference's Pathtracer::raycast counts.
 
-  python bench.py [--gpus N --steps K --warmup W] [--config 2|3|4|5]
+  python bench.py [--gpus N --steps K --warmup W] [--config 2|3|4|5] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the line: what the headline (`value`, `ms_per_step`) needs and
+nothing more.  --full adds everything else this file measures, each in runs of its own after the timed steps: per-kernel
+times and the roofline, the CPU baselines (the restatement, the reference where its binary was built, --cpu-all-cores),
+and the other views of the same frame (serial frames, the generic program, f64, forward only, unbiased, two contexts, host
+buffers, many parameters).  --dump-outputs DIR writes what the last timed step computed, as a caller of the device-pointer
+entry point receives it: DIR/image.npy (float32, H x W x 3; rank 0's rows when N > 1) and, with gradients, DIR/grads.npy
+(float64, n_params x 3).  An image above the size limit is written as every s-th pixel (s fixed by the frame size).
 
 --gpus N > 1 without torchrun's environment: this process starts N ranks itself (a fresh
 `python -m torch.distributed.run` child, one rank per GPU) and relays rank 0's JSON line.  Under
@@ -47,6 +55,7 @@ HBM_COPY_GBS = 6200.0        # measured float4 copy on the pool's boxes (profile
 # vector-instruction issue: a wave64 VALU op takes 2 cycles of its SIMD; 256 CUs x 4 SIMDs at 2.4 GHz
 VALU_PEAK_GINST = 256 * 4 * 2.4 / 2.0     # 1228.8 G wave-instructions / s
 VALU_MEASURED_GINST = 900.0               # what v_fma_f32 alone sustains on the pool's boxes (profiles/r04_microbench_valu_issue.txt)
+DUMP_LIMIT_BYTES = 64 * 10**6             # --dump-outputs: all arrays together
 
 # BASELINE.json configs -> workload per GPU (configs 4, 5: the 1/8 share of one of the 8 GPUs they are quoted on)
 CONFIGS = {
@@ -86,6 +95,21 @@ def load_distributed():
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
     return mod
+
+
+def dump_outputs(out_dir, image, grads):
+    """--dump-outputs: image (H x W x 3 float32) and grads (n_params x 3 float64, or None) as .npy files, DUMP_LIMIT_BYTES in all;
+    a larger image is written as every s-th pixel of the frame in row-major order."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    image = np.ascontiguousarray(image, dtype=np.float32)
+    room = DUMP_LIMIT_BYTES - (grads.nbytes if grads is not None else 0)
+    if image.nbytes > room:
+        pixels = image.reshape(-1, 3)
+        image = pixels[::pixels.shape[0] // (room // pixels[0].nbytes) + 1]
+    np.save(os.path.join(out_dir, "image.npy"), image)
+    if grads is not None:
+        np.save(os.path.join(out_dir, "grads.npy"), np.asarray(grads, dtype=np.float64))
 
 
 def _oracle_shard(args):
@@ -147,7 +171,16 @@ def parse_args(argv):
                     help="target duration of the sample the reference itself (oracle/_ref/ref_harness, when present) is timed on; 0 = skip")
     ap.add_argument("--cpu-all-cores", action="store_true",
                     help="also time the oracle on every host core (independent row-band processes)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure per-kernel times and the roofline, the CPU baselines and the other "
+                         "views of the frame (without it: the headline only)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the image (and gradients) of the last timed step as DIR/<name>.npy")
     a = ap.parse_args(argv)
+    if a.dump_outputs and a.single_process:
+        ap.error("--dump-outputs is not supported with --single-process")
+    if not a.full:
+        a.no_cpu_baseline = a.no_extra_views = True
     cfg = CONFIGS[a.config]
     a.width = a.width or cfg["width"]
     a.height = a.height or cfg["height"]
@@ -308,14 +341,14 @@ def main():
     reduced = [None, None]
     n_step = [0]
 
-    def step(timing=False, params=None):
+    def step(timing=False, params=None, want_stats=None):
         b = n_step[0] & 1
         n_step[0] += 1
         grad = grads[b]
         if reduced[b] is not None:
             ext.wait_event(reduced[b])         # step i - 2's all-reduce read this buffer
         st = r.render_device(cam, params or rp, out_rgb.data_ptr(), grad.data_ptr() if backward else 0,
-                             backward=backward, timing=timing, sync=False)
+                             backward=backward, timing=timing, sync=False, want_stats=want_stats)
         if reduce_mode == "torch":
             rendered = torch.cuda.Event()
             rendered.record(ext)
@@ -374,22 +407,27 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, out_rgb.cpu().numpy(), grads[(n_step[0] - 1) & 1].cpu().numpy() if backward else None)
 
-    # per-kernel HIP-event timing (events on the context's own stream), same workload, same
-    # process, right after the timed region; also yields the segment count of one step
-    kernel_ms = {k: 0.0 for k in pkg.KERNEL_NAMES}
-    kernel_launches = {k: 0 for k in pkg.KERNEL_NAMES}
-    # (a timed step ends in a host round trip -- the event times are read back -- and the device idles meanwhile: an untimed
-    #  step in front of every timed one, enqueued without waiting, keeps the timed kernels in the state the timed region's
-    #  kernels ran in; measured without it on one box: 0.736 ms against the trace's 0.696 for the same kernel)
     n_prof = max(1, min(a.steps, 10))
-    stats = None
-    for _ in range(n_prof):
-        step()
-        stats = step(timing=True)
-        for k in pkg.KERNEL_NAMES:
-            kernel_ms[k] += stats["kernels"][k]["ms"]
-            kernel_launches[k] += stats["kernels"][k]["launches"]
+    if a.full:
+        # per-kernel HIP-event timing (events on the context's own stream), same workload, same
+        # process, right after the timed region; also yields the segment count of one step
+        kernel_ms = {k: 0.0 for k in pkg.KERNEL_NAMES}
+        kernel_launches = {k: 0 for k in pkg.KERNEL_NAMES}
+        # (a timed step ends in a host round trip -- the event times are read back -- and the device idles meanwhile: an untimed
+        #  step in front of every timed one, enqueued without waiting, keeps the timed kernels in the state the timed region's
+        #  kernels ran in; measured without it on one box: 0.736 ms against the trace's 0.696 for the same kernel)
+        stats = None
+        for _ in range(n_prof):
+            step()
+            stats = step(timing=True)
+            for k in pkg.KERNEL_NAMES:
+                kernel_ms[k] += stats["kernels"][k]["ms"]
+                kernel_launches[k] += stats["kernels"][k]["launches"]
+    else:
+        stats = step(want_stats=True)          # the segment count of one step (a pure function of workload and seed)
     fence()
     segments = stats["segments"]
     paths = stats["paths"]
@@ -422,153 +460,155 @@ def main():
     ms_per_step = elapsed / a.steps * 1e3
     value = total_segments * a.steps / elapsed * 1e-6   # Mray/s, whole job
 
-    # ---- per-kernel algorithmic bytes and the roofline of the dominant kernel ----------
-    # units: what the library counted for each kernel (drt_hip_stats.units): paths (K1, K5), segments (K3, K6, k_path),
-    # the rays k_intersect tested (mesh scenes: camera rays only), the candidate rays the BVH walk took
-    units = {k: stats["kernels"][k]["units"] for k in pkg.KERNEL_NAMES}
-    # fused shade: tape 8 B/segment + 32 B per ray read from / written to the queue (the library counts both);
-    # unfused (mesh scenes): ray 24 + id 8 + hit 8 read, ray 24 + id 8 + tape 8 written;
-    # k_path: a path lives in registers from the eye to its end; the launch writes 24 B per pixel and sample range,
-    # 192 B per block (gradient partials) and 8 B per wave (counters): stats["path_bytes"], ~0.4 B per segment;
-    # k_intersect_mesh: per CANDIDATE ray a 36-byte record (slot, origin, direction, analytic t, tie-break index) read and
-    # at most one 8-byte hit written (the BVH itself is L2 / Infinity-Cache resident)
-    seg = max(1, segments)
-    # mesh scenes, k_shade<TAIL> (no k_intersect launch: the shade launch intersects the ray it produces with the analytic shapes
-    # itself): the unfused 80 B + the next depth's hit lane (8 B written) + a 40-byte candidate record per ray that reaches the
-    # mesh bounds (the BVH walk's input: units["intersect_mesh"] of them per step)
-    shade_tail_bytes = 88.0 + 40.0 * units["intersect_mesh"] / seg
-    bpu = {"intersect": 32.0, "intersect_mesh": 44.0,
-           "shade": 80.0 if kernel_launches["intersect"] else
-                    (shade_tail_bytes if kernel_launches["intersect_mesh"] else
-                     (8.0 if kernel_launches["backward"] else 16.0 * paths / seg) + 32.0 * queue_rays / seg),
-           "path": stats.get("path_bytes", 0) / seg,
-           "backward": 8.0, "raygen": 32.0, "gradreduce": 0.0,
-           # K5 reads 16 B of radiance per path; behind k_path it reads the per-range pixel sums that launch wrote
-           "film": stats.get("path_bytes", 0) / max(1, paths) if kernel_launches["path"] else 16.0}
-    per_kernel = {}
-    for k in pkg.KERNEL_NAMES:
-        ms = kernel_ms[k] / n_prof
-        if kernel_launches[k] == 0:
-            continue
-        gbs = units[k] * bpu[k] / (ms * 1e-3) * 1e-9 if ms > 0 else 0.0
-        per_kernel[k] = {"ms_per_step": round(ms, 4), "launches_per_step": kernel_launches[k] // n_prof,
-                         "units_per_step": int(units[k]), "bytes_per_unit": round(bpu[k], 3), "achieved_GBs": round(gbs, 1),
-                         "frac_hbm_peak": round(gbs / HBM_PEAK_GBS, 4)}
-    dominant = max(per_kernel, key=lambda k: per_kernel[k]["ms_per_step"]) if per_kernel else "shade"
-    # rocprofv3 PMC figures of the dominant kernel (profiles/traffic.json, written by tools/profile.sh, one entry per
-    # profiled workload): quoted only for the very workload this run measures
-    pmc = {}
-    tpath = os.path.join(ROOT, "profiles", "traffic.json")
     depth_text = f"roulette from bounce {a.min_bounces} with absorption {a.absorb:g}" if a.roulette else f"depth {a.depth}"
     depth_key = f"rr{a.absorb:g}b{a.min_bounces}" if a.roulette else f"d{a.depth}"
     mode_key = "unbiased" if a.unbiased else ("fwd" if a.forward_only else "fwdbwd")
     workload_key = f"{a.scene}:{a.width}x{a.height}x{a.spp}:{depth_key}:{mode_key}"
-    pmc_note = None
-    if os.path.exists(tpath) and a.bounces_per_launch == 0:
-        try:
-            tj = json.load(open(tpath))
-            wl = tj.get("workloads") or {}
-            entry_w = wl.get(workload_key) or (tj if tj.get("workload") == workload_key else {})
-            pmc = dict(entry_w.get(dominant) or {})
-            if not pmc:
-                # not profiled at this size: the same scene, depth and mode at ANOTHER frame size -- instructions and bytes per
-                # UNIT of the kernel's work (segments, candidate rays) do not depend on the frame
-                my_units = per_kernel.get(dominant, {}).get("units_per_step", 0) / max(1, per_kernel.get(dominant, {}).get("launches_per_step", 1))
-                for key, ent in sorted(wl.items()):
-                    sc, dims, dk_, md = key.split(":")
-                    e2 = ent.get(dominant) or {}
-                    if sc == a.scene and dk_ == depth_key and md == mode_key and e2.get("units_per_launch") and my_units > 0:
-                        scale = my_units / float(e2["units_per_launch"])
-                        pmc = {k2: (v2 * scale if k2.endswith("_per_launch") or k2 in ("fetch_raw_bytes", "write_bytes") else v2)
-                               for k2, v2 in e2.items() if isinstance(v2, (int, float))}
-                        pmc_note = f"PMC counts of '{key}' carried over per unit of work ({scale:g} x per launch): this size was not profiled"
-                        break
-        except Exception:
-            pmc = {}
-    dk = per_kernel.get(dominant, {"achieved_GBs": 0.0, "launches_per_step": 1, "ms_per_step": 0.0})
-    launch_ms = dk["ms_per_step"] / max(1, dk["launches_per_step"])
-    register_resident = dominant == "path" or (dominant == "shade" and not kernel_launches["intersect"]
-                                               and dk["launches_per_step"] < a.depth * max(1, stats["batches"]) and not a.unbiased)
-    traffic = round(pmc["bytes_per_launch"] / (launch_ms * 1e-3) * 1e-9, 1) if pmc.get("bytes_per_launch") and launch_ms > 0 else None
-    pmc_launch_us = pmc.get("avg_launch_us")
-    hbm_view = {"achieved": dk["achieved_GBs"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(dk["achieved_GBs"] / HBM_PEAK_GBS, 4),
-                "frac_of_measured_copy_roof": round(dk["achieved_GBs"] / HBM_COPY_GBS, 4),
-                "note": "algorithmic bytes of the dominant kernel (units x bytes per unit) over its HIP-event time"}
-    valu_view = None
-    # The instruction count is a STORED figure (profiles/traffic.json): it describes this run only if the kernel is still the
-    # one that was profiled.  The profile also recorded the kernel's launch time: where the live time is off by more than 5 %
-    # (boxes of the pool differ by ~3 %) the count is withheld instead of being divided by a time it does not belong to.
-    # Better than a time: the profile records WHICH kernels it counted (a hash of the device sources the library was built from) and the
-    # work of a launch (segments: a pure function of workload and seed).  Same sources and same work = the same instructions, whatever the
-    # box's clock does today; the time check remains for profiles that carry no hash.
-    stale = None
-    same_kernels = None
-    if pmc.get("kernel_sources_sha16") and not pmc_note:
-        live_units = dk.get("units_per_step", 0) / max(1, dk["launches_per_step"]) if dk.get("units_per_step") else None
-        same_kernels = (pmc["kernel_sources_sha16"] == entry.kernel_sources_sha16() and bool(live_units) and bool(pmc.get("units_per_launch")))
-        if same_kernels and float(pmc["units_per_launch"]) != float(live_units):
-            # the same kernels on the same scene, depth and mode, but another share of the frame (a rank of an N-GPU run renders other
-            # rows at N x the samples: a few segments more or less): instructions and bytes per SEGMENT are what carries over
-            scale = float(live_units) / float(pmc["units_per_launch"])
-            if 0.8 <= scale <= 1.25:
-                pmc = {k2: (v2 * scale if isinstance(v2, (int, float)) and (k2.endswith("_per_launch") or k2 in ("fetch_raw_bytes", "write_bytes")) else v2)
-                       for k2, v2 in pmc.items()}
-                traffic = round(pmc["bytes_per_launch"] / (launch_ms * 1e-3) * 1e-9, 1) if pmc.get("bytes_per_launch") and launch_ms > 0 else None
-            else:
-                same_kernels = False
-    if pmc.get("valu_insts_per_launch") and pmc.get("avg_launch_us") and launch_ms > 0 and not pmc_note and not same_kernels:
-        off = launch_ms * 1e3 / float(pmc["avg_launch_us"]) - 1.0
-        if abs(off) > 0.05:
-            stale = (f"profiles/traffic.json holds k_{dominant} at {float(pmc['avg_launch_us']):.1f} us per launch, this run measures "
-                     f"{launch_ms * 1e3:.1f} us ({off:+.1%}): the kernel (or the box) is not the profiled one -- instruction counts "
-                     f"withheld; tools/profile.sh regenerates the profile")
-            pmc_note = stale
-    if pmc.get("valu_insts_per_launch") and launch_ms > 0 and not stale:
-        ginst = pmc["valu_insts_per_launch"] / (launch_ms * 1e-3) * 1e-9
-        valu_view = {"achieved": round(ginst, 1), "peak": VALU_PEAK_GINST, "unit": "G wave-instr/s",
-                     "frac": round(ginst / VALU_PEAK_GINST, 4),
-                     "frac_of_measured_issue_roof": round(ginst / VALU_MEASURED_GINST, 4),
-                     "valu_insts_per_launch": pmc.get("valu_insts_per_launch"),
-                     "salu_insts_per_launch": pmc.get("salu_insts_per_launch"),
-                     "count_valid_because": ("the profile was taken of these very kernels (hash of the device sources "
-                                             f"{pmc.get('kernel_sources_sha16')}) on the same work per launch" if same_kernels else
-                                             "the profile's own launch time is within 5 % of the live one"),
-                     "note": "SQ_INSTS_VALU per launch (profiles/traffic.json, rocprofv3 --pmc on this workload) / live launch "
-                             "time; peak = one wave64 VALU op per 2 cycles per SIMD-32, 256 CUs x 4 SIMDs x 2.4 GHz"}
-    # The top-level achieved / peak / unit / frac describe the roof that BOUNDS the dominant kernel: HBM bytes for the
-    # streaming kernels; vector-instruction issue for the register-resident k_path (it moves ~0.4 B per segment) and
-    # for the BVH walk (divergent, latency-bound: neither roof is near -- both fractions are printed).  The other
-    # view stays beside it (`hbm` / `valu`).
-    issue_bound = register_resident or dominant == "intersect_mesh"
-    # (no rocprofv3 PMC profile of this workload in profiles/traffic.json -- tools/profile.sh makes one --: the HBM view, which
-    #  needs none, is what the top level carries then)
-    top = valu_view if (issue_bound and valu_view) else hbm_view
-    roofline = {"bound": ("valu-issue (paths are register-resident: the kernel moves almost no bytes)" if register_resident
-                          else ("the CU's L1 path (divergent BVH walk out of L2; by the TCP's and TD's own counters, profiles/r06_walk_counters.txt: "
-                                "the L1 clocked 93 % of a launch, 31 % of the cycles stalled behind lines in flight, 780 cycles per wave-load against "
-                                "230 for an L2 hit, the data-return unit 86 % busy) -- neither roof is near: vector issue 0.37 of nominal (SQ_INSTS_VALU "
-                                "x 2 cycles, 37 of 64 lanes per instruction; the fraction printed here), HBM 0.10" if dominant == "intersect_mesh" else "hbm")),
-                "kernel": "k_" + dominant, "achieved": top["achieved"], "peak": top["peak"], "unit": top["unit"],
-                "frac": top["frac"],
-                "traffic": traffic,
-                "traffic_note": "GB/s of PMC-counted HBM bytes per launch (profiles/traffic.json, rocprofv3 --pmc, FETCH_SIZE "
-                                "doubled per the gfx950 correction) over the live launch time" if traffic else None,
-                "avg_launch_ms": round(launch_ms, 4),
-                "mode": "one launch at a time: HIP events around every launch of frames rendered in stream order (as rocprofv3 "
-                        "sees them with DRT_HIP_OVERLAP_FRAMES=0, profiles/); `value` pipelines two frames, see `pipelined`",
-                "pmc_note": pmc_note, "pmc_launch_us": pmc_launch_us,
-                "hbm": hbm_view, "valu": valu_view,
-                "kernels": per_kernel}
-    if dominant == "path" and valu_view and dk["launches_per_step"] > 0:
-        # the chip-level issue rate of the HEADLINE mode: the same instructions per step over the step time of the timed region
-        # (the grids of two consecutive frames overlap: a launch's own begin-to-end time is longer than a step there)
-        g2 = pmc["valu_insts_per_launch"] * dk["launches_per_step"] / (ms_per_step * 1e-3) * 1e-9
-        roofline["pipelined"] = {"achieved": round(g2, 1), "peak": VALU_PEAK_GINST, "unit": "G wave-instr/s",
-                                 "frac": round(g2 / VALU_PEAK_GINST, 4),
-                                 "frac_of_measured_issue_roof": round(g2 / VALU_MEASURED_GINST, 4), "ms_per_step": round(ms_per_step, 4)}
-    if dominant == "intersect_mesh" and pmc.get("lane_stats"):
-        roofline["walk_lanes"] = pmc["lane_stats"]      # tools/bvh_stats.py on the same scene (a -DDRT_BVH_STATS build)
+    roofline = None
+    if a.full:
+        # ---- per-kernel algorithmic bytes and the roofline of the dominant kernel ----------
+        # units: what the library counted for each kernel (drt_hip_stats.units): paths (K1, K5), segments (K3, K6, k_path),
+        # the rays k_intersect tested (mesh scenes: camera rays only), the candidate rays the BVH walk took
+        units = {k: stats["kernels"][k]["units"] for k in pkg.KERNEL_NAMES}
+        # fused shade: tape 8 B/segment + 32 B per ray read from / written to the queue (the library counts both);
+        # unfused (mesh scenes): ray 24 + id 8 + hit 8 read, ray 24 + id 8 + tape 8 written;
+        # k_path: a path lives in registers from the eye to its end; the launch writes 24 B per pixel and sample range,
+        # 192 B per block (gradient partials) and 8 B per wave (counters): stats["path_bytes"], ~0.4 B per segment;
+        # k_intersect_mesh: per CANDIDATE ray a 36-byte record (slot, origin, direction, analytic t, tie-break index) read and
+        # at most one 8-byte hit written (the BVH itself is L2 / Infinity-Cache resident)
+        seg = max(1, segments)
+        # mesh scenes, k_shade<TAIL> (no k_intersect launch: the shade launch intersects the ray it produces with the analytic shapes
+        # itself): the unfused 80 B + the next depth's hit lane (8 B written) + a 40-byte candidate record per ray that reaches the
+        # mesh bounds (the BVH walk's input: units["intersect_mesh"] of them per step)
+        shade_tail_bytes = 88.0 + 40.0 * units["intersect_mesh"] / seg
+        bpu = {"intersect": 32.0, "intersect_mesh": 44.0,
+               "shade": 80.0 if kernel_launches["intersect"] else
+                        (shade_tail_bytes if kernel_launches["intersect_mesh"] else
+                         (8.0 if kernel_launches["backward"] else 16.0 * paths / seg) + 32.0 * queue_rays / seg),
+               "path": stats.get("path_bytes", 0) / seg,
+               "backward": 8.0, "raygen": 32.0, "gradreduce": 0.0,
+               # K5 reads 16 B of radiance per path; behind k_path it reads the per-range pixel sums that launch wrote
+               "film": stats.get("path_bytes", 0) / max(1, paths) if kernel_launches["path"] else 16.0}
+        per_kernel = {}
+        for k in pkg.KERNEL_NAMES:
+            ms = kernel_ms[k] / n_prof
+            if kernel_launches[k] == 0:
+                continue
+            gbs = units[k] * bpu[k] / (ms * 1e-3) * 1e-9 if ms > 0 else 0.0
+            per_kernel[k] = {"ms_per_step": round(ms, 4), "launches_per_step": kernel_launches[k] // n_prof,
+                             "units_per_step": int(units[k]), "bytes_per_unit": round(bpu[k], 3), "achieved_GBs": round(gbs, 1),
+                             "frac_hbm_peak": round(gbs / HBM_PEAK_GBS, 4)}
+        dominant = max(per_kernel, key=lambda k: per_kernel[k]["ms_per_step"]) if per_kernel else "shade"
+        # rocprofv3 PMC figures of the dominant kernel (profiles/traffic.json, written by tools/profile.sh, one entry per
+        # profiled workload): quoted only for the very workload this run measures
+        pmc = {}
+        tpath = os.path.join(ROOT, "profiles", "traffic.json")
+        pmc_note = None
+        if os.path.exists(tpath) and a.bounces_per_launch == 0:
+            try:
+                tj = json.load(open(tpath))
+                wl = tj.get("workloads") or {}
+                entry_w = wl.get(workload_key) or (tj if tj.get("workload") == workload_key else {})
+                pmc = dict(entry_w.get(dominant) or {})
+                if not pmc:
+                    # not profiled at this size: the same scene, depth and mode at ANOTHER frame size -- instructions and bytes per
+                    # UNIT of the kernel's work (segments, candidate rays) do not depend on the frame
+                    my_units = per_kernel.get(dominant, {}).get("units_per_step", 0) / max(1, per_kernel.get(dominant, {}).get("launches_per_step", 1))
+                    for key, ent in sorted(wl.items()):
+                        sc, dims, dk_, md = key.split(":")
+                        e2 = ent.get(dominant) or {}
+                        if sc == a.scene and dk_ == depth_key and md == mode_key and e2.get("units_per_launch") and my_units > 0:
+                            scale = my_units / float(e2["units_per_launch"])
+                            pmc = {k2: (v2 * scale if k2.endswith("_per_launch") or k2 in ("fetch_raw_bytes", "write_bytes") else v2)
+                                   for k2, v2 in e2.items() if isinstance(v2, (int, float))}
+                            pmc_note = f"PMC counts of '{key}' carried over per unit of work ({scale:g} x per launch): this size was not profiled"
+                            break
+            except Exception:
+                pmc = {}
+        dk = per_kernel.get(dominant, {"achieved_GBs": 0.0, "launches_per_step": 1, "ms_per_step": 0.0})
+        launch_ms = dk["ms_per_step"] / max(1, dk["launches_per_step"])
+        register_resident = dominant == "path" or (dominant == "shade" and not kernel_launches["intersect"]
+                                                   and dk["launches_per_step"] < a.depth * max(1, stats["batches"]) and not a.unbiased)
+        traffic = round(pmc["bytes_per_launch"] / (launch_ms * 1e-3) * 1e-9, 1) if pmc.get("bytes_per_launch") and launch_ms > 0 else None
+        pmc_launch_us = pmc.get("avg_launch_us")
+        hbm_view = {"achieved": dk["achieved_GBs"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(dk["achieved_GBs"] / HBM_PEAK_GBS, 4),
+                    "frac_of_measured_copy_roof": round(dk["achieved_GBs"] / HBM_COPY_GBS, 4),
+                    "note": "algorithmic bytes of the dominant kernel (units x bytes per unit) over its HIP-event time"}
+        valu_view = None
+        # The instruction count is a STORED figure (profiles/traffic.json): it describes this run only if the kernel is still the
+        # one that was profiled.  The profile also recorded the kernel's launch time: where the live time is off by more than 5 %
+        # (GPUs of the same model differ by ~3 %) the count is withheld instead of being divided by a time it does not belong to.
+        # Better than a time: the profile records WHICH kernels it counted (a hash of the device sources the library was built from) and the
+        # work of a launch (segments: a pure function of workload and seed).  Same sources and same work = the same instructions, whatever the
+        # box's clock does today; the time check remains for profiles that carry no hash.
+        stale = None
+        same_kernels = None
+        if pmc.get("kernel_sources_sha16") and not pmc_note:
+            live_units = dk.get("units_per_step", 0) / max(1, dk["launches_per_step"]) if dk.get("units_per_step") else None
+            same_kernels = (pmc["kernel_sources_sha16"] == entry.kernel_sources_sha16() and bool(live_units) and bool(pmc.get("units_per_launch")))
+            if same_kernels and float(pmc["units_per_launch"]) != float(live_units):
+                # the same kernels on the same scene, depth and mode, but another share of the frame (a rank of an N-GPU run renders other
+                # rows at N x the samples: a few segments more or less): instructions and bytes per SEGMENT are what carries over
+                scale = float(live_units) / float(pmc["units_per_launch"])
+                if 0.8 <= scale <= 1.25:
+                    pmc = {k2: (v2 * scale if isinstance(v2, (int, float)) and (k2.endswith("_per_launch") or k2 in ("fetch_raw_bytes", "write_bytes")) else v2)
+                           for k2, v2 in pmc.items()}
+                    traffic = round(pmc["bytes_per_launch"] / (launch_ms * 1e-3) * 1e-9, 1) if pmc.get("bytes_per_launch") and launch_ms > 0 else None
+                else:
+                    same_kernels = False
+        if pmc.get("valu_insts_per_launch") and pmc.get("avg_launch_us") and launch_ms > 0 and not pmc_note and not same_kernels:
+            off = launch_ms * 1e3 / float(pmc["avg_launch_us"]) - 1.0
+            if abs(off) > 0.05:
+                stale = (f"profiles/traffic.json holds k_{dominant} at {float(pmc['avg_launch_us']):.1f} us per launch, this run measures "
+                         f"{launch_ms * 1e3:.1f} us ({off:+.1%}): the kernel (or the box) is not the profiled one -- instruction counts "
+                         f"withheld; tools/profile.sh regenerates the profile")
+                pmc_note = stale
+        if pmc.get("valu_insts_per_launch") and launch_ms > 0 and not stale:
+            ginst = pmc["valu_insts_per_launch"] / (launch_ms * 1e-3) * 1e-9
+            valu_view = {"achieved": round(ginst, 1), "peak": VALU_PEAK_GINST, "unit": "G wave-instr/s",
+                         "frac": round(ginst / VALU_PEAK_GINST, 4),
+                         "frac_of_measured_issue_roof": round(ginst / VALU_MEASURED_GINST, 4),
+                         "valu_insts_per_launch": pmc.get("valu_insts_per_launch"),
+                         "salu_insts_per_launch": pmc.get("salu_insts_per_launch"),
+                         "count_valid_because": ("the profile was taken of these very kernels (hash of the device sources "
+                                                 f"{pmc.get('kernel_sources_sha16')}) on the same work per launch" if same_kernels else
+                                                 "the profile's own launch time is within 5 % of the live one"),
+                         "note": "SQ_INSTS_VALU per launch (profiles/traffic.json, rocprofv3 --pmc on this workload) / live launch "
+                                 "time; peak = one wave64 VALU op per 2 cycles per SIMD-32, 256 CUs x 4 SIMDs x 2.4 GHz"}
+        # The top-level achieved / peak / unit / frac describe the roof that BOUNDS the dominant kernel: HBM bytes for the
+        # streaming kernels; vector-instruction issue for the register-resident k_path (it moves ~0.4 B per segment) and
+        # for the BVH walk (divergent, latency-bound: neither roof is near -- both fractions are printed).  The other
+        # view stays beside it (`hbm` / `valu`).
+        issue_bound = register_resident or dominant == "intersect_mesh"
+        # (no rocprofv3 PMC profile of this workload in profiles/traffic.json -- tools/profile.sh makes one --: the HBM view, which
+        #  needs none, is what the top level carries then)
+        top = valu_view if (issue_bound and valu_view) else hbm_view
+        roofline = {"bound": ("valu-issue (paths are register-resident: the kernel moves almost no bytes)" if register_resident
+                              else ("the CU's L1 path (divergent BVH walk out of L2; by the TCP's and TD's own counters, profiles/r06_walk_counters.txt: "
+                                    "the L1 clocked 93 % of a launch, 31 % of the cycles stalled behind lines in flight, 780 cycles per wave-load against "
+                                    "230 for an L2 hit, the data-return unit 86 % busy) -- neither roof is near: vector issue 0.37 of nominal (SQ_INSTS_VALU "
+                                    "x 2 cycles, 37 of 64 lanes per instruction; the fraction printed here), HBM 0.10" if dominant == "intersect_mesh" else "hbm")),
+                    "kernel": "k_" + dominant, "achieved": top["achieved"], "peak": top["peak"], "unit": top["unit"],
+                    "frac": top["frac"],
+                    "traffic": traffic,
+                    "traffic_note": "GB/s of PMC-counted HBM bytes per launch (profiles/traffic.json, rocprofv3 --pmc, FETCH_SIZE "
+                                    "doubled per the gfx950 correction) over the live launch time" if traffic else None,
+                    "avg_launch_ms": round(launch_ms, 4),
+                    "mode": "one launch at a time: HIP events around every launch of frames rendered in stream order (as rocprofv3 "
+                            "sees them with DRT_HIP_OVERLAP_FRAMES=0, profiles/); `value` pipelines two frames, see `pipelined`",
+                    "pmc_note": pmc_note, "pmc_launch_us": pmc_launch_us,
+                    "hbm": hbm_view, "valu": valu_view,
+                    "kernels": per_kernel}
+        if dominant == "path" and valu_view and dk["launches_per_step"] > 0:
+            # the chip-level issue rate of the HEADLINE mode: the same instructions per step over the step time of the timed region
+            # (the grids of two consecutive frames overlap: a launch's own begin-to-end time is longer than a step there)
+            g2 = pmc["valu_insts_per_launch"] * dk["launches_per_step"] / (ms_per_step * 1e-3) * 1e-9
+            roofline["pipelined"] = {"achieved": round(g2, 1), "peak": VALU_PEAK_GINST, "unit": "G wave-instr/s",
+                                     "frac": round(g2 / VALU_PEAK_GINST, 4),
+                                     "frac_of_measured_issue_roof": round(g2 / VALU_MEASURED_GINST, 4), "ms_per_step": round(ms_per_step, 4)}
+        if dominant == "intersect_mesh" and pmc.get("lane_stats"):
+            roofline["walk_lanes"] = pmc["lane_stats"]      # tools/bvh_stats.py on the same scene (a -DDRT_BVH_STATS build)
 
     extra = rank == 0 and world == 1 and not a.no_extra_views
     import dataclasses

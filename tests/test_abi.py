@@ -3,6 +3,9 @@ lays its records out as the ctypes mirror does, and FAILS LOUDLY without a devic
 import ctypes as C
 import os
 import re
+import subprocess
+import sys
+import textwrap
 
 import pytest
 
@@ -15,6 +18,16 @@ def declared_symbols():
     return sorted(set(re.findall(r"\b(drt_hip_[a-z_]+)\s*\(", text)))
 
 
+def in_child(body):
+    """Run `body` (Python; `pkg` is the package) in a child interpreter and return its stdout.  Loading libdrt_hip.so brings
+    up the system's HIP runtime; in the pytest process that must not happen before a GPU test brings up PyTorch's own
+    (bench.py's order: PyTorch's runtime first), or PyTorch finds no device afterwards."""
+    code = f"import sys\nsys.path.insert(0, {ROOT!r})\nimport __graft_entry__ as entry\npkg = entry.load_package()\n" + textwrap.dedent(body)
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    return r.stdout
+
+
 def test_header_declares_the_entry_points():
     syms = declared_symbols()
     for s in ["drt_hip_device_count", "drt_hip_create", "drt_hip_destroy", "drt_hip_upload_scene",
@@ -25,10 +38,13 @@ def test_header_declares_the_entry_points():
 
 def test_library_exports_every_declared_symbol(pkg):
     pkg.build_native()
-    lib = C.CDLL(pkg.LIB_PATH)
-    for s in declared_symbols():
-        assert hasattr(lib, s), f"libdrt_hip.so does not export {s}"
-    assert pkg.load_library().drt_hip_abi_version() == pkg.ABI_VERSION == 8   # v2 meshes, v3 queue statistics, v4 groups + communicators, v5 asynchronous host-buffer renders, v6 scene-specialised path kernels, v7 pinned caller buffers, v8 caller-defined shape kinds
+    in_child("""
+        import ctypes as C
+        lib = C.CDLL(pkg.LIB_PATH)
+        for s in %r:
+            assert hasattr(lib, s), "libdrt_hip.so does not export " + s
+        assert pkg.load_library().drt_hip_abi_version() == pkg.ABI_VERSION == 8
+        """ % declared_symbols())   # ABI 8: v2 meshes, v3 queue statistics, v4 groups + communicators, v5 asynchronous host-buffer renders, v6 scene-specialised path kernels, v7 pinned caller buffers, v8 caller-defined shape kinds
     assert sorted(pkg._ABI_SYMBOLS) == declared_symbols()
 
 
@@ -54,14 +70,17 @@ def test_ctypes_mirror_matches_the_c_layout(pkg, oracle):
 def test_embedded_headers_compile_under_hiprtc(pkg):
     """The library specialises k_path per scene at run time (csrc/drt_jit.h): the headers it embeds must compile under
     hiprtc (no system headers there) -- checked here, where no GPU is needed, for one variant of each kernel template."""
-    lib = pkg.load_library()
-    f = lib.drt_hip_debug_jit_compile
-    f.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_double), C.c_char_p, C.c_int]
-    for name in (b"k_path<float, true, 4, 3, KindSig<0x9249249ull, 0x0ull, 0x0ull, 0x0ull, 12>, true>",
-                 b"k_path_unbiased<float, false, 4, KindSig<0x9249249249ull, 0x1249ull, 0x0ull, 0x0ull, 20>>"):
-        ms, log = C.c_double(), C.create_string_buffer(8000)
-        size = f(b"gfx950", name, C.byref(ms), log, 8000)
-        assert size > 1000, log.value.decode()
+    in_child("""
+        import ctypes as C
+        lib = pkg.load_library()
+        f = lib.drt_hip_debug_jit_compile
+        f.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_double), C.c_char_p, C.c_int]
+        for name in (b"k_path<float, true, 4, 3, KindSig<0x9249249ull, 0x0ull, 0x0ull, 0x0ull, 12>, true>",
+                     b"k_path_unbiased<float, false, 4, KindSig<0x9249249249ull, 0x1249ull, 0x0ull, 0x0ull, 20>>"):
+            ms, log = C.c_double(), C.create_string_buffer(8000)
+            size = f(b"gfx950", name, C.byref(ms), log, 8000)
+            assert size > 1000, log.value.decode()
+        """)
 
 
 def test_environment_variables_are_read_in_one_place_and_documented():
@@ -85,14 +104,21 @@ def test_environment_variables_are_read_in_one_place_and_documented():
 
 def test_no_device_means_an_error_not_a_fallback(pkg):
     """On a box without a GPU the product path must refuse to run."""
-    lib = pkg.load_library()
-    if lib.drt_hip_device_count() > 0:
+    if int(in_child("print(pkg.load_library().drt_hip_device_count())")) > 0:
         pytest.skip("a GPU is present")
-    ctx = C.c_void_p()
-    assert lib.drt_hip_create(0, C.byref(ctx)) == -2      # DRT_ERR_NO_DEVICE
-    assert not ctx.value
-    with pytest.raises(pkg.DrtHipError, match="DRT_ERR_NO_DEVICE"):
-        pkg.HipRenderer(0)
+    in_child("""
+        import ctypes as C
+        lib = pkg.load_library()
+        ctx = C.c_void_p()
+        assert lib.drt_hip_create(0, C.byref(ctx)) == -2      # DRT_ERR_NO_DEVICE
+        assert not ctx.value
+        try:
+            pkg.HipRenderer(0)
+        except pkg.DrtHipError as e:
+            assert "DRT_ERR_NO_DEVICE" in str(e), e
+        else:
+            raise AssertionError("HipRenderer(0) without a device did not raise")
+        """)
 
 
 def test_missing_library_is_loud(pkg, tmp_path):

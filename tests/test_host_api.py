@@ -1,7 +1,6 @@
 """The source-compatible drt:: host API (include/drt/*.hpp) and the sample application."""
 import os
 import re
-import shutil
 import struct
 import subprocess
 
@@ -9,7 +8,7 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_APP = "/root/reference/src/render.cpp"
+REF_APP = os.path.join(ROOT, "oracle", "_ref", "render_ref_app")
 
 
 def sh(cmd, **kw):
@@ -173,17 +172,13 @@ def test_exr_zip_blocks_decode_to_the_uncompressed_file(tmp_path):
             assert os.path.getsize(b) <= os.path.getsize(a) + 64
 
 
-@pytest.mark.skipif(not os.path.exists(REF_APP), reason="reference sources only exist in the build container")
+@pytest.mark.skipif(not os.path.exists(REF_APP), reason="oracle/_ref/render_ref_app is built only where the reference's sources are")
 def test_the_references_own_render_cpp_compiles_and_runs_against_these_headers(pkg, oracle, tmp_path):
-    """Drop-in proof: the UNMODIFIED reference application (copied to a temp dir at test time, never
-    into the repo) builds against include/drt + src/args.hpp + src/write.hpp and renders the same
-    image as the reference headers do (libc stream, bit-equal up to the half conversion)."""
-    shutil.copy(REF_APP, tmp_path / "render.cpp")
-    exe = str(tmp_path / "render_ref_app")
-    sh(["g++", "-O2", "-std=c++17", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "src"),
-        str(tmp_path / "render.cpp"), "-o", exe])
+    """Drop-in proof: the UNMODIFIED reference application (compiled by build() -- oracle/Makefile, target ref -- into
+    oracle/_ref/, never copied into the repo) builds against include/drt + src/args.hpp + src/write.hpp and renders the
+    same image as the reference headers do (libc stream, bit-equal up to the half conversion)."""
     out = str(tmp_path / "ref_app.exr")
-    sh([exe, "-o", out, "-x", "32", "-y", "24", "-n", "4", "-b", "2", "-p", "0.5"])
+    sh([REF_APP, "-o", out, "-x", "32", "-y", "24", "-n", "4", "-b", "2", "-p", "0.5"])
     img = read_exr_half_rgba(out)
     ref = oracle.render(pkg.cornell_box(), pkg.cornell_camera(32, 24),
                         pkg.RenderParams(spp=4, min_bounces=2, absorb=0.5, seed=1),

@@ -16,7 +16,7 @@ for set in "TA_TA_BUSY_sum TA_ADDR_STALLED_BY_TC_CYCLES_sum TA_DATA_STALLED_BY_T
   i=$((i+1))
   d=$OUT/set$i
   if [ -n "$PMC_SETS" ] && ! echo " $PMC_SETS " | grep -q " $i "; then continue; fi
-  timeout -k 5 ${PMC_TIMEOUT:-150} rocprofv3 --pmc $set --kernel-trace --output-format csv -d "$d" -- python3 bench.py --steps 1 --warmup 0 --preheat-ms 0 --no-cpu-baseline --no-extra-views "$@" > /dev/null 2> "$d.err" || { echo "set $i failed:" >&2; tail -3 "$d.err" >&2; continue; }
+  timeout -k 5 ${PMC_TIMEOUT:-150} rocprofv3 --pmc $set --kernel-trace --output-format csv -d "$d" -- python3 bench.py --full --steps 1 --warmup 0 --preheat-ms 0 --no-cpu-baseline --no-extra-views "$@" > /dev/null 2> "$d.err" || { echo "set $i failed:" >&2; tail -3 "$d.err" >&2; continue; }
   python3 - "$d" <<'PY'
 import csv, glob, os, sys, collections
 f = glob.glob(sys.argv[1] + "/**/*counter_collection.csv", recursive=True)
