@@ -127,6 +127,43 @@ hipFunction_t jit_function(drt_hip_ctx* ctx, const std::string& name_expr, bool 
         (S).st->launches[K]++;                                                     \
     } while (0)
 
+// run-time choices as template arguments: f(std::true_type / std::false_type), and f(IntC<V>) for the one V of the listed
+// instantiations that equals v (none: f is not called, the result is value-initialised)
+template <int V>
+using IntC = std::integral_constant<int, V>;
+template <typename F>
+auto with_bool(bool b, F&& f)
+{
+    return b ? f(std::true_type()) : f(std::false_type());
+}
+template <int V, int... Vs, typename F>
+auto with_int(int v, F&& f)
+{
+    if constexpr (sizeof...(Vs) == 0)
+        return v == V ? f(IntC<V>()) : decltype(f(IntC<V>()))();
+    else
+        return v == V ? f(IntC<V>()) : with_int<Vs...>(v, f);
+}
+// the parameters a kernel's gradients are instantiated for: 4 or 8 in registers, `general` beyond
+inline int np_width(int n_params, int general)
+{
+    return n_params <= 4 ? 4 : (n_params <= 8 ? 8 : general);
+}
+
+// ---- which instantiation of the one-launch path kernels a render runs (shard_plan decides it, path_batch launches it) ----
+enum class PathOp { biased, unbiased, mesh };    // k_path (the gradient image included), k_path_unbiased, k_path_mesh
+enum class PathProg { cornell, sorted, scene };  // closest-hit program: the reference's kinds compiled in (SigCornell), kinds read at
+                                                 // run time (SigNone), or compiled by hiprtc for the scene's own KindSig (drt_jit.h)
+struct PathForm {
+    PathOp op;
+    bool f64, spec;
+    int np, nc;                     // gradient parameters / colour columns: 0, 0 without tangents; DRT_NP_ANY the general form
+                                    // (nc = 1: + the lanes' own sums of one row, the gradient image)
+    bool regen;                     // the regenerating form (k_path_mesh: always; k_path_unbiased: never)
+    bool loss;                      // DRT_RENDER_LOSS_L2's instantiation: made at run time only
+    PathProg prog;
+};
+
 // ---- one shard's render: what the caller asked for, what the library decided, what both routes share -------------------
 template <typename R>
 struct Shard {
@@ -157,8 +194,9 @@ struct Shard {
     bool loss_l2;                   // DRT_RENDER_LOSS_L2: every sample seeded with 2 (L_s - target_pixel), d_adjoint is the target
     hipFunction_t loss_kernel = nullptr;   // ... on k_path: the LOSS instantiation, made at run time only (drt_jit.h)
     bool can_fuse;                  // K2 folded into K3: analytic scenes, unless DRT_RENDER_UNFUSED asks for the textbook pipeline
-    bool use_path, path_regen;      // the whole path in one launch (k_path); its regenerating form
-    bool path_gen = false;          // ... its gradients in the general form: any number of parameters (DRT_NP_ANY)
+    bool use_path;                  // the whole path in one launch (k_path)
+    PathForm path;                  // ... its instantiation
+    bool path_gen = false;          // ... its gradients in the general form: any number of parameters (path.np = DRT_NP_ANY)
     uint32_t gen_rows = 0, gen_clog2 = 0;
     bool mesh_path;                 // ... in a scene with a mesh: k_path_mesh (drt_path_mesh.h), the BVH walk inside the launch
     bool shade_tail;                // mesh scenes: the launch that produces a ray also intersects it with the analytic shapes and
@@ -228,23 +266,59 @@ struct Shard {
 };
 
 // "k_path<float, SPEC, NP, NC, KindSig<...>, REGEN[, LOSS]>" / "k_path_unbiased<float, SPEC, NP, KindSig<...>>": the name expression
-// of the f32 instantiation a render would launch, for the scene's own signature
-inline std::string path_kernel_name(const drt_hip_ctx* ctx, bool tangents, bool unbiased, bool regen, bool loss, bool gen, bool f64 = false,
-                                    bool gen_gimg = false)
+// of the form for the scene's own signature, what hiprtc compiles (k_path_mesh has no such form)
+inline std::string path_kernel_name(const drt_hip_ctx* ctx, const PathForm& f)
 {
     const std::string sg = drt_jit::sig_type(ctx->prog_sig, ctx->n_shapes);
-    const char* sp = ctx->has_specular ? "true" : "false";
-    const bool three = ctx->max_colour_param < 3;      // tangent state only for parameters that ARE some BxDF's colour
+    const char* type = f.f64 ? "double" : "float";
+    const char* sp = f.spec ? "true" : "false";
     char name[400];
-    // (gen: the general form, any number of parameters: DRT_NP_ANY = -1)
-    if (unbiased)
-        snprintf(name, sizeof name, "k_path_unbiased<%s, %s, %d, %s>", f64 ? "double" : "float", sp, gen ? -1 : (ctx->n_params > 4 ? 8 : 4), sg.c_str());
-    else {
-        const int np = tangents ? (gen ? -1 : (ctx->n_params > 4 ? 8 : 4)) : 0;
-        const int nc = tangents ? (gen ? (gen_gimg ? 1 : 0) : (ctx->n_params > 4 ? 8 : (three ? 3 : 4))) : 0;   // (general form: 1 = + the lanes' own sums of one row, the gradient image)
-        snprintf(name, sizeof name, "k_path<%s, %s, %d, %d, %s, %s%s>", f64 ? "double" : "float", sp, np, nc, sg.c_str(), regen ? "true" : "false", loss ? ", true" : "");
-    }
+    if (f.op == PathOp::unbiased)
+        snprintf(name, sizeof name, "k_path_unbiased<%s, %s, %d, %s>", type, sp, f.np, sg.c_str());
+    else
+        snprintf(name, sizeof name, "k_path<%s, %s, %d, %d, %s, %s%s>", type, sp, f.np, f.nc, sg.c_str(), f.regen ? "true" : "false", f.loss ? ", true" : "");
     return name;
+}
+
+// The form's instantiation the library carries -- exactly the ones it launches -- or nullptr: the form exists only through
+// hiprtc (LOSS, the scene's own program)
+template <typename R>
+const void* library_path_kernel(const PathForm& f)
+{
+    if (f.loss || f.prog == PathProg::scene)
+        return nullptr;
+    // the gradient columns of k_path and k_path_mesh: the general form, 8 parameters in 8 colour columns, 4 in 3 or 4, none
+    const auto columns = [&f](auto k) {
+        if (f.np == DRT_NP_ANY && f.nc == 0) return k(IntC<DRT_NP_ANY>(), IntC<0>());
+        if (f.np == 8 && f.nc == 8) return k(IntC<8>(), IntC<8>());
+        if (f.np == 4 && f.nc == 3) return k(IntC<4>(), IntC<3>());
+        if (f.np == 4 && f.nc == 4) return k(IntC<4>(), IntC<4>());
+        if (f.np == 0 && f.nc == 0) return k(IntC<0>(), IntC<0>());
+        return (const void*)nullptr;
+    };
+    // SPEC, and the closest-hit program compiled in: the reference's kinds or the kind-sorted program
+    const auto spec_sig = [&f](auto k) {
+        return with_bool(f.spec, [&](auto spec) { return with_bool(f.prog == PathProg::cornell, [&](auto cornell) {
+            return k(spec, std::conditional_t<cornell, SigCornell, SigNone>()); }); });
+    };
+    if (f.op == PathOp::mesh)      // (the kind-sorted program; every lane on its own)
+        return columns([&f](auto np, auto nc) {
+            return with_bool(f.spec, [](auto spec) { return (const void*)k_path_mesh<R, spec, decltype(np)::value, decltype(nc)::value>; });
+        });
+    if (f.op == PathOp::unbiased)
+        return with_int<DRT_NP_ANY, 8, 4>(f.np, [&](auto np) {
+            return spec_sig([](auto spec, auto sg) { return (const void*)k_path_unbiased<R, spec, decltype(np)::value, decltype(sg)>; });
+        });
+    if (f.nc == 1)                 // the general form's gradient image: lockstep only (a lane is a pixel)
+        return f.np != DRT_NP_ANY || f.regen ? nullptr
+                                             : spec_sig([](auto spec, auto sg) { return (const void*)k_path<R, spec, DRT_NP_ANY, 1, decltype(sg), false>; });
+    return columns([&](auto np, auto nc) {
+        return spec_sig([&](auto spec, auto sg) {
+            return with_bool(f.regen, [](auto regen) {
+                return (const void*)k_path<R, decltype(spec)::value, decltype(np)::value, decltype(nc)::value, decltype(sg), regen>;
+            });
+        });
+    });
 }
 
 // ---- which route, how large a batch, which grids ---------------------------------------------------------------------
@@ -277,17 +351,16 @@ void shard_plan(Shard<R>& s)
     // gradients: <= 8 parameters in registers / LDS columns; any number the kernels can stage (136: every analytic scene) through
     // the general form -- vertex history + per-wave tables (drt_path.h, DRT_NP_ANY); the gradient IMAGE (the lanes' own sums) in
     // analytic scenes too
-    const bool grads_ok = !(s.backward || s.gimg_param >= 0) || ctx->n_params <= DRT_FAST_PARAMS ||
+    const bool tangents = s.backward || s.gimg_param >= 0;
+    const bool grads_ok = !tangents || ctx->n_params <= DRT_FAST_PARAMS ||
                           (ctx->n_params <= DRT_PATH_LDS_PARAMS && tuning().path_general && (s.gimg_param < 0 || !ctx->has_mesh));
     s.use_path = ((s.can_fuse && ctx->prog_ok) || mesh_ok) && D > 0 && grads_ok &&
                  rp->bounces_per_launch <= 0 && tuning().shade_bounces <= 0 && tuning().dump_path == -1;
     s.mesh_path = s.use_path && ctx->has_mesh;
-    s.path_regen = tuning().path_regen > 0 || s.mesh_path;    // (k_path_mesh: every lane on its own, always)
-    if (s.unbiased)
-        s.path_regen = false;                  // (k_path_unbiased walks its samples in lockstep)
+    PathForm& f = s.path;
     const bool lane_is_pixel = s.gimg_param >= 0 && !s.mesh_path;   // the gradient image is the lanes' own sums: lockstep form only
-    if (lane_is_pixel)
-        s.path_regen = false;
+    // (k_path_mesh: every lane on its own, always; k_path_unbiased walks its samples in lockstep)
+    f.regen = (tuning().path_regen > 0 || s.mesh_path) && !s.unbiased && !lane_is_pixel;
     if (s.use_path && !s.mesh_path && !lane_is_pixel && tuning().path_regen < 0 && !s.unbiased) {
         // lockstep: a wave runs until the longest of its 64 paths ends -- the depth cap for fixed-depth renders, under the
         // roulette about the depth that 1 path in 256 reaches; regenerating: every lane runs the mean path length, at
@@ -304,8 +377,20 @@ void shard_plan(Shard<R>& s)
             if (alive < 1.0 / 256 && longest == D)
                 longest = k + 1;
         }
-        s.path_regen = 1.7 * mean_len + 0.5 < (double)longest;
+        f.regen = 1.7 * mean_len + 0.5 < (double)longest;
     }
+    // the gradients: in registers / LDS columns for <= 8 parameters, else the general form (also where the register form would do
+    // but is slower: its 5 ... 8-parameter instantiation keeps 24 LDS columns per thread -- 0.78 ms against the general form's 0.75
+    // on config 3's frame with an albedo per wall)
+    const bool gen = tangents && ctx->n_params <= DRT_PATH_LDS_PARAMS &&
+                     (s.gimg_param >= 0 ? ctx->n_params > DRT_FAST_PARAMS && !s.mesh_path       // (the image keeps the column form where it exists)
+                                        : ctx->n_params > tuning().gen_above && (tuning().path_general || ctx->n_params <= DRT_FAST_PARAMS));
+    f.op = s.unbiased ? PathOp::unbiased : (s.mesh_path ? PathOp::mesh : PathOp::biased);
+    f.f64 = sizeof(R) == 8; f.spec = ctx->has_specular;
+    f.np = !tangents ? 0 : (gen ? DRT_NP_ANY : np_width(ctx->n_params, DRT_NP_ANY));
+    f.nc = !tangents ? 0 : gen ? (s.gimg_param >= 0 ? 1 : 0)
+                             : (f.np == 8 ? 8 : (ctx->max_colour_param < 3 ? 3 : 4));   // (tangent state only for parameters that ARE some BxDF's colour)
+    f.loss = s.loss_l2;
     if (s.use_path && s.loss_l2) {
         // The per-sample seed 2 (L_s - target) needs the path's radiance before its gradients.  k_path has it where the path
         // ends on a light -- the only emissive vertex of a path unless some shape carries a BxDF AND an emitter -- in the LOSS
@@ -315,17 +400,19 @@ void shard_plan(Shard<R>& s)
         // (DRT_SPECIALISE_AUTO: no frame waits for the compiler -- the compile runs on the library's own thread from the first
         //  such frame on, and the tape route renders until it has delivered; DRT_SPECIALISE_NOW waits)
         if ((sizeof(R) == 4 || !ctx->user_header.empty()) && !ctx->emissive_bxdf && ctx->jit_mode >= DRT_SPECIALISE_AUTO) {
-            const bool gen_loss = ctx->n_params > tuning().gen_above && ctx->n_params <= DRT_PATH_LDS_PARAMS && (tuning().path_general || ctx->n_params <= DRT_FAST_PARAMS);
-            s.loss_kernel = jit_function(ctx, path_kernel_name(ctx, true, false, s.path_regen, true, gen_loss, sizeof(R) == 8),
-                                         ctx->jit_mode > DRT_SPECIALISE_AUTO || !ctx->user_header.empty());
+            s.loss_kernel = jit_function(ctx, path_kernel_name(ctx, f), ctx->jit_mode > DRT_SPECIALISE_AUTO || !ctx->user_header.empty());
             s.use_path = s.loss_kernel != nullptr;
         }
     }
-    // (the general form also where the register form would do but is slower: its 5 ... 8-parameter instantiation keeps 24 LDS
-    //  columns per thread -- 0.78 ms against the general form's 0.75 on config 3's frame with an albedo per wall)
-    s.path_gen = s.use_path && (s.backward || s.gimg_param >= 0) && ctx->n_params <= DRT_PATH_LDS_PARAMS &&
-                 (s.gimg_param >= 0 ? ctx->n_params > DRT_FAST_PARAMS && !s.mesh_path       // (the image keeps the column form where it exists)
-                                    : ctx->n_params > tuning().gen_above && (tuning().path_general || ctx->n_params <= DRT_FAST_PARAMS));
+    s.path_gen = s.use_path && gen;
+    // The closest-hit program.  The kinds of the reference's own scene are compiled in, in the instantiation the library
+    // carries (f64 too: the verification mode runs the same program with full-precision reciprocals and square roots); any
+    // other analytic scene reads its kinds at run time (the kind-sorted program) until it has rendered enough for a kernel
+    // of its own to pay (path_batch; f32 only: the f64 mode keeps the reference's literal shape loop for such scenes).
+    const bool builtin = tuning().builtin_program && ctx->jit_mode >= 0 && ctx->n_shapes == DRT_NSIG_CORNELL &&
+                         ctx->prog_sig[0] == DRT_SIG_CORNELL && !s.loss_kernel && !s.mesh_path &&
+                         ctx->user_header.empty();      // (caller-defined kinds -- a BxDF on the reference's own shapes -- exist in hiprtc's kernel only)
+    f.prog = builtin ? PathProg::cornell : ((s.loss_kernel || !ctx->user_header.empty()) ? PathProg::scene : PathProg::sorted);
     // Batch = the paths that are in flight at once on the queue route.  The BVH walk wants it LARGE: its launches end in a
     // tail of ~0.1 ms whatever their size (the list counters run dry, every wave finishes what it holds), so config 4 at full
     // size (1024^2 x 256 spp) takes 115 / 101 / 98 / 96 ms with 2^24 / 2^26 / 2^27 / 2^28 paths per batch and one GPU's
@@ -378,7 +465,7 @@ void shard_plan(Shard<R>& s)
     // 8: 0.812, 7: 0.795, 4: 0.811); regenerating lanes balance themselves over their sample range: longer ranges, fewer waves
     const uint32_t path_groups = (s.Pb + DRT_WAVE - 1) / DRT_WAVE;
     {
-        const uint64_t target = (uint64_t)ctx->n_cu * (s.path_regen ? 32 : 112);
+        const uint64_t target = (uint64_t)ctx->n_cu * (f.regen ? 32 : 112);
         const uint64_t want = std::max<uint64_t>(1, (target + path_groups - 1) / path_groups);   // ranges
         s.path_spr = (uint32_t)((s.Sb + want - 1) / want);
         if (tuning().path_spr > 0)
@@ -564,7 +651,7 @@ int path_batch(Shard<R>& s)
     const drt_render_params* rp = s.rp;
     const BatchArgs& a = s.a;
     drt_hip_stats* st = s.st;
-    const bool backward = s.backward, unbiased = s.unbiased, path_regen = s.path_regen;
+    const bool backward = s.backward;
     PathArgs pa;
     memset(&pa, 0, sizeof pa);
     pa.W = a.W; pa.H = a.H; pa.spp = a.spp;
@@ -598,7 +685,7 @@ int path_batch(Shard<R>& s)
     // (the first words in LDS, as many as leave the kernel's blocks per CU alone: four in the lockstep k_path -- 16 vertices --,
     //  none in the regenerating forms, whose static LDS sits right under a block's share; the others in global memory)
     const uint32_t hist_words = gen ? (uint32_t)(a.depth_cap / 4) : 0u;
-    pa.hist_lds = std::min<uint32_t>(hist_words, (path_regen || s.mesh_path) ? 0u : 4u);
+    pa.hist_lds = std::min<uint32_t>(hist_words, (s.path.regen || s.mesh_path) ? 0u : 4u);
     if (tuning().gen_hist_lds >= 0)
         pa.hist_lds = std::min<uint32_t>(hist_words, (uint32_t)tuning().gen_hist_lds);
     const unsigned hist_bytes = pa.hist_lds * DRT_BLOCK * (unsigned)sizeof(uint32_t);
@@ -614,13 +701,6 @@ int path_batch(Shard<R>& s)
     uint32_t* counts = s.counts;
     double* fpart = s.film ? (double*)s.fpart_buf->p : (double*)nullptr;
     double* gpix = s.gimg_param >= 0 ? (double*)ctx->gpix.p : (double*)nullptr;   // gradient image partials
-    // The closest-hit program.  The kinds of the reference's own scene are compiled in, in the instantiation the library
-    // carries (f64 too: the verification mode runs the same program with full-precision reciprocals and square roots); any
-    // other analytic scene reads its kinds at run time (the kind-sorted program) until it has rendered enough for a kernel
-    // of its own to pay (drt_jit.h; f32 only: the f64 mode keeps the reference's literal shape loop for such scenes).
-    const bool builtin = tuning().builtin_program && ctx->jit_mode >= 0 && ctx->n_shapes == DRT_NSIG_CORNELL &&
-                         ctx->prog_sig[0] == DRT_SIG_CORNELL && !s.loss_kernel && !s.mesh_path &&
-                         ctx->user_header.empty();      // (caller-defined kinds -- a BxDF on the reference's own shapes -- exist in hiprtc's kernel only)
     unsigned long long* ptotal = s.path_finish ? s.totals : (unsigned long long*)nullptr;
     // (frames that overlap: this frame's grid goes to the lane's own stream, behind whoever still uses the lane's buffers, and
     //  the finishing launch on the context's stream waits for it.  Scene uploads block until they are done; a parameter update
@@ -645,48 +725,28 @@ int path_batch(Shard<R>& s)
             ctx->params_pending[lane2] = false;
         }
     }
-    const bool three = ctx->max_colour_param < 3;
-    const bool tangents = backward || s.gimg_param >= 0;
+    // (the kind-sorted program gives way to a kernel of the scene's own once it has rendered enough for the compile to pay)
+    PathForm form = s.path;
     hipFunction_t jit = s.loss_kernel;
     ctx->scene_work += (uint64_t)a.n_paths * (uint64_t)(s.D > 0 ? s.D : 1);
-    if (!jit && !builtin && !s.mesh_path && ctx->jit_mode > 0 && sizeof(R) == 4 && ctx->user_header.empty() &&
-        (ctx->jit_mode > 1 || ctx->scene_work >= DRT_JIT_AFTER_WORK))
-        jit = jit_function(ctx, path_kernel_name(ctx, tangents, unbiased, path_regen, false, s.path_gen, false, s.path_gen && s.gimg_param >= 0), ctx->jit_mode > 1);
-    if (!ctx->user_header.empty() && !jit) {
+    if (form.prog == PathProg::sorted && form.op != PathOp::mesh && ctx->jit_mode > 0 && !form.f64 &&
+        (ctx->jit_mode > 1 || ctx->scene_work >= DRT_JIT_AFTER_WORK) && (jit = jit_function(ctx, path_kernel_name(ctx, form), ctx->jit_mode > 1)))
+        form.prog = PathProg::scene;
+    if (form.prog == PathProg::scene && !jit) {
         // caller-defined shape kinds: their code exists only in a kernel compiled for this scene -- made now, waited for, in either
         // compute type (shard_plan has checked that the context may compile)
-        jit = jit_function(ctx, path_kernel_name(ctx, tangents, unbiased, path_regen, false, s.path_gen, sizeof(R) == 8, s.path_gen && s.gimg_param >= 0), true);
+        jit = jit_function(ctx, path_kernel_name(ctx, form), true);
         if (!jit)
             return fail(ctx, DRT_ERR_UNSUPPORTED, ("render: the scene's caller-defined shape kinds did not compile: " + ctx->jit_error).c_str());
     }
-    st->path_program = builtin ? DRT_PROGRAM_BUILTIN : (jit ? DRT_PROGRAM_SPECIALISED : DRT_PROGRAM_SORTED);
+    const void* fn = library_path_kernel<R>(form);
+    if (!jit && !fn)
+        return fail(ctx, DRT_ERR_UNSUPPORTED, "render: the library carries no path kernel of this form");
+    st->path_program = form.prog == PathProg::cornell ? DRT_PROGRAM_BUILTIN : (jit ? DRT_PROGRAM_SPECIALISED : DRT_PROGRAM_SORTED);
     int rc;
     if ((rc = timing_begin(ctx, s.timing, DRT_K_PATH)) != DRT_OK) return rc;
-#define DRT_LAUNCH_PATH(SPEC, NP, NC, SG)                                                                                 \
-    do {                                                                                                                 \
-        if (path_regen)                                                                                                  \
-            hipLaunchKernelGGL((k_path<R, SPEC, NP, NC, SG, true>), dim3(gpath), dim3(DRT_BLOCK), hist_bytes, ks,        \
-                               pa, d_scene, d_params, d_adjoint, gpart, fpart, counts, ptotal, gpix);                   \
-        else                                                                                                             \
-            hipLaunchKernelGGL((k_path<R, SPEC, NP, NC, SG, false>), dim3(gpath), dim3(DRT_BLOCK), hist_bytes, ks,       \
-                               pa, d_scene, d_params, d_adjoint, gpart, fpart, counts, ptotal, gpix);                   \
-    } while (0)
-#define DRT_LAUNCH_PATH_SIG(SPEC, NP, NC)                                                  \
-    do {                                                                                   \
-        if (builtin) DRT_LAUNCH_PATH(SPEC, NP, NC, SigCornell);                            \
-        else DRT_LAUNCH_PATH(SPEC, NP, NC, SigNone);                                       \
-    } while (0)
-#define DRT_LAUNCH_UNB(SPEC, NP)                                                                                              \
-    do {                                                                                                                      \
-        if (builtin)                                                                                                          \
-            hipLaunchKernelGGL((k_path_unbiased<R, SPEC, NP, SigCornell>), dim3(gpath), dim3(DRT_BLOCK), 0,                    \
-                               ks, pa, d_scene, d_params, d_adjoint, gpart, fpart, counts, ptotal);                            \
-        else                                                                                                                  \
-            hipLaunchKernelGGL((k_path_unbiased<R, SPEC, NP, SigNone>), dim3(gpath), dim3(DRT_BLOCK), 0, ks, pa,               \
-                               d_scene, d_params, d_adjoint, gpart, fpart, counts, ptotal);                                    \
-    } while (0)
     uint32_t* ovf = s.mesh_path ? (uint32_t*)ctx->mesh_ovf[(s.overlap_ok && lane2) ? 1 : 0].p : (uint32_t*)nullptr;
-    const uint32_t ovf_stride = (uint32_t)gpath * DRT_BLOCK;
+    uint32_t ovf_stride = (uint32_t)gpath * DRT_BLOCK;
     pa.hist_stride = ovf_stride;
     if (gen && hist_ovf_words > 0) {
         // the general form's history beyond its LDS words: a column per thread of the grid (one area per k_path stream); the
@@ -709,48 +769,16 @@ int path_batch(Shard<R>& s)
             row += ctx->requires_grad[(size_t)p2] ? 1u : 0u;
         pa.gimg_row = row;
     }
-    const DevBvh<R> bvh = s.bvh;
-#define DRT_LAUNCH_MESH(SPEC, NP, NC)                                                                              \
-    hipLaunchKernelGGL((k_path_mesh<R, SPEC, NP, NC>), dim3(gpath), dim3(DRT_BLOCK), hist_bytes, ks, pa, d_scene, d_params, \
-                       d_adjoint, bvh, ovf, ovf_stride, gpart, fpart, counts, ptotal, gpix)
-    if (s.mesh_path) {
-        if (tangents && gen) { if (ctx->has_specular) DRT_LAUNCH_MESH(true, DRT_NP_ANY, 0); else DRT_LAUNCH_MESH(false, DRT_NP_ANY, 0); }
-        else if (tangents && ctx->n_params > 4) { if (ctx->has_specular) DRT_LAUNCH_MESH(true, 8, 8); else DRT_LAUNCH_MESH(false, 8, 8); }
-        else if (tangents && three) { if (ctx->has_specular) DRT_LAUNCH_MESH(true, 4, 3); else DRT_LAUNCH_MESH(false, 4, 3); }
-        else if (tangents) { if (ctx->has_specular) DRT_LAUNCH_MESH(true, 4, 4); else DRT_LAUNCH_MESH(false, 4, 4); }
-        else { if (ctx->has_specular) DRT_LAUNCH_MESH(true, 0, 0); else DRT_LAUNCH_MESH(false, 0, 0); }
-    } else
-#undef DRT_LAUNCH_MESH
-    if (jit) {
-        void* args_path[] = {&pa, &d_scene, &d_params, &d_adjoint, &gpart, &fpart, &counts, &ptotal, &gpix};
-        void* args_unb[] = {&pa, &d_scene, &d_params, &d_adjoint, &gpart, &fpart, &counts, &ptotal};
-        HIPCHK(ctx, hipModuleLaunchKernel(jit, (unsigned)gpath, 1, 1, DRT_BLOCK, 1, 1, unbiased ? 0u : hist_bytes, ks, unbiased ? args_unb : args_path, nullptr));
-    } else if (unbiased) {                      // the unbiased operator: fresh suffix paths per vertex, in registers
-        if (gen) { if (ctx->has_specular) DRT_LAUNCH_UNB(true, DRT_NP_ANY); else DRT_LAUNCH_UNB(false, DRT_NP_ANY); }
-        else if (ctx->n_params > 4) { if (ctx->has_specular) DRT_LAUNCH_UNB(true, 8); else DRT_LAUNCH_UNB(false, 8); }
-        else { if (ctx->has_specular) DRT_LAUNCH_UNB(true, 4); else DRT_LAUNCH_UNB(false, 4); }
-    } else if (tangents && gen && s.gimg_param >= 0) {   // ... and the gradient image of one of them (lockstep: a lane is a pixel)
-#define DRT_LAUNCH_GIMG(SPEC, SG) hipLaunchKernelGGL((k_path<R, SPEC, DRT_NP_ANY, 1, SG, false>), dim3(gpath), dim3(DRT_BLOCK), hist_bytes, ks, \
-                                                     pa, d_scene, d_params, d_adjoint, gpart, fpart, counts, ptotal, gpix)
-        if (ctx->has_specular) { if (builtin) DRT_LAUNCH_GIMG(true, SigCornell); else DRT_LAUNCH_GIMG(true, SigNone); }
-        else { if (builtin) DRT_LAUNCH_GIMG(false, SigCornell); else DRT_LAUNCH_GIMG(false, SigNone); }
-#undef DRT_LAUNCH_GIMG
-    } else if (tangents && gen) {                      // any number of parameters
-        if (ctx->has_specular) DRT_LAUNCH_PATH_SIG(true, DRT_NP_ANY, 0);
-        else DRT_LAUNCH_PATH_SIG(false, DRT_NP_ANY, 0);
-    } else if (tangents && ctx->n_params > 4) {        // 5 .. 8 parameters
-        if (ctx->has_specular) DRT_LAUNCH_PATH_SIG(true, 8, 8);
-        else DRT_LAUNCH_PATH_SIG(false, 8, 8);
-    } else if (tangents) {
-        if (ctx->has_specular) { if (three) DRT_LAUNCH_PATH_SIG(true, 4, 3); else DRT_LAUNCH_PATH_SIG(true, 4, 4); }
-        else { if (three) DRT_LAUNCH_PATH_SIG(false, 4, 3); else DRT_LAUNCH_PATH_SIG(false, 4, 4); }
-    } else {
-        if (ctx->has_specular) DRT_LAUNCH_PATH_SIG(true, 0, 0);
-        else DRT_LAUNCH_PATH_SIG(false, 0, 0);
-    }
-#undef DRT_LAUNCH_UNB
-#undef DRT_LAUNCH_PATH_SIG
-#undef DRT_LAUNCH_PATH
+    // the arguments of each operator: k_path_unbiased has no gradient image, k_path_mesh the BVH and its traversal stacks too
+    void* args_path[] = {&pa, &d_scene, &d_params, &d_adjoint, &gpart, &fpart, &counts, &ptotal, &gpix};
+    void* args_unb[] = {&pa, &d_scene, &d_params, &d_adjoint, &gpart, &fpart, &counts, &ptotal};
+    void* args_mesh[] = {&pa, &d_scene, &d_params, &d_adjoint, &s.bvh, &ovf, &ovf_stride, &gpart, &fpart, &counts, &ptotal, &gpix};
+    void** args = form.op == PathOp::unbiased ? args_unb : (form.op == PathOp::mesh ? args_mesh : args_path);
+    const unsigned lds_bytes = form.op == PathOp::unbiased ? 0u : hist_bytes;
+    if (jit)
+        HIPCHK(ctx, hipModuleLaunchKernel(jit, (unsigned)gpath, 1, 1, DRT_BLOCK, 1, 1, lds_bytes, ks, args, nullptr));
+    else
+        HIPCHK(ctx, hipLaunchKernel(fn, dim3(gpath), dim3(DRT_BLOCK), args, lds_bytes, ks));
     if ((rc = timing_end(ctx, s.timing)) != DRT_OK) return rc;
     if (overlap) {
         HIPCHK(ctx, hipEventRecord(ctx->ev_path[lane2], ks));
@@ -874,36 +902,19 @@ int bounce_loop(Shard<R>& s, int first, int parity0, bool camera_fused, typename
         }
         const TailQueue<R> tq0 = s.tailq(k + 1), tq1 = s.tailq(k + 2);
         uint32_t* cont_row = s.counts + (size_t)(D + 1) * s.max_regions;
-#define DRT_SHADE_ARGS a, k, nbk, s.d_scene, s.d_params, s.ra[cur], s.rb[cur], s.rid[cur], hit_k, s.ra[nxt], s.rb[nxt], s.rid[nxt], tape_k, \
-                       s.nv, ck, (uint32_t)s.max_regions, s.bvh.tri_shade
-#define DRT_SHADE_ARGS_TAIL a, k, tail_nb, s.d_scene, s.d_params, s.ra[cur], s.rb[cur], s.rid[cur], hit_k, s.ra[nxt], s.rb[nxt], s.rid[nxt], tape_k, \
-                            s.nv, ck, (uint32_t)s.max_regions, s.bvh.tri_shade
-#define DRT_SHADE_NO_TAIL s.bvh, tq0, tq1, (uint32_t*)nullptr
-#define DRT_SHADE_TAIL s.bvh, tq0, tq1, cont_row
-#define DRT_LAUNCH_SHADE(SPEC)                                                                                                       \
-    do {                                                                                                                            \
-        if (fused && camera_fused && k == 0)                                                                                        \
-            hipLaunchKernelGGL((k_shade<R, SPEC, true, true>), dim3(g), dim3(DRT_BLOCK), 0, ctx->stream, DRT_SHADE_ARGS, 0,          \
-                               (const uint32_t*)nullptr, sv_a, sv_b, sv_hit, DRT_SHADE_NO_TAIL);                                    \
-        else if (fused)                                                                                                             \
-            hipLaunchKernelGGL((k_shade<R, SPEC, true>), dim3(g), dim3(DRT_BLOCK), 0, ctx->stream, DRT_SHADE_ARGS, seg, dbase,       \
-                               sv_a, sv_b, sv_hit, DRT_SHADE_NO_TAIL);                                                              \
-        else if (tail_here)                                                                                                         \
-            hipLaunchKernelGGL((k_shade<R, SPEC, false, false, true>), dim3(g), dim3(DRT_BLOCK), 0, ctx->stream, DRT_SHADE_ARGS_TAIL, \
-                               seg, dbase, sv_a, sv_b, sv_hit, DRT_SHADE_TAIL);                                                     \
-        else                                                                                                                        \
-            hipLaunchKernelGGL((k_shade<R, SPEC, false>), dim3(g), dim3(DRT_BLOCK), 0, ctx->stream, DRT_SHADE_ARGS, seg, dbase,      \
-                               sv_a, sv_b, sv_hit, DRT_SHADE_NO_TAIL);                                                              \
-    } while (0)
-        if (ctx->has_specular)
-            DRT_TIMED(s, DRT_K_SHADE, DRT_LAUNCH_SHADE(true));
-        else
-            DRT_TIMED(s, DRT_K_SHADE, DRT_LAUNCH_SHADE(false));
-#undef DRT_LAUNCH_SHADE
-#undef DRT_SHADE_TAIL
-#undef DRT_SHADE_NO_TAIL
-#undef DRT_SHADE_ARGS_TAIL
-#undef DRT_SHADE_ARGS
+        // the shade launch: fused through nbk bounces (the depth-0 one with the camera rays), or one bounce (in two stages: TAIL)
+        const auto shade = [&](auto spec, auto fused_c, auto cam_c, auto tail_c) {
+            hipLaunchKernelGGL((k_shade<R, spec, fused_c, cam_c, tail_c>), dim3(g), dim3(DRT_BLOCK), 0, ctx->stream, a, k, tail_c ? tail_nb : nbk,
+                               s.d_scene, s.d_params, s.ra[cur], s.rb[cur], s.rid[cur], hit_k, s.ra[nxt], s.rb[nxt], s.rid[nxt], tape_k, s.nv,
+                               ck, (uint32_t)s.max_regions, s.bvh.tri_shade, seg, dbase, sv_a, sv_b, sv_hit, s.bvh, tq0, tq1,
+                               tail_c ? cont_row : (uint32_t*)nullptr);
+        };
+        DRT_TIMED(s, DRT_K_SHADE, with_bool(ctx->has_specular, [&](auto spec) {
+            if (fused)
+                with_bool(camera_fused && k == 0, [&](auto cam) { shade(spec, std::true_type(), cam, std::false_type()); });
+            else
+                with_bool(tail_here, [&](auto tail) { shade(spec, std::false_type(), std::false_type(), tail); });
+        }));
     }
     return DRT_OK;
 }
@@ -936,18 +947,12 @@ int adjoint_rounds(Shard<R>& s)
         if (s.shade_tail)
             HIPCHK(ctx, hipMemsetAsync(ctx->cand_count[s.cset(sd)].p, 0, (size_t)a.n_regions * sizeof(uint32_t), ctx->stream));
         const int sq = s.shade_tail ? sd % s.tail_ring : sd & 1;   // the queue lanes of depth sd
-#define DRT_LAUNCH_ADJ_VERTEX(SPEC, TAILV)                                                                                  \
-    hipLaunchKernelGGL((k_adj_vertex<R, SPEC, TAILV>), dim3(g), dim3(DRT_BLOCK), 0, ctx->stream, a, r, s.d_scene, s.d_params, s.cs, \
-                       s.bvh.tri_shade, s.ra[sq], s.rb[sq], s.rid[sq], s.nv, s.counts + (size_t)sd * s.max_regions, s.bvh, \
-                       s.shade_tail ? s.hitr[sq] : s.hit, (uint32_t*)ctx->cand[s.cset(sd)].p, (R4*)ctx->cand_a[s.cset(sd)].p, (R4*)ctx->cand_b[s.cset(sd)].p, (uint32_t*)ctx->cand_count[s.cset(sd)].p)
-        if (s.shade_tail) {
-            if (ctx->has_specular) DRT_TIMED(s, DRT_K_BACKWARD, DRT_LAUNCH_ADJ_VERTEX(true, true));
-            else DRT_TIMED(s, DRT_K_BACKWARD, DRT_LAUNCH_ADJ_VERTEX(false, true));
-        } else {
-            if (ctx->has_specular) DRT_TIMED(s, DRT_K_BACKWARD, DRT_LAUNCH_ADJ_VERTEX(true, false));
-            else DRT_TIMED(s, DRT_K_BACKWARD, DRT_LAUNCH_ADJ_VERTEX(false, false));
-        }
-#undef DRT_LAUNCH_ADJ_VERTEX
+        DRT_TIMED(s, DRT_K_BACKWARD, with_bool(s.shade_tail, [&](auto tail) { with_bool(ctx->has_specular, [&](auto spec) {
+            hipLaunchKernelGGL((k_adj_vertex<R, spec, decltype(tail)::value>), dim3(g), dim3(DRT_BLOCK), 0, ctx->stream, a, r, s.d_scene, s.d_params,
+                               s.cs, s.bvh.tri_shade, s.ra[sq], s.rb[sq], s.rid[sq], s.nv, s.counts + (size_t)sd * s.max_regions, s.bvh,
+                               s.shade_tail ? s.hitr[sq] : s.hit, (uint32_t*)ctx->cand[s.cset(sd)].p, (R4*)ctx->cand_a[s.cset(sd)].p,
+                               (R4*)ctx->cand_b[s.cset(sd)].p, (uint32_t*)ctx->cand_count[s.cset(sd)].p);
+        }); }));
         bool chains_done = false;
         if (D > 2 * DRT_POLL_EVERY && r >= 2) {
             // no suffix ray queued in this round => every chain ends with this round
@@ -968,13 +973,10 @@ int adjoint_rounds(Shard<R>& s)
             hipLaunchKernelGGL(k_sum_counts, dim3(64), dim3(DRT_BLOCK), 0, ctx->stream, s.counts + (size_t)sd * s.max_regions,
                                (uint32_t)((size_t)(D + 2 - sd) * s.max_regions), s.totals, (uint32_t)s.max_regions, sfx_read, sfx_written,
                                (uint32_t)(D - sd));
-#define DRT_LAUNCH_ADJ_ACC(NP)                                                                                           \
-    hipLaunchKernelGGL((k_adj_accumulate<R, NP>), dim3(gp), dim3(DRT_BLOCK), 0, ctx->stream, a, r, s.d_scene, s.d_params, \
-                       s.tape, s.nv, s.cs, s.gpart, s.grad, s.g_rows, s.g_stride)
-        if (ctx->n_params <= 4) DRT_TIMED(s, DRT_K_BACKWARD, DRT_LAUNCH_ADJ_ACC(4));
-        else if (ctx->n_params <= 8) DRT_TIMED(s, DRT_K_BACKWARD, DRT_LAUNCH_ADJ_ACC(8));
-        else DRT_TIMED(s, DRT_K_BACKWARD, DRT_LAUNCH_ADJ_ACC(0));
-#undef DRT_LAUNCH_ADJ_ACC
+        DRT_TIMED(s, DRT_K_BACKWARD, with_int<4, 8, 0>(np_width(ctx->n_params, 0), [&](auto np) {
+            hipLaunchKernelGGL((k_adj_accumulate<R, np>), dim3(gp), dim3(DRT_BLOCK), 0, ctx->stream, a, r, s.d_scene, s.d_params, s.tape, s.nv,
+                               s.cs, s.gpart, s.grad, s.g_rows, s.g_stride);
+        }));
         if (tuning().dump_path >= -2 && tuning().dump_path != -1) {       // debugging aid (DRT_HIP_DUMP_PATH = <path of the batch> | -2: every path)
             (void)hipStreamSynchronize(ctx->stream);
             const size_t first = tuning().dump_path >= 0 ? (size_t)tuning().dump_path : 0;
@@ -1061,14 +1063,11 @@ int queue_batch(Shard<R>& s)
         if (s.loss_l2)
             DRT_TIMED(s, DRT_K_BACKWARD,
                       hipLaunchKernelGGL(k_radiance<R>, dim3(gp), dim3(DRT_BLOCK), 0, ctx->stream, a, s.d_scene, s.d_params, s.tape, s.nv, s.lacc));
-#define DRT_LAUNCH_BWD(NP)                                                                                       \
-    hipLaunchKernelGGL((k_backward<R, NP>), dim3(gp), dim3(DRT_BLOCK), 0, ctx->stream, a, s.d_scene, s.d_params, \
-                       s.tape, s.nv, s.d_adjoint, s.gpart, s.grad, (s.film && !s.loss_l2) ? s.lacc : (R4*)nullptr, s.g_rows, \
-                       s.g_stride, s.loss_l2 ? (const R4*)s.lacc : (const R4*)nullptr)
-        if (ctx->n_params <= 4) DRT_TIMED(s, DRT_K_BACKWARD, DRT_LAUNCH_BWD(4));
-        else if (ctx->n_params <= 8) DRT_TIMED(s, DRT_K_BACKWARD, DRT_LAUNCH_BWD(8));
-        else DRT_TIMED(s, DRT_K_BACKWARD, DRT_LAUNCH_BWD(0));
-#undef DRT_LAUNCH_BWD
+        DRT_TIMED(s, DRT_K_BACKWARD, with_int<4, 8, 0>(np_width(ctx->n_params, 0), [&](auto np) {
+            hipLaunchKernelGGL((k_backward<R, np>), dim3(gp), dim3(DRT_BLOCK), 0, ctx->stream, a, s.d_scene, s.d_params, s.tape, s.nv,
+                               s.d_adjoint, s.gpart, s.grad, (s.film && !s.loss_l2) ? s.lacc : (R4*)nullptr, s.g_rows, s.g_stride,
+                               s.loss_l2 ? (const R4*)s.lacc : (const R4*)nullptr);
+        }));
         DRT_TIMED(s, DRT_K_GRADREDUCE,
                   hipLaunchKernelGGL(k_gradreduce, dim3(s.g_rows > 0 ? s.g_rows : 1), dim3(DRT_BLOCK), 0, ctx->stream, s.gpart, gp,
                                      s.g_rows, s.grad, s.g_stride));
