@@ -57,6 +57,7 @@ struct drt_hip_ctx {
     bool has_specular = false;
     bool emissive_bxdf = false;           // some analytic shape carries a BxDF AND an emitter (several emission terms per path)
     int max_colour_param = -1;            // largest parameter index that is some material's colour (device numbering)
+    unsigned colour_mask = 0, emission_mask = 0;   // bit p: parameter p < 8 is some material's colour / some emitter's emission (PathRoles, drt_path.h)
     bool prog_ok = false;                 // k_path's intersection program covers the scene (drt_path.h)
     bool prog_sorted = false;             // the kind-sorted program covers the scene's analytic shapes (k_shade's tail)
     unsigned long long prog_sig[4] = {0, 0, 0, 0};   // the kinds of the scene's shapes, 3 bits each, 16 per word (KindSig, drt_prog.h)

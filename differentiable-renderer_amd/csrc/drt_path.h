@@ -175,11 +175,18 @@ __device__ inline void stage_path_scene(PathSceneLds<R>& lds, const DevScene<R>*
 // Evaluated where a path meets a light: once per sample.  Same sums as the reference's backward functors
 // (vector.hpp:418-484) in closed form; the image is unchanged bit for bit (a channel without zero factors sees the very
 // same multiplications), gradients to f32 rounding.  |c| < 1e-18 counts as zero (its quotient would overflow).
+// Row DRT_TANGENT_REST is for a lane whose path does NOT go on from the vertex: colour (1, 1, 1), increments 0.  The lockstep kernel
+// freezes such a lane by pointing its table index there (the index is a select anyway) and its multiplicand m_k at 1: T * (1 * 1) and
+// counters + 0 are exact, so the lane keeps its bits -- one select on the index and one on m_k instead of three on the factor and one per counter.
+#define DRT_TANGENT_REST DRT_FAST_PARAMS
+#ifndef DRT_FREEZE_BY_ROW
+#define DRT_FREEZE_BY_ROW 1
+#endif
 template <typename R>
 struct TangentLds {              // per colour parameter, wave-uniform except where indexed by the lane's colour id
-    R colnz[DRT_FAST_PARAMS][4];         // the colour with zero channels replaced by 1
+    R colnz[DRT_FAST_PARAMS + (DRT_FREEZE_BY_ROW != 0)][4];     // the colour with zero channels replaced by 1
     R invc[DRT_FAST_PARAMS][4];          // 1 / c per channel, 0 where the channel is zero
-    uint32_t inc[DRT_FAST_PARAMS][4];    // counter increments of a bounce on this colour: n_p (low, high word), zc; [3] = zero-channel bits
+    uint32_t inc[DRT_FAST_PARAMS + (DRT_FREEZE_BY_ROW != 0)][4];   // counter increments of a bounce on this colour: n_p (low, high word), zc; [3] = zero-channel bits
 };
 
 template <typename R, typename SL>
@@ -205,6 +212,10 @@ __device__ inline void stage_tangents(TangentLds<R>& tl, const SL& lds)
         tl.inc[p][1] = p >= 4 ? 1u << (8 * (p - 4)) : 0u;
         tl.inc[p][2] = zinc;
         tl.inc[p][3] = zbits;
+    }
+    if (DRT_FREEZE_BY_ROW != 0 && threadIdx.x >= DRT_WAVE && threadIdx.x < DRT_WAVE + 4) {
+        tl.colnz[DRT_TANGENT_REST][threadIdx.x - DRT_WAVE] = R(1);
+        tl.inc[DRT_TANGENT_REST][threadIdx.x - DRT_WAVE] = 0u;
     }
     __syncthreads();
 }
@@ -432,13 +443,39 @@ __device__ inline void gen_finish(const GenBlock<R>& gb, const PathArgs& a, doub
     }
 }
 
+// ---- the roles of the fast path's parameter slots ------------------------------------------------------------------------
+// The reference's scene has three albedos that never emit and one emission that never scatters (render.cpp:26-29); a scene of the
+// ABI may use any parameter as both.  What the scene's records say about it (drt_hip_upload_scene: every material's colour parameter,
+// every emitter's parameter) reaches the lockstep k_path as part of its NC template argument,
+//     nc | colour mask << 8 | emission mask << 16        (bit p of a mask: slot p can have that role; DRT_NC_ROLES)
+// so a kernel's name says what it was compiled for and the library's instantiations and hiprtc's are the same source.  Masks of zero
+// mean "not known": every slot below NC may be a colour, every slot an emission -- the code every other form keeps.
+#define DRT_NC_ROLES(nc, colour_mask, emission_mask) ((int)(nc) | (int)(colour_mask) << 8 | (int)(emission_mask) << 16)
+#define DRT_NC_OF(ncr) ((int)(ncr) & 0xFF)
+#define DRT_ROLES_OF(ncr) ((int)(ncr) >> 8)
+#define DRT_ROLES_CORNELL DRT_ROLES_OF(DRT_NC_ROLES(0, 0x7, 0x8))      // render.cpp:26-29: colour, colour, colour, emission
+template <int NP, int NC, int ROLES>
+struct PathRoles {
+    static constexpr int all = NP > 0 ? (1 << NP) - 1 : 0;
+    static constexpr int colm = ROLES ? (ROLES & 0xFF) & ((1 << NC) - 1) : (1 << NC) - 1;
+    static constexpr int emitm = ROLES ? (ROLES >> 8) & all : all;
+    static __device__ constexpr bool colour(int p) { return (colm >> p) & 1; }
+    static __device__ constexpr bool emission(int p) { return (emitm >> p) & 1; }
+    static __device__ constexpr bool only_emission(int p) { return emitm == (1 << p); }
+};
+
 // an emissive vertex reached with prefix throughput T: radiance and gradients
 //   L     += T E / p_k                                   (pathtracer.hpp:113-114, 133)
 //   d/dc_p += g dT_p E / p_k      d/dE += g T / p_k       (vector.hpp:418-484 in closed form)
 // LOSS (DRT_RENDER_LOSS_L2, the end of a path only): `g` holds the lane's TARGET pixel and the seed is the derivative of the
 // sample's own squared error, 2 (L - target), with L the path's radiance INCLUDING this emission -- final where the path ends
 // on a light without BxDF, which is the only emissive vertex of a path in the scenes this form is used for.
-template <typename R, int NP, int NC, bool LOSS = false, typename SL = PathSceneLds<R>>
+// ROLES (PathRoles, below; 0 = every slot may be both): which of the NP slots can be a BxDF's colour and which can be a light's
+// emission, as compile-time facts.  A slot that is no emission loses the one-hot term `own ? gT : 0` (+ 0 changes no bit of a sum that
+// is never -0), the only emission slot of a scene takes gT without asking, a slot that is no colour loses its counter, its 1 / c row and
+// its zero-channel cases, a slot that is neither is not touched.  Every term that remains is the same operation on the same operands
+// in the same order: the sums keep their bits.
+template <typename R, int NP, int NC, bool LOSS = false, typename SL = PathSceneLds<R>, int ROLES = 0>
 __device__ inline void add_emission(const SL& lds, const TangentLds<R>& tl, const R* __restrict__ params, uint32_t eid, R inv_pk,
                                     V3<R> T, V3<R> g, V3<R>& L, Tangents<R, NP, NC>& tg)
 {
@@ -471,10 +508,16 @@ __device__ inline void add_emission(const SL& lds, const TangentLds<R>& tl, cons
         const V3<R> gE = g * E, gT = g * Tr * inv_pk;
 #pragma unroll
         for (int p = 0; p < NP; ++p) {
-            const bool own = eid == (uint32_t)p;
+            typedef PathRoles<NP, NC, ROLES> RL;
+            const bool is_colour = (RL::colm >> p) & 1, is_emission = (RL::emitm >> p) & 1;
+            if (ROLES != 0 && !is_colour && !is_emission)
+                continue;
+            const bool own = (ROLES != 0 && RL::emitm == (1 << p)) || eid == (uint32_t)p;
             const V3<R> ap = tg.acc_get(p);
-            const V3<R> a0 = mk<R>(ap.x + (own ? gT.x : R(0)), ap.y + (own ? gT.y : R(0)), ap.z + (own ? gT.z : R(0)));
-            if (p < NC) {
+            V3<R> a0 = mk<R>(ap.x + (own ? gT.x : R(0)), ap.y + (own ? gT.y : R(0)), ap.z + (own ? gT.z : R(0)));
+            if (ROLES != 0 && !is_emission)
+                a0 = ap;
+            if (is_colour) {
                 const uint32_t n = (tg.cnt[p >> 2] >> (8 * (p & 3))) & 0xFFu;
                 const R nf = (R)(int)n;
                 // (read where they are used, once per sample: hoisted out of the sample loop these twelve wave-uniform words
@@ -514,7 +557,7 @@ struct PathVertex {
     bool hit, scattered;       // the ray hit something / something with a BxDF
 };
 
-template <typename R, bool SPEC, int NP, int NC, typename SG>
+template <typename R, bool SPEC, int NP, int NC, typename SG, bool FREEZE_BY_ROW = false>
 __device__ inline void path_bounce(const PathArgs& a, const PathSceneLds<R>& lds, const TangentLds<R>& tl, const DevScene<R>* __restrict__ sc,
                                    const R* __restrict__ params, const ProgRecs<SG::n, R>& recs, uint32_t key,
                                    R pk, R inv_pk, uint32_t n_theta, bool next_rr, bool next_cap, bool live, V3<R> g,
@@ -600,7 +643,9 @@ __device__ inline void path_bounce(const PathArgs& a, const PathSceneLds<R>& lds
     capped = hit && has_bxdf && next_cap && !a.cap_is_roulette && !rr_kills;
     // the throughput moves on only in lanes whose path goes on (the others stay frozen for the light's turn); with
     // gradients it leaves zero colour channels out and counts them, and counts the bounce for its colour (see Tangents)
-    const int cidx = has_bxdf ? (int)cid : 0;
+    // (REST, the lockstep kernel's colour-column form: a lane that does not go on reads the table's row of ones and zero increments)
+    constexpr bool REST = FREEZE_BY_ROW && NC > 0 && NP != DRT_NP_ANY;
+    const int cidx = REST ? (alive ? (int)cid : DRT_TANGENT_REST) : (has_bxdf ? (int)cid : 0);
     V3<R> col;
     if constexpr (NP == DRT_NP_ANY) {
         const R* rec = tg.gl->colnz[cidx < DRT_PATH_LDS_PARAMS ? cidx : 0];
@@ -612,8 +657,14 @@ __device__ inline void path_bounce(const PathArgs& a, const PathSceneLds<R>& lds
             tg.template push<true>(live, alive ? cid : 0xFFu);
     } else
         col = NC > 0 ? mk<R>(tl.colnz[cidx][0], tl.colnz[cidx][1], tl.colnz[cidx][2]) : load_param<R, (NP > 0)>(lds, params, cidx);
-    const V3<R> cmv = col * mk_;
-    const V3<R> cm = mk<R>(alive ? cmv.x : R(1), alive ? cmv.y : R(1), alive ? cmv.z : R(1));
+    const V3<R> cmv = col * (REST ? (alive ? mk_ : R(1)) : mk_);
+    const V3<R> cm = REST ? cmv : mk<R>(alive ? cmv.x : R(1), alive ? cmv.y : R(1), alive ? cmv.z : R(1));
+    if constexpr (REST) {
+        tg.cnt[0] += tl.inc[cidx][0];
+        if (NC > 4)
+            tg.cnt[NC > 4 ? 1 : 0] += tl.inc[cidx][1];
+        tg.zc += tl.inc[cidx][2];
+    } else
     if constexpr (NC > 0 && NP != DRT_NP_ANY) {
         tg.cnt[0] += alive ? tl.inc[cidx][0] : 0u;
         if (NC > 4)
@@ -725,7 +776,8 @@ constexpr int path_min_blocks()
 // path ends.  ~35 % more instructions per bounce, but roulette-terminated renders (the reference's defaults, -b 1
 // -p 0.5: 2.5 vertices per path on average, some paths 20) keep their lanes busy.
 // (waves per SIMD by form: path_min_blocks above)
-template <typename R, bool SPEC, int NP, int NC, typename SG, bool REGEN = false, bool LOSS = false>
+// (NCR: the colour columns NC and, above its low byte, the slots' roles -- DRT_NC_ROLES)
+template <typename R, bool SPEC, int NP, int NCR, typename SG, bool REGEN = false, bool LOSS = false>
 __global__ void __launch_bounds__(DRT_BLOCK, (path_min_blocks<sizeof(R), SPEC, NP, SG::n, REGEN>()))
 k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ params, const float* __restrict__ adjoint,
        double* __restrict__ gpart, double* __restrict__ fpart, uint32_t* __restrict__ counts,
@@ -735,6 +787,7 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
         total[threadIdx.x] = 0;                           // (the finishing kernel behind this launch adds into them)
     typedef typename Q4<R>::T R4;
     typedef typename Q2<R>::T R2;
+    constexpr int NC = DRT_NC_OF(NCR), ROLES = DRT_ROLES_OF(NCR);
     __shared__ PathSceneLds<R> lds;
     __shared__ double s_red[REGEN ? 1 : DRT_BLOCK / DRT_WAVE][DRT_FAST_PARAMS * 3];   // (REGEN: the block's gradient partials reuse the pixel sums' table)
     __shared__ TangentLds<R> s_tl;
@@ -828,7 +881,8 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
             const bool next_cap = (kk + 1) >= a.depth_cap;
             bool alive, capped, on_light;
             uint32_t light;
-            path_bounce<R, SPEC, NP, NC, SG>(a, lds, tl, sc, params, recs, key, pk, inv_pk, n_theta, next_rr, next_cap, live, g,
+            // (the row of ones for lanes that stop: measured on the diffuse f32 kernels of few shapes, theirs alone)
+            path_bounce<R, SPEC, NP, NC, SG, (DRT_FREEZE_BY_ROW != 0 && sizeof(R) == 4 && !SPEC && SG::n <= DRT_LEAN_MAX_SHAPES)>(a, lds, tl, sc, params, recs, key, pk, inv_pk, n_theta, next_rr, next_cap, live, g,
                                                     ra, rb, T, L, tg, alive, capped, on_light, light, nullptr, next_cap);
             // A light without a BxDF ends the path: T and dT stay as they are in this lane, so its emission is added
             // ONCE PER SAMPLE, after the bounce loop, for all lanes together -- not here, where every bounce a few lanes
@@ -841,7 +895,7 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
         }
         if (wave_any(end_ids != DRT_ID_NONE)) {
             if (end_ids != DRT_ID_NONE)
-                add_emission<R, NP, NC, LOSS>(lds, tl, params, end_ids, end_inv_pk, T, g, L, tg);
+                add_emission<R, NP, NC, LOSS, PathSceneLds<R>, ROLES>(lds, tl, params, end_ids, end_inv_pk, T, g, L, tg);
         }
         fx += (double)L.x; fy += (double)L.y; fz += (double)L.z;
     }

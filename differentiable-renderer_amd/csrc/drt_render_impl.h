@@ -161,6 +161,8 @@ struct PathForm {
                                     // (nc = 1: + the lanes' own sums of one row, the gradient image)
     bool regen;                     // the regenerating form (k_path_mesh: always; k_path_unbiased: never)
     bool loss;                      // DRT_RENDER_LOSS_L2's instantiation: made at run time only
+    int roles;                      // the parameter slots' roles, colour mask | emission mask << 8 (drt_path.h: PathRoles); 0: not specialised --
+                                    // every form but the lockstep k_path with <= 8 parameters in columns
     PathProg prog;
 };
 
@@ -265,7 +267,7 @@ struct Shard {
     }
 };
 
-// "k_path<float, SPEC, NP, NC, KindSig<...>, REGEN[, LOSS]>" / "k_path_unbiased<float, SPEC, NP, KindSig<...>>": the name expression
+// "k_path<float, SPEC, NP, NC | roles << 8, KindSig<...>, REGEN[, LOSS]>" / "k_path_unbiased<float, SPEC, NP, KindSig<...>>": the name expression
 // of the form for the scene's own signature, what hiprtc compiles (k_path_mesh has no such form)
 inline std::string path_kernel_name(const drt_hip_ctx* ctx, const PathForm& f)
 {
@@ -276,7 +278,7 @@ inline std::string path_kernel_name(const drt_hip_ctx* ctx, const PathForm& f)
     if (f.op == PathOp::unbiased)
         snprintf(name, sizeof name, "k_path_unbiased<%s, %s, %d, %s>", type, sp, f.np, sg.c_str());
     else
-        snprintf(name, sizeof name, "k_path<%s, %s, %d, %d, %s, %s%s>", type, sp, f.np, f.nc, sg.c_str(), f.regen ? "true" : "false", f.loss ? ", true" : "");
+        snprintf(name, sizeof name, "k_path<%s, %s, %d, %d, %s, %s%s>", type, sp, f.np, DRT_NC_ROLES(f.nc, 0, 0) | f.roles << 8, sg.c_str(), f.regen ? "true" : "false", f.loss ? ", true" : "");
     return name;
 }
 
@@ -301,6 +303,16 @@ const void* library_path_kernel(const PathForm& f)
         return with_bool(f.spec, [&](auto spec) { return with_bool(f.prog == PathProg::cornell, [&](auto cornell) {
             return k(spec, std::conditional_t<cornell, SigCornell, SigNone>()); }); });
     };
+    if (f.roles != 0) {
+        // role-specialised (shard_plan: the diffuse f32 lockstep k_path only): the library carries the roles of the reference's own scene,
+        // render.cpp:26-29 -- three colours, one emission --; any other layout exists in the kernel hiprtc makes for its scene
+        if constexpr (sizeof(R) == 4) {
+            if (f.op == PathOp::biased && !f.spec && !f.regen && f.np == 4 && f.nc == 3 && f.roles == DRT_ROLES_CORNELL)
+                return with_bool(f.prog == PathProg::cornell, [](auto cornell) {
+                    return (const void*)k_path<R, false, 4, DRT_NC_ROLES(3, 0, 0) | DRT_ROLES_CORNELL << 8, std::conditional_t<cornell, SigCornell, SigNone>, false>; });
+        }
+        return nullptr;
+    }
     if (f.op == PathOp::mesh)      // (the kind-sorted program; every lane on its own)
         return columns([&f](auto np, auto nc) {
             return with_bool(f.spec, [](auto spec) { return (const void*)k_path_mesh<R, spec, decltype(np)::value, decltype(nc)::value>; });
@@ -391,6 +403,11 @@ void shard_plan(Shard<R>& s)
     f.nc = !tangents ? 0 : gen ? (s.gimg_param >= 0 ? 1 : 0)
                              : (f.np == 8 ? 8 : (ctx->max_colour_param < 3 ? 3 : 4));   // (tangent state only for parameters that ARE some BxDF's colour)
     f.loss = s.loss_l2;
+    // the slots' roles as the scene's records give them: for the form the headline runs -- diffuse, f32, lockstep, parameters in columns
+    f.roles = 0;
+    if (tuning().path_roles && tangents && !gen && sizeof(R) == 4 && !f.spec && !f.regen && !f.loss && f.op == PathOp::biased && s.gimg_param < 0 &&
+        ctx->colour_mask != 0 && ctx->emission_mask != 0)
+        f.roles = (int)(ctx->colour_mask | ctx->emission_mask << 8);
     if (s.use_path && s.loss_l2) {
         // The per-sample seed 2 (L_s - target) needs the path's radiance before its gradients.  k_path has it where the path
         // ends on a light -- the only emissive vertex of a path unless some shape carries a BxDF AND an emitter -- in the LOSS
@@ -740,6 +757,10 @@ int path_batch(Shard<R>& s)
             return fail(ctx, DRT_ERR_UNSUPPORTED, ("render: the scene's caller-defined shape kinds did not compile: " + ctx->jit_error).c_str());
     }
     const void* fn = library_path_kernel<R>(form);
+    if (!jit && !fn && form.roles != 0) {      // (a layout of roles the library does not carry: its kernel for any layout)
+        form.roles = 0;
+        fn = library_path_kernel<R>(form);
+    }
     if (!jit && !fn)
         return fail(ctx, DRT_ERR_UNSUPPORTED, "render: the library carries no path kernel of this form");
     st->path_program = form.prog == PathProg::cornell ? DRT_PROGRAM_BUILTIN : (jit ? DRT_PROGRAM_SPECIALISED : DRT_PROGRAM_SORTED);

@@ -355,8 +355,15 @@ int upload_scene_one(drt_hip_ctx* ctx, const drt_scene_desc* s)
         ctx->prog_sig[i] = sig[i];
     ctx->user_header = user_header;
     ctx->max_colour_param = -1;
-    for (int i = 0; i < hf->n_materials; ++i)
+    ctx->colour_mask = ctx->emission_mask = 0;
+    for (int i = 0; i < hf->n_materials; ++i) {
         ctx->max_colour_param = std::max(ctx->max_colour_param, hf->materials[i].param);
+        if (hf->materials[i].param >= 0 && hf->materials[i].param < DRT_FAST_PARAMS)
+            ctx->colour_mask |= 1u << hf->materials[i].param;
+    }
+    for (int i = 0; i < hf->n_emitters; ++i)
+        if (hf->emitter_param[i] >= 0 && hf->emitter_param[i] < DRT_FAST_PARAMS)
+            ctx->emission_mask |= 1u << hf->emitter_param[i];
     delete hf;
     delete hd;
     if (rc != DRT_OK)

@@ -17,6 +17,7 @@ struct Tuning {
     bool builtin_program = true;   // DRT_HIP_BUILTIN_PROGRAM  0: the reference's own scene is specialised at run time like any other (test of hiprtc against the library's own build)
     bool overlap_frames = true;    // DRT_HIP_OVERLAP_FRAMES   0: the path kernels of consecutive frames never overlap (what DRT_RENDER_SERIAL asks per frame)
     int path_spr = 0;              // DRT_HIP_PATH_SPR         samples per wave range of k_path; 0 = automatic (~112 waves per CU)
+    bool path_roles = true;        // DRT_HIP_PATH_ROLES       0: the lockstep k_path is not compiled for the roles of the scene's parameters (every slot: colour and emission)
     int path_regen = -1;           // DRT_HIP_PATH_REGEN       1 / 0: force the regenerating / lockstep form of k_path; -1 = the cheaper by the library's estimate
     int path_regen_min = 8;        // DRT_HIP_PATH_REGEN_MIN   idle lanes it takes for the regenerating form to run the camera code
     bool path_general = true;      // DRT_HIP_PATH_GENERAL     0: gradients of more than 8 parameters take the queue wavefront (tape + K6) instead of the one-launch kernels' general form
@@ -57,6 +58,7 @@ inline const Tuning& tuning()
         v.builtin_program = !off("DRT_HIP_BUILTIN_PROGRAM");
         v.overlap_frames = !off("DRT_HIP_OVERLAP_FRAMES");
         v.path_spr = (int)num("DRT_HIP_PATH_SPR", 0);
+        v.path_roles = !off("DRT_HIP_PATH_ROLES");
         v.path_regen = (int)num("DRT_HIP_PATH_REGEN", -1);
         v.path_regen_min = (int)num("DRT_HIP_PATH_REGEN_MIN", 8);
         v.path_general = !off("DRT_HIP_PATH_GENERAL");
