@@ -723,7 +723,7 @@ _ABI_SYMBOLS = ["drt_hip_abi_version", "drt_hip_device_count", "drt_hip_create",
                 "drt_hip_group_size", "drt_hip_device_pci_bus_id", "drt_hip_destroy",
                 "drt_hip_comm_unique_id", "drt_hip_comm_init_rank", "drt_hip_comm_size", "drt_hip_comm_destroy",
                 "drt_hip_upload_scene", "drt_hip_update_params", "drt_hip_set_specialisation", "drt_hip_render", "drt_hip_render_async", "drt_hip_wait",
-                "drt_hip_render_gradient_image", "drt_hip_pin_host", "drt_hip_unpin_host", "drt_hip_stream",
+                "drt_hip_render_gradient_image", "drt_hip_render_tangent", "drt_hip_render_tangent_double", "drt_hip_pin_host", "drt_hip_unpin_host", "drt_hip_stream",
                 "drt_hip_synchronize", "drt_hip_last_error", "drt_hip_kernel_name"]
 
 
@@ -758,6 +758,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.drt_hip_wait.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(HipStats)]
     lib.drt_hip_render_gradient_image.argtypes = [C.c_void_p, C.POINTER(CameraDesc), C.POINTER(RenderParamsDesc),
                                                   C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(HipStats)]
+    lib.drt_hip_render_tangent.argtypes = [C.c_void_p, C.POINTER(CameraDesc), C.POINTER(RenderParamsDesc),
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(HipStats)]
+    lib.drt_hip_render_tangent_double.argtypes = lib.drt_hip_render_tangent.argtypes
     lib.drt_hip_pin_host.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
     lib.drt_hip_unpin_host.argtypes = [C.c_void_p, C.c_void_p]
     lib.drt_hip_stream.argtypes = [C.c_void_p]
@@ -949,6 +952,42 @@ class HipRenderer:
                                                     gimg.ctypes.data_as(C.c_void_p), C.byref(stats))
         self._check(rc, "drt_hip_render_gradient_image")
         return img, gimg, stats.as_dict()
+
+    def render_tangent(self, cam: Camera, rp: RenderParams, tangent: np.ndarray, f64: bool = False, timing: bool = False):
+        """Forward mode (drt_hip_render_tangent): the image and its derivative along `tangent` (shape (n_params, 3)), the
+        Jacobian-vector product J v -- per pixel, the mean over its samples of d radiance / d eps at params + eps * tangent.
+        -> (image [H,W,3], tangent image [H,W,3], stats dict).  Both are float32; with f64=True (the verification mode) they
+        are the float64 the device summed (drt_hip_render_tangent_double)."""
+        assert self.scene is not None
+        v = np.ascontiguousarray(tangent, dtype=np.float64)
+        assert v.shape == (self.scene.n_params, 3), v.shape
+        d = rp.to_desc()
+        d.flags = (rp.flags & ~(RENDER_DEVICE_OUT | RENDER_SYNC)) | (RENDER_F64 if f64 else 0) | (RENDER_TIMING if timing else 0)
+        img = np.zeros((cam.height, cam.width, 3), dtype=np.float64 if f64 else np.float32)
+        timg = np.zeros((cam.height, cam.width, 3), dtype=np.float64 if f64 else np.float32)
+        stats = HipStats()
+        cd = cam.to_desc()
+        fn = self.lib.drt_hip_render_tangent_double if f64 else self.lib.drt_hip_render_tangent
+        rc = fn(self.ctx, C.byref(cd), C.byref(d), v.ctypes.data_as(C.c_void_p), img.ctypes.data_as(C.c_void_p),
+                timg.ctypes.data_as(C.c_void_p), C.byref(stats))
+        self._check(rc, fn.__name__)
+        return img, timg, stats.as_dict()
+
+    def render_tangent_device(self, cam: Camera, rp: RenderParams, tangent: np.ndarray, out_rgb_ptr: int, out_tangent_ptr: int,
+                              timing: bool = False, want_stats: Optional[bool] = None) -> dict:
+        """drt_hip_render_tangent on device pointers (float32 [H,W,3] each; out_rgb_ptr may be 0), enqueued on the context's stream."""
+        if want_stats is None:
+            want_stats = timing
+        v = np.ascontiguousarray(tangent, dtype=np.float64)
+        assert self.scene is not None and v.shape == (self.scene.n_params, 3), v.shape
+        d = rp.to_desc()
+        d.flags = ((rp.flags | RENDER_DEVICE_OUT) & ~RENDER_SYNC) | (RENDER_TIMING if timing else 0)
+        stats = HipStats()
+        cd = cam.to_desc()
+        rc = self.lib.drt_hip_render_tangent(self.ctx, C.byref(cd), C.byref(d), v.ctypes.data_as(C.c_void_p), C.c_void_p(out_rgb_ptr or None),
+                                             C.c_void_p(out_tangent_ptr), C.byref(stats) if want_stats else None)
+        self._check(rc, "drt_hip_render_tangent")
+        return stats.as_dict() if want_stats else {}
 
     def render_device(self, cam: Camera, rp: RenderParams, out_rgb_ptr: int, out_grad_ptr: int,
                       adjoint_ptr: int = 0, backward: bool = True, timing: bool = False,

@@ -15,6 +15,12 @@ struct TimedLaunch {
     hipEvent_t e0, e1;
 };
 
+// A forward-mode render (drt_hip_render_tangent), as render_common / render_launch / render_impl are told about it
+struct TangentRequest {
+    const void* d_params = nullptr;       // [the scene's parameters | the direction] in the render's compute type: the path kernel's `params`
+    bool keep_sums = false;               // the pixels' sums of both images also stay in `film` / `gfilm`, in double (drt_hip_render_tangent_double)
+};
+
 // One render call between its phases: launch (everything enqueued, gradients in ctx->grad[ctx->slot]) -> reduce (the
 // cross-device sum) -> collect (results on their way to the caller) -> finish (wait, hand over, statistics).
 // A plain context runs them back to back; a group context runs each phase on ALL members before the next,
@@ -28,6 +34,8 @@ struct RenderJob {
     float* out_gimg = nullptr;
     drt_hip_stats* stats = nullptr;
     int gimg_param = -1;
+    bool tangent = false;                 // drt_hip_render_tangent: out_gimg is the forward-mode derivative image
+    bool second_image() const { return gimg_param >= 0 || tangent; }   // a per-pixel image beside the radiance goes back to the caller
     bool backward = false, dev_out = false, timing = false, want_segments = false, sync = true;
     bool zero_copy = false;               // the image is written straight into the pinned block (synchronous host-buffer renders; drt_hip_render_async, one-stream form)
     bool direct_out = false, direct_gimg = false;   // ... or into the caller's own buffer, pinned with drt_hip_pin_host: nothing to hand over
@@ -119,6 +127,16 @@ struct drt_hip_ctx {
     unsigned long long* h_probe = nullptr;   // pinned: queue-length polls of deep-cap renders
     double* h_params = nullptr;              // pinned: the values of the last drt_hip_update_params, read by the launch that installs them
     size_t h_params_cap = 0;
+    // drt_hip_render_tangent: the caller's direction in pinned memory, and what the path kernel's forward-mode form takes as its
+    // `params` -- [the scene's parameters | the direction], n_params x 3 each, in the render's compute type
+    // (two pinned copies, alternating: the launch that reads one is behind the previous render in the stream, and a call that rewrote
+    //  the copy it read would have to wait for that whole render -- back-to-back device-pointer calls wait for the one before it instead)
+    double* h_tangent[2] = {nullptr, nullptr};
+    size_t h_tangent_cap[2] = {0, 0};
+    hipEvent_t ev_tangent[2] = {nullptr, nullptr};   // "the launch that read h_tangent[i] is done"
+    uint64_t tangent_calls = 0;
+    std::vector<float> tangent_rgb32;     // drt_hip_render_tangent_double: the float image its double one is gathered beside
+    DevBuf tangent;
     // pinned staging of everything a host-buffer render returns: [segments 8 B | grads | image | gradient
     // image] arrive by DMA in one go, then plain memcpys into the caller's (pageable) buffers -- a
     // pageable hipMemcpy of the 3 MB image alone cost 1 ms

@@ -132,7 +132,7 @@ void drt_hip_destroy(drt_hip_ctx* ctx)
         (void)hipEventDestroy(ctx->ev_done);
     DevBuf* bufs[] = {&ctx->hist_ovf[0], &ctx->hist_ovf[1], &ctx->mesh_ovf[0], &ctx->mesh_ovf[1], &ctx->fpart2, &ctx->gpart2, &ctx->counts2, &ctx->fpart, &ctx->gpix, &ctx->cand[0], &ctx->cand[1], &ctx->cand_a[0], &ctx->cand_a[1], &ctx->cand_b[0], &ctx->cand_b[1], &ctx->cand_count[0], &ctx->cand_count[1], &ctx->ray_a[0], &ctx->ray_a[1], &ctx->ray_a[2], &ctx->ray_b[0], &ctx->ray_b[1], &ctx->ray_b[2], &ctx->ray_id[0], &ctx->ray_id[1], &ctx->ray_id[2], &ctx->hit, &ctx->hit2, &ctx->hit3, &ctx->lacc, &ctx->gpath, &ctx->gfilm, &ctx->gimg_out, &ctx->tape, &ctx->nv,
                       &ctx->ch_cva, &ctx->ch_cvb, &ctx->ch_cvh, &ctx->ch_nxa, &ctx->ch_nxb, &ctx->ch_nxh, &ctx->ch_g,
-                      &ctx->ch_w, &ctx->ch_ids, &ctx->ch_ndraw, &ctx->ch_dbase, &ctx->counts, &ctx->film, &ctx->gpart, &ctx->adjoint};
+                      &ctx->ch_w, &ctx->ch_ids, &ctx->ch_ndraw, &ctx->ch_dbase, &ctx->counts, &ctx->film, &ctx->gpart, &ctx->adjoint, &ctx->tangent};
     for (DevBuf* b : bufs)
         release(*b);
     for (int i = 0; i < DRT_HIP_FRAMES_IN_FLIGHT; ++i) {
@@ -152,6 +152,10 @@ void drt_hip_destroy(drt_hip_ctx* ctx)
         (void)hipHostFree(ctx->h_probe);
     if (ctx->h_params)
         (void)hipHostFree(ctx->h_params);
+    for (int i = 0; i < 2; ++i) {
+        if (ctx->h_tangent[i]) (void)hipHostFree(ctx->h_tangent[i]);
+        if (ctx->ev_tangent[i]) (void)hipEventDestroy(ctx->ev_tangent[i]);
+    }
     for (const drt_hip_ctx::PinnedRange& r : ctx->pinned)
         (void)hipHostUnregister(r.host);
     for (int i = 0; i < DRT_HIP_FRAMES_IN_FLIGHT; ++i) {
@@ -245,6 +249,136 @@ int drt_hip_render_gradient_image(drt_hip_ctx* ctx, const drt_camera_desc* cam, 
     r.flags |= DRT_RENDER_BACKWARD;
     return render_common(ctx, cam, &r, adjoint_rgb, out_rgb, nullptr, stats, param, out_grad_rgb);
 }
+
+} // extern "C"
+
+// ---- forward mode: the derivative of the render along one direction of parameter space (Dual<T> of the reference, dual.hpp) ----
+// dst = [the scene's parameters | the direction] in compute type R; internal constants (a mirror's colour) have direction 0
+template <typename R>
+__global__ void __launch_bounds__(DRT_BLOCK) k_stage_tangent(const R* __restrict__ params, int n_all, const double* __restrict__ h_dir, int n_user,
+                                                             R* __restrict__ dst)
+{
+    for (int i = blockIdx.x * DRT_BLOCK + threadIdx.x; i < n_all; i += gridDim.x * DRT_BLOCK) {
+        dst[i] = params[i];
+        dst[n_all + i] = i < n_user ? (R)h_dir[i] : R(0);
+    }
+}
+
+static int render_tangent_common(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_params* rp, const double* param_tangent,
+                                 float* out_rgb, float* out_tangent_rgb, drt_hip_stats* stats, bool keep_sums)
+{
+    if (!ctx)
+        return DRT_ERR_INVALID;
+    if (!ctx->members.empty())
+        return fail(ctx, DRT_ERR_UNSUPPORTED, "render_tangent: not on a group context");
+    if (!ctx->has_scene)
+        return fail(ctx, DRT_ERR_NO_SCENE, "render before upload_scene");
+    if (!rp || !param_tangent)
+        return fail(ctx, DRT_ERR_INVALID, "render_tangent: NULL render parameters, tangent or output");
+    if (rp->flags & (DRT_RENDER_BACKWARD | DRT_RENDER_UNBIASED | DRT_RENDER_LOSS_L2 | DRT_RENDER_ALLREDUCE | DRT_RENDER_ALLREDUCE_ASYNC))
+        return fail(ctx, DRT_ERR_INVALID, "render_tangent: forward mode takes no reverse-mode flag (DRT_RENDER_BACKWARD, _UNBIASED, _LOSS_L2, _ALLREDUCE*)");
+    const int n_user = ctx->n_user_params * 3, n_all = ctx->n_params * 3;
+    for (int i = 0; i < n_user; ++i)
+        if (!std::isfinite(param_tangent[i]))
+            return fail(ctx, DRT_ERR_INVALID, "render_tangent: the tangent holds a value that is not finite");
+    for (int i = 0; i < DRT_HIP_FRAMES_IN_FLIGHT; ++i)
+        if (ctx->in_flight[i])
+            return fail(ctx, DRT_ERR_INVALID, "render: asynchronous frames are in flight -- drt_hip_wait for them first");
+    if (ctx->has_mesh)
+        return fail(ctx, DRT_ERR_UNSUPPORTED, "render_tangent: no tangent image of a scene that holds a triangle mesh");
+    if (rp->bounces_per_launch >= 1 || (rp->flags & DRT_RENDER_UNFUSED))
+        return fail(ctx, DRT_ERR_UNSUPPORTED, "render_tangent: the tangent image comes from the one-launch path kernel -- not with bounces_per_launch >= 1 "
+                                              "or DRT_RENDER_UNFUSED");
+    if (ctx->n_params > DRT_PATH_LDS_PARAMS)
+        return fail(ctx, DRT_ERR_UNSUPPORTED, "render_tangent: a tangent of more parameters than the path kernels stage (136)");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    // the direction -> pinned memory -> [parameters | direction] on the device, in stream order (the copy this call rewrites was read
+    // by the launch of the call before the previous one)
+    const int hb = (int)(ctx->tangent_calls++ & 1);
+    const size_t need = (size_t)(n_user ? n_user : 1);
+    if (!ctx->ev_tangent[hb])
+        HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_tangent[hb], hipEventDisableTiming));
+    else
+        HIPCHK(ctx, hipEventSynchronize(ctx->ev_tangent[hb]));
+    if (ctx->h_tangent_cap[hb] < need) {
+        if (ctx->h_tangent[hb])
+            (void)hipHostFree(ctx->h_tangent[hb]);
+        ctx->h_tangent[hb] = nullptr;
+        ctx->h_tangent_cap[hb] = 0;
+        HIPCHK(ctx, hipHostMalloc((void**)&ctx->h_tangent[hb], need * sizeof(double)));
+        ctx->h_tangent_cap[hb] = need;
+    }
+    memcpy(ctx->h_tangent[hb], param_tangent, (size_t)n_user * sizeof(double));
+    int rc;
+    if ((rc = ensure(ctx, ctx->tangent, (size_t)(n_all ? n_all : 1) * 2 * sizeof(double))) != DRT_OK) return rc;
+    if (n_all > 0) {
+        const unsigned blocks = (unsigned)((n_all + DRT_BLOCK - 1) / DRT_BLOCK);
+        if (rp->flags & DRT_RENDER_F64)
+            hipLaunchKernelGGL(k_stage_tangent<double>, dim3(blocks), dim3(DRT_BLOCK), 0, ctx->stream, (const double*)ctx->d_params_d, n_all,
+                               (const double*)ctx->h_tangent[hb], n_user, (double*)ctx->tangent.p);
+        else
+            hipLaunchKernelGGL(k_stage_tangent<float>, dim3(blocks), dim3(DRT_BLOCK), 0, ctx->stream, (const float*)ctx->d_params_f, n_all,
+                               (const double*)ctx->h_tangent[hb], n_user, (float*)ctx->tangent.p);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    HIPCHK(ctx, hipEventRecord(ctx->ev_tangent[hb], ctx->stream));
+    TangentRequest req;
+    req.d_params = ctx->tangent.p;
+    req.keep_sums = keep_sums;
+    return render_common(ctx, cam, rp, nullptr, out_rgb, nullptr, stats, -1, out_tangent_rgb, &req);
+}
+
+extern "C" {
+
+int drt_hip_render_tangent(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_params* rp, const double* param_tangent,
+                           float* out_rgb, float* out_tangent_rgb, drt_hip_stats* stats)
+{
+    if (ctx && !out_tangent_rgb)
+        return fail(ctx, DRT_ERR_INVALID, "render_tangent: NULL render parameters, tangent or output");
+    return render_tangent_common(ctx, cam, rp, param_tangent, out_rgb, out_tangent_rgb, stats, false);
+}
+
+int drt_hip_render_tangent_double(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_params* rp, const double* param_tangent,
+                                  double* out_rgb, double* out_tangent_rgb, drt_hip_stats* stats)
+{
+    if (!ctx)
+        return DRT_ERR_INVALID;
+    if (!out_tangent_rgb)
+        return fail(ctx, DRT_ERR_INVALID, "render_tangent: NULL render parameters, tangent or output");
+    if (rp && (rp->flags & DRT_RENDER_DEVICE_OUT))
+        return fail(ctx, DRT_ERR_INVALID, "render_tangent_double: host buffers only");
+    if (!cam || cam->width <= 0 || cam->height <= 0)
+        return fail(ctx, DRT_ERR_INVALID, "render: bad camera or render parameters");
+    // The render goes the way of a frame in several batches: both images' sums are gathered in `film` / `gfilm`, in double, and are
+    // fetched from there.  The float tangent image is resolved on the device and goes nowhere; the float image is what makes the
+    // pipeline keep radiance sums at all: it goes to a frame of the context's own.
+    float* rgb32 = nullptr;
+    if (out_rgb) {
+        ctx->tangent_rgb32.resize((size_t)cam->width * (size_t)cam->height * 3);
+        rgb32 = ctx->tangent_rgb32.data();
+    }
+    int rc = render_tangent_common(ctx, cam, rp, param_tangent, rgb32, nullptr, stats, true);
+    if (rc != DRT_OK)
+        return rc;
+    const RenderJob& j = ctx->job;
+    const size_t row = (size_t)cam->width * 3;
+    const double inv = 1.0 / (double)rp->spp;
+    std::vector<double> sums((size_t)j.n_local_pixels * 3);
+    auto fetch = [&](const DevBuf& src, double* dst) -> int {
+        if (!sums.empty())
+            HIPCHK(ctx, hipMemcpy(sums.data(), src.p, sums.size() * sizeof(double), hipMemcpyDeviceToHost));
+        size_t local = 0;                 // (the shard's rows in band order: how the kernels number its pixels)
+        for_each_band(cam->height, j.band, j.n_shards, j.shard, [&](int y0, int y1) {
+            for (size_t i = (size_t)y0 * row; i < (size_t)y1 * row; ++i)
+                dst[i] = sums[local++] * inv;
+        });
+        return DRT_OK;
+    };
+    if ((rc = fetch(ctx->gfilm, out_tangent_rgb)) != DRT_OK) return rc;
+    if (out_rgb && (rc = fetch(ctx->film, out_rgb)) != DRT_OK) return rc;
+    return DRT_OK;
+}
+
 
 // ---- asynchronous host-buffer renders ---------------------------------------------------------------
 // drt_hip_render returns when the results are in the caller's buffers: every frame pays a 3 MB device-to-host copy and a
@@ -583,11 +717,17 @@ extern "C" int drt_hip_debug_walk_times(unsigned long long* out, int n_waves)
 
 // hiprtc needs no device: the build container checks that the embedded headers still compile under it (tests/test_abi.py).
 // Returns the size of the code object, or a negative status with the compiler's output in `log`.
+// (user_header: caller-defined kinds as drt_hip_upload_scene writes them for hiprtc, NULL: none)
+extern "C" int drt_hip_debug_jit_compile_with(const char* arch, const char* name_expr, const char* user_header, double* ms, char* log, int log_cap);
 extern "C" int drt_hip_debug_jit_compile(const char* arch, const char* name_expr, double* ms, char* log, int log_cap)
+{
+    return drt_hip_debug_jit_compile_with(arch, name_expr, nullptr, ms, log, log_cap);
+}
+extern "C" int drt_hip_debug_jit_compile_with(const char* arch, const char* name_expr, const char* user_header, double* ms, char* log, int log_cap)
 {
     if (!arch || !name_expr)
         return DRT_ERR_INVALID;
-    const drt_jit::EntryPtr e = drt_jit::compile(arch, name_expr);
+    const drt_jit::EntryPtr e = drt_jit::compile(arch, name_expr, user_header ? user_header : "");
     const drt_jit::Code& c = e->code;
     if (ms)
         *ms = c.ms;

@@ -271,6 +271,16 @@ struct Tangents {
 #define DRT_F64_MIN_BLOCKS 4         // blocks per CU the f64 lockstep diffuse k_path is compiled for: 128 registers instead of 142-145, four waves per
                                      // SIMD instead of three (config 3 in f64: 1.938 -> 1.890 ms, an albedo per shape 2.19 -> 1.97; 3 and 5: no gain)
 #endif
+// ... the forward-mode forms (NP = DRT_NP_TANGENT)
+#ifndef DRT_TANGENT_MIN_BLOCKS
+#define DRT_TANGENT_MIN_BLOCKS 6
+#endif
+#ifndef DRT_TANGENT_REGEN_MIN_BLOCKS
+#define DRT_TANGENT_REGEN_MIN_BLOCKS 5
+#endif
+#ifndef DRT_TANGENT_F64_MIN_BLOCKS
+#define DRT_TANGENT_F64_MIN_BLOCKS 3
+#endif
 #ifndef DRT_GEN_TABLE
 #define DRT_GEN_TABLE 408            // elements of a wave's gradient table (rows x copies; 408 = 3 x DRT_PATH_LDS_PARAMS: one copy of every row at least)
 #endif
@@ -396,6 +406,64 @@ struct Tangents<R, DRT_NP_ANY, NC> {
     }
 };
 
+// ---- FORWARD mode: the derivative of the render along ONE direction of parameter space (NP = DRT_NP_TANGENT) -------------
+// d radiance / d eps at params + eps v, per pixel (the reference's Dual<T>, dual.hpp, run through the path tracer): the product
+// form above, contracted with v.  With T = prod_j c_{p_j} m_j,
+//     dT_ch / d eps = T_ch sum_j v_{p_j,ch} / c_{p_j,ch}
+// so a lane carries ONE running sum per channel, S_ch += v / c at every vertex its path goes on from -- for any number of
+// parameters, without counters, vertex history or gradient tables.  Zero channels as above: T leaves the zero factors out and
+// counts them (zc), and Z_ch sums v over the vertices whose channel is zero.  Where the path meets a light of emission e whose
+// own tangent is e' (both / p_k):
+//     zc_ch == 0:  T (e S + e')        zc_ch == 1:  T e Z   (the one zero factor's derivative is its v)        else 0
+// Per parameter, in LDS (staged once per block from [params | v], which is what the kernel's `params` points at in this form):
+// the colour with zero channels replaced by 1 + its zero-count increments, v / c (0 where the channel is zero), v where it is zero,
+// and v itself for the lights.  Row DRT_PATH_LDS_PARAMS is the rest row of a lane whose path does not go on: colour (1, 1, 1), zeros.
+#define DRT_NP_TANGENT (-2)
+template <typename R>
+struct DirLds {
+    R colnz[DRT_PATH_LDS_PARAMS + 1][4];   // colour, zero channels replaced by 1 | [3]: zero-count increments, 8 bits per channel (pid_pack)
+    R dlog[DRT_PATH_LDS_PARAMS + 1][4];    // v / c per channel, 0 where the channel is zero
+    R dzero[DRT_PATH_LDS_PARAMS + 1][4];   // v where the channel is zero, else 0
+    R dir[DRT_PATH_LDS_PARAMS * 3];        // v
+};
+
+template <typename R, typename SL>
+__device__ inline void stage_dir(DirLds<R>& dl, const SL& lds, const R* __restrict__ params)
+{
+    // (after stage_path_scene's barrier; ids beyond the scene's own read as (1, 1, 1) with a zero direction)
+    const int n = lds.sc.n_params < DRT_PATH_LDS_PARAMS ? lds.sc.n_params : DRT_PATH_LDS_PARAMS;
+    for (int p = threadIdx.x; p <= DRT_PATH_LDS_PARAMS; p += blockDim.x) {
+        const bool in = p < n;
+        uint32_t zinc = 0;
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            const R c = in ? lds.params[p * 3 + ch] : R(1);
+            const R v = in ? params[(lds.sc.n_params + p) * 3 + ch] : R(0);
+            const bool zero = abs_r(c) < R(1e-18);
+            dl.colnz[p][ch] = zero ? R(1) : c;
+            dl.dlog[p][ch] = zero ? R(0) : v / c;
+            dl.dzero[p][ch] = zero ? v : R(0);
+            zinc |= zero ? 1u << (8 * ch) : 0u;
+            if (p < DRT_PATH_LDS_PARAMS)
+                dl.dir[p * 3 + ch] = v;
+        }
+        dl.colnz[p][3] = pid_pack(R(0), zinc);
+        dl.dlog[p][3] = R(0);
+        dl.dzero[p][3] = R(0);
+    }
+    __syncthreads();
+}
+
+template <typename R, int NC>
+struct Tangents<R, DRT_NP_TANGENT, NC> {
+    uint32_t zc;                    // zero factors met per channel, 8 bits each
+    V3<R> S, Z;                     // sums of v / c and of v (zero channels) over the vertices of the current path
+    V3<R> dL;                       // d radiance / d eps of the current path
+    const DirLds<R>* dl;
+    R* acc;                         // (unused: the column form's sums)
+    __device__ inline void new_path() { zc = 0; S = Z = dL = mk<R>(R(0), R(0), R(0)); }
+};
+
 // what a block of a general-form kernel keeps in LDS, and the two ends of its life
 template <typename R>
 struct GenBlock {
@@ -481,9 +549,20 @@ __device__ inline void add_emission(const SL& lds, const TangentLds<R>& tl, cons
 {
     const V3<R> E = load_param<R, (NP != 0)>(lds, params, (int)eid) * inv_pk;
     V3<R> Tr = T;
-    if (NC > 0 || NP == DRT_NP_ANY)  // a channel that met a zero colour is dark
+    if (NC > 0 || NP == DRT_NP_ANY || NP == DRT_NP_TANGENT)  // a channel that met a zero colour is dark
         Tr = mk<R>((tg.zc & 0xFFu) ? R(0) : T.x, (tg.zc & 0xFF00u) ? R(0) : T.y, (tg.zc & 0xFF0000u) ? R(0) : T.z);
     L = L + Tr * E;
+    if constexpr (NP == DRT_NP_TANGENT) {
+        // forward mode: T (e S + e') where no factor of the channel is zero, T e Z where exactly one is
+        const R* vd = tg.dl->dir + (eid < DRT_PATH_LDS_PARAMS ? eid : 0u) * 3u;
+        const V3<R> Ed = mk<R>(vd[0], vd[1], vd[2]) * inv_pk;
+        const V3<R> d0 = mk<R>(fma_r(E.x, tg.S.x, Ed.x), fma_r(E.y, tg.S.y, Ed.y), fma_r(E.z, tg.S.z, Ed.z));
+        const V3<R> d1 = E * tg.Z;
+        const uint32_t zx = tg.zc & 0xFFu, zy = tg.zc & 0xFF00u, zz = tg.zc & 0xFF0000u;
+        tg.dL = mk<R>(fma_r(T.x, zx == 0u ? d0.x : (zx == 0x1u ? d1.x : R(0)), tg.dL.x),
+                      fma_r(T.y, zy == 0u ? d0.y : (zy == 0x100u ? d1.y : R(0)), tg.dL.y),
+                      fma_r(T.z, zz == 0u ? d0.z : (zz == 0x10000u ? d1.z : R(0)), tg.dL.z));
+    } else
     if constexpr (NP == DRT_NP_ANY) {
         // any number of parameters: the light's own row, then every vertex of the path's history adds to its colour's row
         if (LOSS)
@@ -645,8 +724,18 @@ __device__ inline void path_bounce(const PathArgs& a, const PathSceneLds<R>& lds
     // gradients it leaves zero colour channels out and counts them, and counts the bounce for its colour (see Tangents)
     // (REST, the lockstep kernel's colour-column form: a lane that does not go on reads the table's row of ones and zero increments)
     constexpr bool REST = FREEZE_BY_ROW && NC > 0 && NP != DRT_NP_ANY;
-    const int cidx = REST ? (alive ? (int)cid : DRT_TANGENT_REST) : (has_bxdf ? (int)cid : 0);
+    // (DIR, forward mode: the same by its own table's rest row, in every form)
+    constexpr bool DIR = NP == DRT_NP_TANGENT, BY_ROW = REST || DIR;
+    const int cidx = DIR ? (alive ? (int)cid : DRT_PATH_LDS_PARAMS) : (REST ? (alive ? (int)cid : DRT_TANGENT_REST) : (has_bxdf ? (int)cid : 0));
     V3<R> col;
+    if constexpr (DIR) {
+        const int row = cidx < DRT_PATH_LDS_PARAMS ? cidx : DRT_PATH_LDS_PARAMS;
+        const R *rec = tg.dl->colnz[row], *ds = tg.dl->dlog[row], *dz = tg.dl->dzero[row];
+        col = mk<R>(rec[0], rec[1], rec[2]);
+        tg.zc += pid_unpack(rec[3]);
+        tg.S = mk<R>(tg.S.x + ds[0], tg.S.y + ds[1], tg.S.z + ds[2]);
+        tg.Z = mk<R>(tg.Z.x + dz[0], tg.Z.y + dz[1], tg.Z.z + dz[2]);
+    } else
     if constexpr (NP == DRT_NP_ANY) {
         const R* rec = tg.gl->colnz[cidx < DRT_PATH_LDS_PARAMS ? cidx : 0];
         col = mk<R>(rec[0], rec[1], rec[2]);
@@ -657,8 +746,8 @@ __device__ inline void path_bounce(const PathArgs& a, const PathSceneLds<R>& lds
             tg.template push<true>(live, alive ? cid : 0xFFu);
     } else
         col = NC > 0 ? mk<R>(tl.colnz[cidx][0], tl.colnz[cidx][1], tl.colnz[cidx][2]) : load_param<R, (NP > 0)>(lds, params, cidx);
-    const V3<R> cmv = col * (REST ? (alive ? mk_ : R(1)) : mk_);
-    const V3<R> cm = REST ? cmv : mk<R>(alive ? cmv.x : R(1), alive ? cmv.y : R(1), alive ? cmv.z : R(1));
+    const V3<R> cmv = col * (BY_ROW ? (alive ? mk_ : R(1)) : mk_);
+    const V3<R> cm = BY_ROW ? cmv : mk<R>(alive ? cmv.x : R(1), alive ? cmv.y : R(1), alive ? cmv.z : R(1));
     if constexpr (REST) {
         tg.cnt[0] += tl.inc[cidx][0];
         if (NC > 4)
@@ -753,6 +842,8 @@ __device__ inline uint32_t path_camera(const PathArgs& a, const CameraLane<R>& c
 template <size_t RB, bool SPEC, int NP, int NSG, bool REGEN>
 constexpr int path_min_blocks()
 {
+    if (NP == DRT_NP_TANGENT)      // forward mode: the forward-only kernel + ten values per lane (S, Z, dL, zc) and 8 / 16 KB of LDS (f32 / f64)
+        return RB == 4 ? (REGEN ? DRT_TANGENT_REGEN_MIN_BLOCKS : DRT_TANGENT_MIN_BLOCKS) : ((REGEN || SPEC) ? 2 : DRT_TANGENT_F64_MIN_BLOCKS);
     if (RB == 4 && NP <= 4) {
         if (!REGEN)
             return SPEC ? ((NP == DRT_NP_ANY || NSG > DRT_LEAN_MAX_SHAPES) ? 5 : DRT_LOCKSTEP_SPEC_MIN_BLOCKS)
@@ -794,6 +885,8 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
     constexpr bool GEN = NP == DRT_NP_ANY;                // any number of parameters: history + per-wave tables (see Tangents<R, DRT_NP_ANY>)
     __shared__ typename PickT<GEN, GenBlock<R>, NoLds>::T s_gen;
     extern __shared__ uint32_t s_hist[];                  // GEN: [a.hist_lds][DRT_BLOCK] history words
+    constexpr bool DIR = NP == DRT_NP_TANGENT;            // forward mode: the derivative along one direction (see DirLds); `params` = [params | direction]
+    __shared__ typename PickT<DIR, DirLds<R>, NoLds>::T s_dir;
     if constexpr (GEN)
         gen_zero(s_gen);
     stage_path_scene(lds, sc, params);
@@ -814,12 +907,17 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
     tg.acc = &s_acc[0][threadIdx.x];
     if constexpr (GEN)
         gen_begin(s_gen, lds, sc, a, s_hist, reinterpret_cast<uint32_t*>(a.hist_ovf), tg);
-    else {
+    else if constexpr (DIR) {
+        stage_dir(s_dir, lds, params);
+        tg.dl = &s_dir;
+        tg.new_path();
+    } else {
 #pragma unroll
         for (int p = 0; p < NP; ++p)
             tg.acc_set(p, mk<R>(R(0), R(0), R(0)));
     }
     double fx = 0, fy = 0, fz = 0;                        // radiance sum of this lane's pixel over the range
+    double tx = 0, ty = 0, tz = 0;                        // DIR: ... and the sum of its samples' derivatives
     uint32_t n_seg = 0, n_capped = 0;                     // wave-uniform counters
 
     uint32_t gpix = 0, px = 0, py = 0;
@@ -867,7 +965,7 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
         V3<R> T = mk<R>(R(1), R(1), R(1)), L = mk<R>(R(0), R(0), R(0));
         uint32_t end_ids = DRT_ID_NONE;                   // emission parameter of the light the path ended on
         R end_inv_pk = R(1);
-        if (NC > 0 || GEN)
+        if (NC > 0 || GEN || DIR)
             tg.new_path();
         for (int kk = 0; kk < a.depth_cap; ++kk) {
             const uint32_t n_live = (uint32_t)__popcll(wave_ballot(live));
@@ -898,6 +996,9 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
                 add_emission<R, NP, NC, LOSS, PathSceneLds<R>, ROLES>(lds, tl, params, end_ids, end_inv_pk, T, g, L, tg);
         }
         fx += (double)L.x; fy += (double)L.y; fz += (double)L.z;
+        if constexpr (DIR) {
+            tx += (double)tg.dL.x; ty += (double)tg.dL.y; tz += (double)tg.dL.z;
+        }
     }
     }
     // ---- REGEN: a wave owns 64 pixels x its sample range, and its LANES are not bound to pixels: a lane whose path has ended
@@ -912,6 +1013,10 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
     __shared__ uint32_t s_pgpix[REGEN ? DRT_BLOCK : 1];
     __shared__ double s_film[REGEN ? 3 : 1][REGEN ? DRT_BLOCK : 1];
     __shared__ uint32_t s_ih[REGEN ? DRT_DRAW_TABLE : 1];      // h(n) of every draw index a path of <= DRT_MAX_DEPTH vertices can reach
+    __shared__ double s_tfilm[REGEN && DIR ? 3 : 1][REGEN && DIR ? DRT_BLOCK : 1];   // DIR: the pixels' derivative sums, like s_film
+    if constexpr (REGEN && DIR) {
+        s_tfilm[0][threadIdx.x] = 0.0; s_tfilm[1][threadIdx.x] = 0.0; s_tfilm[2][threadIdx.x] = 0.0;
+    }
     if (REGEN) {
         for (uint32_t n = threadIdx.x; n < DRT_DRAW_TABLE; n += DRT_BLOCK)
             s_ih[REGEN ? n : 0] = drt_rng_index_hash(a.rng_stream, n);
@@ -933,7 +1038,7 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
         ra.x = ra.y = ra.z = ra.w = R(0);
         rb.x = rb.y = R(0);
         V3<R> T = mk<R>(R(1), R(1), R(1)), L = mk<R>(R(0), R(0), R(0));
-        if (NC > 0 || GEN)
+        if (NC > 0 || GEN || DIR)
             tg.new_path();
         const int first_rr = a.min_bounces > 1 ? a.min_bounces : 1;
         for (;;) {
@@ -956,7 +1061,7 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
                         live = a.depth_cap > 0 && !(a.min_bounces <= 0 && rng_draw(a.rng_stream, key, 2) < a.rr_threshold);
                         T = mk<R>(R(1), R(1), R(1));
                         L = mk<R>(R(0), R(0), R(0));
-                        if (NC > 0 || GEN)
+                        if (NC > 0 || GEN || DIR)
                             tg.new_path();
                     }
                 }
@@ -1000,6 +1105,13 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
                         atomicAdd(&s_film[REGEN ? 1 : 0][pix], (double)L.y);
                         atomicAdd(&s_film[REGEN ? 2 : 0][pix], (double)L.z);
                     }
+                    if constexpr (REGEN && DIR) {
+                        if (tg.dL.x != R(0) || tg.dL.y != R(0) || tg.dL.z != R(0)) {
+                            atomicAdd(&s_tfilm[0][pix], (double)tg.dL.x);
+                            atomicAdd(&s_tfilm[1][pix], (double)tg.dL.y);
+                            atomicAdd(&s_tfilm[2][pix], (double)tg.dL.z);
+                        }
+                    }
                 }
             }
             live = alive;
@@ -1009,6 +1121,9 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
     if (REGEN) {
         __syncthreads();                                  // (every wave's adds have landed)
         fx = s_film[0][threadIdx.x]; fy = s_film[REGEN ? 1 : 0][threadIdx.x]; fz = s_film[REGEN ? 2 : 0][threadIdx.x];
+        if constexpr (REGEN && DIR) {
+            tx = s_tfilm[0][threadIdx.x]; ty = s_tfilm[1][threadIdx.x]; tz = s_tfilm[2][threadIdx.x];
+        }
     }
 
     if (range < a.n_ranges) {
@@ -1020,6 +1135,11 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
             // gradient image, general form: the lane's own adds to the row of the image's parameter
             double* f = gimg_part + ((size_t)range * 3) * a.Pb + lp;
             f[0] = (double)tg.gsum.x; f[(size_t)a.Pb] = (double)tg.gsum.y; f[(size_t)a.Pb * 2] = (double)tg.gsum.z;
+        }
+        if constexpr (DIR) if (gimg_part && have) {
+            // forward mode: the pixel's derivative sums leave where a gradient image's do -- same layout, same finishing kernels
+            double* f = gimg_part + ((size_t)range * 3) * a.Pb + lp;
+            f[0] = tx; f[(size_t)a.Pb] = ty; f[(size_t)a.Pb * 2] = tz;
         }
         if constexpr (NP > 0) if (gimg_part && have) {
             // gradient image (README.md:142-145): a lane IS a pixel, its gradient sum of one parameter over the samples of

@@ -33,7 +33,7 @@ static uint8_t* pinned_alias(const drt_hip_ctx* ctx, const void* p, size_t bytes
 // phase 1: validate, set up, enqueue the whole pipeline; the gradient of THIS context's shard ends up in ctx->grad[ctx->slot]
 static int render_launch(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_params* rp,
                          const float* adjoint_rgb, float* out_rgb, double* out_param_grad, drt_hip_stats* stats,
-                         int gimg_param, float* out_gimg)
+                         int gimg_param, float* out_gimg, const TangentRequest* tangent = nullptr)
 {
     if (!ctx->has_scene)
         return fail(ctx, DRT_ERR_NO_SCENE, "render before upload_scene");
@@ -61,6 +61,7 @@ static int render_launch(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt
     j.adjoint_rgb = adjoint_rgb; j.out_rgb = out_rgb; j.out_param_grad = out_param_grad; j.out_gimg = out_gimg;
     j.stats = stats;
     j.gimg_param = gimg_param;
+    j.tangent = tangent != nullptr;
     j.n_shards = n_shards; j.shard = n_shards > 1 ? rp->shard : 0; j.band = band;
     j.backward = (rp->flags & DRT_RENDER_BACKWARD) != 0;
     j.dev_out = (rp->flags & DRT_RENDER_DEVICE_OUT) != 0;
@@ -142,7 +143,7 @@ static int render_launch(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt
             }
         }
     }
-    if (gimg_param >= 0) {
+    if (j.second_image()) {
         const size_t fb = (size_t)(j.n_local_pixels ? j.n_local_pixels : 1) * 3 * sizeof(double);
         if ((rc = ensure(ctx, ctx->gfilm, fb)) != DRT_OK) return rc;
         HIPCHK(ctx, hipMemsetAsync(ctx->gfilm.p, 0, fb, ctx->stream));
@@ -164,10 +165,10 @@ static int render_launch(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt
     if (j.n_local_pixels > 0) {
         if (f64)
             rc = render_impl<double>(ctx, cam, rp, d_adj, j.d_out, j.backward, j.timing, &j.st, j.n_local_pixels,
-                                     depth_cap, &j.n_count_words, d_film, gimg_param, (double*)ctx->gfilm.p, j.d_gimg);
+                                     depth_cap, &j.n_count_words, d_film, gimg_param, (double*)ctx->gfilm.p, j.d_gimg, tangent);
         else
             rc = render_impl<float>(ctx, cam, rp, d_adj, j.d_out, j.backward, j.timing, &j.st, j.n_local_pixels,
-                                    depth_cap, &j.n_count_words, d_film, gimg_param, (double*)ctx->gfilm.p, j.d_gimg);
+                                    depth_cap, &j.n_count_words, d_film, gimg_param, (double*)ctx->gfilm.p, j.d_gimg, tangent);
     }
     if (ctx->adj_pending) {          // (no kernel wanted it: a shard without rows)
         ctx->adj_pending = false;
@@ -359,7 +360,7 @@ static int render_collect(drt_hip_ctx* ctx, bool with_grad = true, hipStream_t c
         //  renders, the one-stream asynchronous form -- or into the caller's own pinned buffer)
         if (j.out_rgb && j.n_local_pixels && !j.zero_copy && !j.direct_out)
             rows_to_stage(j.d_out, j.off_img);
-        if (j.gimg_param >= 0 && j.out_gimg && j.n_local_pixels && !j.direct_gimg)
+        if (j.second_image() && j.out_gimg && j.n_local_pixels && !j.direct_gimg)
             rows_to_stage(j.d_gimg, j.off_gimg);
         HIPCHK(ctx, e);
         // gradients, totals and the completion word: ONE small launch behind everything else of the frame
@@ -430,7 +431,7 @@ static int render_finish(drt_hip_ctx* ctx, bool with_grad = true, hipEvent_t don
         };
         if (j.out_rgb && j.n_local_pixels && !j.direct_out)
             rows_to_caller(j.out_rgb, j.off_img);
-        if (j.gimg_param >= 0 && j.out_gimg && j.n_local_pixels && !j.direct_gimg)
+        if (j.second_image() && j.out_gimg && j.n_local_pixels && !j.direct_gimg)
             rows_to_caller(j.out_gimg, j.off_gimg);
         if (j.backward && j.out_param_grad && with_grad) {
             memcpy(j.out_param_grad, ctx->h_stage[ctx->slot] + j.off_grad, j.grad_bytes);
@@ -579,7 +580,7 @@ static int render_group(drt_hip_ctx* g, const drt_camera_desc* cam, const drt_re
 
 static int render_common(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_params* rp,
                          const float* adjoint_rgb, float* out_rgb, double* out_param_grad, drt_hip_stats* stats,
-                         int gimg_param, float* out_gimg)
+                         int gimg_param, float* out_gimg, const TangentRequest* tangent = nullptr)
 {
     if (!ctx)
         return DRT_ERR_INVALID;
@@ -596,7 +597,7 @@ static int render_common(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt
                           (rp->flags & DRT_RENDER_DEVICE_OUT) && ctx->comm;
     // Device-pointer renders that do not wait (no DRT_RENDER_SYNC, no statistics): consecutive frames alternate between the
     // context's two sets of per-frame buffers, so that their k_path grids can overlap (render_impl: path_stream)
-    const bool dev_async = rp && gimg_param < 0 && (rp->flags & DRT_RENDER_DEVICE_OUT) &&
+    const bool dev_async = rp && gimg_param < 0 && !tangent && (rp->flags & DRT_RENDER_DEVICE_OUT) &&
                            !(rp->flags & (DRT_RENDER_SYNC | DRT_RENDER_TIMING)) && !stats;
     if (ar_async || dev_async) {
         HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -608,7 +609,7 @@ static int render_common(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt
     ctx->overlap_next = (ar_async || dev_async) && !(rp->flags & DRT_RENDER_SERIAL);
     // (host buffers: the finishing kernels store the image into the context's pinned block -- no copy launch behind them)
     ctx->zero_copy_next = rp && !(rp->flags & DRT_RENDER_DEVICE_OUT) && tuning().sync_zero_copy;
-    rc = render_launch(ctx, cam, rp, adjoint_rgb, out_rgb, out_param_grad, stats, gimg_param, out_gimg);
+    rc = render_launch(ctx, cam, rp, adjoint_rgb, out_rgb, out_param_grad, stats, gimg_param, out_gimg, tangent);
     ctx->overlap_next = false;
     ctx->zero_copy_next = false;
     if (rc != DRT_OK) {

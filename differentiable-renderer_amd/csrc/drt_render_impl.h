@@ -151,13 +151,14 @@ inline int np_width(int n_params, int general)
 }
 
 // ---- which instantiation of the one-launch path kernels a render runs (shard_plan decides it, path_batch launches it) ----
-enum class PathOp { biased, unbiased, mesh };    // k_path (the gradient image included), k_path_unbiased, k_path_mesh
+enum class PathOp { biased, unbiased, mesh, tangent };   // k_path (the gradient image included), k_path_unbiased, k_path_mesh, k_path's forward-mode form
 enum class PathProg { cornell, sorted, scene };  // closest-hit program: the reference's kinds compiled in (SigCornell), kinds read at
                                                  // run time (SigNone), or compiled by hiprtc for the scene's own KindSig (drt_jit.h)
 struct PathForm {
     PathOp op;
     bool f64, spec;
-    int np, nc;                     // gradient parameters / colour columns: 0, 0 without tangents; DRT_NP_ANY the general form
+    int np, nc;                     // gradient parameters / colour columns: 0, 0 without tangents; DRT_NP_ANY the general form;
+                                    // DRT_NP_TANGENT, 0: forward mode (PathOp::tangent)
                                     // (nc = 1: + the lanes' own sums of one row, the gradient image)
     bool regen;                     // the regenerating form (k_path_mesh: always; k_path_unbiased: never)
     bool loss;                      // DRT_RENDER_LOSS_L2's instantiation: made at run time only
@@ -185,6 +186,9 @@ struct Shard {
     int gimg_param;
     double* gfilm;
     float* d_out_gimg;
+    bool fwd_tangent;               // drt_hip_render_tangent: d_params holds [parameters | direction], d_out_gimg gets the derivative image
+    bool keep_sums;                 // ... and both images' sums go through `film` / `gfilm` (double), where the caller reads them
+    bool pixel_sums() const { return gimg_param >= 0 || fwd_tangent; }   // the lanes' per-pixel sums leave the path kernel (gimg_part)
     // the scene in compute type R
     const DevScene<R>* d_scene;
     const R* d_params;
@@ -313,6 +317,10 @@ const void* library_path_kernel(const PathForm& f)
         }
         return nullptr;
     }
+    if (f.op == PathOp::tangent)   // forward mode: both forms, every program
+        return spec_sig([&f](auto spec, auto sg) {
+            return with_bool(f.regen, [](auto regen) { return (const void*)k_path<R, decltype(spec)::value, DRT_NP_TANGENT, 0, decltype(sg), regen>; });
+        });
     if (f.op == PathOp::mesh)      // (the kind-sorted program; every lane on its own)
         return columns([&f](auto np, auto nc) {
             return with_bool(f.spec, [](auto spec) { return (const void*)k_path_mesh<R, spec, decltype(np)::value, decltype(nc)::value>; });
@@ -397,9 +405,9 @@ void shard_plan(Shard<R>& s)
     const bool gen = tangents && ctx->n_params <= DRT_PATH_LDS_PARAMS &&
                      (s.gimg_param >= 0 ? ctx->n_params > DRT_FAST_PARAMS && !s.mesh_path       // (the image keeps the column form where it exists)
                                         : ctx->n_params > tuning().gen_above && (tuning().path_general || ctx->n_params <= DRT_FAST_PARAMS));
-    f.op = s.unbiased ? PathOp::unbiased : (s.mesh_path ? PathOp::mesh : PathOp::biased);
+    f.op = s.unbiased ? PathOp::unbiased : (s.mesh_path ? PathOp::mesh : (s.fwd_tangent ? PathOp::tangent : PathOp::biased));
     f.f64 = sizeof(R) == 8; f.spec = ctx->has_specular;
-    f.np = !tangents ? 0 : (gen ? DRT_NP_ANY : np_width(ctx->n_params, DRT_NP_ANY));
+    f.np = s.fwd_tangent ? DRT_NP_TANGENT : !tangents ? 0 : (gen ? DRT_NP_ANY : np_width(ctx->n_params, DRT_NP_ANY));
     f.nc = !tangents ? 0 : gen ? (s.gimg_param >= 0 ? 1 : 0)
                              : (f.np == 8 ? 8 : (ctx->max_colour_param < 3 ? 3 : 4));   // (tangent state only for parameters that ARE some BxDF's colour)
     f.loss = s.loss_l2;
@@ -500,7 +508,7 @@ void shard_plan(Shard<R>& s)
     const int tail_bounces = tail_bounces_now();
     s.tail_nb = s.shade_tail && (tail_bounces > 1 || (tail_bounces == 0 && s.unbiased)) ? 2 : 1;
     s.tail_ring = s.tail_nb > 1 ? 3 : 2;
-    s.overlap_ok = ctx->overlap_next && s.use_path && !s.timing && s.gimg_param < 0 && ctx->path_stream[0] && ctx->ev_copied[0];
+    s.overlap_ok = ctx->overlap_next && s.use_path && !s.timing && !s.pixel_sums() && ctx->path_stream[0] && ctx->ev_copied[0];
     const bool odd = s.overlap_ok && (ctx->slot & 1);
     s.fpart_buf = odd ? &ctx->fpart2 : &ctx->fpart;
     s.gpart_buf = odd ? &ctx->gpart2 : &ctx->gpart;
@@ -509,7 +517,7 @@ void shard_plan(Shard<R>& s)
                       : (size_t)(D + 2) * s.max_regions;          // counts[depth][region] of one batch (row D: capped paths, D + 1: rays kept in registers)
     // a k_path launch that covers the whole frame is followed by ONE finishing launch that WRITES image, gradients and
     // totals (k_path_finish); every other route accumulates into zeroed buffers
-    s.path_finish = s.use_path && s.Pb == s.n_local_pixels && s.Sb == (uint32_t)s.spp && (!s.film || s.d_out_rgb);
+    s.path_finish = s.use_path && s.Pb == s.n_local_pixels && s.Sb == (uint32_t)s.spp && (!s.film || s.d_out_rgb) && !s.keep_sums;
     if (s.path_gen) {
         // a wave's table holds DRT_GEN_TABLE elements: as many copies of every row as fit, at most 16 (same-address LDS atomics
         // of one instruction serialise; with 16 copies the ~12 lanes of a wave that end a sample on a light rarely meet)
@@ -539,7 +547,7 @@ int shard_buffers(Shard<R>& s)
     memset(&s.cs, 0, sizeof s.cs);
     if (s.use_path) {
         if ((rc = ensure(ctx, *s.fpart_buf, (size_t)s.path_ranges * 3 * s.Pb * sizeof(double))) != DRT_OK) return rc;
-        if (s.gimg_param >= 0)
+        if (s.pixel_sums())
             if ((rc = ensure(ctx, ctx->gpix, (size_t)s.path_ranges * 3 * s.Pb * sizeof(double))) != DRT_OK) return rc;
         if (s.mesh_path) {   // the traversal stack's entries beyond the ones in LDS, per thread of the grid (one area per k_path stream)
             const size_t threads = ((s.path_waves + DRT_BLOCK / DRT_WAVE - 1) / (DRT_BLOCK / DRT_WAVE)) * DRT_BLOCK;
@@ -717,7 +725,7 @@ int path_batch(Shard<R>& s)
     double* gpart = s.gpart;
     uint32_t* counts = s.counts;
     double* fpart = s.film ? (double*)s.fpart_buf->p : (double*)nullptr;
-    double* gpix = s.gimg_param >= 0 ? (double*)ctx->gpix.p : (double*)nullptr;   // gradient image partials
+    double* gpix = s.pixel_sums() ? (double*)ctx->gpix.p : (double*)nullptr;   // gradient image / derivative image partials
     unsigned long long* ptotal = s.path_finish ? s.totals : (unsigned long long*)nullptr;
     // (frames that overlap: this frame's grid goes to the lane's own stream, behind whoever still uses the lane's buffers, and
     //  the finishing launch on the context's stream waits for it.  Scene uploads block until they are done; a parameter update
@@ -1112,7 +1120,8 @@ template <typename R>
 int render_impl(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_params* rp,
                 const float* d_adjoint, float* d_out_rgb, bool backward, bool timing,
                 drt_hip_stats* st, uint32_t n_local_pixels, int depth_cap, size_t* n_count_words,
-                double* film, int gimg_param = -1, double* gfilm = nullptr, float* d_out_gimg = nullptr)
+                double* film, int gimg_param = -1, double* gfilm = nullptr, float* d_out_gimg = nullptr,
+                const TangentRequest* tangent = nullptr)
 {
     Shard<R> s;
     s.ctx = ctx; s.cam = cam; s.rp = rp; s.d_adjoint = d_adjoint; s.d_out_rgb = d_out_rgb; s.backward = backward; s.timing = timing;
@@ -1121,7 +1130,17 @@ int render_impl(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_p
     s.d_scene = sizeof(R) == 4 ? (const DevScene<R>*)ctx->d_scene_f : (const DevScene<R>*)ctx->d_scene_d;
     s.d_params = sizeof(R) == 4 ? (const R*)ctx->d_params_f : (const R*)ctx->d_params_d;
     memcpy(&s.bvh, sizeof(R) == 4 ? (const void*)&ctx->bvh_f : (const void*)&ctx->bvh_d, sizeof s.bvh);
+    s.fwd_tangent = tangent != nullptr;
+    s.keep_sums = tangent && tangent->keep_sums;
+    if (s.fwd_tangent)
+        s.d_params = (const R*)tangent->d_params;
     shard_plan(s);
+    if (s.fwd_tangent && s.D > 0 && (!s.use_path || s.mesh_path))
+        return fail(ctx, DRT_ERR_UNSUPPORTED, s.mesh_path || ctx->has_mesh
+                        ? "render_tangent: no tangent image of a scene that holds a triangle mesh"
+                        : "render_tangent: the tangent image comes from the one-launch path kernel, which this render does not take "
+                          "(bounces_per_launch >= 1, DRT_RENDER_UNFUSED, a DRT_HIP_* setting that forces the queue wavefront, or a scene its "
+                          "intersection program does not cover)");
     if (!ctx->user_header.empty()) {
         // caller-defined shape kinds live in the one-launch path kernel hiprtc compiles for the scene, nowhere else
         if (ctx->jit_mode <= 0)
@@ -1183,7 +1202,7 @@ int render_impl(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_p
     st->paths = s.total_paths;
     if (film && d_out_rgb && !s.path_finished)
         hipLaunchKernelGGL(k_resolve, dim3(grid_for(ctx, n_local_pixels)), dim3(DRT_BLOCK), 0, ctx->stream, a, n_local_pixels, film, d_out_rgb);
-    if (gimg_param >= 0 && gfilm && d_out_gimg && !s.path_finished)
+    if (s.pixel_sums() && gfilm && d_out_gimg && !s.path_finished)
         hipLaunchKernelGGL(k_resolve, dim3(grid_for(ctx, n_local_pixels)), dim3(DRT_BLOCK), 0, ctx->stream, a, n_local_pixels, gfilm, d_out_gimg);
     {   // this render's lane of partial-sum buffers is free once the context's stream has come this far
         const int lane = s.overlap_ok ? (ctx->slot & 1) : 0;

@@ -58,6 +58,7 @@ inline std::ostream& operator<<(std::ostream& os, const Dual<T>& n)
 }
 
 template <typename T> inline T real(const Dual<T>& n) { return n.real(); }
+template <typename T> inline T dual_part(const Dual<T>& n) { return n.dual(); }
 
 template <typename T>
 inline Dual<T> sqrt(const Dual<T>& n)

@@ -11,6 +11,13 @@
 // (drt_hip_create_group): the library deals the row bands to the devices, runs them side by side and
 // sums the gradient vector across them with a single RCCL all-reduce; this header adds nothing.
 //
+//   drt::hip::render_tangent(scene, cam, tracer, spp, {{param, direction}, ...}, img, tangent_img [, options])
+//   drt::hip::render(scene of Dual<U>, ...)
+//
+// forward mode (drt_hip_render_tangent): the image and its derivative along one direction of parameter space -- given as
+// (handle, direction) pairs, or as the dual parts of a Scene<Dual<U>>'s parameters, the reference's own validation run
+// (dual.hpp) on the device.
+//
 // No CPU fallback: if libdrt_hip.so cannot create a context this throws std::runtime_error.
 #pragma once
 
@@ -21,10 +28,12 @@
 #include <mutex>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../drt_hip.h"
 #include "camera.hpp"
+#include "dual.hpp"
 #include "mesh.hpp"
 #include "pathtracer.hpp"
 
@@ -679,6 +688,149 @@ inline Stats render_gradient_image(const Scene<T>& scene, const Camera<T>& cam, 
     out.segments = st.segments;
     out.ms = st.ms_total;
     return out;
+}
+
+// ---- forward mode ----------------------------------------------------------------------------------------------
+namespace detail {
+// one drt_hip_render_tangent of a flattened scene along `v` (n_params x 3): both images in double (opt.f64: the device's own
+// sums, drt_hip_render_tangent_double; else its float images).  Single device.
+template <typename T>
+inline Stats tangent_call(const char* who, const FlatScene<T>& flat, const drt_camera_desc& cd, double absorb, std::size_t min_bounces,
+                          std::size_t spp, const std::vector<double>& v, std::vector<double>& img, std::vector<double>& timg,
+                          const Options& opt)
+{
+    if (opt.backward || opt.unbiased || opt.sample_loss_l2)
+        throw std::runtime_error(std::string(who) + ": forward mode takes no reverse-mode option (backward, unbiased, sample_loss_l2)");
+    const std::size_t n = (std::size_t)cd.width * (std::size_t)cd.height * 3;
+    img.assign(n, 0.0);
+    timg.assign(n, 0.0);
+    std::unique_ptr<Context> own;
+    if (!opt.reuse_context)
+        own.reset(new Context(opt.devices.empty() ? 0 : opt.devices[0]));
+    Context& ctx = own ? *own : pooled_context(opt.devices.empty() ? 0 : opt.devices[0]);
+    std::lock_guard<std::mutex> lock(ctx.mutex());
+    ctx.set_scene(flat);
+    drt_render_params rp{};
+    rp.spp = (int32_t)spp;
+    rp.min_bounces = (int32_t)min_bounces;
+    rp.absorb = absorb;
+    rp.max_depth = opt.max_depth;
+    rp.seed = opt.seed;
+    rp.flags = opt.f64 ? DRT_RENDER_F64 : 0u;
+    rp.batch_paths = opt.batch_paths;
+    rp.bounces_per_launch = opt.bounces_per_launch;
+    drt_hip_stats st{};
+    if (opt.f64)
+        ctx.check(drt_hip_render_tangent_double(ctx.get(), &cd, &rp, v.data(), img.data(), timg.data(), &st), "drt_hip_render_tangent_double");
+    else {
+        std::vector<float> rgb(n, 0.f), trgb(n, 0.f);
+        ctx.check(drt_hip_render_tangent(ctx.get(), &cd, &rp, v.data(), rgb.data(), trgb.data(), &st), "drt_hip_render_tangent");
+        for (std::size_t i = 0; i < n; ++i) {
+            img[i] = rgb[i];
+            timg[i] = trgb[i];
+        }
+    }
+    Stats out;
+    out.paths = st.paths;
+    out.segments = st.segments;
+    out.capped_paths = st.capped_paths;
+    out.ms = st.ms_total;
+    return out;
+}
+} // namespace detail
+
+// J v: tangent_img[pixel] = mean over the pixel's samples of d radiance / d eps at params + eps * direction, `tangents` pairing
+// parameter handles with their directions (handles not listed: direction 0; a listed handle the scene does not use throws, as
+// render_gradient_image does; one listed twice adds up).  img may be nullptr.
+template <typename T>
+inline Stats render_tangent(const Scene<T>& scene, const Camera<T>& cam, const Pathtracer<T>& tracer, std::size_t spp,
+                            const std::vector<std::pair<Vector<T, 3, true>, Vector<T, 3>>>& tangents, Vector<T, 3>* img,
+                            Vector<T, 3>* tangent_img, const Options& opt = Options())
+{
+    FlatScene<T> flat = flatten(scene);
+    std::vector<double> v(flat.handles.size() * 3, 0.0);
+    for (const auto& t : tangents) {
+        int index = -1;
+        for (std::size_t p = 0; p < flat.handles.size(); ++p)
+            if (flat.handles[p].id() == t.first.id())
+                index = (int)p;
+        if (index < 0)
+            throw std::runtime_error("drt::hip::render_tangent: a listed parameter is not used by the scene");
+        for (int c = 0; c < 3; ++c)
+            v[(std::size_t)index * 3 + c] += double(real(t.second[c]));
+    }
+    std::vector<double> rgb, trgb;
+    const Stats st = detail::tangent_call("drt::hip::render_tangent", flat, describe(cam), tracer.absorb(), tracer.min_bounces(), spp, v, rgb, trgb, opt);
+    const std::size_t npix = cam.width() * cam.height();
+    for (std::size_t i = 0; i < npix; ++i)
+        for (int c = 0; c < 3; ++c) {
+            if (img) img[i][c] = T(rgb[i * 3 + c]);
+            tangent_img[i][c] = T(trgb[i * 3 + c]);
+        }
+    return st;
+}
+
+// A Scene<Dual<U>> for the device: the real parts as the scene, the dual parts of its PARAMETERS as the direction (n_params x 3).
+// A nonzero dual part anywhere the device does not differentiate -- a plane's normal, a sphere's centre, a mesh's vertices --
+// throws and names the field: a seed is never dropped silently.  (Offsets, radii, exponents and the tracer's absorb are plain
+// doubles in this API: they cannot carry one.)
+template <typename U>
+inline FlatScene<Dual<U>> flatten_dual(const Scene<Dual<U>>& scene, std::vector<double>& tangent)
+{
+    std::size_t i = 0;
+    for (Shape<Dual<U>>* shape : scene) {
+        const ShapeRecord rec = shape->describe();
+        for (int k = 0; k < 4; ++k)
+            if (rec.dual[k] != 0)
+                throw std::runtime_error("drt::hip: shape " + std::to_string(i) + " carries a dual part on its " +
+                                         (rec.kind == ShapeKind::Plane ? "normal" : rec.kind == ShapeKind::Sphere ? "centre" : "record") +
+                                         ": geometry is not differentiated on the device");
+        if (auto* mesh = dynamic_cast<Mesh<Dual<U>>*>(shape))
+            for (const auto& vtx : mesh->vertices())
+                for (int c = 0; c < 3; ++c)
+                    if (dual_part(vtx[c]) != U(0))
+                        throw std::runtime_error("drt::hip: shape " + std::to_string(i) + " carries a dual part on a mesh vertex: geometry is not "
+                                                 "differentiated on the device");
+        ++i;
+    }
+    FlatScene<Dual<U>> flat = flatten(scene);
+    tangent.assign(flat.handles.size() * 3, 0.0);
+    for (std::size_t p = 0; p < flat.handles.size(); ++p)
+        for (int c = 0; c < 3; ++c)
+            tangent[p * 3 + c] = double(dual_part(flat.handles[p][c]));
+    return flat;
+}
+template <typename U>
+inline drt_camera_desc describe_dual(const Camera<Dual<U>>& cam)
+{
+    const char* names[4] = {"eye", "forward", "right", "up"};
+    const Vector<Dual<U>, 3> vs[4] = {cam.eye(), cam.forward(), cam.right(), cam.up()};
+    for (int k = 0; k < 4; ++k)
+        for (int c = 0; c < 3; ++c)
+            if (dual_part(vs[k][c]) != U(0))
+                throw std::runtime_error(std::string("drt::hip: the camera carries a dual part on its ") + names[k] +
+                                         ": the camera is not differentiated on the device");
+    return describe(cam);
+}
+
+// T = Dual<U>: the reference's own validation run (its README: reverse mode "validated against ... forward mode"), on the device.
+// img[pixel] = Dual(radiance, d radiance / d eps), eps the scene's dual unit.  Reverse-mode options and an adjoint image throw.
+template <typename U>
+inline Stats render(const Scene<Dual<U>>& scene, const Camera<Dual<U>>& cam, const Pathtracer<Dual<U>>& tracer, std::size_t spp,
+                    Vector<Dual<U>, 3>* img, const Options& opt = Options(), const Vector<Dual<U>, 3>* adjoint = nullptr)
+{
+    if (adjoint)
+        throw std::runtime_error("drt::hip::render: Dual numbers are forward mode: no adjoint image (a reverse-mode notion)");
+    std::vector<double> v;
+    const FlatScene<Dual<U>> flat = flatten_dual(scene, v);
+    const drt_camera_desc cd = describe_dual(cam);
+    std::vector<double> rgb, trgb;
+    const Stats st = detail::tangent_call("drt::hip::render (Dual)", flat, cd, tracer.absorb(), tracer.min_bounces(), spp, v, rgb, trgb, opt);
+    const std::size_t npix = cam.width() * cam.height();
+    for (std::size_t i = 0; i < npix; ++i)
+        for (int c = 0; c < 3; ++c)
+            img[i][c] = Dual<U>(U(rgb[i * 3 + c]), U(trgb[i * 3 + c]));
+    return st;
 }
 
 } } // namespace drt::hip

@@ -25,6 +25,7 @@ struct ShapeRecord {
     ShapeKind kind = ShapeKind::Other;
     double p[4] = {0, 0, 0, 0};   // Plane: normal.xyz, offset   Sphere: center.xyz, radius   User: values 0..3 of the record
     double q[4] = {0, 0, 0, 0};   // User: values 4..7
+    double dual[4] = {0, 0, 0, 0};   // T = Dual<U>: the dual parts of p -- geometry is not differentiated on the device, which refuses a nonzero one
     const char* kind_name = nullptr;        // User
     const char* intersect_src = nullptr;    // User: body of  template <typename R> bool intersect(const R* p, V3<R> o, V3<R> d, R& t)
     const char* normal_src = nullptr;       // User: body of  template <typename R> V3<R> normal(const R* p, V3<R> P)
@@ -70,6 +71,7 @@ public:
         ShapeRecord r;
         r.kind = ShapeKind::Plane;
         r.p[0] = real(m_n[0]); r.p[1] = real(m_n[1]); r.p[2] = real(m_n[2]); r.p[3] = m_d;
+        r.dual[0] = double(dual_part(m_n[0])); r.dual[1] = double(dual_part(m_n[1])); r.dual[2] = double(dual_part(m_n[2]));
         return r;
     }
 
@@ -114,6 +116,7 @@ public:
         ShapeRecord r;
         r.kind = ShapeKind::Sphere;
         r.p[0] = real(m_c[0]); r.p[1] = real(m_c[1]); r.p[2] = real(m_c[2]); r.p[3] = m_r;
+        r.dual[0] = double(dual_part(m_c[0])); r.dual[1] = double(dual_part(m_c[1])); r.dual[2] = double(dual_part(m_c[2]));
         return r;
     }
 

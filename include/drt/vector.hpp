@@ -37,6 +37,10 @@ class Vector;
 // plugins take real() of such quantities; this is what lets T = Dual<double> compile end to end.
 inline double real(double x) { return x; }
 inline float real(float x) { return x; }
+// ... and its derivative part: zero for built-in types, the dual part of a drt::Dual.  What flattens a scene for the device asks
+// for it where the device cannot differentiate (geometry, the camera), so that such a seed is refused instead of dropped.
+inline double dual_part(double) { return 0; }
+inline float dual_part(float) { return 0; }
 
 // ---- plain value vector ------------------------------------------------------------------------
 template <typename T, std::size_t N>

@@ -388,6 +388,29 @@ int drt_hip_wait(drt_hip_ctx* ctx, uint64_t ticket, drt_hip_stats* stats /* may 
 int drt_hip_render_gradient_image(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_params* rp,
                                   int32_t param, const float* adjoint_rgb, float* out_rgb,
                                   float* out_grad_rgb, drt_hip_stats* stats);
+/* Forward mode (the reference's Dual<T>, include/drt/dual.hpp, run through the path tracer): the image AND its derivative
+ * along ONE direction of parameter space, the Jacobian-vector product J v --
+ *   out_tangent_rgb[pixel] = mean over the pixel's samples of d radiance / d eps at params + eps * param_tangent
+ * (3 channels; param_tangent: n_params x 3, one direction per parameter value).  One render whatever n_params is; no seed, no
+ * accumulator: it shares nothing with the reverse mode but the paths, and <J v, w> = <v, J^T w> ties the two together
+ * (spp * sum_pixels w . out_tangent_rgb = sum_params out_param_grad(adjoint = w) . param_tangent).
+ * Conventions of drt_hip_render_gradient_image: only this shard's rows of either image are written; out_rgb may be NULL; host
+ * buffers (pinned ranges are written directly) or device pointers with DRT_RENDER_DEVICE_OUT; DRT_RENDER_TIMING, _F64, _SERIAL;
+ * refused (DRT_ERR_INVALID) while asynchronous frames are in flight.  requires_grad is a reverse-mode notion and is ignored.
+ * DRT_ERR_INVALID: NULL param_tangent or out_tangent_rgb, a tangent value that is not finite, DRT_RENDER_BACKWARD, _UNBIASED,
+ * _LOSS_L2 or _ALLREDUCE* in rp->flags.  DRT_ERR_UNSUPPORTED (the message says "tangent"): a scene that holds a triangle mesh,
+ * bounces_per_launch >= 1, DRT_RENDER_UNFUSED -- the tangent image comes from the one-launch path kernel of analytic scenes
+ * (caller-defined kinds included) --, and a GROUP context: render the shards on plain contexts.
+ * Geometry, camera and exponents are not differentiable on the device, in either mode. */
+int drt_hip_render_tangent(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_params* rp,
+                           const double* param_tangent /* n_params x 3 */, float* out_rgb /* may be NULL */,
+                           float* out_tangent_rgb, drt_hip_stats* stats);
+/* ... with both images in double, as the device summed them (a float holds 7 digits; the DRT_RENDER_F64 verification mode is
+ * good for 1e-9: this is what a Dual<double> render is compared through).  Host buffers only (DRT_RENDER_DEVICE_OUT:
+ * DRT_ERR_INVALID), synchronous; everything else as above. */
+int drt_hip_render_tangent_double(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_params* rp,
+                                  const double* param_tangent, double* out_rgb /* may be NULL */,
+                                  double* out_tangent_rgb, drt_hip_stats* stats);
 /* stream the context launches on (a hipStream_t), for event timing / interop */
 void* drt_hip_stream(drt_hip_ctx* ctx);
 int drt_hip_synchronize(drt_hip_ctx* ctx);
