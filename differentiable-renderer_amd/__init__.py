@@ -723,7 +723,7 @@ _ABI_SYMBOLS = ["drt_hip_abi_version", "drt_hip_device_count", "drt_hip_create",
                 "drt_hip_group_size", "drt_hip_device_pci_bus_id", "drt_hip_destroy",
                 "drt_hip_comm_unique_id", "drt_hip_comm_init_rank", "drt_hip_comm_size", "drt_hip_comm_destroy",
                 "drt_hip_upload_scene", "drt_hip_update_params", "drt_hip_set_specialisation", "drt_hip_render", "drt_hip_render_async", "drt_hip_wait",
-                "drt_hip_render_gradient_image", "drt_hip_render_tangent", "drt_hip_render_tangent_double", "drt_hip_pin_host", "drt_hip_unpin_host", "drt_hip_stream",
+                "drt_hip_render_gradient_image", "drt_hip_render_tangent", "drt_hip_render_tangent_double", "drt_hip_render_normal_equations", "drt_hip_pin_host", "drt_hip_unpin_host", "drt_hip_stream",
                 "drt_hip_synchronize", "drt_hip_last_error", "drt_hip_kernel_name"]
 
 
@@ -761,6 +761,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.drt_hip_render_tangent.argtypes = [C.c_void_p, C.POINTER(CameraDesc), C.POINTER(RenderParamsDesc),
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(HipStats)]
     lib.drt_hip_render_tangent_double.argtypes = lib.drt_hip_render_tangent.argtypes
+    lib.drt_hip_render_normal_equations.argtypes = [C.c_void_p, C.POINTER(CameraDesc), C.POINTER(RenderParamsDesc), C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(HipStats)]
     lib.drt_hip_pin_host.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
     lib.drt_hip_unpin_host.argtypes = [C.c_void_p, C.c_void_p]
     lib.drt_hip_stream.argtypes = [C.c_void_p]
@@ -987,6 +989,58 @@ class HipRenderer:
         rc = self.lib.drt_hip_render_tangent(self.ctx, C.byref(cd), C.byref(d), v.ctypes.data_as(C.c_void_p), C.c_void_p(out_rgb_ptr or None),
                                              C.c_void_p(out_tangent_ptr), C.byref(stats) if want_stats else None)
         self._check(rc, "drt_hip_render_tangent")
+        return stats.as_dict() if want_stats else {}
+
+    def render_normal_equations(self, cam: Camera, rp: RenderParams, target: Optional[np.ndarray] = None,
+                                residual: Optional[np.ndarray] = None, f64: bool = False, jacobian: bool = False, timing: bool = False) -> dict:
+        """drt_hip_render_normal_equations: the Gauss-Newton normal equations of the frame from one render.  Exactly one of
+        `target` (r = this render's pixel means - target) and `residual` (r as given), float32 [H,W,3].
+        -> {"image" [H,W,3] float32, "A" [3,P,P], "b" [3,P], "loss" [3] (float64, sums over this shard's pixels),
+            "jacobian" [P,H,W,3] float32 or None, "stats"}"""
+        assert self.scene is not None
+        P = self.scene.n_params
+        d = rp.to_desc()
+        d.flags = (rp.flags & ~(RENDER_DEVICE_OUT | RENDER_SYNC)) | (RENDER_F64 if f64 else 0) | (RENDER_TIMING if timing else 0)
+
+        def image(a):
+            if a is None:
+                return None, None
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            assert a.shape == (cam.height, cam.width, 3), a.shape
+            return a, a.ctypes.data_as(C.c_void_p)
+        target, t_ptr = image(target)
+        residual, r_ptr = image(residual)
+        img = np.zeros((cam.height, cam.width, 3), dtype=np.float32)
+        A = np.zeros((3, P, P), dtype=np.float64)
+        b = np.zeros((3, P), dtype=np.float64)
+        loss = np.zeros(3, dtype=np.float64)
+        jac = np.zeros((P, cam.height, cam.width, 3), dtype=np.float32) if jacobian else None
+        stats = HipStats()
+        cd = cam.to_desc()
+        rc = self.lib.drt_hip_render_normal_equations(self.ctx, C.byref(cd), C.byref(d), t_ptr, r_ptr, img.ctypes.data_as(C.c_void_p),
+                                                      A.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p), loss.ctypes.data_as(C.c_void_p),
+                                                      jac.ctypes.data_as(C.c_void_p) if jacobian else None, C.byref(stats))
+        self._check(rc, "drt_hip_render_normal_equations")
+        return {"image": img, "A": A, "b": b, "loss": loss, "jacobian": jac, "stats": stats.as_dict()}
+
+    def render_normal_equations_device(self, cam: Camera, rp: RenderParams, out_A_ptr: int, out_b_ptr: int, target_ptr: int = 0,
+                                       residual_ptr: int = 0, out_rgb_ptr: int = 0, out_loss_ptr: int = 0, out_jacobian_ptr: int = 0,
+                                       f64: bool = False, timing: bool = False, sync: bool = False, want_stats: Optional[bool] = None) -> dict:
+        """drt_hip_render_normal_equations on device pointers (images float32, A [3,P,P] / b [3,P] / loss [3] float64), enqueued on
+        the context's stream; exactly one of target_ptr and residual_ptr."""
+        if want_stats is None:
+            want_stats = timing
+        assert self.scene is not None
+        d = rp.to_desc()
+        d.flags = ((rp.flags | RENDER_DEVICE_OUT) & ~RENDER_SYNC) | (RENDER_F64 if f64 else 0) | (RENDER_TIMING if timing else 0) | \
+                  (RENDER_SYNC if sync else 0)
+        stats = HipStats()
+        cd = cam.to_desc()
+        rc = self.lib.drt_hip_render_normal_equations(self.ctx, C.byref(cd), C.byref(d), C.c_void_p(target_ptr or None),
+                                                      C.c_void_p(residual_ptr or None), C.c_void_p(out_rgb_ptr or None), C.c_void_p(out_A_ptr or None),
+                                                      C.c_void_p(out_b_ptr or None), C.c_void_p(out_loss_ptr or None),
+                                                      C.c_void_p(out_jacobian_ptr or None), C.byref(stats) if want_stats else None)
+        self._check(rc, "drt_hip_render_normal_equations")
         return stats.as_dict() if want_stats else {}
 
     def render_device(self, cam: Camera, rp: RenderParams, out_rgb_ptr: int, out_grad_ptr: int,

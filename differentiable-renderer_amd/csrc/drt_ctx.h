@@ -16,9 +16,18 @@ struct TimedLaunch {
 };
 
 // A forward-mode render (drt_hip_render_tangent), as render_common / render_launch / render_impl are told about it
+// ... and the normal equations of a frame (drt_hip_render_normal_equations): the path kernel's Jacobian form, then k_normal_eq.  All pointers
+// are the device's; exactly one of d_target / d_residual is set
+struct NormalEqRequest {
+    const float* d_target = nullptr;
+    const float* d_residual = nullptr;
+    float* d_jacobian = nullptr;          // P x H x W x 3, or none
+    double *d_A = nullptr, *d_b = nullptr, *d_loss = nullptr;
+};
 struct TangentRequest {
     const void* d_params = nullptr;       // [the scene's parameters | the direction] in the render's compute type: the path kernel's `params`
     bool keep_sums = false;               // the pixels' sums of both images also stay in `film` / `gfilm`, in double (drt_hip_render_tangent_double)
+    const NormalEqRequest* neq = nullptr; // not a forward-mode render at all: the normal equations (d_params, keep_sums unused)
 };
 
 // One render call between its phases: launch (everything enqueued, gradients in ctx->grad[ctx->slot]) -> reduce (the
@@ -137,6 +146,9 @@ struct drt_hip_ctx {
     uint64_t tangent_calls = 0;
     std::vector<float> tangent_rgb32;     // drt_hip_render_tangent_double: the float image its double one is gathered beside
     DevBuf tangent;
+    // drt_hip_render_normal_equations: k_normal_eq's partials per block, the results and the caller's images where they are host buffers
+    DevBuf neq_part, neq_out, neq_in, neq_jac, neq_rgb;
+    std::vector<float> neq_host;          // ... the Jacobian images on their way to the rows of a host buffer
     // pinned staging of everything a host-buffer render returns: [segments 8 B | grads | image | gradient
     // image] arrive by DMA in one go, then plain memcpys into the caller's (pageable) buffers -- a
     // pageable hipMemcpy of the 3 MB image alone cost 1 ms

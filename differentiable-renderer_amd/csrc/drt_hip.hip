@@ -132,7 +132,8 @@ void drt_hip_destroy(drt_hip_ctx* ctx)
         (void)hipEventDestroy(ctx->ev_done);
     DevBuf* bufs[] = {&ctx->hist_ovf[0], &ctx->hist_ovf[1], &ctx->mesh_ovf[0], &ctx->mesh_ovf[1], &ctx->fpart2, &ctx->gpart2, &ctx->counts2, &ctx->fpart, &ctx->gpix, &ctx->cand[0], &ctx->cand[1], &ctx->cand_a[0], &ctx->cand_a[1], &ctx->cand_b[0], &ctx->cand_b[1], &ctx->cand_count[0], &ctx->cand_count[1], &ctx->ray_a[0], &ctx->ray_a[1], &ctx->ray_a[2], &ctx->ray_b[0], &ctx->ray_b[1], &ctx->ray_b[2], &ctx->ray_id[0], &ctx->ray_id[1], &ctx->ray_id[2], &ctx->hit, &ctx->hit2, &ctx->hit3, &ctx->lacc, &ctx->gpath, &ctx->gfilm, &ctx->gimg_out, &ctx->tape, &ctx->nv,
                       &ctx->ch_cva, &ctx->ch_cvb, &ctx->ch_cvh, &ctx->ch_nxa, &ctx->ch_nxb, &ctx->ch_nxh, &ctx->ch_g,
-                      &ctx->ch_w, &ctx->ch_ids, &ctx->ch_ndraw, &ctx->ch_dbase, &ctx->counts, &ctx->film, &ctx->gpart, &ctx->adjoint, &ctx->tangent};
+                      &ctx->ch_w, &ctx->ch_ids, &ctx->ch_ndraw, &ctx->ch_dbase, &ctx->counts, &ctx->film, &ctx->gpart, &ctx->adjoint, &ctx->tangent,
+                      &ctx->neq_part, &ctx->neq_out, &ctx->neq_in, &ctx->neq_jac, &ctx->neq_rgb};
     for (DevBuf* b : bufs)
         release(*b);
     for (int i = 0; i < DRT_HIP_FRAMES_IN_FLIGHT; ++i) {
@@ -379,6 +380,108 @@ int drt_hip_render_tangent_double(drt_hip_ctx* ctx, const drt_camera_desc* cam, 
     return DRT_OK;
 }
 
+
+// ---- the Gauss-Newton normal equations of a frame: the path kernel's Jacobian form, then k_normal_eq (drt_path.h) ----
+int drt_hip_render_normal_equations(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_params* rp, const float* target_rgb,
+                                    const float* residual_rgb, float* out_rgb, double* out_A, double* out_b, double* out_loss,
+                                    float* out_jacobian, drt_hip_stats* stats)
+{
+    if (!ctx)
+        return DRT_ERR_INVALID;
+    if (!ctx->members.empty())
+        return fail(ctx, DRT_ERR_UNSUPPORTED, "normal equations: not on a group context (render the shards on plain contexts and add them)");
+    if (!ctx->has_scene)
+        return fail(ctx, DRT_ERR_NO_SCENE, "render before upload_scene");
+    if (!cam || !rp || cam->width <= 0 || cam->height <= 0)
+        return fail(ctx, DRT_ERR_INVALID, "normal equations: bad camera or render parameters");
+    if ((target_rgb != nullptr) == (residual_rgb != nullptr))
+        return fail(ctx, DRT_ERR_INVALID, "normal equations: exactly one of target_rgb and residual_rgb");
+    if (!out_A || !out_b)
+        return fail(ctx, DRT_ERR_INVALID, "normal equations: NULL out_A or out_b");
+    for (int i = 0; i < DRT_HIP_FRAMES_IN_FLIGHT; ++i)
+        if (ctx->in_flight[i])
+            return fail(ctx, DRT_ERR_INVALID, "normal equations: asynchronous frames are in flight -- drt_hip_wait for them first");
+    if (rp->flags & (DRT_RENDER_UNFUSED | DRT_RENDER_UNBIASED | DRT_RENDER_LOSS_L2 | DRT_RENDER_ALLREDUCE | DRT_RENDER_ALLREDUCE_ASYNC))
+        return fail(ctx, DRT_ERR_UNSUPPORTED, "normal equations: not with DRT_RENDER_UNFUSED, _UNBIASED, _LOSS_L2 or _ALLREDUCE* -- the biased operator on the "
+                                              "one-launch path kernel, one context");
+    if (ctx->has_mesh)
+        return fail(ctx, DRT_ERR_UNSUPPORTED, "normal equations: not of a scene that holds a triangle mesh");
+    if (rp->bounces_per_launch >= 1)
+        return fail(ctx, DRT_ERR_UNSUPPORTED, "normal equations: they come from the one-launch path kernel -- not with bounces_per_launch >= 1");
+    if (ctx->n_params > DRT_FAST_PARAMS)
+        return fail(ctx, DRT_ERR_UNSUPPORTED, ctx->n_user_params > DRT_FAST_PARAMS
+            ? "normal equations: more than DRT_FAST_PARAMS = 8 parameters (the Jacobian is the path kernel's gradient "
+              "columns, which stop there; J^T J v by drt_hip_render_tangent + drt_hip_render is the matrix-free route)"
+            : "normal equations: the scene's parameters and the constant a mirror material adds take more than DRT_FAST_PARAMS = 8 "
+              "gradient columns of the path kernel (a mirror costs one: at most 7 parameters beside it)");
+    if ((uint64_t)cam->width * (uint64_t)cam->height * (uint64_t)(rp->spp > 0 ? rp->spp : 1) > 0x7FFFFFFFull)
+        return fail(ctx, DRT_ERR_UNSUPPORTED, "normal equations: more than 2^31 camera samples in one frame (the shard renders in one batch)");
+    const bool dev = (rp->flags & DRT_RENDER_DEVICE_OUT) != 0;
+    const size_t npix = (size_t)cam->width * (size_t)cam->height;
+    const size_t P = (size_t)ctx->n_user_params, nA = 3 * P * P, nb = 3 * P;
+    const float* src = target_rgb ? target_rgb : residual_rgb;
+    if (!dev)
+        for (size_t i = 0; i < npix * 3; ++i)
+            if (!std::isfinite(src[i]))
+                return fail(ctx, DRT_ERR_INVALID, "normal equations: the target / residual image holds a value that is not finite");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int rc;
+    NormalEqRequest q;
+    float* rgb = out_rgb;
+    if (dev) {
+        q.d_A = out_A; q.d_b = out_b; q.d_loss = out_loss;
+        q.d_jacobian = out_jacobian;
+        if (!rgb) {       // (the radiance sums are part of the pipeline: an image of the context's own)
+            if ((rc = ensure(ctx, ctx->neq_rgb, npix * 3 * sizeof(float))) != DRT_OK) return rc;
+            rgb = (float*)ctx->neq_rgb.p;
+        }
+    } else {
+        if ((rc = ensure(ctx, ctx->neq_in, npix * 3 * sizeof(float))) != DRT_OK) return rc;
+        if ((rc = ensure(ctx, ctx->neq_out, (nA + nb + 3) * sizeof(double))) != DRT_OK) return rc;
+        HIPCHK(ctx, hipMemcpyAsync(ctx->neq_in.p, src, npix * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+        src = (const float*)ctx->neq_in.p;
+        q.d_A = (double*)ctx->neq_out.p; q.d_b = q.d_A + nA; q.d_loss = q.d_b + nb;
+        if (out_jacobian) {
+            if ((rc = ensure(ctx, ctx->neq_jac, (P ? P : 1) * npix * 3 * sizeof(float))) != DRT_OK) return rc;
+            q.d_jacobian = (float*)ctx->neq_jac.p;
+        }
+        if (!rgb) {
+            ctx->tangent_rgb32.resize(npix * 3);
+            rgb = ctx->tangent_rgb32.data();
+        }
+    }
+    (target_rgb ? q.d_target : q.d_residual) = src;
+    // (a shard without rows launches nothing: its sums are zero)
+    if (nA) HIPCHK(ctx, hipMemsetAsync(q.d_A, 0, nA * sizeof(double), ctx->stream));
+    if (nb) HIPCHK(ctx, hipMemsetAsync(q.d_b, 0, nb * sizeof(double), ctx->stream));
+    if (q.d_loss) HIPCHK(ctx, hipMemsetAsync(q.d_loss, 0, 3 * sizeof(double), ctx->stream));
+    drt_render_params r = *rp;
+    r.flags &= ~(uint32_t)DRT_RENDER_BACKWARD;       // (the Jacobian needs no seed and no summed gradient)
+    TangentRequest req;
+    req.neq = &q;
+    if ((rc = render_common(ctx, cam, &r, nullptr, rgb, nullptr, stats, -1, nullptr, &req)) != DRT_OK)
+        return rc;
+    if (dev)
+        return DRT_OK;
+    // host buffers: the render has waited for its stream; a few hundred bytes of sums, and the Jacobian's rows of this shard where asked for
+    std::vector<double> sums(nA + nb + 3);
+    HIPCHK(ctx, hipMemcpy(sums.data(), ctx->neq_out.p, sums.size() * sizeof(double), hipMemcpyDeviceToHost));
+    if (nA) memcpy(out_A, sums.data(), nA * sizeof(double));
+    if (nb) memcpy(out_b, sums.data() + nA, nb * sizeof(double));
+    if (out_loss) memcpy(out_loss, sums.data() + nA + nb, 3 * sizeof(double));
+    if (out_jacobian && P) {
+        const RenderJob& j = ctx->job;
+        ctx->neq_host.resize(P * npix * 3);
+        HIPCHK(ctx, hipMemcpy(ctx->neq_host.data(), ctx->neq_jac.p, ctx->neq_host.size() * sizeof(float), hipMemcpyDeviceToHost));
+        const size_t row = (size_t)cam->width * 3;
+        for (size_t p = 0; p < P; ++p)
+            for_each_band(cam->height, j.band, j.n_shards, j.shard, [&](int y0, int y1) {
+                memcpy(out_jacobian + p * npix * 3 + (size_t)y0 * row, ctx->neq_host.data() + p * npix * 3 + (size_t)y0 * row,
+                       (size_t)(y1 - y0) * row * sizeof(float));
+            });
+    }
+    return DRT_OK;
+}
 
 // ---- asynchronous host-buffer renders ---------------------------------------------------------------
 // drt_hip_render returns when the results are in the caller's buffers: every frame pays a 3 MB device-to-host copy and a

@@ -519,8 +519,12 @@ __device__ inline void gen_finish(const GenBlock<R>& gb, const PathArgs& a, doub
 // so a kernel's name says what it was compiled for and the library's instantiations and hiprtc's are the same source.  Masks of zero
 // mean "not known": every slot below NC may be a colour, every slot an emission -- the code every other form keeps.
 #define DRT_NC_ROLES(nc, colour_mask, emission_mask) ((int)(nc) | (int)(colour_mask) << 8 | (int)(emission_mask) << 16)
-#define DRT_NC_OF(ncr) ((int)(ncr) & 0xFF)
+#define DRT_NC_OF(ncr) ((int)(ncr) & 0x3F)
 #define DRT_ROLES_OF(ncr) ((int)(ncr) >> 8)
+// ... and in the low byte, above the column count, one bit: the JACOBIAN form of the lockstep column kernels (drt_hip_render_normal_equations) -- at the end of its
+// sample range a lane writes EVERY row of its gradient column out per pixel (the gradient image writes one), and the block's sums are not formed
+#define DRT_NC_JACOBIAN 0x40
+#define DRT_JACOBIAN_OF(ncr) ((((int)(ncr)) & DRT_NC_JACOBIAN) != 0)
 #define DRT_ROLES_CORNELL DRT_ROLES_OF(DRT_NC_ROLES(0, 0x7, 0x8))      // render.cpp:26-29: colour, colour, colour, emission
 template <int NP, int NC, int ROLES>
 struct PathRoles {
@@ -879,6 +883,7 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
     typedef typename Q4<R>::T R4;
     typedef typename Q2<R>::T R2;
     constexpr int NC = DRT_NC_OF(NCR), ROLES = DRT_ROLES_OF(NCR);
+    constexpr bool JAC = DRT_JACOBIAN_OF(NCR) && NP > 0 && !REGEN;   // the Jacobian form: every row of the lane's column leaves per pixel
     __shared__ PathSceneLds<R> lds;
     __shared__ double s_red[REGEN ? 1 : DRT_BLOCK / DRT_WAVE][DRT_FAST_PARAMS * 3];   // (REGEN: the block's gradient partials reuse the pixel sums' table)
     __shared__ TangentLds<R> s_tl;
@@ -1141,7 +1146,17 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
             double* f = gimg_part + ((size_t)range * 3) * a.Pb + lp;
             f[0] = tx; f[(size_t)a.Pb] = ty; f[(size_t)a.Pb * 2] = tz;
         }
-        if constexpr (NP > 0) if (gimg_part && have) {
+        if constexpr (JAC) if (gimg_part && have) {
+            // the Jacobian: all rows of the lane's column -- the pixel's gradient sums of every parameter over the samples of this range,
+            // [range][row][pixel] with the scene's own 3 x n_params rows (k_normal_eq reads them back, coalesced like the radiance partials)
+            const int rows = (lds.sc.n_params < NP ? lds.sc.n_params : NP) * 3;
+            double* f = gimg_part + ((size_t)range * (size_t)rows) * a.Pb + lp;
+#pragma unroll
+            for (int r = 0; r < NP * 3; ++r)
+                if (r < rows)
+                    f[(size_t)r * a.Pb] = (double)tg.acc[r * DRT_BLOCK];
+        }
+        if constexpr (NP > 0 && !JAC) if (gimg_part && have) {
             // gradient image (README.md:142-145): a lane IS a pixel, its gradient sum of one parameter over the samples of
             // this range is that pixel's share -- same layout as the radiance partials, same finishing kernels
             const V3<R> v = tg.acc_get(a.gimg_param > 0 && a.gimg_param < NP ? a.gimg_param : 0);
@@ -1156,7 +1171,7 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
     if constexpr (GEN)
         gen_finish(s_gen, a, gpart);
     else
-    if (NP > 0) {
+    if (NP > 0 && !JAC) {
         // block reduction in fp64: thread -> wave (shuffles) -> block (LDS), fixed order; K7 adds the blocks
         const int wv = threadIdx.x / DRT_WAVE;
         double (*red)[DRT_FAST_PARAMS * 3] = s_red;
@@ -1539,4 +1554,144 @@ k_path_finish(PathArgs a, const double* __restrict__ fpart, float* __restrict__ 
             if (wlk) atomicAdd(total + 5, wlk);
         }
     }
+}
+
+// ---- the Gauss-Newton normal equations of a frame (drt_hip_render_normal_equations) -------------------------------------
+// Behind a launch of k_path's Jacobian form: jpart[range][3 p + ch][pixel] holds, per pixel of the shard, the sums over one sample range of
+// d radiance_ch / d c_{p,ch} (a radiance channel depends on the same channel of every parameter only: T_ch = prod c_{p_j,ch} m_j), fpart the
+// radiance sums.  Per channel (blockIdx.y) and pixel, in fp64:
+//     J_p = (sum over the ranges, in range order) / spp          0 where the parameter requires no gradient
+//     r   = radiance mean - target   |   the caller's residual
+//     A[p][q] += J_p J_q  (q >= p)      b[p] += J_p r      loss += r r          DRT_NEQ_VALUES(NP) running sums per thread
+// then thread -> wave (shuffles) -> block (LDS) in a fixed order, one partial per block and channel; k_normal_eq_finish adds the blocks
+// in a fixed order and mirrors A.  No atomics: the same call gives the same bits.  Memory-bound: 8 n_ranges (P + 1) bytes come in per
+// pixel and channel, coalesced (VW = 2: two neighbouring pixels per lane, 16-byte loads; the host picks it where the batch's pixel count is even).
+// The Jacobian images leave in the same pass where the caller wants them (float, the layout of P gradient images): n_out of them, the
+// caller's parameters -- n_par, the rows of jpart, also counts the constant the scene appends for a mirror.
+#define DRT_NEQ_VALUES(np) ((np) * ((np) + 1) / 2 + (np) + 1)
+template <int NP, int VW>
+__global__ void __launch_bounds__(DRT_BLOCK)
+k_normal_eq(PathArgs a, const double* __restrict__ jpart, const double* __restrict__ fpart, int n_par, int n_out, uint32_t grad_mask,
+            const float* __restrict__ target, const float* __restrict__ residual, float* __restrict__ out_jac, double* __restrict__ part)
+{
+    constexpr int NV = DRT_NEQ_VALUES(NP);
+    typedef typename PickT<VW == 2, double2, double>::T DV;
+    const int ch = (int)blockIdx.y;
+    const size_t Pb = a.Pb, rows = (size_t)n_par * 3, npix = (size_t)a.W * (size_t)a.H;
+    const double inv = 1.0 / (double)a.spp;
+    double acc[NV];
+#pragma unroll
+    for (int k = 0; k < NV; ++k)
+        acc[k] = 0.0;
+    const uint32_t n_items = (a.Pb + VW - 1) / VW;
+    for (uint32_t it = blockIdx.x * DRT_BLOCK + threadIdx.x; it < n_items; it += gridDim.x * DRT_BLOCK) {
+        const uint32_t j = it * VW;
+        double Js[NP][VW], Ls[VW];
+#pragma unroll
+        for (int v = 0; v < VW; ++v) {
+            Ls[v] = 0.0;
+#pragma unroll
+            for (int p = 0; p < NP; ++p)
+                Js[p][v] = 0.0;
+        }
+        for (uint32_t q = 0; q < a.n_ranges; ++q) {
+            const double* fj = jpart + ((size_t)q * rows + (size_t)ch) * Pb + j;
+            const DV lv = *reinterpret_cast<const DV*>(fpart + ((size_t)q * 3 + (size_t)ch) * Pb + j);
+#pragma unroll
+            for (int p = 0; p < NP; ++p)
+                if (p < n_par) {
+                    const DV jv = *reinterpret_cast<const DV*>(fj + (size_t)(p * 3) * Pb);
+#pragma unroll
+                    for (int v = 0; v < VW; ++v)
+                        Js[p][v] += reinterpret_cast<const double*>(&jv)[v];
+                }
+#pragma unroll
+            for (int v = 0; v < VW; ++v)
+                Ls[v] += reinterpret_cast<const double*>(&lv)[v];
+        }
+#pragma unroll
+        for (int v = 0; v < VW; ++v) {
+            const size_t gp = path_global_pixel(a, a.p0 + j + (uint32_t)v);
+            double J[NP];
+#pragma unroll
+            for (int p = 0; p < NP; ++p)
+                J[p] = ((grad_mask >> p) & 1u) ? Js[p][v] * inv : 0.0;
+            const double r = target ? Ls[v] * inv - (double)target[gp * 3 + (size_t)ch] : (double)residual[gp * 3 + (size_t)ch];
+            if (out_jac) {
+#pragma unroll
+                for (int p = 0; p < NP; ++p)
+                    if (p < n_out)             // (the caller's parameters: a mirror's internal constant behind them has a row in jpart, no image)
+                        out_jac[((size_t)p * npix + gp) * 3 + (size_t)ch] = (float)J[p];
+            }
+            int k = 0;
+#pragma unroll
+            for (int p = 0; p < NP; ++p)
+#pragma unroll
+                for (int q2 = p; q2 < NP; ++q2)
+                    acc[k++] += J[p] * J[q2];
+#pragma unroll
+            for (int p = 0; p < NP; ++p)
+                acc[k++] += J[p] * r;
+            acc[k] += r * r;
+        }
+    }
+    __shared__ double red[DRT_BLOCK / DRT_WAVE][NV];
+    const int wv = threadIdx.x / DRT_WAVE;
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+        double v = acc[k];
+#pragma unroll
+        for (int o2 = DRT_WAVE / 2; o2 > 0; o2 >>= 1)
+            v += __shfl_down(v, o2);
+        if ((threadIdx.x & (DRT_WAVE - 1)) == 0)
+            red[wv][k] = v;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < NV) {
+        double v = 0;
+        for (int ww = 0; ww < DRT_BLOCK / DRT_WAVE; ++ww)
+            v += red[ww][threadIdx.x];
+        part[((size_t)ch * gridDim.x + blockIdx.x) * NV + threadIdx.x] = v;
+    }
+}
+
+// ... its second stage: block (channel, value) adds that value's partials over k_normal_eq's blocks -- a strided sum per thread, then an LDS
+// tree, both in a fixed order -- and writes it where it belongs: A[ch][p][q] and its mirror A[ch][q][p], b[ch][p], loss[ch], for the n_out
+// parameters of the caller (np_w: the width k_normal_eq was instantiated for)
+__global__ void __launch_bounds__(DRT_BLOCK)
+k_normal_eq_finish(const double* __restrict__ part, int n_blocks, int np_w, int n_out, double* __restrict__ out_A, double* __restrict__ out_b,
+                   double* __restrict__ out_loss)
+{
+    __shared__ double red[DRT_BLOCK];
+    const int nv = DRT_NEQ_VALUES(np_w);
+    const int ch = (int)blockIdx.x / nv, k = (int)blockIdx.x - ch * nv;
+    double v = 0;
+    for (int b = threadIdx.x; b < n_blocks; b += DRT_BLOCK)
+        v += part[((size_t)ch * n_blocks + b) * nv + k];
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int off = DRT_BLOCK / 2; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off)
+            red[threadIdx.x] += red[threadIdx.x + off];
+        __syncthreads();
+    }
+    if (threadIdx.x != 0)
+        return;
+    const int n_tri = np_w * (np_w + 1) / 2;
+    if (k < n_tri) {
+        int p = 0, first = 0;                                // row p of the upper triangle starts at `first` and holds np_w - p values
+        while (k >= first + (np_w - p)) {
+            first += np_w - p;
+            ++p;
+        }
+        const int q = p + (k - first);
+        if (p < n_out && q < n_out) {
+            out_A[((size_t)ch * n_out + p) * n_out + q] = red[0];
+            out_A[((size_t)ch * n_out + q) * n_out + p] = red[0];
+        }
+    } else if (k < n_tri + np_w) {
+        if (k - n_tri < n_out)
+            out_b[(size_t)ch * n_out + (k - n_tri)] = red[0];
+    } else if (out_loss)
+        out_loss[ch] = red[0];
 }

@@ -151,7 +151,8 @@ inline int np_width(int n_params, int general)
 }
 
 // ---- which instantiation of the one-launch path kernels a render runs (shard_plan decides it, path_batch launches it) ----
-enum class PathOp { biased, unbiased, mesh, tangent };   // k_path (the gradient image included), k_path_unbiased, k_path_mesh, k_path's forward-mode form
+enum class PathOp { biased, unbiased, mesh, tangent, jacobian };   // k_path (the gradient image included), k_path_unbiased, k_path_mesh, k_path's forward-mode form,
+                                                                    // its Jacobian form (lockstep, parameters in columns: DRT_NC_JACOBIAN)
 enum class PathProg { cornell, sorted, scene };  // closest-hit program: the reference's kinds compiled in (SigCornell), kinds read at
                                                  // run time (SigNone), or compiled by hiprtc for the scene's own KindSig (drt_jit.h)
 struct PathForm {
@@ -188,7 +189,11 @@ struct Shard {
     float* d_out_gimg;
     bool fwd_tangent;               // drt_hip_render_tangent: d_params holds [parameters | direction], d_out_gimg gets the derivative image
     bool keep_sums;                 // ... and both images' sums go through `film` / `gfilm` (double), where the caller reads them
-    bool pixel_sums() const { return gimg_param >= 0 || fwd_tangent; }   // the lanes' per-pixel sums leave the path kernel (gimg_part)
+    const NormalEqRequest* neq = nullptr;   // drt_hip_render_normal_equations: the Jacobian form, then k_normal_eq
+    uint32_t neq_blocks = 0;        // ... k_normal_eq's blocks per channel
+    int neq_vw = 1;                 // ... pixels per lane (2: 16-byte loads, an even number of pixels)
+    int jac_rows() const { return neq ? ctx->n_params * 3 : 3; }   // rows a pixel's sums have in `gpix`
+    bool pixel_sums() const { return gimg_param >= 0 || fwd_tangent || neq; }   // the lanes' per-pixel sums leave the path kernel (gimg_part)
     // the scene in compute type R
     const DevScene<R>* d_scene;
     const R* d_params;
@@ -282,7 +287,8 @@ inline std::string path_kernel_name(const drt_hip_ctx* ctx, const PathForm& f)
     if (f.op == PathOp::unbiased)
         snprintf(name, sizeof name, "k_path_unbiased<%s, %s, %d, %s>", type, sp, f.np, sg.c_str());
     else
-        snprintf(name, sizeof name, "k_path<%s, %s, %d, %d, %s, %s%s>", type, sp, f.np, DRT_NC_ROLES(f.nc, 0, 0) | f.roles << 8, sg.c_str(), f.regen ? "true" : "false", f.loss ? ", true" : "");
+        snprintf(name, sizeof name, "k_path<%s, %s, %d, %d, %s, %s%s>", type, sp, f.np,
+                 DRT_NC_ROLES(f.nc, 0, 0) | f.roles << 8 | (f.op == PathOp::jacobian ? DRT_NC_JACOBIAN : 0), sg.c_str(), f.regen ? "true" : "false", f.loss ? ", true" : "");
     return name;
 }
 
@@ -307,6 +313,21 @@ const void* library_path_kernel(const PathForm& f)
         return with_bool(f.spec, [&](auto spec) { return with_bool(f.prog == PathProg::cornell, [&](auto cornell) {
             return k(spec, std::conditional_t<cornell, SigCornell, SigNone>()); }); });
     };
+    if (f.op == PathOp::jacobian) {   // the Jacobian form: the column forms, lockstep, every program
+        if (f.regen || f.roles != 0)
+            return nullptr;
+        const auto jcols = [&f](auto k) {
+            if (f.np == 8 && f.nc == 8) return k(IntC<8>(), IntC<8>());
+            if (f.np == 4 && f.nc == 3) return k(IntC<4>(), IntC<3>());
+            if (f.np == 4 && f.nc == 4) return k(IntC<4>(), IntC<4>());
+            return (const void*)nullptr;
+        };
+        return jcols([&](auto np, auto nc) {
+            return spec_sig([](auto spec, auto sg) {
+                return (const void*)k_path<R, decltype(spec)::value, decltype(np)::value, decltype(nc)::value | DRT_NC_JACOBIAN, decltype(sg), false>;
+            });
+        });
+    }
     if (f.roles != 0) {
         // role-specialised (shard_plan: the diffuse f32 lockstep k_path only): the library carries the roles of the reference's own scene,
         // render.cpp:26-29 -- three colours, one emission --; any other layout exists in the kernel hiprtc makes for its scene
@@ -371,14 +392,14 @@ void shard_plan(Shard<R>& s)
     // gradients: <= 8 parameters in registers / LDS columns; any number the kernels can stage (136: every analytic scene) through
     // the general form -- vertex history + per-wave tables (drt_path.h, DRT_NP_ANY); the gradient IMAGE (the lanes' own sums) in
     // analytic scenes too
-    const bool tangents = s.backward || s.gimg_param >= 0;
+    const bool tangents = s.backward || s.gimg_param >= 0 || s.neq;
     const bool grads_ok = !tangents || ctx->n_params <= DRT_FAST_PARAMS ||
                           (ctx->n_params <= DRT_PATH_LDS_PARAMS && tuning().path_general && (s.gimg_param < 0 || !ctx->has_mesh));
     s.use_path = ((s.can_fuse && ctx->prog_ok) || mesh_ok) && D > 0 && grads_ok &&
                  rp->bounces_per_launch <= 0 && tuning().shade_bounces <= 0 && tuning().dump_path == -1;
     s.mesh_path = s.use_path && ctx->has_mesh;
     PathForm& f = s.path;
-    const bool lane_is_pixel = s.gimg_param >= 0 && !s.mesh_path;   // the gradient image is the lanes' own sums: lockstep form only
+    const bool lane_is_pixel = (s.gimg_param >= 0 || s.neq) && !s.mesh_path;   // the gradient image / the Jacobian is the lanes' own sums: lockstep form only
     // (k_path_mesh: every lane on its own, always; k_path_unbiased walks its samples in lockstep)
     f.regen = (tuning().path_regen > 0 || s.mesh_path) && !s.unbiased && !lane_is_pixel;
     if (s.use_path && !s.mesh_path && !lane_is_pixel && tuning().path_regen < 0 && !s.unbiased) {
@@ -402,10 +423,10 @@ void shard_plan(Shard<R>& s)
     // the gradients: in registers / LDS columns for <= 8 parameters, else the general form (also where the register form would do
     // but is slower: its 5 ... 8-parameter instantiation keeps 24 LDS columns per thread -- 0.78 ms against the general form's 0.75
     // on config 3's frame with an albedo per wall)
-    const bool gen = tangents && ctx->n_params <= DRT_PATH_LDS_PARAMS &&
+    const bool gen = tangents && !s.neq && ctx->n_params <= DRT_PATH_LDS_PARAMS &&     // (the Jacobian IS the columns)
                      (s.gimg_param >= 0 ? ctx->n_params > DRT_FAST_PARAMS && !s.mesh_path       // (the image keeps the column form where it exists)
                                         : ctx->n_params > tuning().gen_above && (tuning().path_general || ctx->n_params <= DRT_FAST_PARAMS));
-    f.op = s.unbiased ? PathOp::unbiased : (s.mesh_path ? PathOp::mesh : (s.fwd_tangent ? PathOp::tangent : PathOp::biased));
+    f.op = s.unbiased ? PathOp::unbiased : (s.mesh_path ? PathOp::mesh : (s.fwd_tangent ? PathOp::tangent : (s.neq ? PathOp::jacobian : PathOp::biased)));
     f.f64 = sizeof(R) == 8; f.spec = ctx->has_specular;
     f.np = s.fwd_tangent ? DRT_NP_TANGENT : !tangents ? 0 : (gen ? DRT_NP_ANY : np_width(ctx->n_params, DRT_NP_ANY));
     f.nc = !tangents ? 0 : gen ? (s.gimg_param >= 0 ? 1 : 0)
@@ -413,7 +434,7 @@ void shard_plan(Shard<R>& s)
     f.loss = s.loss_l2;
     // the slots' roles as the scene's records give them: for the form the headline runs -- diffuse, f32, lockstep, parameters in columns
     f.roles = 0;
-    if (tuning().path_roles && tangents && !gen && sizeof(R) == 4 && !f.spec && !f.regen && !f.loss && f.op == PathOp::biased && s.gimg_param < 0 &&
+    if (tuning().path_roles && tangents && !gen && sizeof(R) == 4 && !f.spec && !f.regen && !f.loss && f.op == PathOp::biased && s.gimg_param < 0 && !s.neq &&
         ctx->colour_mask != 0 && ctx->emission_mask != 0)
         f.roles = (int)(ctx->colour_mask | ctx->emission_mask << 8);
     if (s.use_path && s.loss_l2) {
@@ -467,6 +488,8 @@ void shard_plan(Shard<R>& s)
         cap = s.total_paths;               // no per-path memory: one batch covers the frame
     if (tuning().batch_paths > 0)
         cap = (uint64_t)tuning().batch_paths;
+    if (s.neq)
+        cap = s.total_paths;               // k_normal_eq reads every range of every pixel of the shard: one batch (render_impl refuses frames beyond 2^31 paths)
     if (cap > s.total_paths) cap = s.total_paths;
     if (cap < 1) cap = 1;
     if (cap > 0x7FFFFFFFull) cap = 0x7FFFFFFFull;
@@ -548,7 +571,14 @@ int shard_buffers(Shard<R>& s)
     if (s.use_path) {
         if ((rc = ensure(ctx, *s.fpart_buf, (size_t)s.path_ranges * 3 * s.Pb * sizeof(double))) != DRT_OK) return rc;
         if (s.pixel_sums())
-            if ((rc = ensure(ctx, ctx->gpix, (size_t)s.path_ranges * 3 * s.Pb * sizeof(double))) != DRT_OK) return rc;
+            if ((rc = ensure(ctx, ctx->gpix, (size_t)s.path_ranges * (size_t)s.jac_rows() * s.Pb * sizeof(double))) != DRT_OK) return rc;
+        if (s.neq) {
+            // k_normal_eq: a memory-bound grid-stride pass per channel -- up to four blocks per CU and channel keep twelve resident
+            s.neq_vw = (s.Pb & 1u) ? 1 : 2;
+            const uint64_t items = ((uint64_t)s.Pb + s.neq_vw - 1) / s.neq_vw;
+            s.neq_blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((items + DRT_BLOCK - 1) / DRT_BLOCK, (uint64_t)ctx->n_cu * 4));
+            if ((rc = ensure(ctx, ctx->neq_part, (size_t)3 * s.neq_blocks * DRT_NEQ_VALUES(DRT_FAST_PARAMS) * sizeof(double))) != DRT_OK) return rc;
+        }
         if (s.mesh_path) {   // the traversal stack's entries beyond the ones in LDS, per thread of the grid (one area per k_path stream)
             const size_t threads = ((s.path_waves + DRT_BLOCK / DRT_WAVE - 1) / (DRT_BLOCK / DRT_WAVE)) * DRT_BLOCK;
             if ((rc = ensure(ctx, ctx->mesh_ovf[(s.overlap_ok && (ctx->slot & 1)) ? 1 : 0],
@@ -832,6 +862,28 @@ int path_batch(Shard<R>& s)
             hipLaunchKernelGGL(k_path_finish, dim3(gb), dim3(DRT_BLOCK), 0, ctx->stream, pa, (const double*)gpix, s.d_out_gimg, gb,
                                (const double*)nullptr, 0, 0, DRT_FAST_PARAMS * 3, (double*)nullptr, 0u, (const uint32_t*)counts,
                                0u, s.totals);
+        }
+        if (s.neq) {
+            // the normal equations: per-pixel products reduced per block, then over the blocks (timed in the reduction's slot)
+            const NormalEqRequest& q = *s.neq;
+            uint32_t mask = 0;
+            for (int p2 = 0; p2 < ctx->n_params && p2 < DRT_FAST_PARAMS; ++p2)
+                mask |= (p2 < ctx->n_user_params && ctx->requires_grad[(size_t)p2]) ? 1u << p2 : 0u;
+            const int npw = np_width(ctx->n_params, DRT_FAST_PARAMS);
+            double* part = (double*)ctx->neq_part.p;
+            DRT_TIMED(s, DRT_K_GRADREDUCE, with_int<4, 8>(npw, [&](auto np) {
+                with_bool(s.neq_vw == 2, [&](auto wide) {
+                    hipLaunchKernelGGL((k_normal_eq<decltype(np)::value, decltype(wide)::value ? 2 : 1>), dim3(s.neq_blocks, 3), dim3(DRT_BLOCK), 0, ctx->stream, pa,
+                                       (const double*)gpix, (const double*)fpart, ctx->n_params, ctx->n_user_params, mask, q.d_target, q.d_residual, q.d_jacobian, part);
+                    return 0;
+                });
+                return 0;
+            }));
+            DRT_TIMED(s, DRT_K_GRADREDUCE,
+                      hipLaunchKernelGGL(k_normal_eq_finish, dim3(3 * DRT_NEQ_VALUES(npw)), dim3(DRT_BLOCK), 0, ctx->stream, (const double*)part,
+                                         (int)s.neq_blocks, npw, ctx->n_user_params, q.d_A, q.d_b, q.d_loss));
+            st->units[DRT_K_GRADREDUCE] += (uint64_t)a.Pb;
+            st->path_bytes += (uint64_t)pa.n_ranges * a.Pb * (uint64_t)s.jac_rows() * sizeof(double);
         }
         s.path_finished = true;
         return DRT_OK;
@@ -1130,8 +1182,9 @@ int render_impl(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_p
     s.d_scene = sizeof(R) == 4 ? (const DevScene<R>*)ctx->d_scene_f : (const DevScene<R>*)ctx->d_scene_d;
     s.d_params = sizeof(R) == 4 ? (const R*)ctx->d_params_f : (const R*)ctx->d_params_d;
     memcpy(&s.bvh, sizeof(R) == 4 ? (const void*)&ctx->bvh_f : (const void*)&ctx->bvh_d, sizeof s.bvh);
-    s.fwd_tangent = tangent != nullptr;
-    s.keep_sums = tangent && tangent->keep_sums;
+    s.neq = tangent ? tangent->neq : nullptr;
+    s.fwd_tangent = tangent != nullptr && !s.neq;
+    s.keep_sums = s.fwd_tangent && tangent->keep_sums;
     if (s.fwd_tangent)
         s.d_params = (const R*)tangent->d_params;
     shard_plan(s);
@@ -1141,6 +1194,10 @@ int render_impl(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_p
                         : "render_tangent: the tangent image comes from the one-launch path kernel, which this render does not take "
                           "(bounces_per_launch >= 1, DRT_RENDER_UNFUSED, a DRT_HIP_* setting that forces the queue wavefront, or a scene its "
                           "intersection program does not cover)");
+    if (s.neq && (!s.use_path || s.mesh_path || !s.path_finish || s.path.op != PathOp::jacobian))
+        return fail(ctx, DRT_ERR_UNSUPPORTED, "normal equations: they come from the one-launch path kernel's Jacobian form over the whole shard in one "
+                                              "batch, which this render does not take (a DRT_HIP_* setting that forces the queue wavefront or a batch size, "
+                                              "more than 2^31 camera samples, or a scene its intersection program does not cover)");
     if (!ctx->user_header.empty()) {
         // caller-defined shape kinds live in the one-launch path kernel hiprtc compiles for the scene, nowhere else
         if (ctx->jit_mode <= 0)

@@ -22,6 +22,7 @@
 #pragma once
 
 #include <cstdint>
+#include <cmath>
 #include <cstring>
 #include <map>
 #include <memory>
@@ -768,6 +769,133 @@ inline Stats render_tangent(const Scene<T>& scene, const Camera<T>& cam, const P
             tangent_img[i][c] = T(trgb[i * 3 + c]);
         }
     return st;
+}
+
+// ---- the Gauss-Newton normal equations of a frame (drt_hip_render_normal_equations) --------------------------------
+// Per colour channel ch (channels do not mix): A[ch] = J^T J (P x P, row-major), b[ch] = J^T r, loss[ch] = r . r over the frame's pixels,
+// with J the per-pixel derivative of the radiance with respect to that channel of every parameter of the scene, in the order of
+// `handles` (FlatScene's: the order the scene's shapes name them).
+template <typename T>
+struct NormalEquations {
+    std::size_t n_params = 0;
+    std::vector<double> A, b, loss;             // 3 x P x P, 3 x P, 3
+    std::vector<uint8_t> requires_grad;         // per parameter: rows that take part in solve()
+    std::vector<Vector<T, 3, true>> handles;    // the parameters, sharing the scene's nodes
+    Stats stats;
+
+    // The Levenberg-Marquardt step: per channel, (A + lambda diag A) step = -b over the rows that require gradients, by a Cholesky
+    // factorisation.  -> the step per (handle, channel), step[p * 3 + ch]; 0 for rows that require none.  Throws where the damped
+    // matrix of a channel is not positive definite (a parameter no pixel depends on: give it lambda > 0 and a nonzero diagonal, or
+    // requires_grad = false).
+    std::vector<double> solve(double lambda) const
+    {
+        const std::size_t P = n_params;
+        std::vector<double> step(P * 3, 0.0);
+        std::vector<std::size_t> rows;
+        for (std::size_t p = 0; p < P; ++p)
+            if (p >= requires_grad.size() || requires_grad[p])
+                rows.push_back(p);
+        const std::size_t n = rows.size();
+        std::vector<double> L(n * n), y(n);
+        for (int ch = 0; ch < 3; ++ch) {
+            const double* Ac = A.data() + (std::size_t)ch * P * P;
+            const double* bc = b.data() + (std::size_t)ch * P;
+            // M = A + lambda diag A = L L^T (lower triangle, row by row)
+            for (std::size_t i = 0; i < n; ++i)
+                for (std::size_t j = 0; j <= i; ++j) {
+                    double v = Ac[rows[i] * P + rows[j]] * (i == j ? 1.0 + lambda : 1.0);
+                    for (std::size_t k = 0; k < j; ++k)
+                        v -= L[i * n + k] * L[j * n + k];
+                    if (i == j) {
+                        if (!(v > 0.0))
+                            throw std::runtime_error("drt::hip::NormalEquations::solve: the damped matrix of a channel is not positive definite");
+                        L[i * n + i] = std::sqrt(v);
+                    } else
+                        L[i * n + j] = v / L[j * n + j];
+                }
+            for (std::size_t i = 0; i < n; ++i) {          // L y = -b
+                double v = -bc[rows[i]];
+                for (std::size_t k = 0; k < i; ++k)
+                    v -= L[i * n + k] * y[k];
+                y[i] = v / L[i * n + i];
+            }
+            for (std::size_t ii = n; ii-- > 0;) {           // L^T x = y
+                double v = y[ii];
+                for (std::size_t k = ii + 1; k < n; ++k)
+                    v -= L[k * n + ii] * step[rows[k] * 3 + (std::size_t)ch];
+                step[rows[ii] * 3 + (std::size_t)ch] = v / L[ii * n + ii];
+            }
+        }
+        return step;
+    }
+};
+
+// What the residual of normal_equations() is taken from: a target image (r = this render's own pixel means - target: one render per
+// step, J and r share their samples) or the caller's residual (e.g. from an independently seeded forward render)
+template <typename T>
+struct TargetOrResidual {
+    const Vector<T, 3>* image = nullptr;   // width x height
+    bool is_residual = false;
+    static TargetOrResidual target(const Vector<T, 3>* img) { TargetOrResidual t; t.image = img; return t; }
+    static TargetOrResidual residual(const Vector<T, 3>* img) { TargetOrResidual t; t.image = img; t.is_residual = true; return t; }
+};
+
+// One render -> A, b, loss.  Single device; throws (std::runtime_error, with the library's message: "normal equations") where the
+// device refuses: more than 8 parameters, a mesh, bounces_per_launch >= 1, the reverse-mode options, several devices.
+template <typename T>
+inline NormalEquations<T> normal_equations(const Scene<T>& scene, const Camera<T>& cam, const Pathtracer<T>& tracer, std::size_t spp,
+                                           const Options& opt, const TargetOrResidual<T>& target_or_residual, Vector<T, 3>* img = nullptr)
+{
+    if (opt.backward || opt.unbiased || opt.sample_loss_l2)
+        throw std::runtime_error("drt::hip::normal_equations: the normal equations take no reverse-mode option (backward, unbiased, sample_loss_l2)");
+    if (opt.devices.size() > 1)
+        throw std::runtime_error("drt::hip::normal_equations: the normal equations come from one device (render shards on plain contexts and add them)");
+    if (!target_or_residual.image)
+        throw std::runtime_error("drt::hip::normal_equations: the normal equations need a target or a residual image");
+    FlatScene<T> flat = flatten(scene);
+    const drt_camera_desc cd = describe(cam);
+    const std::size_t npix = cam.width() * cam.height(), P = flat.handles.size();
+    std::vector<float> in(npix * 3), rgb(npix * 3, 0.f);
+    for (std::size_t i = 0; i < npix; ++i)
+        for (int c = 0; c < 3; ++c)
+            in[i * 3 + c] = (float)double(real(target_or_residual.image[i][c]));
+    NormalEquations<T> ne;
+    ne.n_params = P;
+    ne.A.assign(3 * P * P, 0.0);
+    ne.b.assign(3 * P, 0.0);
+    ne.loss.assign(3, 0.0);
+    ne.requires_grad = flat.requires_grad;
+    ne.handles = flat.handles;
+    std::unique_ptr<Context> own;
+    if (!opt.reuse_context)
+        own.reset(new Context(opt.devices.empty() ? 0 : opt.devices[0]));
+    Context& ctx = own ? *own : pooled_context(opt.devices.empty() ? 0 : opt.devices[0]);
+    std::lock_guard<std::mutex> lock(ctx.mutex());
+    ctx.set_scene(flat);
+    drt_render_params rp{};
+    rp.spp = (int32_t)spp;
+    rp.min_bounces = (int32_t)tracer.min_bounces();
+    rp.absorb = tracer.absorb();
+    rp.max_depth = opt.max_depth;
+    rp.seed = opt.seed;
+    rp.flags = opt.f64 ? DRT_RENDER_F64 : 0u;
+    rp.batch_paths = opt.batch_paths;
+    rp.bounces_per_launch = opt.bounces_per_launch;
+    drt_hip_stats st{};
+    std::vector<double> dummy(1);
+    ctx.check(drt_hip_render_normal_equations(ctx.get(), &cd, &rp, target_or_residual.is_residual ? nullptr : in.data(),
+                                              target_or_residual.is_residual ? in.data() : nullptr, rgb.data(), P ? ne.A.data() : dummy.data(),
+                                              P ? ne.b.data() : dummy.data(), ne.loss.data(), nullptr, &st),
+              "drt_hip_render_normal_equations");
+    if (img)
+        for (std::size_t i = 0; i < npix; ++i)
+            for (int c = 0; c < 3; ++c)
+                img[i][c] = T(rgb[i * 3 + c]);
+    ne.stats.paths = st.paths;
+    ne.stats.segments = st.segments;
+    ne.stats.capped_paths = st.capped_paths;
+    ne.stats.ms = st.ms_total;
+    return ne;
 }
 
 // A Scene<Dual<U>> for the device: the real parts as the scene, the dual parts of its PARAMETERS as the direction (n_params x 3).

@@ -411,6 +411,35 @@ int drt_hip_render_tangent(drt_hip_ctx* ctx, const drt_camera_desc* cam, const d
 int drt_hip_render_tangent_double(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_params* rp,
                                   const double* param_tangent, double* out_rgb /* may be NULL */,
                                   double* out_tangent_rgb, drt_hip_stats* stats);
+/* The Gauss-Newton normal equations of a frame, and on request its whole Jacobian image, from ONE render.  With P = n_params and
+ *   J[x,p,ch] = what drt_hip_render_tangent returns at pixel x, channel ch, along the direction that is 1 on the three channels of
+ *               parameter p and 0 elsewhere (same camera, same rp); 0 for a parameter with requires_grad == 0
+ * -- a radiance channel depends on the same channel of every parameter only, so J is block-diagonal by channel -- the call returns
+ *   out_A[ch][p][q] = sum_x J[x,p,ch] J[x,q,ch]   (3 x P x P doubles, symmetric, both triangles written)
+ *   out_b[ch][p]    = sum_x J[x,p,ch] r[x,ch]     (3 x P)
+ *   out_loss[ch]    = sum_x r[x,ch]^2             (3, may be NULL)
+ * summed over the pixels of this call's shard (the caller adds shards), in fp64, without atomics: the same call returns the same bits.
+ * Exactly one of target_rgb and residual_rgb (H x W x 3 floats) is given: with target_rgb, r = this render's own pixel means - target --
+ * one render per step, but J and r then share their samples and b is biased (tools/fit_albedo.py says by how much); with residual_rgb,
+ * r is the caller's, e.g. from an independently seeded forward render, and out_b is what drt_hip_render returns as out_param_grad / spp
+ * for that adjoint.  out_jacobian (P x H x W x 3 floats, may be NULL) receives the P images drt_hip_render_gradient_image returns one
+ * at a time; out_rgb may be NULL; of both only this shard's rows are written.  DRT_RENDER_DEVICE_OUT: every image-sized pointer and
+ * out_A, out_b, out_loss are device pointers, written in the order of drt_hip_stream().  DRT_RENDER_F64, _SYNC, _TIMING (k_normal_eq is
+ * counted in the gradient reduction's slot) and shards as in drt_hip_render_tangent.
+ * Roulette-terminated renders are allowed, but a lane of the path kernel is a pixel here, so they run in lockstep: every wave lasts as
+ * long as the longest of its 64 paths, where the regenerating form drt_hip_render takes for such renders keeps its lanes busy (the
+ * reference's defaults, -b 1 -p 0.5: 0.87 against 0.50 ms on a 512 x 512 x 64 frame).
+ * DRT_ERR_UNSUPPORTED (the message says "normal equations"): more than DRT_FAST_PARAMS (8) parameters -- J^T J v by tangent + reverse
+ * is the matrix-free route for those; a mirror material costs one of the 8 columns (its internal colour constant), so a scene with a
+ * mirror may have 7 --, more than 2^31 camera samples in the frame (the shard renders in one batch; batch_paths is ignored), a render
+ * that a DRT_HIP_* setting forces onto the queue wavefront or into several batches, a scene that holds a triangle mesh, bounces_per_launch >= 1, DRT_RENDER_UNFUSED, _UNBIASED,
+ * _LOSS_L2, _ALLREDUCE, _ALLREDUCE_ASYNC, a group context.  DRT_ERR_INVALID: both or neither of target_rgb and residual_rgb, NULL
+ * out_A or out_b, a value of a host image that is not finite, asynchronous frames in flight.  The context stays usable after either. */
+int drt_hip_render_normal_equations(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_params* rp,
+                                    const float* target_rgb /* or NULL */, const float* residual_rgb /* or NULL */,
+                                    float* out_rgb /* may be NULL */, double* out_A /* 3 x P x P */, double* out_b /* 3 x P */,
+                                    double* out_loss /* 3, may be NULL */, float* out_jacobian /* P x H x W x 3, may be NULL */,
+                                    drt_hip_stats* stats);
 /* stream the context launches on (a hipStream_t), for event timing / interop */
 void* drt_hip_stream(drt_hip_ctx* ctx);
 int drt_hip_synchronize(drt_hip_ctx* ctx);
