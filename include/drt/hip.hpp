@@ -347,11 +347,6 @@ public:
         m_has_scene = true;
     }
 
-private:
-    drt_hip_ctx* m_ctx = nullptr;
-    uint64_t m_scene_key = 0;
-    std::vector<double> m_params;      // the parameter values the device holds
-public:
     // host buffers of the (at most DRT_HIP_FRAMES_IN_FLIGHT) frames in flight: kept, so that a frame costs no 3 MB allocation
     std::vector<float> frame_pool[DRT_HIP_FRAMES_IN_FLIGHT];
     std::vector<double> grad_pool[DRT_HIP_FRAMES_IN_FLIGHT];
@@ -372,11 +367,13 @@ public:
         }
         return m_sync_frame.data();
     }
+
 private:
+    drt_hip_ctx* m_ctx = nullptr;
+    uint64_t m_scene_key = 0;
+    std::vector<double> m_params;      // the parameter values the device holds
     std::vector<float> m_sync_frame;
     bool m_sync_pinned = false;
-public:
-private:
     bool m_has_scene = false;
     std::mutex m_mutex;        // a context is not thread-safe: pooled ones are locked for the duration of a call
 };
@@ -418,6 +415,113 @@ inline void release_contexts()
     p.contexts.clear();
 }
 
+// ---- what the entry points below share ------------------------------------------------------------------------------
+namespace detail {
+// THE place a drt_render_params is filled.  Every entry point renders whole frames: n_shards = 1 (the library reads band_rows
+// only where it deals bands out -- a group context to its devices -- and normalises n_shards <= 1 to 1: csrc/drt_render.h).
+inline drt_render_params render_params(double absorb, std::size_t min_bounces, std::size_t spp, const Options& opt, uint32_t flags)
+{
+    drt_render_params rp{};
+    rp.spp = (int32_t)spp;
+    rp.min_bounces = (int32_t)min_bounces;
+    rp.absorb = absorb;
+    rp.max_depth = opt.max_depth;
+    rp.seed = opt.seed;
+    rp.shard = 0;
+    rp.n_shards = 1;
+    rp.band_rows = opt.band_rows;
+    rp.flags = flags;
+    rp.batch_paths = opt.batch_paths;
+    rp.bounces_per_launch = opt.bounces_per_launch;
+    return rp;
+}
+inline uint32_t f64_flag(const Options& opt) { return opt.f64 ? DRT_RENDER_F64 : 0u; }
+// render / submit: the operator and the per-sample loss are notions of the backward pass
+inline uint32_t reverse_flags(const Options& opt)
+{
+    return f64_flag(opt) | (opt.backward ? DRT_RENDER_BACKWARD : 0u) | (opt.backward && opt.unbiased ? DRT_RENDER_UNBIASED : 0u) |
+           (opt.backward && opt.sample_loss_l2 ? DRT_RENDER_LOSS_L2 : 0u);
+}
+inline Stats to_stats(const drt_hip_stats& st)
+{
+    Stats out;
+    out.paths = st.paths;
+    out.segments = st.segments;
+    out.capped_paths = st.capped_paths;
+    out.ms = st.ms_total;
+    return out;
+}
+
+// A context for the duration of one call -- the call's own (Options::reuse_context off: destroyed with the session) or the pooled
+// one of its devices --, locked, holding the scene.
+struct Session {
+    std::unique_ptr<Context> own;
+    Context& ctx;
+    std::lock_guard<std::mutex> lock;
+    // render: every device of opt.devices (several: one group context)
+    template <typename T>
+    static Session on_all_devices(const Options& opt, const FlatScene<T>& flat) { return Session(opt.devices, opt.reuse_context, flat); }
+    // the single-device entry points: the first device listed, device 0 where none is
+    template <typename T>
+    static Session on_first_device(const Options& opt, const FlatScene<T>& flat)
+    {
+        return Session(std::vector<int>{opt.devices.empty() ? 0 : opt.devices[0]}, opt.reuse_context, flat);
+    }
+
+private:
+    template <typename T>
+    Session(const std::vector<int>& devices, bool reuse_context, const FlatScene<T>& flat)
+        : own(reuse_context ? nullptr : new Context(devices)), ctx(own ? *own : pooled_context(devices)), lock(ctx.mutex())
+    {
+        ctx.set_scene(flat);
+    }
+};
+
+// width x height pixels <-> the library's buffers of 3 values per pixel
+template <typename T>
+inline std::vector<float> to_floats(const Vector<T, 3>* src, std::size_t npix)
+{
+    std::vector<float> out(npix * 3);
+    for (std::size_t i = 0; i < npix; ++i)
+        for (int c = 0; c < 3; ++c)
+            out[i * 3 + c] = float(real(src[i][c]));
+    return out;
+}
+template <typename F, typename T>
+inline void from_buffer(const F* src, std::size_t npix, Vector<T, 3>* dst)
+{
+    if (!dst)
+        return;
+    for (std::size_t i = 0; i < npix; ++i)
+        for (int c = 0; c < 3; ++c)
+            dst[i][c] = T(src[i * 3 + c]);
+}
+
+// the returned gradients ADDED to the parameters that take one, like m_grad += grad (vector.hpp:185-188)
+template <typename T>
+inline void accumulate_grads(std::vector<Vector<T, 3, true>>& handles, const std::vector<uint8_t>& requires_grad, const double* grads)
+{
+    for (std::size_t p = 0; p < handles.size(); ++p) {
+        if (!requires_grad[p])
+            continue;
+        Vector<T, 3> g(T(0));
+        for (int c = 0; c < 3; ++c)
+            g[c] = T(grads[p * 3 + c]);
+        handles[p].grad() += g;
+    }
+}
+
+// the scene's parameter that shares `handle`'s node
+template <typename T>
+inline int param_index(const FlatScene<T>& flat, const Vector<T, 3, true>& handle, const char* message_if_unused)
+{
+    for (std::size_t p = 0; p < flat.handles.size(); ++p)
+        if (flat.handles[p].id() == handle.id())
+            return (int)p;
+    throw std::runtime_error(message_if_unused);
+}
+} // namespace detail
+
 // img: width*height row-major (render.cpp:66,82); adjoint: optional per-pixel seed, same layout.
 template <typename T>
 inline Stats render(const Scene<T>& scene, const Camera<T>& cam, const Pathtracer<T>& tracer, std::size_t spp,
@@ -426,74 +530,25 @@ inline Stats render(const Scene<T>& scene, const Camera<T>& cam, const Pathtrace
     FlatScene<T> flat = flatten(scene);
     const drt_camera_desc cd = describe(cam);
     const std::size_t npix = cam.width() * cam.height();
-    const int n_dev = (int)opt.devices.size();
-    if (n_dev < 1)
+    if (opt.devices.empty())
         throw std::runtime_error("drt::hip::render: no device given");
-
-    std::vector<float> adj;
-    if (adjoint) {
-        adj.resize(npix * 3);
-        for (std::size_t i = 0; i < npix; ++i)
-            for (int c = 0; c < 3; ++c)
-                adj[i * 3 + c] = float(real(adjoint[i][c]));
-    }
-    const std::size_t P = flat.requires_grad.size();
-    std::vector<float> own_frame;
-    const float* frame = nullptr;
-    std::vector<double> grads(P * 3, 0.0);
+    const std::vector<float> adj = adjoint ? detail::to_floats(adjoint, npix) : std::vector<float>();
+    const drt_render_params rp = detail::render_params(tracer.absorb(), tracer.min_bounces(), spp, opt, detail::reverse_flags(opt));
+    std::vector<double> grads(flat.requires_grad.size() * 3, 0.0);
     drt_hip_stats st{};
     {
-        std::unique_ptr<Context> own;
-        if (!opt.reuse_context)
-            own.reset(new Context(opt.devices));
-        Context& ctx = own ? *own : pooled_context(opt.devices);
-        std::lock_guard<std::mutex> lock(ctx.mutex());
-        ctx.set_scene(flat);
-        float* out = nullptr;
-        if (own) {
-            own_frame.assign(npix * 3, 0.f);
-            out = own_frame.data();
-        } else
-            out = ctx.sync_frame(npix * 3, n_dev == 1);      // (the pooled context's own buffer, pinned on a plain context)
-        frame = out;
-        drt_render_params rp{};
-        rp.spp = (int32_t)spp;
-        rp.min_bounces = (int32_t)tracer.min_bounces();
-        rp.absorb = tracer.absorb();
-        rp.max_depth = opt.max_depth;
-        rp.seed = opt.seed;
-        rp.shard = 0;
-        rp.n_shards = 1;                // a group context deals the bands to its devices itself
-        rp.band_rows = opt.band_rows;
-        rp.flags = (opt.backward ? DRT_RENDER_BACKWARD : 0u) | (opt.f64 ? DRT_RENDER_F64 : 0u) |
-                   (opt.backward && opt.unbiased ? DRT_RENDER_UNBIASED : 0u) |
-                   (opt.backward && opt.sample_loss_l2 ? DRT_RENDER_LOSS_L2 : 0u);
-        rp.batch_paths = opt.batch_paths;
-        rp.bounces_per_launch = opt.bounces_per_launch;
-        // n_dev > 1: out_param_grad comes back ALREADY summed over the devices (one ncclAllReduce in the library)
-        ctx.check(drt_hip_render(ctx.get(), &cd, &rp, adjoint ? adj.data() : nullptr, out,
-                                 opt.backward ? grads.data() : nullptr, &st),
-                  "drt_hip_render");
-        for (std::size_t i = 0; i < npix; ++i)                 // (under the context's lock: the buffer is the context's)
-            for (int c = 0; c < 3; ++c)
-                img[i][c] = T(frame[i * 3 + c]);
+        detail::Session s = detail::Session::on_all_devices(opt, flat);
+        // the frame: a buffer of this call's beside a context of its own, else the pooled context's (pinned on a plain context)
+        std::vector<float> own_frame(s.own ? npix * 3 : 0, 0.f);
+        float* frame = s.own ? own_frame.data() : s.ctx.sync_frame(npix * 3, opt.devices.size() == 1);
+        // several devices: out_param_grad comes back ALREADY summed over them (one ncclAllReduce in the library)
+        s.ctx.check(drt_hip_render(s.ctx.get(), &cd, &rp, adjoint ? adj.data() : nullptr, frame, opt.backward ? grads.data() : nullptr, &st),
+                    "drt_hip_render");
+        detail::from_buffer(frame, npix, img);                 // (under the context's lock: the buffer is the context's)
     }
-    Stats total;
-    total.paths = st.paths;
-    total.segments = st.segments;
-    total.capped_paths = st.capped_paths;
-    total.ms = st.ms_total;
-    if (opt.backward) {
-        for (std::size_t p = 0; p < P; ++p) {
-            if (!flat.requires_grad[p])
-                continue;
-            Vector<T, 3> g(T(0));
-            for (int c = 0; c < 3; ++c)
-                g[c] = T(grads[p * 3 + c]);
-            flat.handles[p].grad() += g;          // accumulate, like m_grad += grad
-        }
-    }
-    return total;
+    if (opt.backward)
+        detail::accumulate_grads(flat.handles, flat.requires_grad, grads.data());
+    return detail::to_stats(st);
 }
 
 // ---- frames in flight ----------------------------------------------------------------------------------
@@ -542,25 +597,10 @@ public:
         const int rc = drt_hip_wait(ctx->get(), m_ticket, &st);
         ctx->slot_in_flight[m_slot] = false;
         ctx->check(rc, "drt_hip_wait");
-        const std::size_t npix = m_npix;
-        for (std::size_t i = 0; i < npix; ++i)
-            for (int c = 0; c < 3; ++c)
-                m_img[i][c] = T(m_frame[i * 3 + c]);
+        detail::from_buffer(m_frame, m_npix, m_img);
         if (m_backward)
-            for (std::size_t p = 0; p < m_handles.size(); ++p) {
-                if (!m_requires_grad[p])
-                    continue;
-                Vector<T, 3> g(T(0));
-                for (int c = 0; c < 3; ++c)
-                    g[c] = T(m_grads[p * 3 + c]);
-                m_handles[p].grad() += g;
-            }
-        Stats total;
-        total.paths = st.paths;
-        total.segments = st.segments;
-        total.capped_paths = st.capped_paths;
-        total.ms = st.ms_total;
-        return total;
+            detail::accumulate_grads(m_handles, m_requires_grad, m_grads);
+        return detail::to_stats(st);
     }
 
 private:
@@ -598,13 +638,7 @@ inline Pending<T> submit(const Scene<T>& scene, const Camera<T>& cam, const Path
     FlatScene<T> flat = flatten(scene);
     const drt_camera_desc cd = describe(cam);
     const std::size_t npix = cam.width() * cam.height();
-    std::vector<float> adj;
-    if (adjoint) {
-        adj.resize(npix * 3);
-        for (std::size_t i = 0; i < npix; ++i)
-            for (int c = 0; c < 3; ++c)
-                adj[i * 3 + c] = float(real(adjoint[i][c]));
-    }
+    const std::vector<float> adj = adjoint ? detail::to_floats(adjoint, npix) : std::vector<float>();
     Pending<T> f;
     f.m_img = img;
     f.m_backward = opt.backward;
@@ -622,19 +656,7 @@ inline Pending<T> submit(const Scene<T>& scene, const Camera<T>& cam, const Path
     f.m_grads = ctx.grad_pool[slot].data();
     f.m_npix = npix;
     ctx.set_scene(flat);
-    drt_render_params rp{};
-    rp.spp = (int32_t)spp;
-    rp.min_bounces = (int32_t)tracer.min_bounces();
-    rp.absorb = tracer.absorb();
-    rp.max_depth = opt.max_depth;
-    rp.seed = opt.seed;
-    rp.n_shards = 1;
-    rp.band_rows = opt.band_rows;
-    rp.flags = (opt.backward ? DRT_RENDER_BACKWARD : 0u) | (opt.f64 ? DRT_RENDER_F64 : 0u) |
-               (opt.backward && opt.unbiased ? DRT_RENDER_UNBIASED : 0u) |
-               (opt.backward && opt.sample_loss_l2 ? DRT_RENDER_LOSS_L2 : 0u);
-    rp.batch_paths = opt.batch_paths;
-    rp.bounces_per_launch = opt.bounces_per_launch;
+    const drt_render_params rp = detail::render_params(tracer.absorb(), tracer.min_bounces(), spp, opt, detail::reverse_flags(opt));
     ctx.check(drt_hip_render_async(ctx.get(), &cd, &rp, adjoint ? adj.data() : nullptr, f.m_frame,
                                    opt.backward ? f.m_grads : nullptr, &f.m_ticket),
               "drt_hip_render_async");
@@ -653,42 +675,19 @@ inline Stats render_gradient_image(const Scene<T>& scene, const Camera<T>& cam, 
                                    Vector<T, 3>* gimg, const Options& opt = Options())
 {
     FlatScene<T> flat = flatten(scene);
-    int index = -1;
-    for (std::size_t p = 0; p < flat.handles.size(); ++p)
-        if (flat.handles[p].id() == param.id())
-            index = (int)p;
-    if (index < 0)
-        throw std::runtime_error("drt::hip::render_gradient_image: the parameter is not used by the scene");
+    const int index = detail::param_index(flat, param, "drt::hip::render_gradient_image: the parameter is not used by the scene");
     const drt_camera_desc cd = describe(cam);
     const std::size_t npix = cam.width() * cam.height();
     std::vector<float> rgb(npix * 3, 0.f), grad(npix * 3, 0.f);
-    std::unique_ptr<Context> own;
-    if (!opt.reuse_context)
-        own.reset(new Context(opt.devices.empty() ? 0 : opt.devices[0]));
-    Context& ctx = own ? *own : pooled_context(opt.devices.empty() ? 0 : opt.devices[0]);
-    std::lock_guard<std::mutex> lock(ctx.mutex());
-    ctx.set_scene(flat);
-    drt_render_params rp{};
-    rp.spp = (int32_t)spp;
-    rp.min_bounces = (int32_t)tracer.min_bounces();
-    rp.absorb = tracer.absorb();
-    rp.max_depth = opt.max_depth;
-    rp.seed = opt.seed;
-    rp.flags = opt.f64 ? DRT_RENDER_F64 : 0u;
-    rp.batch_paths = opt.batch_paths;
+    drt_render_params rp = detail::render_params(tracer.absorb(), tracer.min_bounces(), spp, opt, detail::f64_flag(opt));
+    rp.bounces_per_launch = 0;      // NOT the caller's: the gradient image keeps the route the library picks (>= 1 would move it to the queues)
     drt_hip_stats st{};
-    ctx.check(drt_hip_render_gradient_image(ctx.get(), &cd, &rp, index, nullptr, rgb.data(), grad.data(), &st),
-              "drt_hip_render_gradient_image");
-    for (std::size_t i = 0; i < npix; ++i)
-        for (int c = 0; c < 3; ++c) {
-            if (img) img[i][c] = T(rgb[i * 3 + c]);
-            gimg[i][c] = T(grad[i * 3 + c]);
-        }
-    Stats out;
-    out.paths = st.paths;
-    out.segments = st.segments;
-    out.ms = st.ms_total;
-    return out;
+    detail::Session s = detail::Session::on_first_device(opt, flat);
+    s.ctx.check(drt_hip_render_gradient_image(s.ctx.get(), &cd, &rp, index, nullptr, rgb.data(), grad.data(), &st),
+                "drt_hip_render_gradient_image");
+    detail::from_buffer(rgb.data(), npix, img);
+    detail::from_buffer(grad.data(), npix, gimg);
+    return detail::to_stats(st);
 }
 
 // ---- forward mode ----------------------------------------------------------------------------------------------
@@ -703,40 +702,20 @@ inline Stats tangent_call(const char* who, const FlatScene<T>& flat, const drt_c
     if (opt.backward || opt.unbiased || opt.sample_loss_l2)
         throw std::runtime_error(std::string(who) + ": forward mode takes no reverse-mode option (backward, unbiased, sample_loss_l2)");
     const std::size_t n = (std::size_t)cd.width * (std::size_t)cd.height * 3;
-    img.assign(n, 0.0);
-    timg.assign(n, 0.0);
-    std::unique_ptr<Context> own;
-    if (!opt.reuse_context)
-        own.reset(new Context(opt.devices.empty() ? 0 : opt.devices[0]));
-    Context& ctx = own ? *own : pooled_context(opt.devices.empty() ? 0 : opt.devices[0]);
-    std::lock_guard<std::mutex> lock(ctx.mutex());
-    ctx.set_scene(flat);
-    drt_render_params rp{};
-    rp.spp = (int32_t)spp;
-    rp.min_bounces = (int32_t)min_bounces;
-    rp.absorb = absorb;
-    rp.max_depth = opt.max_depth;
-    rp.seed = opt.seed;
-    rp.flags = opt.f64 ? DRT_RENDER_F64 : 0u;
-    rp.batch_paths = opt.batch_paths;
-    rp.bounces_per_launch = opt.bounces_per_launch;
+    const drt_render_params rp = render_params(absorb, min_bounces, spp, opt, f64_flag(opt));
     drt_hip_stats st{};
-    if (opt.f64)
-        ctx.check(drt_hip_render_tangent_double(ctx.get(), &cd, &rp, v.data(), img.data(), timg.data(), &st), "drt_hip_render_tangent_double");
-    else {
+    Session s = Session::on_first_device(opt, flat);
+    if (opt.f64) {
+        img.assign(n, 0.0);
+        timg.assign(n, 0.0);
+        s.ctx.check(drt_hip_render_tangent_double(s.ctx.get(), &cd, &rp, v.data(), img.data(), timg.data(), &st), "drt_hip_render_tangent_double");
+    } else {
         std::vector<float> rgb(n, 0.f), trgb(n, 0.f);
-        ctx.check(drt_hip_render_tangent(ctx.get(), &cd, &rp, v.data(), rgb.data(), trgb.data(), &st), "drt_hip_render_tangent");
-        for (std::size_t i = 0; i < n; ++i) {
-            img[i] = rgb[i];
-            timg[i] = trgb[i];
-        }
+        s.ctx.check(drt_hip_render_tangent(s.ctx.get(), &cd, &rp, v.data(), rgb.data(), trgb.data(), &st), "drt_hip_render_tangent");
+        img.assign(rgb.begin(), rgb.end());
+        timg.assign(trgb.begin(), trgb.end());
     }
-    Stats out;
-    out.paths = st.paths;
-    out.segments = st.segments;
-    out.capped_paths = st.capped_paths;
-    out.ms = st.ms_total;
-    return out;
+    return to_stats(st);
 }
 } // namespace detail
 
@@ -751,23 +730,15 @@ inline Stats render_tangent(const Scene<T>& scene, const Camera<T>& cam, const P
     FlatScene<T> flat = flatten(scene);
     std::vector<double> v(flat.handles.size() * 3, 0.0);
     for (const auto& t : tangents) {
-        int index = -1;
-        for (std::size_t p = 0; p < flat.handles.size(); ++p)
-            if (flat.handles[p].id() == t.first.id())
-                index = (int)p;
-        if (index < 0)
-            throw std::runtime_error("drt::hip::render_tangent: a listed parameter is not used by the scene");
+        const int index = detail::param_index(flat, t.first, "drt::hip::render_tangent: a listed parameter is not used by the scene");
         for (int c = 0; c < 3; ++c)
             v[(std::size_t)index * 3 + c] += double(real(t.second[c]));
     }
     std::vector<double> rgb, trgb;
     const Stats st = detail::tangent_call("drt::hip::render_tangent", flat, describe(cam), tracer.absorb(), tracer.min_bounces(), spp, v, rgb, trgb, opt);
     const std::size_t npix = cam.width() * cam.height();
-    for (std::size_t i = 0; i < npix; ++i)
-        for (int c = 0; c < 3; ++c) {
-            if (img) img[i][c] = T(rgb[i * 3 + c]);
-            tangent_img[i][c] = T(trgb[i * 3 + c]);
-        }
+    detail::from_buffer(rgb.data(), npix, img);
+    detail::from_buffer(trgb.data(), npix, tangent_img);
     return st;
 }
 
@@ -855,10 +826,8 @@ inline NormalEquations<T> normal_equations(const Scene<T>& scene, const Camera<T
     FlatScene<T> flat = flatten(scene);
     const drt_camera_desc cd = describe(cam);
     const std::size_t npix = cam.width() * cam.height(), P = flat.handles.size();
-    std::vector<float> in(npix * 3), rgb(npix * 3, 0.f);
-    for (std::size_t i = 0; i < npix; ++i)
-        for (int c = 0; c < 3; ++c)
-            in[i * 3 + c] = (float)double(real(target_or_residual.image[i][c]));
+    const std::vector<float> in = detail::to_floats(target_or_residual.image, npix);
+    std::vector<float> rgb(npix * 3, 0.f);
     NormalEquations<T> ne;
     ne.n_params = P;
     ne.A.assign(3 * P * P, 0.0);
@@ -866,35 +835,16 @@ inline NormalEquations<T> normal_equations(const Scene<T>& scene, const Camera<T
     ne.loss.assign(3, 0.0);
     ne.requires_grad = flat.requires_grad;
     ne.handles = flat.handles;
-    std::unique_ptr<Context> own;
-    if (!opt.reuse_context)
-        own.reset(new Context(opt.devices.empty() ? 0 : opt.devices[0]));
-    Context& ctx = own ? *own : pooled_context(opt.devices.empty() ? 0 : opt.devices[0]);
-    std::lock_guard<std::mutex> lock(ctx.mutex());
-    ctx.set_scene(flat);
-    drt_render_params rp{};
-    rp.spp = (int32_t)spp;
-    rp.min_bounces = (int32_t)tracer.min_bounces();
-    rp.absorb = tracer.absorb();
-    rp.max_depth = opt.max_depth;
-    rp.seed = opt.seed;
-    rp.flags = opt.f64 ? DRT_RENDER_F64 : 0u;
-    rp.batch_paths = opt.batch_paths;
-    rp.bounces_per_launch = opt.bounces_per_launch;
+    const drt_render_params rp = detail::render_params(tracer.absorb(), tracer.min_bounces(), spp, opt, detail::f64_flag(opt));
     drt_hip_stats st{};
     std::vector<double> dummy(1);
-    ctx.check(drt_hip_render_normal_equations(ctx.get(), &cd, &rp, target_or_residual.is_residual ? nullptr : in.data(),
-                                              target_or_residual.is_residual ? in.data() : nullptr, rgb.data(), P ? ne.A.data() : dummy.data(),
-                                              P ? ne.b.data() : dummy.data(), ne.loss.data(), nullptr, &st),
-              "drt_hip_render_normal_equations");
-    if (img)
-        for (std::size_t i = 0; i < npix; ++i)
-            for (int c = 0; c < 3; ++c)
-                img[i][c] = T(rgb[i * 3 + c]);
-    ne.stats.paths = st.paths;
-    ne.stats.segments = st.segments;
-    ne.stats.capped_paths = st.capped_paths;
-    ne.stats.ms = st.ms_total;
+    detail::Session s = detail::Session::on_first_device(opt, flat);
+    s.ctx.check(drt_hip_render_normal_equations(s.ctx.get(), &cd, &rp, target_or_residual.is_residual ? nullptr : in.data(),
+                                                target_or_residual.is_residual ? in.data() : nullptr, rgb.data(), P ? ne.A.data() : dummy.data(),
+                                                P ? ne.b.data() : dummy.data(), ne.loss.data(), nullptr, &st),
+                "drt_hip_render_normal_equations");
+    detail::from_buffer(rgb.data(), npix, img);
+    ne.stats = detail::to_stats(st);
     return ne;
 }
 

@@ -72,6 +72,17 @@ def test_host_api_known_answers(tmp_path):
     assert out.strip() == "ok", out
 
 
+def test_what_the_glue_sends_and_what_it_does_with_the_answers(tmp_path):
+    """tests/cpp/glue_calls.cpp: every entry point of drt::hip (include/drt/hip.hpp) against recording stubs of the drt_hip_*
+    functions -- the drt_render_params and camera each one sends, the C function it reaches, which pointers are NULL, where the
+    returned images, gradients, sums and statistics end up, and the exceptions with their texts.  libdrt_hip.so is not linked."""
+    exe = str(tmp_path / "glue_calls")
+    sh(["g++", "-O1", "-std=c++17", "-Wall", "-I" + os.path.join(ROOT, "include"),
+        os.path.join(ROOT, "tests", "cpp", "glue_calls.cpp"), "-o", exe, "-lpthread"])
+    out = sh([exe]).stdout
+    assert out.strip() == "ok", out
+
+
 def test_dual_numbers_end_to_end_match_reverse_mode(tmp_path):
     """SURVEY 8f rank 4 / README.md:140: T = Dual<double> through shapes, BxDFs and the path tracer
     (does not compile in the reference); forward-mode derivatives == reverse-mode gradients."""
@@ -322,6 +333,19 @@ int main()
         "-Wl,-rpath," + lib_dir, "-lpthread"])
     out = sh([exe])
     assert "bad 0" in out.stdout
+
+
+@pytest.mark.gpu
+def test_the_glue_adds_nothing_to_what_the_library_computes(tmp_path):
+    """tests/cpp/glue_adds_nothing.cpp: render (backward), submit + get, render_gradient_image, render_tangent (f32 and f64) and
+    normal_equations through drt::hip against the drt_hip_* function underneath, called directly with the same scene, camera and
+    parameters: every image, gradient, sum and count equal bit for bit."""
+    exe = str(tmp_path / "glue_adds_nothing")
+    lib_dir = os.path.join(ROOT, "differentiable-renderer_amd")
+    sh(["g++", "-O1", "-std=c++17", "-Wall", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "glue_adds_nothing.cpp"),
+        "-o", exe, "-L" + lib_dir, "-ldrt_hip", "-Wl,-rpath," + lib_dir, "-lpthread"])
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0 and "bad 0" in out.stdout, out.stdout + out.stderr
 
 
 @pytest.mark.gpu
