@@ -43,6 +43,7 @@ FRAMES_IN_FLIGHT = 4          # drt_hip_render_async: DRT_HIP_FRAMES_IN_FLIGHT
 MAX_DEPTH = 64
 K_RAYGEN, K_INTERSECT, K_SHADE, K_FILM, K_BACKWARD, K_GRADREDUCE, K_INTERSECT_MESH, K_PATH, K_COUNT = 0, 1, 2, 3, 4, 5, 6, 7, 8
 KERNEL_NAMES = ["raygen", "intersect", "shade", "film", "backward", "gradreduce", "intersect_mesh", "path"]
+MAX_DIRS = 8                 # DRT_HIP_MAX_DIRS: directions per render_tangents / render_normal_equations_along call
 ABI_VERSION = 8
 UNIQUE_ID_BYTES = 128
 
@@ -723,7 +724,8 @@ _ABI_SYMBOLS = ["drt_hip_abi_version", "drt_hip_device_count", "drt_hip_create",
                 "drt_hip_group_size", "drt_hip_device_pci_bus_id", "drt_hip_destroy",
                 "drt_hip_comm_unique_id", "drt_hip_comm_init_rank", "drt_hip_comm_size", "drt_hip_comm_destroy",
                 "drt_hip_upload_scene", "drt_hip_update_params", "drt_hip_set_specialisation", "drt_hip_render", "drt_hip_render_async", "drt_hip_wait",
-                "drt_hip_render_gradient_image", "drt_hip_render_tangent", "drt_hip_render_tangent_double", "drt_hip_render_normal_equations", "drt_hip_pin_host", "drt_hip_unpin_host", "drt_hip_stream",
+                "drt_hip_render_gradient_image", "drt_hip_render_tangent", "drt_hip_render_tangent_double", "drt_hip_render_normal_equations", "drt_hip_render_tangents",
+                "drt_hip_render_normal_equations_along", "drt_hip_pin_host", "drt_hip_unpin_host", "drt_hip_stream",
                 "drt_hip_synchronize", "drt_hip_last_error", "drt_hip_kernel_name"]
 
 
@@ -763,6 +765,11 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.drt_hip_render_tangent_double.argtypes = lib.drt_hip_render_tangent.argtypes
     lib.drt_hip_render_normal_equations.argtypes = [C.c_void_p, C.POINTER(CameraDesc), C.POINTER(RenderParamsDesc), C.c_void_p, C.c_void_p,
                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(HipStats)]
+    lib.drt_hip_render_tangents.argtypes = [C.c_void_p, C.POINTER(CameraDesc), C.POINTER(RenderParamsDesc), C.c_int32, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.POINTER(HipStats)]
+    lib.drt_hip_render_normal_equations_along.argtypes = [C.c_void_p, C.POINTER(CameraDesc), C.POINTER(RenderParamsDesc), C.c_int32, C.c_void_p,
+                                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                          C.POINTER(HipStats)]
     lib.drt_hip_pin_host.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
     lib.drt_hip_unpin_host.argtypes = [C.c_void_p, C.c_void_p]
     lib.drt_hip_stream.argtypes = [C.c_void_p]
@@ -1041,6 +1048,104 @@ class HipRenderer:
                                                       C.c_void_p(out_b_ptr or None), C.c_void_p(out_loss_ptr or None),
                                                       C.c_void_p(out_jacobian_ptr or None), C.byref(stats) if want_stats else None)
         self._check(rc, "drt_hip_render_normal_equations")
+        return stats.as_dict() if want_stats else {}
+
+    def _directions(self, tangents) -> np.ndarray:
+        """K directions of parameter space as the ABI takes them: float64 [K, n_params, 3]"""
+        assert self.scene is not None
+        v = np.ascontiguousarray(tangents, dtype=np.float64)
+        if v.size == 0:
+            v = v.reshape(0, self.scene.n_params, 3)
+        assert v.ndim == 3 and v.shape[1:] == (self.scene.n_params, 3), v.shape
+        return v
+
+    def render_tangents(self, cam: Camera, rp: RenderParams, tangents: np.ndarray, f64: bool = False, timing: bool = False):
+        """drt_hip_render_tangents: J v_k for the K <= MAX_DIRS directions `tangents` ([K, n_params, 3]) in ONE render.
+        -> (image [H,W,3], tangent images [K,H,W,3], stats dict), float32 (with f64=True: the device's float64 sums, rounded)."""
+        v = self._directions(tangents)
+        K = v.shape[0]
+        d = rp.to_desc()
+        d.flags = (rp.flags & ~(RENDER_DEVICE_OUT | RENDER_SYNC)) | (RENDER_F64 if f64 else 0) | (RENDER_TIMING if timing else 0)
+        img = np.zeros((cam.height, cam.width, 3), dtype=np.float32)
+        timg = np.zeros((max(K, 1), cam.height, cam.width, 3), dtype=np.float32)
+        stats = HipStats()
+        cd = cam.to_desc()
+        rc = self.lib.drt_hip_render_tangents(self.ctx, C.byref(cd), C.byref(d), K, v.ctypes.data_as(C.c_void_p), img.ctypes.data_as(C.c_void_p),
+                                              timg.ctypes.data_as(C.c_void_p), C.byref(stats))
+        self._check(rc, "drt_hip_render_tangents")
+        return img, timg[:K], stats.as_dict()
+
+    def render_tangents_device(self, cam: Camera, rp: RenderParams, tangents: np.ndarray, out_rgb_ptr: int, out_tangents_ptr: int,
+                               f64: bool = False, timing: bool = False, sync: bool = False, want_stats: Optional[bool] = None) -> dict:
+        """drt_hip_render_tangents on device pointers (float32 [H,W,3] and [K,H,W,3]; out_rgb_ptr may be 0), enqueued on the context's stream."""
+        if want_stats is None:
+            want_stats = timing
+        v = self._directions(tangents)
+        d = rp.to_desc()
+        d.flags = ((rp.flags | RENDER_DEVICE_OUT) & ~RENDER_SYNC) | (RENDER_F64 if f64 else 0) | (RENDER_TIMING if timing else 0) | \
+                  (RENDER_SYNC if sync else 0)
+        stats = HipStats()
+        cd = cam.to_desc()
+        rc = self.lib.drt_hip_render_tangents(self.ctx, C.byref(cd), C.byref(d), v.shape[0], v.ctypes.data_as(C.c_void_p),
+                                              C.c_void_p(out_rgb_ptr or None), C.c_void_p(out_tangents_ptr or None),
+                                              C.byref(stats) if want_stats else None)
+        self._check(rc, "drt_hip_render_tangents")
+        return stats.as_dict() if want_stats else {}
+
+    def render_normal_equations_along(self, cam: Camera, rp: RenderParams, tangents: np.ndarray, target: Optional[np.ndarray] = None,
+                                      residual: Optional[np.ndarray] = None, f64: bool = False, images: bool = False,
+                                      timing: bool = False) -> dict:
+        """drt_hip_render_normal_equations_along: the normal equations in the span of the K directions `tangents` ([K, n_params, 3]),
+        from one render; exactly one of `target` and `residual` (float32 [H,W,3]).
+        -> {"image" [H,W,3] float32, "A" [3,K,K], "b" [3,K], "loss" [3] (float64, sums over this shard's pixels),
+            "tangents" [K,H,W,3] float32 or None, "stats"}"""
+        v = self._directions(tangents)
+        K = v.shape[0]
+        d = rp.to_desc()
+        d.flags = (rp.flags & ~(RENDER_DEVICE_OUT | RENDER_SYNC)) | (RENDER_F64 if f64 else 0) | (RENDER_TIMING if timing else 0)
+
+        def image(a):
+            if a is None:
+                return None, None
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            assert a.shape == (cam.height, cam.width, 3), a.shape
+            return a, a.ctypes.data_as(C.c_void_p)
+        target, t_ptr = image(target)
+        residual, r_ptr = image(residual)
+        img = np.zeros((cam.height, cam.width, 3), dtype=np.float32)
+        A = np.zeros((3, max(K, 1), max(K, 1)), dtype=np.float64)
+        b = np.zeros((3, max(K, 1)), dtype=np.float64)
+        loss = np.zeros(3, dtype=np.float64)
+        timg = np.zeros((max(K, 1), cam.height, cam.width, 3), dtype=np.float32) if images else None
+        stats = HipStats()
+        cd = cam.to_desc()
+        rc = self.lib.drt_hip_render_normal_equations_along(self.ctx, C.byref(cd), C.byref(d), K, v.ctypes.data_as(C.c_void_p), t_ptr, r_ptr,
+                                                            img.ctypes.data_as(C.c_void_p), A.ctypes.data_as(C.c_void_p),
+                                                            b.ctypes.data_as(C.c_void_p), loss.ctypes.data_as(C.c_void_p),
+                                                            timg.ctypes.data_as(C.c_void_p) if images else None, C.byref(stats))
+        self._check(rc, "drt_hip_render_normal_equations_along")
+        return {"image": img, "A": A[:, :K, :K], "b": b[:, :K], "loss": loss, "tangents": timg[:K] if images else None, "stats": stats.as_dict()}
+
+    def render_normal_equations_along_device(self, cam: Camera, rp: RenderParams, tangents: np.ndarray, out_A_ptr: int, out_b_ptr: int,
+                                             target_ptr: int = 0, residual_ptr: int = 0, out_rgb_ptr: int = 0, out_loss_ptr: int = 0,
+                                             out_tangents_ptr: int = 0, f64: bool = False, timing: bool = False, sync: bool = False,
+                                             want_stats: Optional[bool] = None) -> dict:
+        """drt_hip_render_normal_equations_along on device pointers (images float32, A [3,K,K] / b [3,K] / loss [3] float64), enqueued
+        on the context's stream; the directions are host memory; exactly one of target_ptr and residual_ptr."""
+        if want_stats is None:
+            want_stats = timing
+        v = self._directions(tangents)
+        d = rp.to_desc()
+        d.flags = ((rp.flags | RENDER_DEVICE_OUT) & ~RENDER_SYNC) | (RENDER_F64 if f64 else 0) | (RENDER_TIMING if timing else 0) | \
+                  (RENDER_SYNC if sync else 0)
+        stats = HipStats()
+        cd = cam.to_desc()
+        rc = self.lib.drt_hip_render_normal_equations_along(self.ctx, C.byref(cd), C.byref(d), v.shape[0], v.ctypes.data_as(C.c_void_p),
+                                                            C.c_void_p(target_ptr or None), C.c_void_p(residual_ptr or None),
+                                                            C.c_void_p(out_rgb_ptr or None), C.c_void_p(out_A_ptr or None),
+                                                            C.c_void_p(out_b_ptr or None), C.c_void_p(out_loss_ptr or None),
+                                                            C.c_void_p(out_tangents_ptr or None), C.byref(stats) if want_stats else None)
+        self._check(rc, "drt_hip_render_normal_equations_along")
         return stats.as_dict() if want_stats else {}
 
     def render_device(self, cam: Camera, rp: RenderParams, out_rgb_ptr: int, out_grad_ptr: int,

@@ -28,6 +28,9 @@ struct TangentRequest {
     const void* d_params = nullptr;       // [the scene's parameters | the direction] in the render's compute type: the path kernel's `params`
     bool keep_sums = false;               // the pixels' sums of both images also stay in `film` / `gfilm`, in double (drt_hip_render_tangent_double)
     const NormalEqRequest* neq = nullptr; // not a forward-mode render at all: the normal equations (d_params, keep_sums unused)
+    int n_dirs = 0;                       // > 0, with neq: the K-direction forward form (drt_hip_render_tangents / _normal_equations_along) -- d_params holds
+                                          // [parameters | v_1 | ... | v_K], K = n_dirs padded up to an instantiated width with zero directions, and the
+                                          // rows k_normal_eq reduces are the n_dirs directions instead of the parameters
 };
 
 // One render call between its phases: launch (everything enqueued, gradients in ctx->grad[ctx->slot]) -> reduce (the

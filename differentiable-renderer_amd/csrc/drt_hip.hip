@@ -329,6 +329,90 @@ static int render_tangent_common(drt_hip_ctx* ctx, const drt_camera_desc* cam, c
     return render_common(ctx, cam, rp, nullptr, out_rgb, nullptr, stats, -1, out_tangent_rgb, &req);
 }
 
+// the call behind its refusals, for P rows -- the scene's parameters (the Jacobian form) or the directions of req (the K-direction forward
+// form): the caller's images to the device, the render, the sums and the P images back.  Without a target and a residual (the tangent
+// images alone) the reduction runs on a zero residual; without out_A its sums stay in the context.
+static int normal_equations_run(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_params* rp, const float* target_rgb,
+                                const float* residual_rgb, float* out_rgb, double* out_A, double* out_b, double* out_loss,
+                                float* out_jacobian, drt_hip_stats* stats, size_t P, TangentRequest& req, const char* who)
+{
+    const bool dev = (rp->flags & DRT_RENDER_DEVICE_OUT) != 0;
+    const size_t npix = (size_t)cam->width * (size_t)cam->height;
+    const size_t nA = 3 * P * P, nb = 3 * P;
+    const float* src = target_rgb ? target_rgb : residual_rgb;
+    if (!dev && src)
+        for (size_t i = 0; i < npix * 3; ++i)
+            if (!std::isfinite(src[i]))
+                return fail(ctx, DRT_ERR_INVALID, (std::string(who) + ": the target / residual image holds a value that is not finite").c_str());
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int rc;
+    NormalEqRequest q;
+    float* rgb = out_rgb;
+    if (!src || !dev) {
+        if ((rc = ensure(ctx, ctx->neq_in, npix * 3 * sizeof(float))) != DRT_OK) return rc;
+        if (!src)
+            HIPCHK(ctx, hipMemsetAsync(ctx->neq_in.p, 0, npix * 3 * sizeof(float), ctx->stream));
+    }
+    if (!dev || !out_A) {
+        if ((rc = ensure(ctx, ctx->neq_out, (nA + nb + 3) * sizeof(double))) != DRT_OK) return rc;
+        q.d_A = (double*)ctx->neq_out.p; q.d_b = q.d_A + nA; q.d_loss = q.d_b + nb;
+    }
+    if (dev) {
+        if (out_A) {
+            q.d_A = out_A; q.d_b = out_b; q.d_loss = out_loss;
+        }
+        q.d_jacobian = out_jacobian;
+        if (!rgb) {       // (the radiance sums are part of the pipeline: an image of the context's own)
+            if ((rc = ensure(ctx, ctx->neq_rgb, npix * 3 * sizeof(float))) != DRT_OK) return rc;
+            rgb = (float*)ctx->neq_rgb.p;
+        }
+        if (!src)
+            src = (const float*)ctx->neq_in.p;
+    } else {
+        if (src)
+            HIPCHK(ctx, hipMemcpyAsync(ctx->neq_in.p, src, npix * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+        src = (const float*)ctx->neq_in.p;
+        if (out_jacobian) {
+            if ((rc = ensure(ctx, ctx->neq_jac, (P ? P : 1) * npix * 3 * sizeof(float))) != DRT_OK) return rc;
+            q.d_jacobian = (float*)ctx->neq_jac.p;
+        }
+        if (!rgb) {
+            ctx->tangent_rgb32.resize(npix * 3);
+            rgb = ctx->tangent_rgb32.data();
+        }
+    }
+    (target_rgb ? q.d_target : q.d_residual) = src;
+    // (a shard without rows launches nothing: its sums are zero)
+    if (nA) HIPCHK(ctx, hipMemsetAsync(q.d_A, 0, nA * sizeof(double), ctx->stream));
+    if (nb) HIPCHK(ctx, hipMemsetAsync(q.d_b, 0, nb * sizeof(double), ctx->stream));
+    if (q.d_loss) HIPCHK(ctx, hipMemsetAsync(q.d_loss, 0, 3 * sizeof(double), ctx->stream));
+    drt_render_params r = *rp;
+    r.flags &= ~(uint32_t)DRT_RENDER_BACKWARD;       // (the Jacobian needs no seed and no summed gradient)
+    req.neq = &q;
+    if ((rc = render_common(ctx, cam, &r, nullptr, rgb, nullptr, stats, -1, nullptr, &req)) != DRT_OK)
+        return rc;
+    if (dev)
+        return DRT_OK;
+    // host buffers: the render has waited for its stream; a few hundred bytes of sums, and the Jacobian's rows of this shard where asked for
+    std::vector<double> sums(nA + nb + 3);
+    HIPCHK(ctx, hipMemcpy(sums.data(), ctx->neq_out.p, sums.size() * sizeof(double), hipMemcpyDeviceToHost));
+    if (nA && out_A) memcpy(out_A, sums.data(), nA * sizeof(double));
+    if (nb && out_b) memcpy(out_b, sums.data() + nA, nb * sizeof(double));
+    if (out_loss) memcpy(out_loss, sums.data() + nA + nb, 3 * sizeof(double));
+    if (out_jacobian && P) {
+        const RenderJob& j = ctx->job;
+        ctx->neq_host.resize(P * npix * 3);
+        HIPCHK(ctx, hipMemcpy(ctx->neq_host.data(), ctx->neq_jac.p, ctx->neq_host.size() * sizeof(float), hipMemcpyDeviceToHost));
+        const size_t row = (size_t)cam->width * 3;
+        for (size_t p = 0; p < P; ++p)
+            for_each_band(cam->height, j.band, j.n_shards, j.shard, [&](int y0, int y1) {
+                memcpy(out_jacobian + p * npix * 3 + (size_t)y0 * row, ctx->neq_host.data() + p * npix * 3 + (size_t)y0 * row,
+                       (size_t)(y1 - y0) * row * sizeof(float));
+            });
+    }
+    return DRT_OK;
+}
+
 extern "C" {
 
 int drt_hip_render_tangent(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_params* rp, const double* param_tangent,
@@ -416,71 +500,117 @@ int drt_hip_render_normal_equations(drt_hip_ctx* ctx, const drt_camera_desc* cam
               "gradient columns of the path kernel (a mirror costs one: at most 7 parameters beside it)");
     if ((uint64_t)cam->width * (uint64_t)cam->height * (uint64_t)(rp->spp > 0 ? rp->spp : 1) > 0x7FFFFFFFull)
         return fail(ctx, DRT_ERR_UNSUPPORTED, "normal equations: more than 2^31 camera samples in one frame (the shard renders in one batch)");
-    const bool dev = (rp->flags & DRT_RENDER_DEVICE_OUT) != 0;
-    const size_t npix = (size_t)cam->width * (size_t)cam->height;
-    const size_t P = (size_t)ctx->n_user_params, nA = 3 * P * P, nb = 3 * P;
-    const float* src = target_rgb ? target_rgb : residual_rgb;
-    if (!dev)
-        for (size_t i = 0; i < npix * 3; ++i)
-            if (!std::isfinite(src[i]))
-                return fail(ctx, DRT_ERR_INVALID, "normal equations: the target / residual image holds a value that is not finite");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    int rc;
-    NormalEqRequest q;
-    float* rgb = out_rgb;
-    if (dev) {
-        q.d_A = out_A; q.d_b = out_b; q.d_loss = out_loss;
-        q.d_jacobian = out_jacobian;
-        if (!rgb) {       // (the radiance sums are part of the pipeline: an image of the context's own)
-            if ((rc = ensure(ctx, ctx->neq_rgb, npix * 3 * sizeof(float))) != DRT_OK) return rc;
-            rgb = (float*)ctx->neq_rgb.p;
-        }
-    } else {
-        if ((rc = ensure(ctx, ctx->neq_in, npix * 3 * sizeof(float))) != DRT_OK) return rc;
-        if ((rc = ensure(ctx, ctx->neq_out, (nA + nb + 3) * sizeof(double))) != DRT_OK) return rc;
-        HIPCHK(ctx, hipMemcpyAsync(ctx->neq_in.p, src, npix * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-        src = (const float*)ctx->neq_in.p;
-        q.d_A = (double*)ctx->neq_out.p; q.d_b = q.d_A + nA; q.d_loss = q.d_b + nb;
-        if (out_jacobian) {
-            if ((rc = ensure(ctx, ctx->neq_jac, (P ? P : 1) * npix * 3 * sizeof(float))) != DRT_OK) return rc;
-            q.d_jacobian = (float*)ctx->neq_jac.p;
-        }
-        if (!rgb) {
-            ctx->tangent_rgb32.resize(npix * 3);
-            rgb = ctx->tangent_rgb32.data();
-        }
-    }
-    (target_rgb ? q.d_target : q.d_residual) = src;
-    // (a shard without rows launches nothing: its sums are zero)
-    if (nA) HIPCHK(ctx, hipMemsetAsync(q.d_A, 0, nA * sizeof(double), ctx->stream));
-    if (nb) HIPCHK(ctx, hipMemsetAsync(q.d_b, 0, nb * sizeof(double), ctx->stream));
-    if (q.d_loss) HIPCHK(ctx, hipMemsetAsync(q.d_loss, 0, 3 * sizeof(double), ctx->stream));
-    drt_render_params r = *rp;
-    r.flags &= ~(uint32_t)DRT_RENDER_BACKWARD;       // (the Jacobian needs no seed and no summed gradient)
     TangentRequest req;
-    req.neq = &q;
-    if ((rc = render_common(ctx, cam, &r, nullptr, rgb, nullptr, stats, -1, nullptr, &req)) != DRT_OK)
-        return rc;
-    if (dev)
-        return DRT_OK;
-    // host buffers: the render has waited for its stream; a few hundred bytes of sums, and the Jacobian's rows of this shard where asked for
-    std::vector<double> sums(nA + nb + 3);
-    HIPCHK(ctx, hipMemcpy(sums.data(), ctx->neq_out.p, sums.size() * sizeof(double), hipMemcpyDeviceToHost));
-    if (nA) memcpy(out_A, sums.data(), nA * sizeof(double));
-    if (nb) memcpy(out_b, sums.data() + nA, nb * sizeof(double));
-    if (out_loss) memcpy(out_loss, sums.data() + nA + nb, 3 * sizeof(double));
-    if (out_jacobian && P) {
-        const RenderJob& j = ctx->job;
-        ctx->neq_host.resize(P * npix * 3);
-        HIPCHK(ctx, hipMemcpy(ctx->neq_host.data(), ctx->neq_jac.p, ctx->neq_host.size() * sizeof(float), hipMemcpyDeviceToHost));
-        const size_t row = (size_t)cam->width * 3;
-        for (size_t p = 0; p < P; ++p)
-            for_each_band(cam->height, j.band, j.n_shards, j.shard, [&](int y0, int y1) {
-                memcpy(out_jacobian + p * npix * 3 + (size_t)y0 * row, ctx->neq_host.data() + p * npix * 3 + (size_t)y0 * row,
-                       (size_t)(y1 - y0) * row * sizeof(float));
-            });
+    return normal_equations_run(ctx, cam, rp, target_rgb, residual_rgb, out_rgb, out_A, out_b, out_loss, out_jacobian, stats,
+                                (size_t)ctx->n_user_params, req, "normal equations");
+}
+
+
+} // extern "C"
+
+// ---- J V for up to DRT_HIP_MAX_DIRS directions in one render, and the normal equations in their span ----
+// dst = [the scene's parameters | v_1 | ... | v_K] in compute type R: directions at and above n_dirs are zero (padding up to the
+// kernel's width), and so are internal constants (a mirror's colour)
+template <typename R>
+__global__ void __launch_bounds__(DRT_BLOCK) k_stage_tangents(const R* __restrict__ params, int n_all, const double* __restrict__ h_dirs, int n_user,
+                                                              int n_dirs, int K, R* __restrict__ dst)
+{
+    for (int i = blockIdx.x * DRT_BLOCK + threadIdx.x; i < n_all; i += gridDim.x * DRT_BLOCK) {
+        dst[i] = params[i];
+        for (int k = 0; k < K; ++k)
+            dst[(size_t)(1 + k) * n_all + i] = (k < n_dirs && i < n_user) ? (R)h_dirs[(size_t)k * n_user + i] : R(0);
     }
-    return DRT_OK;
+}
+
+static int render_tangents_common(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_params* rp, int32_t n_dirs,
+                                  const double* param_tangents, const float* target_rgb, const float* residual_rgb, float* out_rgb,
+                                  double* out_A, double* out_b, double* out_loss, float* out_tangents, drt_hip_stats* stats, bool along)
+{
+    if (!ctx)
+        return DRT_ERR_INVALID;
+    const std::string who = along ? "normal equations along" : "tangents";
+    const auto no = [&](int code, const char* what) { return fail(ctx, code, (who + ": " + what).c_str()); };
+    if (!ctx->members.empty())
+        return no(DRT_ERR_UNSUPPORTED, "not on a group context (render the shards on plain contexts)");
+    if (!ctx->has_scene)
+        return fail(ctx, DRT_ERR_NO_SCENE, "render before upload_scene");
+    if (!cam || !rp || cam->width <= 0 || cam->height <= 0)
+        return no(DRT_ERR_INVALID, "bad camera or render parameters");
+    if (n_dirs < 1 || n_dirs > DRT_HIP_MAX_DIRS)
+        return no(DRT_ERR_INVALID, "n_dirs outside 1 ... DRT_HIP_MAX_DIRS = 8");
+    if (!param_tangents || (along ? (!out_A || !out_b) : !out_tangents))
+        return no(DRT_ERR_INVALID, "NULL directions or output");
+    if (along && (target_rgb != nullptr) == (residual_rgb != nullptr))
+        return no(DRT_ERR_INVALID, "exactly one of target_rgb and residual_rgb");
+    const int n_user = ctx->n_user_params * 3, n_all = ctx->n_params * 3;
+    for (size_t i = 0; i < (size_t)n_dirs * (size_t)n_user; ++i)
+        if (!std::isfinite(param_tangents[i]))
+            return no(DRT_ERR_INVALID, "a direction holds a value that is not finite");
+    for (int i = 0; i < DRT_HIP_FRAMES_IN_FLIGHT; ++i)
+        if (ctx->in_flight[i])
+            return no(DRT_ERR_INVALID, "asynchronous frames are in flight -- drt_hip_wait for them first");
+    if (rp->flags & (DRT_RENDER_UNFUSED | DRT_RENDER_UNBIASED | DRT_RENDER_LOSS_L2 | DRT_RENDER_ALLREDUCE | DRT_RENDER_ALLREDUCE_ASYNC))
+        return no(DRT_ERR_UNSUPPORTED, "not with DRT_RENDER_UNFUSED, _UNBIASED, _LOSS_L2 or _ALLREDUCE* -- forward mode on the one-launch path kernel, one context");
+    if (ctx->has_mesh)
+        return no(DRT_ERR_UNSUPPORTED, "not of a scene that holds a triangle mesh");
+    if (rp->bounces_per_launch >= 1)
+        return no(DRT_ERR_UNSUPPORTED, "they come from the one-launch path kernel -- not with bounces_per_launch >= 1");
+    if (ctx->n_params > DRT_PATH_LDS_PARAMS)
+        return no(DRT_ERR_UNSUPPORTED, "more parameters than the path kernels stage (136)");
+    if ((uint64_t)cam->width * (uint64_t)cam->height * (uint64_t)(rp->spp > 0 ? rp->spp : 1) > 0x7FFFFFFFull)
+        return no(DRT_ERR_UNSUPPORTED, "more than 2^31 camera samples in one frame (the shard renders in one batch)");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    // the directions -> pinned memory -> [parameters | v_1 | ... | v_K] on the device, in stream order: drt_hip_render_tangent's
+    // double buffer and events (the copy this call rewrites was read by the launch of the call before the previous one)
+    const int K = n_dirs <= 2 ? 2 : (n_dirs <= 4 ? 4 : 8);
+    const int hb = (int)(ctx->tangent_calls++ & 1);
+    const size_t need = (size_t)n_dirs * (size_t)(n_user ? n_user : 1);
+    if (!ctx->ev_tangent[hb])
+        HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_tangent[hb], hipEventDisableTiming));
+    else
+        HIPCHK(ctx, hipEventSynchronize(ctx->ev_tangent[hb]));
+    if (ctx->h_tangent_cap[hb] < need) {
+        if (ctx->h_tangent[hb])
+            (void)hipHostFree(ctx->h_tangent[hb]);
+        ctx->h_tangent[hb] = nullptr;
+        ctx->h_tangent_cap[hb] = 0;
+        HIPCHK(ctx, hipHostMalloc((void**)&ctx->h_tangent[hb], need * sizeof(double)));
+        ctx->h_tangent_cap[hb] = need;
+    }
+    memcpy(ctx->h_tangent[hb], param_tangents, (size_t)n_dirs * (size_t)n_user * sizeof(double));
+    int rc;
+    if ((rc = ensure(ctx, ctx->tangent, (size_t)(n_all ? n_all : 1) * (size_t)(1 + K) * sizeof(double))) != DRT_OK) return rc;
+    if (n_all > 0) {
+        const unsigned blocks = (unsigned)((n_all + DRT_BLOCK - 1) / DRT_BLOCK);
+        if (rp->flags & DRT_RENDER_F64)
+            hipLaunchKernelGGL(k_stage_tangents<double>, dim3(blocks), dim3(DRT_BLOCK), 0, ctx->stream, (const double*)ctx->d_params_d, n_all,
+                               (const double*)ctx->h_tangent[hb], n_user, (int)n_dirs, K, (double*)ctx->tangent.p);
+        else
+            hipLaunchKernelGGL(k_stage_tangents<float>, dim3(blocks), dim3(DRT_BLOCK), 0, ctx->stream, (const float*)ctx->d_params_f, n_all,
+                               (const double*)ctx->h_tangent[hb], n_user, (int)n_dirs, K, (float*)ctx->tangent.p);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    HIPCHK(ctx, hipEventRecord(ctx->ev_tangent[hb], ctx->stream));
+    TangentRequest req;
+    req.d_params = ctx->tangent.p;
+    req.n_dirs = n_dirs;
+    return normal_equations_run(ctx, cam, rp, target_rgb, residual_rgb, out_rgb, out_A, out_b, out_loss, out_tangents, stats, (size_t)n_dirs, req,
+                                who.c_str());
+}
+
+extern "C" {
+
+int drt_hip_render_tangents(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_params* rp, int32_t n_dirs,
+                            const double* param_tangents, float* out_rgb, float* out_tangents, drt_hip_stats* stats)
+{
+    return render_tangents_common(ctx, cam, rp, n_dirs, param_tangents, nullptr, nullptr, out_rgb, nullptr, nullptr, nullptr, out_tangents, stats, false);
+}
+
+int drt_hip_render_normal_equations_along(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_params* rp, int32_t n_dirs,
+                                          const double* param_tangents, const float* target_rgb, const float* residual_rgb, float* out_rgb,
+                                          double* out_A, double* out_b, double* out_loss, float* out_tangents, drt_hip_stats* stats)
+{
+    return render_tangents_common(ctx, cam, rp, n_dirs, param_tangents, target_rgb, residual_rgb, out_rgb, out_A, out_b, out_loss, out_tangents, stats, true);
 }
 
 // ---- asynchronous host-buffer renders ---------------------------------------------------------------

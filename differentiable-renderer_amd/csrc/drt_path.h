@@ -62,6 +62,11 @@ struct PathArgs {
     // (at the END of the record: the f64 kernels' argument offsets stay what their register allocation was tuned at)
     float p_rr_f, inv_p_rr_f;
     float eye_f[3], fwd_f[3], right_f[3], up_f[3], cs_step_f, ct_step_f;   // (cs = cs0 + u1 cs_step: camera.hpp:53-58 in CameraLane's form)
+    // The K-direction forward form (NP = DRT_NP_TANGENT, NC = K): how many of the kernel's K directions are the caller's -- their sums leave
+    // the kernel, 3 rows each.  It has no gradient tables, so the count shares the word of gen_rows (no field in the middle of the record,
+    // none appended: the f64 kernels' argument offsets stay); read and written through these two only.
+    __host__ __device__ uint32_t dirs_out() const { return gen_rows; }
+    __host__ __device__ void set_dirs_out(uint32_t n) { gen_rows = n; }
 };
 
 __device__ inline uint32_t path_global_pixel(const PathArgs& a, uint32_t lp)
@@ -281,6 +286,16 @@ struct Tangents {
 #ifndef DRT_TANGENT_F64_MIN_BLOCKS
 #define DRT_TANGENT_F64_MIN_BLOCKS 3
 #endif
+// ... and their K-direction forms (NC = K: 9 K values per lane beside the forward-only kernel's, and 3 K sums in fp64; f64: twice that)
+#ifndef DRT_TANGENTS2_MIN_BLOCKS
+#define DRT_TANGENTS2_MIN_BLOCKS 5
+#endif
+#ifndef DRT_TANGENTS4_MIN_BLOCKS
+#define DRT_TANGENTS4_MIN_BLOCKS 3
+#endif
+#ifndef DRT_TANGENTS8_MIN_BLOCKS
+#define DRT_TANGENTS8_MIN_BLOCKS 2
+#endif
 #ifndef DRT_GEN_TABLE
 #define DRT_GEN_TABLE 408            // elements of a wave's gradient table (rows x copies; 408 = 3 x DRT_PATH_LDS_PARAMS: one copy of every row at least)
 #endif
@@ -454,14 +469,76 @@ __device__ inline void stage_dir(DirLds<R>& dl, const SL& lds, const R* __restri
     __syncthreads();
 }
 
-template <typename R, int NC>
-struct Tangents<R, DRT_NP_TANGENT, NC> {
+template <typename R>
+struct Tangents<R, DRT_NP_TANGENT, 0> {
     uint32_t zc;                    // zero factors met per channel, 8 bits each
     V3<R> S, Z;                     // sums of v / c and of v (zero channels) over the vertices of the current path
     V3<R> dL;                       // d radiance / d eps of the current path
     const DirLds<R>* dl;
     R* acc;                         // (unused: the column form's sums)
     __device__ inline void new_path() { zc = 0; S = Z = dL = mk<R>(R(0), R(0), R(0)); }
+};
+
+// ---- ... along K directions in ONE render (NP = DRT_NP_TANGENT, NC = K in {2, 4, 8}; drt_hip_render_tangents) ----------------
+// The path, its throughput T, the zero counts zc and the RNG key do not depend on the direction: K directions cost one path and K
+// sets of (S, Z, dL).  The tables are sized by the SCENE's parameter count n, not by DRT_PATH_LDS_PARAMS (which would be ~6 KB per
+// direction in f32): dynamic shared memory, in units of R, rows of four --
+//     colnz[n + 1]                       the colour row, read once per bounce (row n: the rest row, colour (1, 1, 1), zeros)
+//     dlog_k[n + 1], dzero_k[n + 1]      per direction k: v_k / c, and v_k where the channel is zero
+//     dir_k[3 n]                         per direction: v_k itself, for the lights
+// staged from [params | v_1 | ... | v_K] behind the kernel's `params`.  Every per-direction operation is the single-direction form's on
+// that direction's own operands: direction k's sums do not see what the other directions hold, and a padded direction (all zeros) adds
+// exact zeros.  Lockstep form only (a lane is a pixel): at the end of its sample range a lane writes its 3 K sums in the Jacobian form's
+// layout, gpix[range][3 k + ch][pixel], for k below the caller's count (PathArgs::dirs_out()).
+__host__ __device__ inline uint32_t dirs_table_words(uint32_t n, uint32_t K) { return (1u + 2u * K) * (n + 1u) * 4u + K * 3u * n; }
+template <typename R, int K, typename SL>
+__device__ inline void stage_dirs(R* __restrict__ tab, const SL& lds, const R* __restrict__ params)
+{
+    // (after stage_path_scene's barrier)
+    const int n = lds.sc.n_params < DRT_PATH_LDS_PARAMS ? lds.sc.n_params : DRT_PATH_LDS_PARAMS;
+    const int stride = (n + 1) * 4;
+    R* dir = tab + (1 + 2 * K) * stride;
+    for (int p = threadIdx.x; p <= n; p += blockDim.x) {
+        const bool in = p < n;
+        uint32_t zinc = 0;
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            const R c = in ? lds.params[p * 3 + ch] : R(1);
+            const bool zero = abs_r(c) < R(1e-18);
+            tab[p * 4 + ch] = zero ? R(1) : c;
+            zinc |= zero ? 1u << (8 * ch) : 0u;
+            for (int k = 0; k < K; ++k) {
+                const R v = in ? params[((size_t)(1 + k) * lds.sc.n_params + p) * 3 + ch] : R(0);
+                tab[(1 + 2 * k) * stride + p * 4 + ch] = zero ? R(0) : v / c;
+                tab[(2 + 2 * k) * stride + p * 4 + ch] = zero ? v : R(0);
+                if (in)
+                    dir[k * 3 * n + p * 3 + ch] = v;
+            }
+        }
+        tab[p * 4 + 3] = pid_pack(R(0), zinc);
+        for (int k = 0; k < K; ++k) {
+            tab[(1 + 2 * k) * stride + p * 4 + 3] = R(0);
+            tab[(2 + 2 * k) * stride + p * 4 + 3] = R(0);
+        }
+    }
+    __syncthreads();
+}
+
+template <typename R, int NC>
+struct Tangents<R, DRT_NP_TANGENT, NC> {
+    uint32_t zc;                    // zero factors met per channel, 8 bits each (shared by the directions)
+    V3<R> S[NC], Z[NC];             // per direction: sums of v / c and of v (zero channels) over the vertices of the current path
+    V3<R> dL[NC];                   // ... d radiance / d eps of the current path
+    const R* tab;                   // the block's tables (see above)
+    uint32_t rest, stride;          // the rest row = the scene's parameter count; words of one table
+    R* acc;                         // (unused: the column form's sums)
+    __device__ inline void new_path()
+    {
+        zc = 0;
+#pragma unroll
+        for (int k = 0; k < NC; ++k)
+            S[k] = Z[k] = dL[k] = mk<R>(R(0), R(0), R(0));
+    }
 };
 
 // what a block of a general-form kernel keeps in LDS, and the two ends of its life
@@ -556,6 +633,21 @@ __device__ inline void add_emission(const SL& lds, const TangentLds<R>& tl, cons
     if (NC > 0 || NP == DRT_NP_ANY || NP == DRT_NP_TANGENT)  // a channel that met a zero colour is dark
         Tr = mk<R>((tg.zc & 0xFFu) ? R(0) : T.x, (tg.zc & 0xFF00u) ? R(0) : T.y, (tg.zc & 0xFF0000u) ? R(0) : T.z);
     L = L + Tr * E;
+    if constexpr (NP == DRT_NP_TANGENT && NC > 0) {
+        // K directions: the single-direction case below, once per direction
+        const R* dir = tg.tab + (1u + 2u * NC) * tg.stride + (eid < tg.rest ? eid : 0u) * 3u;
+        const uint32_t zx = tg.zc & 0xFFu, zy = tg.zc & 0xFF00u, zz = tg.zc & 0xFF0000u;
+#pragma unroll
+        for (int k = 0; k < NC; ++k) {
+            const R* vd = dir + (uint32_t)k * 3u * tg.rest;
+            const V3<R> Ed = mk<R>(vd[0], vd[1], vd[2]) * inv_pk;
+            const V3<R> d0 = mk<R>(fma_r(E.x, tg.S[k].x, Ed.x), fma_r(E.y, tg.S[k].y, Ed.y), fma_r(E.z, tg.S[k].z, Ed.z));
+            const V3<R> d1 = E * tg.Z[k];
+            tg.dL[k] = mk<R>(fma_r(T.x, zx == 0u ? d0.x : (zx == 0x1u ? d1.x : R(0)), tg.dL[k].x),
+                             fma_r(T.y, zy == 0u ? d0.y : (zy == 0x100u ? d1.y : R(0)), tg.dL[k].y),
+                             fma_r(T.z, zz == 0u ? d0.z : (zz == 0x10000u ? d1.z : R(0)), tg.dL[k].z));
+        }
+    } else
     if constexpr (NP == DRT_NP_TANGENT) {
         // forward mode: T (e S + e') where no factor of the channel is zero, T e Z where exactly one is
         const R* vd = tg.dl->dir + (eid < DRT_PATH_LDS_PARAMS ? eid : 0u) * 3u;
@@ -727,11 +819,24 @@ __device__ inline void path_bounce(const PathArgs& a, const PathSceneLds<R>& lds
     // the throughput moves on only in lanes whose path goes on (the others stay frozen for the light's turn); with
     // gradients it leaves zero colour channels out and counts them, and counts the bounce for its colour (see Tangents)
     // (REST, the lockstep kernel's colour-column form: a lane that does not go on reads the table's row of ones and zero increments)
-    constexpr bool REST = FREEZE_BY_ROW && NC > 0 && NP != DRT_NP_ANY;
+    constexpr bool REST = FREEZE_BY_ROW && NC > 0 && NP != DRT_NP_ANY && NP != DRT_NP_TANGENT;
     // (DIR, forward mode: the same by its own table's rest row, in every form)
     constexpr bool DIR = NP == DRT_NP_TANGENT, BY_ROW = REST || DIR;
     const int cidx = DIR ? (alive ? (int)cid : DRT_PATH_LDS_PARAMS) : (REST ? (alive ? (int)cid : DRT_TANGENT_REST) : (has_bxdf ? (int)cid : 0));
     V3<R> col;
+    if constexpr (DIR && NC > 0) {
+        // K directions: the colour row once, a row of v / c and of v (zero channels) per direction; a lane that stops reads the rest row
+        const uint32_t row = ((uint32_t)cidx < tg.rest ? (uint32_t)cidx : tg.rest) * 4u;
+        const R* rec = tg.tab + row;
+        col = mk<R>(rec[0], rec[1], rec[2]);
+        tg.zc += pid_unpack(rec[3]);
+#pragma unroll
+        for (int k = 0; k < NC; ++k) {
+            const R *ds = tg.tab + (1u + 2u * k) * tg.stride + row, *dz = ds + tg.stride;
+            tg.S[k] = mk<R>(tg.S[k].x + ds[0], tg.S[k].y + ds[1], tg.S[k].z + ds[2]);
+            tg.Z[k] = mk<R>(tg.Z[k].x + dz[0], tg.Z[k].y + dz[1], tg.Z[k].z + dz[2]);
+        }
+    } else
     if constexpr (DIR) {
         const int row = cidx < DRT_PATH_LDS_PARAMS ? cidx : DRT_PATH_LDS_PARAMS;
         const R *rec = tg.dl->colnz[row], *ds = tg.dl->dlog[row], *dz = tg.dl->dzero[row];
@@ -758,7 +863,7 @@ __device__ inline void path_bounce(const PathArgs& a, const PathSceneLds<R>& lds
             tg.cnt[NC > 4 ? 1 : 0] += tl.inc[cidx][1];
         tg.zc += tl.inc[cidx][2];
     } else
-    if constexpr (NC > 0 && NP != DRT_NP_ANY) {
+    if constexpr (NC > 0 && NP != DRT_NP_ANY && NP != DRT_NP_TANGENT) {
         tg.cnt[0] += alive ? tl.inc[cidx][0] : 0u;
         if (NC > 4)
             tg.cnt[NC > 4 ? 1 : 0] += alive ? tl.inc[cidx][1] : 0u;
@@ -843,9 +948,12 @@ __device__ inline uint32_t path_camera(const PathArgs& a, const CameraLane<R>& c
 #define DRT_LEAN_MAX_SHAPES 10
 #endif
 #endif
-template <size_t RB, bool SPEC, int NP, int NSG, bool REGEN>
+template <size_t RB, bool SPEC, int NP, int NSG, bool REGEN, int NCR = 0>
 constexpr int path_min_blocks()
 {
+    if (NP == DRT_NP_TANGENT && DRT_NC_OF(NCR) > 0)   // K directions, lockstep: f64 takes what a block per CU has
+        return RB == 4 ? (DRT_NC_OF(NCR) <= 2 ? DRT_TANGENTS2_MIN_BLOCKS : (DRT_NC_OF(NCR) <= 4 ? DRT_TANGENTS4_MIN_BLOCKS : DRT_TANGENTS8_MIN_BLOCKS))
+                       : (DRT_NC_OF(NCR) <= 2 ? 2 : 1);
     if (NP == DRT_NP_TANGENT)      // forward mode: the forward-only kernel + ten values per lane (S, Z, dL, zc) and 8 / 16 KB of LDS (f32 / f64)
         return RB == 4 ? (REGEN ? DRT_TANGENT_REGEN_MIN_BLOCKS : DRT_TANGENT_MIN_BLOCKS) : ((REGEN || SPEC) ? 2 : DRT_TANGENT_F64_MIN_BLOCKS);
     if (RB == 4 && NP <= 4) {
@@ -873,7 +981,7 @@ constexpr int path_min_blocks()
 // (waves per SIMD by form: path_min_blocks above)
 // (NCR: the colour columns NC and, above its low byte, the slots' roles -- DRT_NC_ROLES)
 template <typename R, bool SPEC, int NP, int NCR, typename SG, bool REGEN = false, bool LOSS = false>
-__global__ void __launch_bounds__(DRT_BLOCK, (path_min_blocks<sizeof(R), SPEC, NP, SG::n, REGEN>()))
+__global__ void __launch_bounds__(DRT_BLOCK, (path_min_blocks<sizeof(R), SPEC, NP, SG::n, REGEN, NCR>()))
 k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ params, const float* __restrict__ adjoint,
        double* __restrict__ gpart, double* __restrict__ fpart, uint32_t* __restrict__ counts,
        unsigned long long* __restrict__ total, double* __restrict__ gimg_part)
@@ -891,12 +999,14 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
     __shared__ typename PickT<GEN, GenBlock<R>, NoLds>::T s_gen;
     extern __shared__ uint32_t s_hist[];                  // GEN: [a.hist_lds][DRT_BLOCK] history words
     constexpr bool DIR = NP == DRT_NP_TANGENT;            // forward mode: the derivative along one direction (see DirLds); `params` = [params | direction]
-    __shared__ typename PickT<DIR, DirLds<R>, NoLds>::T s_dir;
+    constexpr bool DIRS = DIR && NC > 0;                  // ... along NC directions at once: tables in dynamic shared memory (see stage_dirs)
+    static_assert(!(DIRS && REGEN), "the K-direction form is a lockstep form: a lane is a pixel");
+    __shared__ typename PickT<(DIR && !DIRS), DirLds<R>, NoLds>::T s_dir;
     if constexpr (GEN)
         gen_zero(s_gen);
     stage_path_scene(lds, sc, params);
     const TangentLds<R>& tl = s_tl;
-    if (NC > 0 && !GEN)
+    if (NC > 0 && !GEN && !DIR)
         stage_tangents(s_tl, lds);
 
     const uint32_t lane = threadIdx.x & (DRT_WAVE - 1);
@@ -912,7 +1022,15 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
     tg.acc = &s_acc[0][threadIdx.x];
     if constexpr (GEN)
         gen_begin(s_gen, lds, sc, a, s_hist, reinterpret_cast<uint32_t*>(a.hist_ovf), tg);
-    else if constexpr (DIR) {
+    else if constexpr (DIRS) {
+        extern __shared__ __attribute__((aligned(16))) unsigned char s_dirs[];
+        R* tab = reinterpret_cast<R*>(s_dirs);
+        stage_dirs<R, NC>(tab, lds, params);
+        tg.tab = tab;
+        tg.rest = (uint32_t)(lds.sc.n_params < DRT_PATH_LDS_PARAMS ? lds.sc.n_params : DRT_PATH_LDS_PARAMS);
+        tg.stride = (tg.rest + 1u) * 4u;
+        tg.new_path();
+    } else if constexpr (DIR) {
         stage_dir(s_dir, lds, params);
         tg.dl = &s_dir;
         tg.new_path();
@@ -923,6 +1041,12 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
     }
     double fx = 0, fy = 0, fz = 0;                        // radiance sum of this lane's pixel over the range
     double tx = 0, ty = 0, tz = 0;                        // DIR: ... and the sum of its samples' derivatives
+    double tk[DIRS ? NC : 1][3];                          // DIRS: ... per direction
+    if constexpr (DIRS) {
+#pragma unroll
+        for (int k = 0; k < NC; ++k)
+            tk[k][0] = tk[k][1] = tk[k][2] = 0.0;
+    }
     uint32_t n_seg = 0, n_capped = 0;                     // wave-uniform counters
 
     uint32_t gpix = 0, px = 0, py = 0;
@@ -1001,6 +1125,12 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
                 add_emission<R, NP, NC, LOSS, PathSceneLds<R>, ROLES>(lds, tl, params, end_ids, end_inv_pk, T, g, L, tg);
         }
         fx += (double)L.x; fy += (double)L.y; fz += (double)L.z;
+        if constexpr (DIRS) {
+#pragma unroll
+            for (int k = 0; k < NC; ++k) {
+                tk[k][0] += (double)tg.dL[k].x; tk[k][1] += (double)tg.dL[k].y; tk[k][2] += (double)tg.dL[k].z;
+            }
+        } else
         if constexpr (DIR) {
             tx += (double)tg.dL.x; ty += (double)tg.dL.y; tz += (double)tg.dL.z;
         }
@@ -1141,7 +1271,17 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
             double* f = gimg_part + ((size_t)range * 3) * a.Pb + lp;
             f[0] = (double)tg.gsum.x; f[(size_t)a.Pb] = (double)tg.gsum.y; f[(size_t)a.Pb * 2] = (double)tg.gsum.z;
         }
-        if constexpr (DIR) if (gimg_part && have) {
+        if constexpr (DIRS) if (gimg_part && have) {
+            // K directions: the pixel's sums in the Jacobian form's layout, [range][3 k + ch][pixel], for the directions the caller gave
+            const uint32_t nd = a.dirs_out() < (uint32_t)NC ? a.dirs_out() : (uint32_t)NC;
+            double* f = gimg_part + ((size_t)range * (size_t)(nd * 3u)) * a.Pb + lp;
+#pragma unroll
+            for (int k = 0; k < NC; ++k)
+                if ((uint32_t)k < nd) {
+                    f[(size_t)(k * 3) * a.Pb] = tk[k][0]; f[(size_t)(k * 3 + 1) * a.Pb] = tk[k][1]; f[(size_t)(k * 3 + 2) * a.Pb] = tk[k][2];
+                }
+        }
+        if constexpr (DIR && !DIRS) if (gimg_part && have) {
             // forward mode: the pixel's derivative sums leave where a gradient image's do -- same layout, same finishing kernels
             double* f = gimg_part + ((size_t)range * 3) * a.Pb + lp;
             f[0] = tx; f[(size_t)a.Pb] = ty; f[(size_t)a.Pb * 2] = tz;

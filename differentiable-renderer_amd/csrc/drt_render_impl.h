@@ -151,15 +151,16 @@ inline int np_width(int n_params, int general)
 }
 
 // ---- which instantiation of the one-launch path kernels a render runs (shard_plan decides it, path_batch launches it) ----
-enum class PathOp { biased, unbiased, mesh, tangent, jacobian };   // k_path (the gradient image included), k_path_unbiased, k_path_mesh, k_path's forward-mode form,
-                                                                    // its Jacobian form (lockstep, parameters in columns: DRT_NC_JACOBIAN)
+enum class PathOp { biased, unbiased, mesh, tangent, jacobian, tangents };   // k_path (the gradient image included), k_path_unbiased, k_path_mesh, k_path's forward-mode form,
+                                                                    // its Jacobian form (lockstep, parameters in columns: DRT_NC_JACOBIAN),
+                                                                    // its K-direction forward form (lockstep, nc = K)
 enum class PathProg { cornell, sorted, scene };  // closest-hit program: the reference's kinds compiled in (SigCornell), kinds read at
                                                  // run time (SigNone), or compiled by hiprtc for the scene's own KindSig (drt_jit.h)
 struct PathForm {
     PathOp op;
     bool f64, spec;
     int np, nc;                     // gradient parameters / colour columns: 0, 0 without tangents; DRT_NP_ANY the general form;
-                                    // DRT_NP_TANGENT, 0: forward mode (PathOp::tangent)
+                                    // DRT_NP_TANGENT, 0: forward mode (PathOp::tangent); DRT_NP_TANGENT, K: along K directions (PathOp::tangents)
                                     // (nc = 1: + the lanes' own sums of one row, the gradient image)
     bool regen;                     // the regenerating form (k_path_mesh: always; k_path_unbiased: never)
     bool loss;                      // DRT_RENDER_LOSS_L2's instantiation: made at run time only
@@ -192,7 +193,8 @@ struct Shard {
     const NormalEqRequest* neq = nullptr;   // drt_hip_render_normal_equations: the Jacobian form, then k_normal_eq
     uint32_t neq_blocks = 0;        // ... k_normal_eq's blocks per channel
     int neq_vw = 1;                 // ... pixels per lane (2: 16-byte loads, an even number of pixels)
-    int jac_rows() const { return neq ? ctx->n_params * 3 : 3; }   // rows a pixel's sums have in `gpix`
+    int n_dirs = 0;                 // ... > 0: its rows are directions -- k_path's K-direction forward form in place of the Jacobian form
+    int jac_rows() const { return neq ? (n_dirs > 0 ? n_dirs : ctx->n_params) * 3 : 3; }   // rows a pixel's sums have in `gpix`
     bool pixel_sums() const { return gimg_param >= 0 || fwd_tangent || neq; }   // the lanes' per-pixel sums leave the path kernel (gimg_part)
     // the scene in compute type R
     const DevScene<R>* d_scene;
@@ -338,6 +340,10 @@ const void* library_path_kernel(const PathForm& f)
         }
         return nullptr;
     }
+    if (f.op == PathOp::tangents)  // ... along K directions: lockstep, every program
+        return f.regen ? nullptr : with_int<2, 4, 8>(f.nc, [&](auto k) {
+            return spec_sig([](auto spec, auto sg) { return (const void*)k_path<R, decltype(spec)::value, DRT_NP_TANGENT, decltype(k)::value, decltype(sg), false>; });
+        });
     if (f.op == PathOp::tangent)   // forward mode: both forms, every program
         return spec_sig([&f](auto spec, auto sg) {
             return with_bool(f.regen, [](auto regen) { return (const void*)k_path<R, decltype(spec)::value, DRT_NP_TANGENT, 0, decltype(sg), regen>; });
@@ -393,7 +399,7 @@ void shard_plan(Shard<R>& s)
     // the general form -- vertex history + per-wave tables (drt_path.h, DRT_NP_ANY); the gradient IMAGE (the lanes' own sums) in
     // analytic scenes too
     const bool tangents = s.backward || s.gimg_param >= 0 || s.neq;
-    const bool grads_ok = !tangents || ctx->n_params <= DRT_FAST_PARAMS ||
+    const bool grads_ok = !tangents || ctx->n_params <= DRT_FAST_PARAMS || (s.n_dirs > 0 && ctx->n_params <= DRT_PATH_LDS_PARAMS) ||
                           (ctx->n_params <= DRT_PATH_LDS_PARAMS && tuning().path_general && (s.gimg_param < 0 || !ctx->has_mesh));
     s.use_path = ((s.can_fuse && ctx->prog_ok) || mesh_ok) && D > 0 && grads_ok &&
                  rp->bounces_per_launch <= 0 && tuning().shade_bounces <= 0 && tuning().dump_path == -1;
@@ -431,6 +437,11 @@ void shard_plan(Shard<R>& s)
     f.np = s.fwd_tangent ? DRT_NP_TANGENT : !tangents ? 0 : (gen ? DRT_NP_ANY : np_width(ctx->n_params, DRT_NP_ANY));
     f.nc = !tangents ? 0 : gen ? (s.gimg_param >= 0 ? 1 : 0)
                              : (f.np == 8 ? 8 : (ctx->max_colour_param < 3 ? 3 : 4));   // (tangent state only for parameters that ARE some BxDF's colour)
+    if (s.neq && s.n_dirs > 0 && !s.mesh_path) {   // the K-direction forward form: the caller's count padded up to an instantiated width
+        f.op = PathOp::tangents;
+        f.np = DRT_NP_TANGENT;
+        f.nc = s.n_dirs <= 2 ? 2 : (s.n_dirs <= 4 ? 4 : 8);
+    }
     f.loss = s.loss_l2;
     // the slots' roles as the scene's records give them: for the form the headline runs -- diffuse, f32, lockstep, parameters in columns
     f.roles = 0;
@@ -735,6 +746,8 @@ int path_batch(Shard<R>& s)
     pa.ct_step_f = (float)(2. * pa.tan_half * pa.inv_H);
     pa.gimg_param = s.gimg_param;
     pa.gen_rows = s.gen_rows; pa.gen_clog2 = s.gen_clog2;
+    if (s.path.op == PathOp::tangents)
+        pa.set_dirs_out((uint32_t)s.n_dirs);       // (the K-direction form: the directions whose sums leave the kernel)
     // the general form's vertex history: a word per four vertices and thread, in dynamic shared memory
     const bool gen = s.path_gen;
     // (the first words in LDS, as many as leave the kernel's blocks per CU alone: four in the lockstep k_path -- 16 vertices --,
@@ -833,7 +846,11 @@ int path_batch(Shard<R>& s)
     void* args_unb[] = {&pa, &d_scene, &d_params, &d_adjoint, &gpart, &fpart, &counts, &ptotal};
     void* args_mesh[] = {&pa, &d_scene, &d_params, &d_adjoint, &s.bvh, &ovf, &ovf_stride, &gpart, &fpart, &counts, &ptotal, &gpix};
     void** args = form.op == PathOp::unbiased ? args_unb : (form.op == PathOp::mesh ? args_mesh : args_path);
-    const unsigned lds_bytes = form.op == PathOp::unbiased ? 0u : hist_bytes;
+    // (the K-direction form's tables, sized by the scene's own parameter count: stage_dirs.  Up to 100.6 KB in f64; this runtime launches a
+    //  block with any amount of dynamic LDS the CU has, for library and hiprtc kernels alike: tests/test_gpu_tangents.py fills both)
+    const unsigned dirs_bytes = form.op == PathOp::tangents
+        ? dirs_table_words((uint32_t)std::min(ctx->n_params, DRT_PATH_LDS_PARAMS), (uint32_t)form.nc) * (unsigned)sizeof(R) : 0u;
+    const unsigned lds_bytes = form.op == PathOp::unbiased ? 0u : (form.op == PathOp::tangents ? dirs_bytes : hist_bytes);
     if (jit)
         HIPCHK(ctx, hipModuleLaunchKernel(jit, (unsigned)gpath, 1, 1, DRT_BLOCK, 1, 1, lds_bytes, ks, args, nullptr));
     else
@@ -869,19 +886,23 @@ int path_batch(Shard<R>& s)
             uint32_t mask = 0;
             for (int p2 = 0; p2 < ctx->n_params && p2 < DRT_FAST_PARAMS; ++p2)
                 mask |= (p2 < ctx->n_user_params && ctx->requires_grad[(size_t)p2]) ? 1u << p2 : 0u;
-            const int npw = np_width(ctx->n_params, DRT_FAST_PARAMS);
+            // (rows that are directions: all of them count -- requires_grad is a reverse-mode notion)
+            const int n_par = s.n_dirs > 0 ? s.n_dirs : ctx->n_params, n_out = s.n_dirs > 0 ? s.n_dirs : ctx->n_user_params;
+            if (s.n_dirs > 0)
+                mask = 0xFFu;
+            const int npw = np_width(n_par, DRT_FAST_PARAMS);
             double* part = (double*)ctx->neq_part.p;
             DRT_TIMED(s, DRT_K_GRADREDUCE, with_int<4, 8>(npw, [&](auto np) {
                 with_bool(s.neq_vw == 2, [&](auto wide) {
                     hipLaunchKernelGGL((k_normal_eq<decltype(np)::value, decltype(wide)::value ? 2 : 1>), dim3(s.neq_blocks, 3), dim3(DRT_BLOCK), 0, ctx->stream, pa,
-                                       (const double*)gpix, (const double*)fpart, ctx->n_params, ctx->n_user_params, mask, q.d_target, q.d_residual, q.d_jacobian, part);
+                                       (const double*)gpix, (const double*)fpart, n_par, n_out, mask, q.d_target, q.d_residual, q.d_jacobian, part);
                     return 0;
                 });
                 return 0;
             }));
             DRT_TIMED(s, DRT_K_GRADREDUCE,
                       hipLaunchKernelGGL(k_normal_eq_finish, dim3(3 * DRT_NEQ_VALUES(npw)), dim3(DRT_BLOCK), 0, ctx->stream, (const double*)part,
-                                         (int)s.neq_blocks, npw, ctx->n_user_params, q.d_A, q.d_b, q.d_loss));
+                                         (int)s.neq_blocks, npw, n_out, q.d_A, q.d_b, q.d_loss));
             st->units[DRT_K_GRADREDUCE] += (uint64_t)a.Pb;
             st->path_bytes += (uint64_t)pa.n_ranges * a.Pb * (uint64_t)s.jac_rows() * sizeof(double);
         }
@@ -1185,7 +1206,8 @@ int render_impl(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_p
     s.neq = tangent ? tangent->neq : nullptr;
     s.fwd_tangent = tangent != nullptr && !s.neq;
     s.keep_sums = s.fwd_tangent && tangent->keep_sums;
-    if (s.fwd_tangent)
+    s.n_dirs = s.neq ? tangent->n_dirs : 0;
+    if (s.fwd_tangent || s.n_dirs > 0)
         s.d_params = (const R*)tangent->d_params;
     shard_plan(s);
     if (s.fwd_tangent && s.D > 0 && (!s.use_path || s.mesh_path))
@@ -1194,7 +1216,11 @@ int render_impl(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_p
                         : "render_tangent: the tangent image comes from the one-launch path kernel, which this render does not take "
                           "(bounces_per_launch >= 1, DRT_RENDER_UNFUSED, a DRT_HIP_* setting that forces the queue wavefront, or a scene its "
                           "intersection program does not cover)");
-    if (s.neq && (!s.use_path || s.mesh_path || !s.path_finish || s.path.op != PathOp::jacobian))
+    if (s.neq && s.n_dirs > 0 && (!s.use_path || s.mesh_path || !s.path_finish || s.path.op != PathOp::tangents))
+        return fail(ctx, DRT_ERR_UNSUPPORTED, "tangents / normal equations along: they come from the one-launch path kernel's K-direction form over the whole "
+                                              "shard in one batch, which this render does not take (a DRT_HIP_* setting that forces the queue wavefront or a "
+                                              "batch size, more than 2^31 camera samples, or a scene its intersection program does not cover)");
+    if (s.neq && s.n_dirs <= 0 && (!s.use_path || s.mesh_path || !s.path_finish || s.path.op != PathOp::jacobian))
         return fail(ctx, DRT_ERR_UNSUPPORTED, "normal equations: they come from the one-launch path kernel's Jacobian form over the whole shard in one "
                                               "batch, which this render does not take (a DRT_HIP_* setting that forces the queue wavefront or a batch size, "
                                               "more than 2^31 camera samples, or a scene its intersection program does not cover)");

@@ -12,6 +12,8 @@
 // sums the gradient vector across them with a single RCCL all-reduce; this header adds nothing.
 //
 //   drt::hip::render_tangent(scene, cam, tracer, spp, {{param, direction}, ...}, img, tangent_img [, options])
+//   drt::hip::render_tangents(scene, cam, tracer, spp, {direction, ...}, img, tangent_imgs [, options])      up to 8 directions, one render
+//   drt::hip::normal_equations_along(scene, cam, tracer, spp, {direction, ...}, options, target_or_residual) Gauss-Newton in their span
 //   drt::hip::render(scene of Dual<U>, ...)
 //
 // forward mode (drt_hip_render_tangent): the image and its derivative along one direction of parameter space -- given as
@@ -845,6 +847,153 @@ inline NormalEquations<T> normal_equations(const Scene<T>& scene, const Camera<T
                 "drt_hip_render_normal_equations");
     detail::from_buffer(rgb.data(), npix, img);
     ne.stats = detail::to_stats(st);
+    return ne;
+}
+
+// ---- K directions in one render (drt_hip_render_tangents / drt_hip_render_normal_equations_along) -------------------
+// A direction of parameter space as render_tangent takes it: (handle, direction) pairs; handles not listed have direction 0
+template <typename T>
+using Direction = std::vector<std::pair<Vector<T, 3, true>, Vector<T, 3>>>;
+
+namespace detail {
+// K directions as the ABI takes them, K x n_params x 3
+template <typename T>
+inline std::vector<double> directions_of(const char* who, const FlatScene<T>& flat, const std::vector<Direction<T>>& directions)
+{
+    const std::size_t n = flat.handles.size() * 3;
+    std::vector<double> v(directions.size() * n, 0.0);
+    for (std::size_t k = 0; k < directions.size(); ++k)
+        for (const auto& t : directions[k]) {
+            const int index = param_index(flat, t.first, (std::string(who) + ": a listed parameter is not used by the scene").c_str());
+            for (int c = 0; c < 3; ++c)
+                v[k * n + (std::size_t)index * 3 + c] += double(real(t.second[c]));
+        }
+    return v;
+}
+// the one call behind render_tangents and normal_equations_along: A, b, loss where `in` is given, the K images where `timg` is
+template <typename T>
+inline Stats tangents_call(const char* who, const FlatScene<T>& flat, const drt_camera_desc& cd, double absorb, std::size_t min_bounces,
+                           std::size_t spp, std::size_t K, const std::vector<double>& v, const float* in, bool in_is_residual,
+                           std::vector<float>& rgb, std::vector<float>* timg, double* A, double* b, double* loss, const Options& opt)
+{
+    if (opt.backward || opt.unbiased || opt.sample_loss_l2)
+        throw std::runtime_error(std::string(who) + ": forward mode takes no reverse-mode option (backward, unbiased, sample_loss_l2)");
+    if (opt.devices.size() > 1)
+        throw std::runtime_error(std::string(who) + ": one device (render shards on plain contexts and add them)");
+    const std::size_t n = (std::size_t)cd.width * (std::size_t)cd.height * 3;
+    rgb.assign(n, 0.f);
+    if (timg)
+        timg->assign((K ? K : 1) * n, 0.f);
+    const drt_render_params rp = render_params(absorb, min_bounces, spp, opt, f64_flag(opt));
+    drt_hip_stats st{};
+    Session s = Session::on_first_device(opt, flat);
+    if (A)
+        s.ctx.check(drt_hip_render_normal_equations_along(s.ctx.get(), &cd, &rp, (int32_t)K, v.data(), in_is_residual ? nullptr : in,
+                                                          in_is_residual ? in : nullptr, rgb.data(), A, b, loss, timg ? timg->data() : nullptr, &st),
+                    "drt_hip_render_normal_equations_along");
+    else
+        s.ctx.check(drt_hip_render_tangents(s.ctx.get(), &cd, &rp, (int32_t)K, v.data(), rgb.data(), timg ? timg->data() : nullptr, &st),
+                    "drt_hip_render_tangents");
+    return to_stats(st);
+}
+} // namespace detail
+
+// J v_k for up to DRT_HIP_MAX_DIRS directions in one render: tangent_imgs[k * width * height + pixel] is what render_tangent gives for
+// directions[k] (the device's float images; with opt.f64 its double sums, rounded).  img may be nullptr.
+template <typename T>
+inline Stats render_tangents(const Scene<T>& scene, const Camera<T>& cam, const Pathtracer<T>& tracer, std::size_t spp,
+                             const std::vector<Direction<T>>& directions, Vector<T, 3>* img, Vector<T, 3>* tangent_imgs,
+                             const Options& opt = Options())
+{
+    FlatScene<T> flat = flatten(scene);
+    const std::vector<double> v = detail::directions_of("drt::hip::render_tangents", flat, directions);
+    std::vector<float> rgb, trgb;
+    const Stats st = detail::tangents_call("drt::hip::render_tangents", flat, describe(cam), tracer.absorb(), tracer.min_bounces(), spp,
+                                           directions.size(), v, nullptr, false, rgb, &trgb, nullptr, nullptr, nullptr, opt);
+    const std::size_t npix = cam.width() * cam.height();
+    detail::from_buffer(rgb.data(), npix, img);
+    detail::from_buffer(trgb.data(), npix * directions.size(), tangent_imgs);
+    return st;
+}
+
+// The normal equations in the span of K directions: per channel A[ch] = V^T J^T J V (K x K, row-major), b[ch] = V^T J^T r,
+// loss[ch] = r . r -- for a scene of any number of parameters the path kernels stage.  solve() gives the Levenberg-Marquardt step in
+// the directions' coordinates, step[k * 3 + ch]: the parameters move by sum_k step[k * 3 + ch] directions[k].
+// A direction that leaves a channel alone -- d theta / d tint_red in green -- has a zero diagonal there: solve() keeps such a row out of
+// that channel's system and returns step 0 for it.
+template <typename T>
+struct NormalEquationsAlong {
+    std::size_t n_dirs = 0;
+    std::vector<double> A, b, loss;             // 3 x K x K, 3 x K, 3
+    Stats stats;
+    std::vector<double> solve(double lambda) const
+    {
+        // (NormalEquations::solve's Cholesky step, with the rows chosen per channel: those whose diagonal is positive)
+        const std::size_t K = n_dirs;
+        std::vector<double> step(K * 3, 0.0);
+        for (int ch = 0; ch < 3; ++ch) {
+            const double* Ac = A.data() + (std::size_t)ch * K * K;
+            const double* bc = b.data() + (std::size_t)ch * K;
+            std::vector<std::size_t> rows;
+            for (std::size_t k = 0; k < K; ++k)
+                if (Ac[k * K + k] > 0.0)
+                    rows.push_back(k);
+            const std::size_t n = rows.size();
+            std::vector<double> L(n * n), y(n);
+            for (std::size_t i = 0; i < n; ++i)
+                for (std::size_t j = 0; j <= i; ++j) {
+                    double v = Ac[rows[i] * K + rows[j]] * (i == j ? 1.0 + lambda : 1.0);
+                    for (std::size_t k = 0; k < j; ++k)
+                        v -= L[i * n + k] * L[j * n + k];
+                    if (i == j) {
+                        if (!(v > 0.0))
+                            throw std::runtime_error("drt::hip::NormalEquationsAlong::solve: the damped matrix of a channel is not positive definite "
+                                                     "(linearly dependent directions: give it lambda > 0)");
+                        L[i * n + i] = std::sqrt(v);
+                    } else
+                        L[i * n + j] = v / L[j * n + j];
+                }
+            for (std::size_t i = 0; i < n; ++i) {          // L y = -b
+                double v = -bc[rows[i]];
+                for (std::size_t k = 0; k < i; ++k)
+                    v -= L[i * n + k] * y[k];
+                y[i] = v / L[i * n + i];
+            }
+            for (std::size_t ii = n; ii-- > 0;) {           // L^T x = y
+                double v = y[ii];
+                for (std::size_t k = ii + 1; k < n; ++k)
+                    v -= L[k * n + ii] * step[rows[k] * 3 + (std::size_t)ch];
+                step[rows[ii] * 3 + (std::size_t)ch] = v / L[ii * n + ii];
+            }
+        }
+        return step;
+    }
+};
+
+template <typename T>
+inline NormalEquationsAlong<T> normal_equations_along(const Scene<T>& scene, const Camera<T>& cam, const Pathtracer<T>& tracer, std::size_t spp,
+                                                      const std::vector<Direction<T>>& directions, const Options& opt,
+                                                      const TargetOrResidual<T>& target_or_residual, Vector<T, 3>* img = nullptr,
+                                                      Vector<T, 3>* tangent_imgs = nullptr)
+{
+    if (!target_or_residual.image)
+        throw std::runtime_error("drt::hip::normal_equations_along: the normal equations need a target or a residual image");
+    FlatScene<T> flat = flatten(scene);
+    const std::vector<double> v = detail::directions_of("drt::hip::normal_equations_along", flat, directions);
+    const std::size_t npix = cam.width() * cam.height(), K = directions.size();
+    const std::vector<float> in = detail::to_floats(target_or_residual.image, npix);
+    NormalEquationsAlong<T> ne;
+    ne.n_dirs = K;
+    ne.A.assign(3 * (K ? K * K : 1), 0.0);
+    ne.b.assign(3 * (K ? K : 1), 0.0);
+    ne.loss.assign(3, 0.0);
+    std::vector<float> rgb, trgb;
+    ne.stats = detail::tangents_call("drt::hip::normal_equations_along", flat, describe(cam), tracer.absorb(), tracer.min_bounces(), spp, K, v,
+                                     in.data(), target_or_residual.is_residual, rgb, tangent_imgs ? &trgb : nullptr, ne.A.data(), ne.b.data(),
+                                     ne.loss.data(), opt);
+    detail::from_buffer(rgb.data(), npix, img);
+    if (tangent_imgs)
+        detail::from_buffer(trgb.data(), npix * K, tangent_imgs);
     return ne;
 }
 

@@ -429,8 +429,8 @@ int drt_hip_render_tangent_double(drt_hip_ctx* ctx, const drt_camera_desc* cam, 
  * Roulette-terminated renders are allowed, but a lane of the path kernel is a pixel here, so they run in lockstep: every wave lasts as
  * long as the longest of its 64 paths, where the regenerating form drt_hip_render takes for such renders keeps its lanes busy (the
  * reference's defaults, -b 1 -p 0.5: 0.87 against 0.50 ms on a 512 x 512 x 64 frame).
- * DRT_ERR_UNSUPPORTED (the message says "normal equations"): more than DRT_FAST_PARAMS (8) parameters -- J^T J v by tangent + reverse
- * is the matrix-free route for those; a mirror material costs one of the 8 columns (its internal colour constant), so a scene with a
+ * DRT_ERR_UNSUPPORTED (the message says "normal equations"): more than DRT_FAST_PARAMS (8) parameters -- drt_hip_render_normal_equations_along
+ * (8 directions per render) or J^T J v by tangent + reverse are the routes for those; a mirror material costs one of the 8 columns (its internal colour constant), so a scene with a
  * mirror may have 7 --, more than 2^31 camera samples in the frame (the shard renders in one batch; batch_paths is ignored), a render
  * that a DRT_HIP_* setting forces onto the queue wavefront or into several batches, a scene that holds a triangle mesh, bounces_per_launch >= 1, DRT_RENDER_UNFUSED, _UNBIASED,
  * _LOSS_L2, _ALLREDUCE, _ALLREDUCE_ASYNC, a group context.  DRT_ERR_INVALID: both or neither of target_rgb and residual_rgb, NULL
@@ -440,6 +440,40 @@ int drt_hip_render_normal_equations(drt_hip_ctx* ctx, const drt_camera_desc* cam
                                     float* out_rgb /* may be NULL */, double* out_A /* 3 x P x P */, double* out_b /* 3 x P */,
                                     double* out_loss /* 3, may be NULL */, float* out_jacobian /* P x H x W x 3, may be NULL */,
                                     drt_hip_stats* stats);
+/* J v_k for k < n_dirs directions of parameter space in ONE render: out_tangents[k] (H x W x 3 floats each) is what
+ * drt_hip_render_tangent returns for param_tangents[k] (n_params x 3 doubles each) -- the same path, the same sums per direction, for any
+ * number of scene parameters the path kernels stage (136): the forward mode keeps one running sum per direction and channel and no
+ * per-parameter state.  1 <= n_dirs <= DRT_HIP_MAX_DIRS; the kernel is instantiated for 2, 4 and 8 directions and a call's count is
+ * padded up with zero directions, which add exact zeros: the image of a direction depends neither on the other directions nor on n_dirs,
+ * bit for bit.  With V = unit vectors of a block of parameters this is the Jacobian image of a P-parameter scene in ceil(P / 8) renders;
+ * with V = the columns of d theta / d phi it is the Jacobian of a reparametrised scene (one tint over ten albedos; albedo = s base).
+ * Rules of drt_hip_render_normal_equations for everything but the directions (shards, DRT_RENDER_DEVICE_OUT -- out_rgb and out_tangents
+ * are then device pointers; the directions are host memory always --, _F64, _SYNC, _TIMING, one batch, lockstep under the roulette);
+ * rules of drt_hip_render_tangent for the directions (finite values, requires_grad ignored).  With DRT_RENDER_F64 the float images are
+ * the double sums rounded.
+ * DRT_ERR_INVALID: n_dirs outside 1 ... DRT_HIP_MAX_DIRS, NULL param_tangents or out_tangents, a direction value that is not finite,
+ * asynchronous frames in flight.  DRT_ERR_UNSUPPORTED: a scene that holds a triangle mesh, bounces_per_launch >= 1, DRT_RENDER_UNFUSED,
+ * _UNBIASED, _LOSS_L2, _ALLREDUCE*, a group context, more than 136 parameters, a render forced into several batches or onto the queue
+ * wavefront.  The message of either says "tangents"; the context stays usable. */
+#define DRT_HIP_MAX_DIRS 8
+int drt_hip_render_tangents(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_params* rp, int32_t n_dirs,
+                            const double* param_tangents /* n_dirs x n_params x 3 */, float* out_rgb /* may be NULL */,
+                            float* out_tangents /* n_dirs x H x W x 3 */, drt_hip_stats* stats);
+/* ... and the normal equations in their span -- Gauss-Newton / Levenberg-Marquardt over span(V), exact for a reparametrised scene,
+ * for scenes of any number of parameters (drt_hip_render_normal_equations stops at 8).  With T[x,k,ch] = out_tangents[k][x][ch]:
+ *   out_A[ch][k][l] = sum_x T[x,k,ch] T[x,l,ch]   (3 x K x K doubles, K = n_dirs, both triangles written)
+ *   out_b[ch][k]    = sum_x T[x,k,ch] r[x,ch]     (3 x K)
+ *   out_loss[ch]    = sum_x r[x,ch]^2             (3, may be NULL)
+ * from the same render, reduced by the kernels of drt_hip_render_normal_equations (fp64, no atomics: the same call returns the same
+ * bits; the sums are over this call's shard).  Exactly one of target_rgb and residual_rgb, as there; out_tangents may be NULL.
+ * Refusals as above plus DRT_ERR_INVALID for both or neither of target_rgb and residual_rgb, NULL out_A or out_b and a value of a host
+ * image that is not finite; the message says "normal equations along". */
+int drt_hip_render_normal_equations_along(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_params* rp, int32_t n_dirs,
+                                          const double* param_tangents /* n_dirs x n_params x 3 */,
+                                          const float* target_rgb /* or NULL */, const float* residual_rgb /* or NULL */,
+                                          float* out_rgb /* may be NULL */, double* out_A /* 3 x K x K */, double* out_b /* 3 x K */,
+                                          double* out_loss /* 3, may be NULL */, float* out_tangents /* n_dirs x H x W x 3, may be NULL */,
+                                          drt_hip_stats* stats);
 /* stream the context launches on (a hipStream_t), for event timing / interop */
 void* drt_hip_stream(drt_hip_ctx* ctx);
 int drt_hip_synchronize(drt_hip_ctx* ctx);

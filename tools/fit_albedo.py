@@ -40,7 +40,15 @@ objective has its minimum -- ~9 % below the true albedo at 16 spp with one sampl
 Here the same covariance is divided by a J^T J that the pixels' variance inflates, and the Gauss-Newton fixed point is lower still:
 measured on the device at the defaults, red settles at 0.286 (6 steps, the last two 0.2866 and 0.2857), so this form exits with
 status 1 at the defaults; it is for frames with enough samples that the bias is below what the caller needs.
---oracle runs the same loop on the CPU restatement, J assembled from oracle.render(backward=True, grad_image_param=p)."""
+--oracle runs the same loop on the CPU restatement, J assembled from oracle.render(backward=True, grad_image_param=p).
+
+--gauss-newton --scene cornell_shapes: ALL parameters of a scene past the eight the normal equations take (ten: an albedo per shape, the
+unused `white`, the emission), from a perturbed start, through drt_hip_render_normal_equations_along -- unit-vector directions in blocks
+of at most eight (8 + 2), block Gauss-Seidel: per step every block in turn takes the two-seed Levenberg-Marquardt step above (its own
+K x K system per channel; a row whose diagonal is zero -- `white`, a channel nothing depends on -- stays where it is), 4 renders per
+block.  --subspace tint fits ONE tint over the albedos instead (three directions d theta / d tint_ch, one block).  Printed beside it:
+Adam over the same parameters from the same start with the same number of renders, and both fits' loss on a fixed pair of evaluation
+seeds (sum of r_A r_B, the unbiased estimate of the squared error against the target)."""
 import argparse
 import os
 import sys
@@ -75,6 +83,7 @@ def fit(render, n_params, p_index, start, steps, spp, n_values, lr=0.08, decay=0
     return params[p_index].copy(), hist
 
 
+ALONG_STEPS = 4       # block Gauss-Seidel steps over cornell_shapes by default (64 x 64 x 8: what the CPU loop needs, tests/test_gpu_tangents.py has its trace)
 GN_STEPS = 5          # Gauss-Newton steps the tool takes by default: what the CPU loop (--oracle) needs at 128 x 128 x 16 (HISTORY.md has its trace)
 
 
@@ -116,12 +125,145 @@ def fit_gauss_newton(render, p_index, start, steps, one_render=False, lam=1e-3, 
     return params[p_index].copy(), hist
 
 
+def used_params(scene):
+    """the parameters some shape's material or emitter refers to (cornell_shapes declares `white` and uses it nowhere: no pixel depends on it)"""
+    used = set()
+    for _, m, e, _ in scene.shapes:
+        if m >= 0:
+            used.add(scene.materials[m][1])
+        if e >= 0:
+            used.add(scene.emitters[e])
+    return used
+
+
+def unit_blocks(n_params, width=8):
+    """unit-vector directions (1 on the three channels of one parameter) in blocks of at most `width`: [K, P, 3] each"""
+    blocks = []
+    for p0 in range(0, n_params, width):
+        V = np.zeros((min(width, n_params - p0), n_params, 3))
+        for k in range(V.shape[0]):
+            V[k, p0 + k, :] = 1.0
+        blocks.append(V)
+    return blocks
+
+
+def lm_solve(A, b, lam):
+    """per channel (A + lam diag A) x = -b over the rows whose diagonal is positive; the others stay: [K, 3]"""
+    K = A.shape[1]
+    x = np.zeros((K, 3))
+    for ch in range(3):
+        d = np.diag(A[ch])
+        rows = np.flatnonzero(d > 0)
+        if rows.size:
+            M = A[ch][np.ix_(rows, rows)] + lam * np.diag(d[rows])
+            x[rows, ch] = np.linalg.solve(M, -b[ch][rows])
+    return x
+
+
+def eval_loss(render, params, seeds=(9001, 9002), spp=128):
+    """sum over the pixel values of r_A r_B on a fixed pair of sample sets of `spp` samples (not counted as renders of a fit): E = the
+    squared error of the true image against the target; the pair's noise falls with 1 / spp"""
+    a, _ = render(params, seeds[0], False, None, spp=spp)
+    ra = a.astype(np.float64) - render.target
+    b, _ = render(params, seeds[1], False, None, spp=spp)
+    return float((ra * (b.astype(np.float64) - render.target)).sum())
+
+
+def fit_gauss_newton_along(render, blocks, start, steps, lam=1e-3, lo=0.0, hi=None, log=None):
+    """render as in fit(), plus render.normal_equations_along(params, seed, V, residual) -> (A [3,K,K], b [3,K], image).  `blocks`: lists
+    of directions [K, P, 3]; per step every block in turn takes a two-seed Levenberg-Marquardt step along its directions (block
+    Gauss-Seidel; a lambda per block).  4 renders per block and step.  -> (fitted params, history of the two-seed loss per step)"""
+    params = np.array(start, dtype=np.float64)
+    hi = np.full(params.shape, 1.0) if hi is None else hi
+    lams = [lam] * len(blocks)
+    hist = []
+    for k in range(steps):
+        for bi, V in enumerate(blocks):
+            sa, sb = 1000 + 2 * (k * len(blocks) + bi), 1001 + 2 * (k * len(blocks) + bi)
+            img, _ = render(params, sa, False, None)
+            r = img.astype(np.float64) - render.target
+            A, b, img_b = render.normal_equations_along(params, sb, V, r.astype(np.float32))
+            loss = float((r * (img_b.astype(np.float64) - render.target)).sum())
+            x = lm_solve(A, b, lams[bi])
+            cand = np.clip(params + np.einsum("kc,kpc->pc", x, V), lo, hi)
+            ca, _ = render(cand, sa, False, None)
+            ra = ca.astype(np.float64) - render.target
+            cb, _ = render(cand, sb, False, None)
+            loss_c = float((ra * (cb.astype(np.float64) - render.target)).sum())
+            if loss_c < loss:
+                params, lams[bi], verdict, loss = cand, max(lams[bi] / 3.0, 1e-9), "accepted", loss_c
+            else:
+                lams[bi], verdict = lams[bi] * 4.0, "rejected"
+            if log:
+                log(f"step {k:3d} block {bi}  loss {loss:.6f}  lambda {lams[bi]:.2e}  {verdict}")
+        hist.append(loss)
+    return params, hist
+
+
+def fit_adam_all(render, free, start, steps, spp, n_values, lr=0.05, decay=0.97, lo=0.0, hi=None, log=None):
+    """Adam on every parameter row listed in `free`, two renders per step as in fit().  -> (fitted params, history of the loss)"""
+    params = np.array(start, dtype=np.float64)
+    hi = np.full(params.shape, 1.0) if hi is None else hi
+    m = np.zeros_like(params); v = np.zeros_like(params)
+    b1, b2, eps = 0.8, 0.99, 1e-8
+    mask = np.zeros(params.shape[0], bool)
+    mask[list(free)] = True
+    hist = []
+    for k in range(steps):
+        img, _ = render(params, 1000 + 2 * k, False, None)
+        r = img.astype(np.float64) - render.target
+        _, grads = render(params, 1001 + 2 * k, True, (2.0 * r / n_values).astype(np.float32))
+        g = np.where(mask[:, None], grads / spp, 0.0)
+        m = b1 * m + (1 - b1) * g
+        v = b2 * v + (1 - b2) * g * g
+        params = np.clip(params - lr * decay ** k * (m / (1 - b1 ** (k + 1))) / (np.sqrt(v / (1 - b2 ** (k + 1))) + eps), lo, hi)
+        hist.append(float((r ** 2).sum()))
+        if log and (k % 4 == 3 or k == steps - 1):
+            log(f"adam step {k:3d}  loss {hist[-1]:.6f}")
+    return params, hist
+
+
+def perturbed_start(params0, seed=7, amount=0.2):
+    """every value moved by up to `amount`, kept inside (0, 1] for albedos (rows whose true value exceeds 1, the emission, only below by amount)"""
+    p = params0 + np.random.RandomState(seed).uniform(-amount, amount, params0.shape)
+    return np.clip(p, 0.02, np.maximum(1.0, params0 + amount))
+
+
+def fit_scene(render, steps, subspace=None, log=None):
+    """the Levenberg-Marquardt fit of every parameter of render.scene (or of one tint over its albedos) beside Adam with the same number of
+    renders, from the same perturbed start -> dict of figures"""
+    P = len(render.params0)
+    hi = np.maximum(1.0, render.params0 + 0.5)
+    if subspace == "tint":
+        albedo = [p for p in range(P) if render.params0[p].max() <= 1.0]
+        V = np.zeros((3, P, 3))
+        for ch in range(3):
+            V[ch, albedo, ch] = render.params0[albedo, ch]
+        blocks, start, free = [V], render.params0.copy(), albedo
+        start[albedo] *= np.array([0.7, 1.25, 0.8])
+        start = np.clip(start, 0.0, hi)
+    else:
+        blocks, start, free = unit_blocks(P), perturbed_start(render.params0), range(P)
+    calls0 = render.calls
+    fitted, hist = fit_gauss_newton_along(render, blocks, start, steps, hi=hi, log=log)
+    gn_renders = render.calls - calls0
+    calls0 = render.calls
+    adam, ahist = fit_adam_all(render, free, start, gn_renders // 2, render.spp, render.target.size, hi=hi, log=log)
+    adam_renders = render.calls - calls0
+    used = [p for p in free if p in render.used_params()]
+    free = used
+    return {"start_loss": eval_loss(render, start), "gn_loss": eval_loss(render, fitted), "adam_loss": eval_loss(render, adam),
+            "gn_renders": gn_renders, "adam_renders": adam_renders, "gn_steps": steps, "adam_steps": gn_renders // 2,
+            "gn_error": float(np.abs(fitted - render.params0)[list(free)].max()), "adam_error": float(np.abs(adam - render.params0)[list(free)].max()),
+            "gn_params": fitted, "adam_params": adam, "gn_hist": hist}
+
+
 class DeviceRender:
     """The device through the C ABI (drt_hip_render, or drt_hip_render_async + drt_hip_wait)."""
 
-    def __init__(self, pkg, size, spp, depth, use_async=False):
+    def __init__(self, pkg, size, spp, depth, use_async=False, scene="cornell"):
         self.pkg = pkg
-        self.scene = pkg.cornell_box()
+        self.scene = pkg.scene_by_name(scene)
         self.cam = pkg.cornell_camera(size, size)
         self.spp, self.depth, self.use_async = spp, depth, use_async
         self.r = pkg.HipRenderer(0)
@@ -155,19 +297,35 @@ class DeviceRender:
         o = self.r.render_normal_equations(self.cam, rp, target=target, residual=residual)
         return o["A"], o["b"], o["loss"], o["image"]
 
+    def normal_equations_along(self, params, seed, V, residual):
+        self.r.update_params(params)
+        rp = self.pkg.RenderParams(spp=self.spp, min_bounces=self.depth, absorb=1.0, seed=seed)
+        self.calls += 1
+        o = self.r.render_normal_equations_along(self.cam, rp, V, residual=residual)
+        return o["A"], o["b"], o["image"]
+
+    def close(self):
+        self.r.close()
+
+    def used_params(self):
+        return used_params(self.scene)
+
 
 class OracleRender:
     """TEST INFRASTRUCTURE: the same loop on the CPU restatement."""
 
-    def __init__(self, pkg, oracle, size, spp, depth):
+    def __init__(self, pkg, oracle, size, spp, depth, scene="cornell"):
         self.pkg, self.oracle = pkg, oracle
-        self.scene = pkg.cornell_box()
+        self.calls = 0
+        self.scene = pkg.scene_by_name(scene)
         self.cam = pkg.cornell_camera(size, size)
         self.spp, self.depth = spp, depth
         self.params0 = np.array(self.scene.params, dtype=np.float64)
         self.target, _ = self(self.params0, 1, False, None, spp=256)
+        self.calls = 0
 
     def __call__(self, params, seed, backward, adjoint, spp=None):
+        self.calls += 1
         self.scene.params = [tuple(p) for p in params]
         rp = self.pkg.RenderParams(spp=spp or self.spp, min_bounces=self.depth, absorb=1.0, seed=seed)
         o = self.oracle.render(self.scene, self.cam, rp, backward=backward, adjoint=adjoint)
@@ -185,6 +343,26 @@ class OracleRender:
         r = np.asarray(residual, np.float64) if residual is not None else img - np.asarray(target, np.float64)
         return np.einsum("pxyc,qxyc->cpq", J, J), np.einsum("pxyc,xyc->cp", J, r), (r * r).sum((0, 1)), img
 
+    def normal_equations_along(self, params, seed, V, residual):
+        """the restatement in place of drt_hip_render_normal_equations_along: T_k = sum_p grad_image(p) v_k[p]"""
+        self.calls += 1
+        self.scene.params = [tuple(p) for p in params]
+        rp = self.pkg.RenderParams(spp=self.spp, min_bounces=self.depth, absorb=1.0, seed=seed)
+        T = np.zeros((V.shape[0],) + self.target.shape)
+        img = None
+        for p in np.flatnonzero(np.abs(V).sum((0, 2)) > 0):
+            o = self.oracle.render(self.scene, self.cam, rp, backward=True, grad_image_param=int(p))
+            img = o["image"]
+            T += np.asarray(o["grad_image"], np.float64)[None] * V[:, p][:, None, None, :]
+        r = np.asarray(residual, np.float64)
+        return np.einsum("kxyc,lxyc->ckl", T, T), np.einsum("kxyc,xyc->ck", T, r), img
+
+    def close(self):
+        pass
+
+    def used_params(self):
+        return used_params(self.scene)
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -197,13 +375,24 @@ def main():
     ap.add_argument("--async", dest="use_async", action="store_true")
     ap.add_argument("--oracle", action="store_true")
     ap.add_argument("--quiet", action="store_true")
+    ap.add_argument("--scene", default="cornell", help="cornell: the red albedo (the loops above); cornell_shapes: every parameter, with --gauss-newton")
+    ap.add_argument("--subspace", choices=("tint",), default=None, help="with --scene cornell_shapes: one tint over the albedos instead of every parameter")
     a = ap.parse_args()
     import __graft_entry__ as e
     pkg = e.load_package()
     if a.oracle:
-        render = OracleRender(pkg, e.load_oracle(), a.size, a.spp, a.depth)
+        render = OracleRender(pkg, e.load_oracle(), a.size, a.spp, a.depth, a.scene)
     else:
-        render = DeviceRender(pkg, a.size, a.spp, a.depth, a.use_async)
+        render = DeviceRender(pkg, a.size, a.spp, a.depth, a.use_async, a.scene)
+    if a.scene != "cornell":
+        if not a.gauss_newton:
+            ap.error("--scene other than cornell goes with --gauss-newton")
+        t0 = time.time()
+        f = fit_scene(render, a.steps or ALONG_STEPS, a.subspace, log=None if a.quiet else print)
+        print(f"{a.scene}{' (tint)' if a.subspace else ''}: two-seed loss at the start {f['start_loss']:.5f}; Levenberg-Marquardt {f['gn_steps']} steps, "
+              f"{f['gn_renders']} renders: loss {f['gn_loss']:.5f}, max parameter error {f['gn_error']:.4f}; Adam {f['adam_steps']} steps, "
+              f"{f['adam_renders']} renders: loss {f['adam_loss']:.5f}, max parameter error {f['adam_error']:.4f}  ({time.time() - t0:.2f} s)")
+        return 0 if f["gn_loss"] < f["adam_loss"] else 1
     if a.steps is None:
         a.steps = GN_STEPS if a.gauss_newton else 60
     if a.gauss_newton:
