@@ -44,6 +44,7 @@ MAX_DEPTH = 64
 K_RAYGEN, K_INTERSECT, K_SHADE, K_FILM, K_BACKWARD, K_GRADREDUCE, K_INTERSECT_MESH, K_PATH, K_COUNT = 0, 1, 2, 3, 4, 5, 6, 7, 8
 KERNEL_NAMES = ["raygen", "intersect", "shade", "film", "backward", "gradreduce", "intersect_mesh", "path"]
 MAX_DIRS = 8                 # DRT_HIP_MAX_DIRS: directions per render_tangents / render_normal_equations_along call
+MAX_PARAM_SETS = 8           # DRT_HIP_MAX_PARAM_SETS: parameter sets per render_param_sets call
 ABI_VERSION = 8
 UNIQUE_ID_BYTES = 128
 
@@ -720,12 +721,25 @@ class DrtHipError(RuntimeError):
     pass
 
 
+def check_param_sets(sets, n_params: int) -> np.ndarray:
+    """K parameter sets as drt_hip_render_param_sets takes them: float64 [K, n_params, 3], 1 <= K <= MAX_PARAM_SETS, finite values.
+    Raises ValueError otherwise (what the library would refuse, said before the call)."""
+    v = np.ascontiguousarray(sets, dtype=np.float64)
+    if v.ndim != 3 or v.shape[1:] != (n_params, 3):
+        raise ValueError(f"param sets: expected shape [n_sets, {n_params}, 3], got {list(v.shape)}")
+    if not 1 <= v.shape[0] <= MAX_PARAM_SETS:
+        raise ValueError(f"param sets: n_sets = {v.shape[0]} outside 1 ... MAX_PARAM_SETS = {MAX_PARAM_SETS}")
+    if not np.isfinite(v).all():
+        raise ValueError("param sets: a set holds a value that is not finite")
+    return v
+
+
 _ABI_SYMBOLS = ["drt_hip_abi_version", "drt_hip_device_count", "drt_hip_create", "drt_hip_create_group",
                 "drt_hip_group_size", "drt_hip_device_pci_bus_id", "drt_hip_destroy",
                 "drt_hip_comm_unique_id", "drt_hip_comm_init_rank", "drt_hip_comm_size", "drt_hip_comm_destroy",
                 "drt_hip_upload_scene", "drt_hip_update_params", "drt_hip_set_specialisation", "drt_hip_render", "drt_hip_render_async", "drt_hip_wait",
                 "drt_hip_render_gradient_image", "drt_hip_render_tangent", "drt_hip_render_tangent_double", "drt_hip_render_normal_equations", "drt_hip_render_tangents",
-                "drt_hip_render_normal_equations_along", "drt_hip_pin_host", "drt_hip_unpin_host", "drt_hip_stream",
+                "drt_hip_render_normal_equations_along", "drt_hip_render_param_sets", "drt_hip_render_param_sets_double", "drt_hip_pin_host", "drt_hip_unpin_host", "drt_hip_stream",
                 "drt_hip_synchronize", "drt_hip_last_error", "drt_hip_kernel_name"]
 
 
@@ -770,6 +784,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.drt_hip_render_normal_equations_along.argtypes = [C.c_void_p, C.POINTER(CameraDesc), C.POINTER(RenderParamsDesc), C.c_int32, C.c_void_p,
                                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                           C.POINTER(HipStats)]
+    lib.drt_hip_render_param_sets.argtypes = [C.c_void_p, C.POINTER(CameraDesc), C.POINTER(RenderParamsDesc), C.c_int32, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(HipStats)]
+    lib.drt_hip_render_param_sets_double.argtypes = lib.drt_hip_render_param_sets.argtypes
     lib.drt_hip_pin_host.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
     lib.drt_hip_unpin_host.argtypes = [C.c_void_p, C.c_void_p]
     lib.drt_hip_stream.argtypes = [C.c_void_p]
@@ -1146,6 +1163,57 @@ class HipRenderer:
                                                             C.c_void_p(out_b_ptr or None), C.c_void_p(out_loss_ptr or None),
                                                             C.c_void_p(out_tangents_ptr or None), C.byref(stats) if want_stats else None)
         self._check(rc, "drt_hip_render_normal_equations_along")
+        return stats.as_dict() if want_stats else {}
+
+    def render_param_sets(self, cam: Camera, rp: RenderParams, sets: np.ndarray, target: Optional[np.ndarray] = None, f64: bool = False,
+                          images: bool = True, timing: bool = False, double: bool = False) -> dict:
+        """drt_hip_render_param_sets: the frame under the K <= MAX_PARAM_SETS parameter vectors `sets` ([K, n_params, 3]) in ONE trace;
+        the context's own parameters stay what they are.  `target` (float32 [H,W,3]) asks for the losses.
+        -> {"images" [K,H,W,3] float32 (double=True: float64, the means as the device formed them) or None,
+            "loss" [K,3] float64 = sum over this shard's pixels of (mean_k - target)^2, or None, "stats"}"""
+        assert self.scene is not None
+        v = check_param_sets(sets, self.scene.n_params)
+        K = v.shape[0]
+        if not images and target is None:
+            raise ValueError("param sets: no output requested (images=False without a target)")
+        d = rp.to_desc()
+        d.flags = (rp.flags & ~(RENDER_DEVICE_OUT | RENDER_SYNC)) | (RENDER_F64 if f64 else 0) | (RENDER_TIMING if timing else 0)
+        t_ptr = None
+        if target is not None:
+            target = np.ascontiguousarray(target, dtype=np.float32)
+            if target.shape != (cam.height, cam.width, 3):
+                raise ValueError(f"param sets: expected a target of shape {[cam.height, cam.width, 3]}, got {list(target.shape)}")
+            t_ptr = target.ctypes.data_as(C.c_void_p)
+        imgs = np.zeros((K, cam.height, cam.width, 3), dtype=np.float64 if double else np.float32) if images else None
+        loss = np.zeros((K, 3), dtype=np.float64) if target is not None else None
+        stats = HipStats()
+        cd = cam.to_desc()
+        fn = self.lib.drt_hip_render_param_sets_double if double else self.lib.drt_hip_render_param_sets
+        rc = fn(self.ctx, C.byref(cd), C.byref(d), K, v.ctypes.data_as(C.c_void_p), t_ptr,
+                imgs.ctypes.data_as(C.c_void_p) if images else None, loss.ctypes.data_as(C.c_void_p) if loss is not None else None,
+                None, C.byref(stats))
+        self._check(rc, "drt_hip_render_param_sets")
+        return {"images": imgs, "loss": loss, "stats": stats.as_dict()}
+
+    def render_param_sets_device(self, cam: Camera, rp: RenderParams, sets: np.ndarray, out_images_ptr: int = 0, out_loss_ptr: int = 0,
+                                 target_ptr: int = 0, out_rgb_ptr: int = 0, f64: bool = False, timing: bool = False, sync: bool = False,
+                                 want_stats: Optional[bool] = None) -> dict:
+        """drt_hip_render_param_sets on device pointers (images float32 [K,H,W,3], target float32 [H,W,3], loss float64 [K,3]), enqueued
+        on the context's stream; the sets are host memory."""
+        if want_stats is None:
+            want_stats = timing
+        assert self.scene is not None
+        v = check_param_sets(sets, self.scene.n_params)
+        d = rp.to_desc()
+        d.flags = ((rp.flags | RENDER_DEVICE_OUT) & ~RENDER_SYNC) | (RENDER_F64 if f64 else 0) | (RENDER_TIMING if timing else 0) | \
+                  (RENDER_SYNC if sync else 0)
+        stats = HipStats()
+        cd = cam.to_desc()
+        rc = self.lib.drt_hip_render_param_sets(self.ctx, C.byref(cd), C.byref(d), v.shape[0], v.ctypes.data_as(C.c_void_p),
+                                                C.c_void_p(target_ptr or None), C.c_void_p(out_images_ptr or None),
+                                                C.c_void_p(out_loss_ptr or None), C.c_void_p(out_rgb_ptr or None),
+                                                C.byref(stats) if want_stats else None)
+        self._check(rc, "drt_hip_render_param_sets")
         return stats.as_dict() if want_stats else {}
 
     def render_device(self, cam: Camera, rp: RenderParams, out_rgb_ptr: int, out_grad_ptr: int,

@@ -24,10 +24,20 @@ struct NormalEqRequest {
     float* d_jacobian = nullptr;          // P x H x W x 3, or none
     double *d_A = nullptr, *d_b = nullptr, *d_loss = nullptr;
 };
+// ... and one frame under several parameter sets (drt_hip_render_param_sets): the path kernel's parameter-set form, then k_sets_finish.  All
+// pointers are the device's
+struct ParamSetsRequest {
+    int n_sets = 0, width = 0;            // the caller's sets; the kernel's width K (padded with copies of the context's own parameters)
+    const float* d_target = nullptr;      // H x W x 3, or none
+    float* d_images = nullptr;            // n_sets x H x W x 3, or none
+    double* d_images64 = nullptr;         // ... the means in double (drt_hip_render_param_sets_double), or none
+    double* d_loss = nullptr;             // n_sets x 3, or none (needs d_target)
+};
 struct TangentRequest {
     const void* d_params = nullptr;       // [the scene's parameters | the direction] in the render's compute type: the path kernel's `params`
     bool keep_sums = false;               // the pixels' sums of both images also stay in `film` / `gfilm`, in double (drt_hip_render_tangent_double)
     const NormalEqRequest* neq = nullptr; // not a forward-mode render at all: the normal equations (d_params, keep_sums unused)
+    const ParamSetsRequest* sets = nullptr;   // not a forward-mode render either: d_params holds [parameters | P_1 | ... | P_K]
     int n_dirs = 0;                       // > 0, with neq: the K-direction forward form (drt_hip_render_tangents / _normal_equations_along) -- d_params holds
                                           // [parameters | v_1 | ... | v_K], K = n_dirs padded up to an instantiated width with zero directions, and the
                                           // rows k_normal_eq reduces are the n_dirs directions instead of the parameters

@@ -613,6 +613,178 @@ int drt_hip_render_normal_equations_along(drt_hip_ctx* ctx, const drt_camera_des
     return render_tangents_common(ctx, cam, rp, n_dirs, param_tangents, target_rgb, residual_rgb, out_rgb, out_A, out_b, out_loss, out_tangents, stats, true);
 }
 
+} // extern "C"
+
+// ---- one frame under up to DRT_HIP_MAX_PARAM_SETS parameter sets in one trace ----
+// dst = [the scene's parameters | P_1 | ... | P_K] in compute type R: sets at and above n_sets are the context's own parameters (padding up
+// to the kernel's width; the last one is the plain image's), and so are internal constants (a mirror's colour) in every set
+template <typename R>
+__global__ void __launch_bounds__(DRT_BLOCK) k_stage_param_sets(const R* __restrict__ params, int n_all, const double* __restrict__ h_sets, int n_user,
+                                                                int n_sets, int K, R* __restrict__ dst)
+{
+    for (int i = blockIdx.x * DRT_BLOCK + threadIdx.x; i < n_all; i += gridDim.x * DRT_BLOCK) {
+        dst[i] = params[i];
+        for (int k = 0; k < K; ++k)
+            dst[(size_t)(1 + k) * n_all + i] = (k < n_sets && i < n_user) ? (R)h_sets[(size_t)k * n_user + i] : params[i];
+    }
+}
+
+static int render_param_sets_common(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_params* rp, int32_t n_sets,
+                                    const double* param_sets, const float* target_rgb, float* out_images, double* out_images64,
+                                    double* out_loss, float* out_rgb, drt_hip_stats* stats)
+{
+    if (!ctx)
+        return DRT_ERR_INVALID;
+    const auto no = [&](int code, const char* what) { return fail(ctx, code, (std::string("param sets: ") + what).c_str()); };
+    if (!ctx->members.empty())
+        return no(DRT_ERR_UNSUPPORTED, "not on a group context (render the shards on plain contexts)");
+    if (!ctx->has_scene)
+        return fail(ctx, DRT_ERR_NO_SCENE, "render before upload_scene");
+    if (!cam || !rp || cam->width <= 0 || cam->height <= 0)
+        return no(DRT_ERR_INVALID, "bad camera or render parameters");
+    if (n_sets < 1 || n_sets > DRT_HIP_MAX_PARAM_SETS)
+        return no(DRT_ERR_INVALID, "n_sets outside 1 ... DRT_HIP_MAX_PARAM_SETS = 8");
+    if (!param_sets)
+        return no(DRT_ERR_INVALID, "NULL param_sets");
+    if (!out_images && !out_images64 && !out_loss)
+        return no(DRT_ERR_INVALID, "no output requested (out_images and out_loss are both NULL)");
+    if (out_loss && !target_rgb)
+        return no(DRT_ERR_INVALID, "out_loss needs target_rgb");
+    if (rp->flags & DRT_RENDER_BACKWARD)
+        return no(DRT_ERR_INVALID, "a forward render: no DRT_RENDER_BACKWARD");
+    const bool dev = (rp->flags & DRT_RENDER_DEVICE_OUT) != 0;
+    const int n_user = ctx->n_user_params * 3, n_all = ctx->n_params * 3;
+    for (size_t i = 0; i < (size_t)n_sets * (size_t)n_user; ++i)
+        if (!std::isfinite(param_sets[i]))
+            return no(DRT_ERR_INVALID, "a set holds a value that is not finite");
+    const size_t npix = (size_t)cam->width * (size_t)cam->height;
+    if (!dev && target_rgb)
+        for (size_t i = 0; i < npix * 3; ++i)
+            if (!std::isfinite(target_rgb[i]))
+                return no(DRT_ERR_INVALID, "the target image holds a value that is not finite");
+    for (int i = 0; i < DRT_HIP_FRAMES_IN_FLIGHT; ++i)
+        if (ctx->in_flight[i])
+            return no(DRT_ERR_INVALID, "asynchronous frames are in flight -- drt_hip_wait for them first");
+    if (rp->flags & (DRT_RENDER_UNFUSED | DRT_RENDER_UNBIASED | DRT_RENDER_LOSS_L2 | DRT_RENDER_ALLREDUCE | DRT_RENDER_ALLREDUCE_ASYNC))
+        return no(DRT_ERR_UNSUPPORTED, "not with DRT_RENDER_UNFUSED, _UNBIASED, _LOSS_L2 or _ALLREDUCE* -- a forward render on the one-launch path kernel, one context");
+    if (ctx->has_mesh)
+        return no(DRT_ERR_UNSUPPORTED, "not of a scene that holds a triangle mesh");
+    if (rp->bounces_per_launch >= 1)
+        return no(DRT_ERR_UNSUPPORTED, "they come from the one-launch path kernel -- not with bounces_per_launch >= 1");
+    if (ctx->n_params > DRT_PATH_LDS_PARAMS)
+        return no(DRT_ERR_UNSUPPORTED, "more parameters than the path kernels stage (136)");
+    if ((uint64_t)cam->width * (uint64_t)cam->height * (uint64_t)(rp->spp > 0 ? rp->spp : 1) > 0x7FFFFFFFull)
+        return no(DRT_ERR_UNSUPPORTED, "more than 2^31 camera samples in one frame (the shard renders in one batch)");
+    // (the plain image is the kernel's last set, the context's own parameters: one set more)
+    const int n_int = n_sets + (out_rgb ? 1 : 0);
+    if (n_int > DRT_HIP_MAX_PARAM_SETS)
+        return no(DRT_ERR_UNSUPPORTED, "out_rgb beside 8 sets (the plain image takes one of the kernel's eight: drt_hip_render gives it)");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    // the sets -> pinned memory -> [parameters | P_1 | ... | P_K] on the device, in stream order: drt_hip_render_tangent's double buffer
+    // and events (the copy this call rewrites was read by the launch of the call before the previous one)
+    const int K = n_int <= 2 ? 2 : (n_int <= 4 ? 4 : 8);
+    const int hb = (int)(ctx->tangent_calls++ & 1);
+    const size_t need = (size_t)n_sets * (size_t)(n_user ? n_user : 1);
+    if (!ctx->ev_tangent[hb])
+        HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_tangent[hb], hipEventDisableTiming));
+    else
+        HIPCHK(ctx, hipEventSynchronize(ctx->ev_tangent[hb]));
+    if (ctx->h_tangent_cap[hb] < need) {
+        if (ctx->h_tangent[hb])
+            (void)hipHostFree(ctx->h_tangent[hb]);
+        ctx->h_tangent[hb] = nullptr;
+        ctx->h_tangent_cap[hb] = 0;
+        HIPCHK(ctx, hipHostMalloc((void**)&ctx->h_tangent[hb], need * sizeof(double)));
+        ctx->h_tangent_cap[hb] = need;
+    }
+    memcpy(ctx->h_tangent[hb], param_sets, (size_t)n_sets * (size_t)n_user * sizeof(double));
+    int rc;
+    if ((rc = ensure(ctx, ctx->tangent, (size_t)(n_all ? n_all : 1) * (size_t)(1 + K) * sizeof(double))) != DRT_OK) return rc;
+    if (n_all > 0) {
+        const unsigned blocks = (unsigned)((n_all + DRT_BLOCK - 1) / DRT_BLOCK);
+        if (rp->flags & DRT_RENDER_F64)
+            hipLaunchKernelGGL(k_stage_param_sets<double>, dim3(blocks), dim3(DRT_BLOCK), 0, ctx->stream, (const double*)ctx->d_params_d, n_all,
+                               (const double*)ctx->h_tangent[hb], n_user, (int)n_sets, K, (double*)ctx->tangent.p);
+        else
+            hipLaunchKernelGGL(k_stage_param_sets<float>, dim3(blocks), dim3(DRT_BLOCK), 0, ctx->stream, (const float*)ctx->d_params_f, n_all,
+                               (const double*)ctx->h_tangent[hb], n_user, (int)n_sets, K, (float*)ctx->tangent.p);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    HIPCHK(ctx, hipEventRecord(ctx->ev_tangent[hb], ctx->stream));
+    // the caller's images: device pointers as they are; host buffers through buffers of the context's own
+    ParamSetsRequest q;
+    q.n_sets = n_sets;
+    q.width = K;
+    const size_t n_img = (size_t)n_sets * npix * 3;
+    if (dev) {
+        q.d_target = target_rgb;
+        q.d_images = out_images;
+        q.d_loss = out_loss;
+    } else {
+        if (target_rgb) {
+            if ((rc = ensure(ctx, ctx->neq_in, npix * 3 * sizeof(float))) != DRT_OK) return rc;
+            HIPCHK(ctx, hipMemcpyAsync(ctx->neq_in.p, target_rgb, npix * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+            q.d_target = (const float*)ctx->neq_in.p;
+        }
+        if (out_images || out_images64) {
+            if ((rc = ensure(ctx, ctx->neq_jac, n_img * (out_images64 ? sizeof(double) : sizeof(float)))) != DRT_OK) return rc;
+            if (out_images64)
+                q.d_images64 = (double*)ctx->neq_jac.p;
+            else
+                q.d_images = (float*)ctx->neq_jac.p;
+        }
+        if (out_loss) {
+            if ((rc = ensure(ctx, ctx->neq_out, (size_t)DRT_SETS_VALUES * sizeof(double))) != DRT_OK) return rc;
+            q.d_loss = (double*)ctx->neq_out.p;
+        }
+    }
+    // (a shard without rows launches nothing: its sums are zero)
+    if (q.d_loss)
+        HIPCHK(ctx, hipMemsetAsync(q.d_loss, 0, (size_t)n_sets * 3 * sizeof(double), ctx->stream));
+    TangentRequest req;
+    req.d_params = ctx->tangent.p;
+    req.sets = &q;
+    if ((rc = render_common(ctx, cam, rp, nullptr, out_rgb, nullptr, stats, -1, nullptr, &req)) != DRT_OK)
+        return rc;
+    if (dev)
+        return DRT_OK;
+    // host buffers: the render has waited for its stream; the losses, and the images' rows of this shard
+    if (out_loss)
+        HIPCHK(ctx, hipMemcpy(out_loss, ctx->neq_out.p, (size_t)n_sets * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    if (out_images || out_images64) {
+        const RenderJob& j = ctx->job;
+        const size_t el = out_images64 ? sizeof(double) : sizeof(float), row = (size_t)cam->width * 3 * el;
+        uint8_t* dst = out_images64 ? (uint8_t*)out_images64 : (uint8_t*)out_images;
+        hipError_t e = hipSuccess;
+        for (size_t k = 0; k < (size_t)n_sets; ++k)
+            for_each_band(cam->height, j.band, j.n_shards, j.shard, [&](int y0, int y1) {
+                const size_t at = k * npix * 3 * el + (size_t)y0 * row;
+                if (e == hipSuccess)
+                    e = hipMemcpy(dst + at, (const uint8_t*)ctx->neq_jac.p + at, (size_t)(y1 - y0) * row, hipMemcpyDeviceToHost);
+            });
+        HIPCHK(ctx, e);
+    }
+    return DRT_OK;
+}
+
+extern "C" {
+
+int drt_hip_render_param_sets(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_params* rp, int32_t n_sets,
+                              const double* param_sets, const float* target_rgb, float* out_images, double* out_loss, float* out_rgb,
+                              drt_hip_stats* stats)
+{
+    return render_param_sets_common(ctx, cam, rp, n_sets, param_sets, target_rgb, out_images, nullptr, out_loss, out_rgb, stats);
+}
+
+int drt_hip_render_param_sets_double(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_params* rp, int32_t n_sets,
+                                     const double* param_sets, const float* target_rgb, double* out_images, double* out_loss, float* out_rgb,
+                                     drt_hip_stats* stats)
+{
+    if (ctx && rp && (rp->flags & DRT_RENDER_DEVICE_OUT))
+        return fail(ctx, DRT_ERR_INVALID, "param sets: the double images come through host buffers only (no DRT_RENDER_DEVICE_OUT)");
+    return render_param_sets_common(ctx, cam, rp, n_sets, param_sets, target_rgb, nullptr, out_images, out_loss, out_rgb, stats);
+}
+
 // ---- asynchronous host-buffer renders ---------------------------------------------------------------
 // drt_hip_render returns when the results are in the caller's buffers: every frame pays a 3 MB device-to-host copy and a
 // stream synchronisation with the GPU idle meanwhile (config 3: 1.13 instead of 0.86 ms per frame).  An optimisation loop

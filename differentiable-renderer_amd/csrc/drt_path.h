@@ -541,6 +541,60 @@ struct Tangents<R, DRT_NP_TANGENT, NC> {
     }
 };
 
+// ---- ONE path under K parameter SETS (NP = DRT_NP_SETS, NC = K in {2, 4, 8}; drt_hip_render_param_sets) --------------------------
+// A parameter is a colour or an emission and nothing else: the closest hit, the BxDF sample, the roulette and the draw indices do not
+// see its value, so a path under parameter set A is the same path under set B.  K sets cost one ray, one key, one hit, one m_k and K
+// pairs (T_k, L_k), moved by the forward-only form's own operations on set k's operands in its order:
+//     per bounce  T_k = T_k * (col_k * m)          per light  L_k = L_k + T_k * (e_k * inv_pk)
+// No zero-channel bookkeeping: a forward render keeps real zeros in T.  Tables: K of (n + 1) rows of four, n the SCENE's parameter
+// count, in dynamic shared memory, staged from [params | P_1 | ... | P_K] behind the kernel's `params`; row n is the rest row (1, 1, 1)
+// of a lane whose path does not go on.  Lockstep form only (a lane is a pixel): at the end of its sample range a lane writes its sums in
+// the Jacobian form's layout, gpix[range][3 k + ch][pixel], for k below the caller's count (PathArgs::dirs_out()); the radiance partials
+// (`fpart`, where the caller wants the plain image) are the sums of set K - 1, which the host fills with the context's own parameters.
+#define DRT_NP_SETS (-3)
+// blocks per CU (= waves per SIMD) of the f32 forms: the most that stay free of scratch (the compiler's report: DESIGN.md 9b)
+#ifndef DRT_SETS2_MIN_BLOCKS
+#define DRT_SETS2_MIN_BLOCKS 6
+#endif
+#ifndef DRT_SETS4_MIN_BLOCKS
+#define DRT_SETS4_MIN_BLOCKS 4
+#endif
+#ifndef DRT_SETS8_MIN_BLOCKS
+#define DRT_SETS8_MIN_BLOCKS 2
+#endif
+__host__ __device__ inline uint32_t sets_table_words(uint32_t n, uint32_t K) { return K * (n + 1u) * 4u; }
+template <typename R, int K, typename SL>
+__device__ inline void stage_sets(R* __restrict__ tab, const SL& lds, const R* __restrict__ params)
+{
+    // (after stage_path_scene's barrier)
+    const int n = lds.sc.n_params < DRT_PATH_LDS_PARAMS ? lds.sc.n_params : DRT_PATH_LDS_PARAMS;
+    for (int i = threadIdx.x; i < K * (n + 1); i += blockDim.x) {
+        const int k = i / (n + 1), p = i - k * (n + 1);
+        const R* src = params + ((size_t)(1 + k) * lds.sc.n_params + p) * 3;
+        R* row = tab + (size_t)i * 4;
+        row[0] = p < n ? src[0] : R(1);
+        row[1] = p < n ? src[1] : R(1);
+        row[2] = p < n ? src[2] : R(1);
+        row[3] = R(0);
+    }
+    __syncthreads();
+}
+
+template <typename R, int NC>
+struct Tangents<R, DRT_NP_SETS, NC> {
+    V3<R> T[NC], L[NC];             // per set: prefix throughput and radiance of the current path
+    const R* tab;                   // the block's tables (see above)
+    uint32_t rest, stride;          // the rest row = the scene's parameter count; words of one table
+    __device__ inline void new_path()
+    {
+#pragma unroll
+        for (int k = 0; k < NC; ++k) {
+            T[k] = mk<R>(R(1), R(1), R(1));
+            L[k] = mk<R>(R(0), R(0), R(0));
+        }
+    }
+};
+
 // what a block of a general-form kernel keeps in LDS, and the two ends of its life
 template <typename R>
 struct GenBlock {
@@ -628,86 +682,97 @@ template <typename R, int NP, int NC, bool LOSS = false, typename SL = PathScene
 __device__ inline void add_emission(const SL& lds, const TangentLds<R>& tl, const R* __restrict__ params, uint32_t eid, R inv_pk,
                                     V3<R> T, V3<R> g, V3<R>& L, Tangents<R, NP, NC>& tg)
 {
-    const V3<R> E = load_param<R, (NP != 0)>(lds, params, (int)eid) * inv_pk;
-    V3<R> Tr = T;
-    if (NC > 0 || NP == DRT_NP_ANY || NP == DRT_NP_TANGENT)  // a channel that met a zero colour is dark
-        Tr = mk<R>((tg.zc & 0xFFu) ? R(0) : T.x, (tg.zc & 0xFF00u) ? R(0) : T.y, (tg.zc & 0xFF0000u) ? R(0) : T.z);
-    L = L + Tr * E;
-    if constexpr (NP == DRT_NP_TANGENT && NC > 0) {
-        // K directions: the single-direction case below, once per direction
-        const R* dir = tg.tab + (1u + 2u * NC) * tg.stride + (eid < tg.rest ? eid : 0u) * 3u;
-        const uint32_t zx = tg.zc & 0xFFu, zy = tg.zc & 0xFF00u, zz = tg.zc & 0xFF0000u;
+    if constexpr (NP == DRT_NP_SETS) {
+        // K parameter sets: the forward-only form's L = L + T (e inv_pk), once per set on the set's own emission, T and L
+        const R* er = tg.tab + (eid < tg.rest ? eid : 0u) * 4u;
 #pragma unroll
         for (int k = 0; k < NC; ++k) {
-            const R* vd = dir + (uint32_t)k * 3u * tg.rest;
-            const V3<R> Ed = mk<R>(vd[0], vd[1], vd[2]) * inv_pk;
-            const V3<R> d0 = mk<R>(fma_r(E.x, tg.S[k].x, Ed.x), fma_r(E.y, tg.S[k].y, Ed.y), fma_r(E.z, tg.S[k].z, Ed.z));
-            const V3<R> d1 = E * tg.Z[k];
-            tg.dL[k] = mk<R>(fma_r(T.x, zx == 0u ? d0.x : (zx == 0x1u ? d1.x : R(0)), tg.dL[k].x),
-                             fma_r(T.y, zy == 0u ? d0.y : (zy == 0x100u ? d1.y : R(0)), tg.dL[k].y),
-                             fma_r(T.z, zz == 0u ? d0.z : (zz == 0x10000u ? d1.z : R(0)), tg.dL[k].z));
+            const R* e = er + (uint32_t)k * tg.stride;
+            const V3<R> Ek = mk<R>(e[0], e[1], e[2]) * inv_pk;
+            tg.L[k] = tg.L[k] + tg.T[k] * Ek;
         }
-    } else
-    if constexpr (NP == DRT_NP_TANGENT) {
-        // forward mode: T (e S + e') where no factor of the channel is zero, T e Z where exactly one is
-        const R* vd = tg.dl->dir + (eid < DRT_PATH_LDS_PARAMS ? eid : 0u) * 3u;
-        const V3<R> Ed = mk<R>(vd[0], vd[1], vd[2]) * inv_pk;
-        const V3<R> d0 = mk<R>(fma_r(E.x, tg.S.x, Ed.x), fma_r(E.y, tg.S.y, Ed.y), fma_r(E.z, tg.S.z, Ed.z));
-        const V3<R> d1 = E * tg.Z;
-        const uint32_t zx = tg.zc & 0xFFu, zy = tg.zc & 0xFF00u, zz = tg.zc & 0xFF0000u;
-        tg.dL = mk<R>(fma_r(T.x, zx == 0u ? d0.x : (zx == 0x1u ? d1.x : R(0)), tg.dL.x),
-                      fma_r(T.y, zy == 0u ? d0.y : (zy == 0x100u ? d1.y : R(0)), tg.dL.y),
-                      fma_r(T.z, zz == 0u ? d0.z : (zz == 0x10000u ? d1.z : R(0)), tg.dL.z));
-    } else
-    if constexpr (NP == DRT_NP_ANY) {
-        // any number of parameters: the light's own row, then every vertex of the path's history adds to its colour's row
-        if (LOSS)
-            g = mk<R>(R(2) * (L.x - g.x), R(2) * (L.y - g.y), R(2) * (L.z - g.z));
-        const V3<R> gE = g * E;
-        const uint32_t ebits = pid_unpack(tg.gl->invc[eid < DRT_PATH_LDS_PARAMS ? eid : 0][3]);
-        if ((ebits & 0xFFFFu) != DRT_SLOT_NONE && eid < DRT_PATH_LDS_PARAMS)
-            tg.add(ebits & 0xFFFFu, g * Tr * inv_pk);
-        const V3<R> TgE = Tr * gE;
-        const V3<R> U = mk<R>((tg.zc & 0xFFu) == 0x1u ? T.x * gE.x : R(0), (tg.zc & 0xFF00u) == 0x100u ? T.y * gE.y : R(0),
-                              (tg.zc & 0xFF0000u) == 0x10000u ? T.z * gE.z : R(0));
-        const uint32_t nw = tg.nv >> 2;
-        for (uint32_t w = 0; wave_any(w < nw); ++w)
-            tg.add_word(w < nw ? tg.load_word(w) : 0xFFFFFFFFu, TgE, U);
-        tg.add_word(tg.cur, TgE, U);
-    } else
-    if constexpr (NP > 0) {
-        if (NC > 0)
-            asm volatile("" ::: "memory");    // (keeps the reads of `tl` below where they are: see there)
-        if (LOSS)
-            g = mk<R>(R(2) * (L.x - g.x), R(2) * (L.y - g.y), R(2) * (L.z - g.z));
-        const V3<R> gE = g * E, gT = g * Tr * inv_pk;
+    } else {
+        const V3<R> E = load_param<R, (NP != 0)>(lds, params, (int)eid) * inv_pk;
+        V3<R> Tr = T;
+        if (NC > 0 || NP == DRT_NP_ANY || NP == DRT_NP_TANGENT)  // a channel that met a zero colour is dark
+            Tr = mk<R>((tg.zc & 0xFFu) ? R(0) : T.x, (tg.zc & 0xFF00u) ? R(0) : T.y, (tg.zc & 0xFF0000u) ? R(0) : T.z);
+        L = L + Tr * E;
+        if constexpr (NP == DRT_NP_TANGENT && NC > 0) {
+            // K directions: the single-direction case below, once per direction
+            const R* dir = tg.tab + (1u + 2u * NC) * tg.stride + (eid < tg.rest ? eid : 0u) * 3u;
+            const uint32_t zx = tg.zc & 0xFFu, zy = tg.zc & 0xFF00u, zz = tg.zc & 0xFF0000u;
 #pragma unroll
-        for (int p = 0; p < NP; ++p) {
-            typedef PathRoles<NP, NC, ROLES> RL;
-            const bool is_colour = (RL::colm >> p) & 1, is_emission = (RL::emitm >> p) & 1;
-            if (ROLES != 0 && !is_colour && !is_emission)
-                continue;
-            const bool own = (ROLES != 0 && RL::emitm == (1 << p)) || eid == (uint32_t)p;
-            const V3<R> ap = tg.acc_get(p);
-            V3<R> a0 = mk<R>(ap.x + (own ? gT.x : R(0)), ap.y + (own ? gT.y : R(0)), ap.z + (own ? gT.z : R(0)));
-            if (ROLES != 0 && !is_emission)
-                a0 = ap;
-            if (is_colour) {
-                const uint32_t n = (tg.cnt[p >> 2] >> (8 * (p & 3))) & 0xFFu;
-                const R nf = (R)(int)n;
-                // (read where they are used, once per sample: hoisted out of the sample loop these twelve wave-uniform words
-                //  cost the kernel its fifth wave per SIMD)
-                V3<R> dT = mk<R>(Tr.x * (nf * tl.invc[p][0]), Tr.y * (nf * tl.invc[p][1]), Tr.z * (nf * tl.invc[p][2]));
-                const uint32_t zb = __builtin_amdgcn_readfirstlane(tl.inc[p][3]);
-                if (zb) {
-                    const bool one = n == 1u;
-                    if (zb & 1u) dT.x = (one && (tg.zc & 0xFFu) == 0x1u) ? T.x : R(0);
-                    if (zb & 2u) dT.y = (one && (tg.zc & 0xFF00u) == 0x100u) ? T.y : R(0);
-                    if (zb & 4u) dT.z = (one && (tg.zc & 0xFF0000u) == 0x10000u) ? T.z : R(0);
-                }
-                tg.acc_set(p, mk<R>(fma_r(dT.x, gE.x, a0.x), fma_r(dT.y, gE.y, a0.y), fma_r(dT.z, gE.z, a0.z)));
-            } else
-                tg.acc_set(p, a0);
+            for (int k = 0; k < NC; ++k) {
+                const R* vd = dir + (uint32_t)k * 3u * tg.rest;
+                const V3<R> Ed = mk<R>(vd[0], vd[1], vd[2]) * inv_pk;
+                const V3<R> d0 = mk<R>(fma_r(E.x, tg.S[k].x, Ed.x), fma_r(E.y, tg.S[k].y, Ed.y), fma_r(E.z, tg.S[k].z, Ed.z));
+                const V3<R> d1 = E * tg.Z[k];
+                tg.dL[k] = mk<R>(fma_r(T.x, zx == 0u ? d0.x : (zx == 0x1u ? d1.x : R(0)), tg.dL[k].x),
+                                 fma_r(T.y, zy == 0u ? d0.y : (zy == 0x100u ? d1.y : R(0)), tg.dL[k].y),
+                                 fma_r(T.z, zz == 0u ? d0.z : (zz == 0x10000u ? d1.z : R(0)), tg.dL[k].z));
+            }
+        } else
+        if constexpr (NP == DRT_NP_TANGENT) {
+            // forward mode: T (e S + e') where no factor of the channel is zero, T e Z where exactly one is
+            const R* vd = tg.dl->dir + (eid < DRT_PATH_LDS_PARAMS ? eid : 0u) * 3u;
+            const V3<R> Ed = mk<R>(vd[0], vd[1], vd[2]) * inv_pk;
+            const V3<R> d0 = mk<R>(fma_r(E.x, tg.S.x, Ed.x), fma_r(E.y, tg.S.y, Ed.y), fma_r(E.z, tg.S.z, Ed.z));
+            const V3<R> d1 = E * tg.Z;
+            const uint32_t zx = tg.zc & 0xFFu, zy = tg.zc & 0xFF00u, zz = tg.zc & 0xFF0000u;
+            tg.dL = mk<R>(fma_r(T.x, zx == 0u ? d0.x : (zx == 0x1u ? d1.x : R(0)), tg.dL.x),
+                          fma_r(T.y, zy == 0u ? d0.y : (zy == 0x100u ? d1.y : R(0)), tg.dL.y),
+                          fma_r(T.z, zz == 0u ? d0.z : (zz == 0x10000u ? d1.z : R(0)), tg.dL.z));
+        } else
+        if constexpr (NP == DRT_NP_ANY) {
+            // any number of parameters: the light's own row, then every vertex of the path's history adds to its colour's row
+            if (LOSS)
+                g = mk<R>(R(2) * (L.x - g.x), R(2) * (L.y - g.y), R(2) * (L.z - g.z));
+            const V3<R> gE = g * E;
+            const uint32_t ebits = pid_unpack(tg.gl->invc[eid < DRT_PATH_LDS_PARAMS ? eid : 0][3]);
+            if ((ebits & 0xFFFFu) != DRT_SLOT_NONE && eid < DRT_PATH_LDS_PARAMS)
+                tg.add(ebits & 0xFFFFu, g * Tr * inv_pk);
+            const V3<R> TgE = Tr * gE;
+            const V3<R> U = mk<R>((tg.zc & 0xFFu) == 0x1u ? T.x * gE.x : R(0), (tg.zc & 0xFF00u) == 0x100u ? T.y * gE.y : R(0),
+                                  (tg.zc & 0xFF0000u) == 0x10000u ? T.z * gE.z : R(0));
+            const uint32_t nw = tg.nv >> 2;
+            for (uint32_t w = 0; wave_any(w < nw); ++w)
+                tg.add_word(w < nw ? tg.load_word(w) : 0xFFFFFFFFu, TgE, U);
+            tg.add_word(tg.cur, TgE, U);
+        } else
+        if constexpr (NP > 0) {
+            if (NC > 0)
+                asm volatile("" ::: "memory");    // (keeps the reads of `tl` below where they are: see there)
+            if (LOSS)
+                g = mk<R>(R(2) * (L.x - g.x), R(2) * (L.y - g.y), R(2) * (L.z - g.z));
+            const V3<R> gE = g * E, gT = g * Tr * inv_pk;
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                typedef PathRoles<NP, NC, ROLES> RL;
+                const bool is_colour = (RL::colm >> p) & 1, is_emission = (RL::emitm >> p) & 1;
+                if (ROLES != 0 && !is_colour && !is_emission)
+                    continue;
+                const bool own = (ROLES != 0 && RL::emitm == (1 << p)) || eid == (uint32_t)p;
+                const V3<R> ap = tg.acc_get(p);
+                V3<R> a0 = mk<R>(ap.x + (own ? gT.x : R(0)), ap.y + (own ? gT.y : R(0)), ap.z + (own ? gT.z : R(0)));
+                if (ROLES != 0 && !is_emission)
+                    a0 = ap;
+                if (is_colour) {
+                    const uint32_t n = (tg.cnt[p >> 2] >> (8 * (p & 3))) & 0xFFu;
+                    const R nf = (R)(int)n;
+                    // (read where they are used, once per sample: hoisted out of the sample loop these twelve wave-uniform words
+                    //  cost the kernel its fifth wave per SIMD)
+                    V3<R> dT = mk<R>(Tr.x * (nf * tl.invc[p][0]), Tr.y * (nf * tl.invc[p][1]), Tr.z * (nf * tl.invc[p][2]));
+                    const uint32_t zb = __builtin_amdgcn_readfirstlane(tl.inc[p][3]);
+                    if (zb) {
+                        const bool one = n == 1u;
+                        if (zb & 1u) dT.x = (one && (tg.zc & 0xFFu) == 0x1u) ? T.x : R(0);
+                        if (zb & 2u) dT.y = (one && (tg.zc & 0xFF00u) == 0x100u) ? T.y : R(0);
+                        if (zb & 4u) dT.z = (one && (tg.zc & 0xFF0000u) == 0x10000u) ? T.z : R(0);
+                    }
+                    tg.acc_set(p, mk<R>(fma_r(dT.x, gE.x, a0.x), fma_r(dT.y, gE.y, a0.y), fma_r(dT.z, gE.z, a0.z)));
+                } else
+                    tg.acc_set(p, a0);
+            }
         }
     }
 }
@@ -819,57 +884,68 @@ __device__ inline void path_bounce(const PathArgs& a, const PathSceneLds<R>& lds
     // the throughput moves on only in lanes whose path goes on (the others stay frozen for the light's turn); with
     // gradients it leaves zero colour channels out and counts them, and counts the bounce for its colour (see Tangents)
     // (REST, the lockstep kernel's colour-column form: a lane that does not go on reads the table's row of ones and zero increments)
-    constexpr bool REST = FREEZE_BY_ROW && NC > 0 && NP != DRT_NP_ANY && NP != DRT_NP_TANGENT;
+    constexpr bool REST = FREEZE_BY_ROW && NC > 0 && NP != DRT_NP_ANY && NP != DRT_NP_TANGENT && NP != DRT_NP_SETS;
     // (DIR, forward mode: the same by its own table's rest row, in every form)
     constexpr bool DIR = NP == DRT_NP_TANGENT, BY_ROW = REST || DIR;
-    const int cidx = DIR ? (alive ? (int)cid : DRT_PATH_LDS_PARAMS) : (REST ? (alive ? (int)cid : DRT_TANGENT_REST) : (has_bxdf ? (int)cid : 0));
-    V3<R> col;
-    if constexpr (DIR && NC > 0) {
-        // K directions: the colour row once, a row of v / c and of v (zero channels) per direction; a lane that stops reads the rest row
-        const uint32_t row = ((uint32_t)cidx < tg.rest ? (uint32_t)cidx : tg.rest) * 4u;
-        const R* rec = tg.tab + row;
-        col = mk<R>(rec[0], rec[1], rec[2]);
-        tg.zc += pid_unpack(rec[3]);
+    if constexpr (NP == DRT_NP_SETS) {
+        // K parameter sets: every set's throughput moves on by its own colour row; a lane that stops reads the rest row and m = 1
+        const uint32_t row = (alive && cid < tg.rest ? cid : tg.rest) * 4u;
+        const R mm = alive ? mk_ : R(1);
 #pragma unroll
         for (int k = 0; k < NC; ++k) {
-            const R *ds = tg.tab + (1u + 2u * k) * tg.stride + row, *dz = ds + tg.stride;
-            tg.S[k] = mk<R>(tg.S[k].x + ds[0], tg.S[k].y + ds[1], tg.S[k].z + ds[2]);
-            tg.Z[k] = mk<R>(tg.Z[k].x + dz[0], tg.Z[k].y + dz[1], tg.Z[k].z + dz[2]);
+            const R* rec = tg.tab + (uint32_t)k * tg.stride + row;
+            tg.T[k] = tg.T[k] * (mk<R>(rec[0], rec[1], rec[2]) * mm);
         }
-    } else
-    if constexpr (DIR) {
-        const int row = cidx < DRT_PATH_LDS_PARAMS ? cidx : DRT_PATH_LDS_PARAMS;
-        const R *rec = tg.dl->colnz[row], *ds = tg.dl->dlog[row], *dz = tg.dl->dzero[row];
-        col = mk<R>(rec[0], rec[1], rec[2]);
-        tg.zc += pid_unpack(rec[3]);
-        tg.S = mk<R>(tg.S.x + ds[0], tg.S.y + ds[1], tg.S.z + ds[2]);
-        tg.Z = mk<R>(tg.Z.x + dz[0], tg.Z.y + dz[1], tg.Z.z + dz[2]);
-    } else
-    if constexpr (NP == DRT_NP_ANY) {
-        const R* rec = tg.gl->colnz[cidx < DRT_PATH_LDS_PARAMS ? cidx : 0];
-        col = mk<R>(rec[0], rec[1], rec[2]);
-        tg.zc += alive ? pid_unpack(rec[3]) : 0u;
-        if (ih)
-            tg.template push<false>(alive, cid);      // (a lane on its own: only vertices the path goes on from)
-        else
-            tg.template push<true>(live, alive ? cid : 0xFFu);
-    } else
-        col = NC > 0 ? mk<R>(tl.colnz[cidx][0], tl.colnz[cidx][1], tl.colnz[cidx][2]) : load_param<R, (NP > 0)>(lds, params, cidx);
-    const V3<R> cmv = col * (BY_ROW ? (alive ? mk_ : R(1)) : mk_);
-    const V3<R> cm = BY_ROW ? cmv : mk<R>(alive ? cmv.x : R(1), alive ? cmv.y : R(1), alive ? cmv.z : R(1));
-    if constexpr (REST) {
-        tg.cnt[0] += tl.inc[cidx][0];
-        if (NC > 4)
-            tg.cnt[NC > 4 ? 1 : 0] += tl.inc[cidx][1];
-        tg.zc += tl.inc[cidx][2];
-    } else
-    if constexpr (NC > 0 && NP != DRT_NP_ANY && NP != DRT_NP_TANGENT) {
-        tg.cnt[0] += alive ? tl.inc[cidx][0] : 0u;
-        if (NC > 4)
-            tg.cnt[NC > 4 ? 1 : 0] += alive ? tl.inc[cidx][1] : 0u;
-        tg.zc += alive ? tl.inc[cidx][2] : 0u;
+    } else {
+        const int cidx = DIR ? (alive ? (int)cid : DRT_PATH_LDS_PARAMS) : (REST ? (alive ? (int)cid : DRT_TANGENT_REST) : (has_bxdf ? (int)cid : 0));
+        V3<R> col;
+        if constexpr (DIR && NC > 0) {
+            // K directions: the colour row once, a row of v / c and of v (zero channels) per direction; a lane that stops reads the rest row
+            const uint32_t row = ((uint32_t)cidx < tg.rest ? (uint32_t)cidx : tg.rest) * 4u;
+            const R* rec = tg.tab + row;
+            col = mk<R>(rec[0], rec[1], rec[2]);
+            tg.zc += pid_unpack(rec[3]);
+#pragma unroll
+            for (int k = 0; k < NC; ++k) {
+                const R *ds = tg.tab + (1u + 2u * k) * tg.stride + row, *dz = ds + tg.stride;
+                tg.S[k] = mk<R>(tg.S[k].x + ds[0], tg.S[k].y + ds[1], tg.S[k].z + ds[2]);
+                tg.Z[k] = mk<R>(tg.Z[k].x + dz[0], tg.Z[k].y + dz[1], tg.Z[k].z + dz[2]);
+            }
+        } else
+        if constexpr (DIR) {
+            const int row = cidx < DRT_PATH_LDS_PARAMS ? cidx : DRT_PATH_LDS_PARAMS;
+            const R *rec = tg.dl->colnz[row], *ds = tg.dl->dlog[row], *dz = tg.dl->dzero[row];
+            col = mk<R>(rec[0], rec[1], rec[2]);
+            tg.zc += pid_unpack(rec[3]);
+            tg.S = mk<R>(tg.S.x + ds[0], tg.S.y + ds[1], tg.S.z + ds[2]);
+            tg.Z = mk<R>(tg.Z.x + dz[0], tg.Z.y + dz[1], tg.Z.z + dz[2]);
+        } else
+        if constexpr (NP == DRT_NP_ANY) {
+            const R* rec = tg.gl->colnz[cidx < DRT_PATH_LDS_PARAMS ? cidx : 0];
+            col = mk<R>(rec[0], rec[1], rec[2]);
+            tg.zc += alive ? pid_unpack(rec[3]) : 0u;
+            if (ih)
+                tg.template push<false>(alive, cid);      // (a lane on its own: only vertices the path goes on from)
+            else
+                tg.template push<true>(live, alive ? cid : 0xFFu);
+        } else
+            col = NC > 0 ? mk<R>(tl.colnz[cidx][0], tl.colnz[cidx][1], tl.colnz[cidx][2]) : load_param<R, (NP > 0)>(lds, params, cidx);
+        const V3<R> cmv = col * (BY_ROW ? (alive ? mk_ : R(1)) : mk_);
+        const V3<R> cm = BY_ROW ? cmv : mk<R>(alive ? cmv.x : R(1), alive ? cmv.y : R(1), alive ? cmv.z : R(1));
+        if constexpr (REST) {
+            tg.cnt[0] += tl.inc[cidx][0];
+            if (NC > 4)
+                tg.cnt[NC > 4 ? 1 : 0] += tl.inc[cidx][1];
+            tg.zc += tl.inc[cidx][2];
+        } else
+        if constexpr (NC > 0 && NP != DRT_NP_ANY && NP != DRT_NP_TANGENT && NP != DRT_NP_SETS) {
+            tg.cnt[0] += alive ? tl.inc[cidx][0] : 0u;
+            if (NC > 4)
+                tg.cnt[NC > 4 ? 1 : 0] += alive ? tl.inc[cidx][1] : 0u;
+            tg.zc += alive ? tl.inc[cidx][2] : 0u;
+        }
+        T = T * cm;
     }
-    T = T * cm;
     const V3<R> no = P + wo * R(1e-3);                                // pathtracer.hpp:99
     ra.x = no.x; ra.y = no.y; ra.z = no.z; ra.w = wo.x;
     rb.x = wo.y; rb.y = wo.z;
@@ -951,6 +1027,9 @@ __device__ inline uint32_t path_camera(const PathArgs& a, const CameraLane<R>& c
 template <size_t RB, bool SPEC, int NP, int NSG, bool REGEN, int NCR = 0>
 constexpr int path_min_blocks()
 {
+    if (NP == DRT_NP_SETS)         // K parameter sets, lockstep: six values and three fp64 sums per set beside the forward-only kernel's
+        return RB == 4 ? (DRT_NC_OF(NCR) <= 2 ? DRT_SETS2_MIN_BLOCKS : (DRT_NC_OF(NCR) <= 4 ? DRT_SETS4_MIN_BLOCKS : DRT_SETS8_MIN_BLOCKS))
+                       : (DRT_NC_OF(NCR) <= 2 ? (SPEC ? 2 : 3) : (DRT_NC_OF(NCR) <= 4 ? 2 : 1));
     if (NP == DRT_NP_TANGENT && DRT_NC_OF(NCR) > 0)   // K directions, lockstep: f64 takes what a block per CU has
         return RB == 4 ? (DRT_NC_OF(NCR) <= 2 ? DRT_TANGENTS2_MIN_BLOCKS : (DRT_NC_OF(NCR) <= 4 ? DRT_TANGENTS4_MIN_BLOCKS : DRT_TANGENTS8_MIN_BLOCKS))
                        : (DRT_NC_OF(NCR) <= 2 ? 2 : 1);
@@ -1001,12 +1080,14 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
     constexpr bool DIR = NP == DRT_NP_TANGENT;            // forward mode: the derivative along one direction (see DirLds); `params` = [params | direction]
     constexpr bool DIRS = DIR && NC > 0;                  // ... along NC directions at once: tables in dynamic shared memory (see stage_dirs)
     static_assert(!(DIRS && REGEN), "the K-direction form is a lockstep form: a lane is a pixel");
+    constexpr bool SETS = NP == DRT_NP_SETS;              // one path under NC parameter sets: tables in dynamic shared memory (see stage_sets)
+    static_assert(!(SETS && (REGEN || NC < 1)), "the parameter-set form is a lockstep form of K >= 1 sets: a lane is a pixel");
     __shared__ typename PickT<(DIR && !DIRS), DirLds<R>, NoLds>::T s_dir;
     if constexpr (GEN)
         gen_zero(s_gen);
     stage_path_scene(lds, sc, params);
     const TangentLds<R>& tl = s_tl;
-    if (NC > 0 && !GEN && !DIR)
+    if (NC > 0 && !GEN && !DIR && !SETS)
         stage_tangents(s_tl, lds);
 
     const uint32_t lane = threadIdx.x & (DRT_WAVE - 1);
@@ -1019,13 +1100,22 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
 
     Tangents<R, NP, NC> tg;
     __shared__ R s_acc[NP > 0 ? NP * 3 : 1][DRT_BLOCK];
-    tg.acc = &s_acc[0][threadIdx.x];
+    if constexpr (!SETS)
+        tg.acc = &s_acc[0][threadIdx.x];
     if constexpr (GEN)
         gen_begin(s_gen, lds, sc, a, s_hist, reinterpret_cast<uint32_t*>(a.hist_ovf), tg);
     else if constexpr (DIRS) {
         extern __shared__ __attribute__((aligned(16))) unsigned char s_dirs[];
         R* tab = reinterpret_cast<R*>(s_dirs);
         stage_dirs<R, NC>(tab, lds, params);
+        tg.tab = tab;
+        tg.rest = (uint32_t)(lds.sc.n_params < DRT_PATH_LDS_PARAMS ? lds.sc.n_params : DRT_PATH_LDS_PARAMS);
+        tg.stride = (tg.rest + 1u) * 4u;
+        tg.new_path();
+    } else if constexpr (SETS) {
+        extern __shared__ __attribute__((aligned(16))) unsigned char s_dirs[];
+        R* tab = reinterpret_cast<R*>(s_dirs);
+        stage_sets<R, NC>(tab, lds, params);
         tg.tab = tab;
         tg.rest = (uint32_t)(lds.sc.n_params < DRT_PATH_LDS_PARAMS ? lds.sc.n_params : DRT_PATH_LDS_PARAMS);
         tg.stride = (tg.rest + 1u) * 4u;
@@ -1041,8 +1131,8 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
     }
     double fx = 0, fy = 0, fz = 0;                        // radiance sum of this lane's pixel over the range
     double tx = 0, ty = 0, tz = 0;                        // DIR: ... and the sum of its samples' derivatives
-    double tk[DIRS ? NC : 1][3];                          // DIRS: ... per direction
-    if constexpr (DIRS) {
+    double tk[(DIRS || SETS) ? NC : 1][3];                // DIRS: ... per direction; SETS: the radiance sums per set
+    if constexpr (DIRS || SETS) {
 #pragma unroll
         for (int k = 0; k < NC; ++k)
             tk[k][0] = tk[k][1] = tk[k][2] = 0.0;
@@ -1124,7 +1214,14 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
             if (end_ids != DRT_ID_NONE)
                 add_emission<R, NP, NC, LOSS, PathSceneLds<R>, ROLES>(lds, tl, params, end_ids, end_inv_pk, T, g, L, tg);
         }
-        fx += (double)L.x; fy += (double)L.y; fz += (double)L.z;
+        if constexpr (SETS) {
+#pragma unroll
+            for (int k = 0; k < NC; ++k) {
+                tk[k][0] += (double)tg.L[k].x; tk[k][1] += (double)tg.L[k].y; tk[k][2] += (double)tg.L[k].z;
+            }
+        } else {
+            fx += (double)L.x; fy += (double)L.y; fz += (double)L.z;
+        }
         if constexpr (DIRS) {
 #pragma unroll
             for (int k = 0; k < NC; ++k) {
@@ -1261,6 +1358,9 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
         }
     }
 
+    if constexpr (SETS) {                                 // the plain image's sums: the last set (the context's own parameters)
+        fx = tk[NC - 1][0]; fy = tk[NC - 1][1]; fz = tk[NC - 1][2];
+    }
     if (range < a.n_ranges) {
         if (fpart && have) {
             double* f = fpart + ((size_t)range * 3) * a.Pb + lp;       // [range][channel][pixel]: coalesced
@@ -1271,8 +1371,8 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
             double* f = gimg_part + ((size_t)range * 3) * a.Pb + lp;
             f[0] = (double)tg.gsum.x; f[(size_t)a.Pb] = (double)tg.gsum.y; f[(size_t)a.Pb * 2] = (double)tg.gsum.z;
         }
-        if constexpr (DIRS) if (gimg_part && have) {
-            // K directions: the pixel's sums in the Jacobian form's layout, [range][3 k + ch][pixel], for the directions the caller gave
+        if constexpr (DIRS || SETS) if (gimg_part && have) {
+            // K directions / K sets: the pixel's sums in the Jacobian form's layout, [range][3 k + ch][pixel], for those the caller gave
             const uint32_t nd = a.dirs_out() < (uint32_t)NC ? a.dirs_out() : (uint32_t)NC;
             double* f = gimg_part + ((size_t)range * (size_t)(nd * 3u)) * a.Pb + lp;
 #pragma unroll
@@ -1311,7 +1411,7 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
     if constexpr (GEN)
         gen_finish(s_gen, a, gpart);
     else
-    if (NP > 0 && !JAC) {
+    if constexpr (NP > 0 && !JAC) {
         // block reduction in fp64: thread -> wave (shuffles) -> block (LDS), fixed order; K7 adds the blocks
         const int wv = threadIdx.x / DRT_WAVE;
         double (*red)[DRT_FAST_PARAMS * 3] = s_red;
@@ -1834,4 +1934,87 @@ k_normal_eq_finish(const double* __restrict__ part, int n_blocks, int np_w, int 
             out_b[(size_t)ch * n_out + (k - n_tri)] = red[0];
     } else if (out_loss)
         out_loss[ch] = red[0];
+}
+
+// ---- the images and losses of a frame under K parameter sets (drt_hip_render_param_sets) -----------------------------------------
+// Behind a launch of k_path's parameter-set form: spart[range][3 k + ch][pixel] holds, per pixel of the shard, set k's radiance sums over
+// one sample range.  Per pixel and set, in fp64: the sum over the ranges in range order, the mean, the set's image (float and / or
+// double, the layout of n_sets images) where the caller wants it, and with a target the residual mean - target, whose square goes into the
+// thread's running sum of (set, channel) -- at most DRT_SETS_VALUES = 3 DRT_HIP_MAX_PARAM_SETS of them.  Then thread -> wave (shuffles) ->
+// block (LDS) in a fixed order, one partial per block; k_sets_loss_finish adds the blocks in a fixed order.  No atomics: the same call
+// gives the same bits.  k_normal_eq's structure and grid rule, a pixel per thread.
+#define DRT_SETS_VALUES 24
+__global__ void __launch_bounds__(DRT_BLOCK)
+k_sets_finish(PathArgs a, const double* __restrict__ spart, int n_sets, const float* __restrict__ target, float* __restrict__ out_img,
+              double* __restrict__ out_img64, double* __restrict__ part)
+{
+    const size_t Pb = a.Pb, rows = (size_t)n_sets * 3, npix = (size_t)a.W * (size_t)a.H;
+    const double inv = 1.0 / (double)a.spp;
+    double acc[DRT_SETS_VALUES];
+#pragma unroll
+    for (int v = 0; v < DRT_SETS_VALUES; ++v)
+        acc[v] = 0.0;
+    for (uint32_t j = blockIdx.x * DRT_BLOCK + threadIdx.x; j < a.Pb; j += gridDim.x * DRT_BLOCK) {
+        const size_t gp = path_global_pixel(a, a.p0 + j);
+        double tg[3] = {0.0, 0.0, 0.0};
+        if (target) {
+            tg[0] = (double)target[gp * 3]; tg[1] = (double)target[gp * 3 + 1]; tg[2] = (double)target[gp * 3 + 2];
+        }
+#pragma unroll
+        for (int v = 0; v < DRT_SETS_VALUES; ++v)
+            if (v < (int)rows) {
+                double sum = 0.0;
+                for (uint32_t q = 0; q < a.n_ranges; ++q)
+                    sum += spart[((size_t)q * rows + (size_t)v) * Pb + j];
+                const double mean = sum * inv;
+                const size_t at = ((size_t)(v / 3) * npix + gp) * 3 + (size_t)(v % 3);
+                if (out_img) out_img[at] = (float)mean;
+                if (out_img64) out_img64[at] = mean;
+                if (target) {
+                    const double r = mean - tg[v % 3];
+                    acc[v] += r * r;
+                }
+            }
+    }
+    if (!part)
+        return;
+    __shared__ double red[DRT_BLOCK / DRT_WAVE][DRT_SETS_VALUES];
+    const int wv = threadIdx.x / DRT_WAVE;
+#pragma unroll
+    for (int v = 0; v < DRT_SETS_VALUES; ++v) {
+        double s = acc[v];
+#pragma unroll
+        for (int o2 = DRT_WAVE / 2; o2 > 0; o2 >>= 1)
+            s += __shfl_down(s, o2);
+        if ((threadIdx.x & (DRT_WAVE - 1)) == 0)
+            red[wv][v] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < DRT_SETS_VALUES) {
+        double s = 0;
+        for (int ww = 0; ww < DRT_BLOCK / DRT_WAVE; ++ww)
+            s += red[ww][threadIdx.x];
+        part[(size_t)blockIdx.x * DRT_SETS_VALUES + threadIdx.x] = s;
+    }
+}
+
+// ... its second stage: block v adds value v's partials over k_sets_finish's blocks -- a strided sum per thread, then an LDS tree, both
+// in a fixed order -- into out_loss[set][channel]
+__global__ void __launch_bounds__(DRT_BLOCK)
+k_sets_loss_finish(const double* __restrict__ part, int n_blocks, int n_values, double* __restrict__ out_loss)
+{
+    __shared__ double red[DRT_BLOCK];
+    const int v = (int)blockIdx.x;
+    double s = 0;
+    for (int b = threadIdx.x; b < n_blocks; b += DRT_BLOCK)
+        s += part[(size_t)b * DRT_SETS_VALUES + v];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int off = DRT_BLOCK / 2; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off)
+            red[threadIdx.x] += red[threadIdx.x + off];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0 && v < n_values)
+        out_loss[v] = red[0];
 }

@@ -151,9 +151,10 @@ inline int np_width(int n_params, int general)
 }
 
 // ---- which instantiation of the one-launch path kernels a render runs (shard_plan decides it, path_batch launches it) ----
-enum class PathOp { biased, unbiased, mesh, tangent, jacobian, tangents };   // k_path (the gradient image included), k_path_unbiased, k_path_mesh, k_path's forward-mode form,
+enum class PathOp { biased, unbiased, mesh, tangent, jacobian, tangents, param_sets };   // k_path (the gradient image included), k_path_unbiased, k_path_mesh, k_path's forward-mode form,
                                                                     // its Jacobian form (lockstep, parameters in columns: DRT_NC_JACOBIAN),
-                                                                    // its K-direction forward form (lockstep, nc = K)
+                                                                    // its K-direction forward form (lockstep, nc = K),
+                                                                    // its parameter-set form (lockstep, np = DRT_NP_SETS, nc = K)
 enum class PathProg { cornell, sorted, scene };  // closest-hit program: the reference's kinds compiled in (SigCornell), kinds read at
                                                  // run time (SigNone), or compiled by hiprtc for the scene's own KindSig (drt_jit.h)
 struct PathForm {
@@ -194,8 +195,9 @@ struct Shard {
     uint32_t neq_blocks = 0;        // ... k_normal_eq's blocks per channel
     int neq_vw = 1;                 // ... pixels per lane (2: 16-byte loads, an even number of pixels)
     int n_dirs = 0;                 // ... > 0: its rows are directions -- k_path's K-direction forward form in place of the Jacobian form
-    int jac_rows() const { return neq ? (n_dirs > 0 ? n_dirs : ctx->n_params) * 3 : 3; }   // rows a pixel's sums have in `gpix`
-    bool pixel_sums() const { return gimg_param >= 0 || fwd_tangent || neq; }   // the lanes' per-pixel sums leave the path kernel (gimg_part)
+    const ParamSetsRequest* sets = nullptr;   // drt_hip_render_param_sets: the parameter-set form, then k_sets_finish (n_dirs: the caller's sets)
+    int jac_rows() const { return (neq || sets) ? (n_dirs > 0 ? n_dirs : ctx->n_params) * 3 : 3; }   // rows a pixel's sums have in `gpix`
+    bool pixel_sums() const { return gimg_param >= 0 || fwd_tangent || neq || sets; }   // the lanes' per-pixel sums leave the path kernel (gimg_part)
     // the scene in compute type R
     const DevScene<R>* d_scene;
     const R* d_params;
@@ -340,6 +342,10 @@ const void* library_path_kernel(const PathForm& f)
         }
         return nullptr;
     }
+    if (f.op == PathOp::param_sets)  // one path under K parameter sets: lockstep, every program
+        return f.regen ? nullptr : with_int<2, 4, 8>(f.nc, [&](auto k) {
+            return spec_sig([](auto spec, auto sg) { return (const void*)k_path<R, decltype(spec)::value, DRT_NP_SETS, decltype(k)::value, decltype(sg), false>; });
+        });
     if (f.op == PathOp::tangents)  // ... along K directions: lockstep, every program
         return f.regen ? nullptr : with_int<2, 4, 8>(f.nc, [&](auto k) {
             return spec_sig([](auto spec, auto sg) { return (const void*)k_path<R, decltype(spec)::value, DRT_NP_TANGENT, decltype(k)::value, decltype(sg), false>; });
@@ -405,7 +411,7 @@ void shard_plan(Shard<R>& s)
                  rp->bounces_per_launch <= 0 && tuning().shade_bounces <= 0 && tuning().dump_path == -1;
     s.mesh_path = s.use_path && ctx->has_mesh;
     PathForm& f = s.path;
-    const bool lane_is_pixel = (s.gimg_param >= 0 || s.neq) && !s.mesh_path;   // the gradient image / the Jacobian is the lanes' own sums: lockstep form only
+    const bool lane_is_pixel = (s.gimg_param >= 0 || s.neq || s.sets) && !s.mesh_path;   // the gradient image / the Jacobian is the lanes' own sums: lockstep form only
     // (k_path_mesh: every lane on its own, always; k_path_unbiased walks its samples in lockstep)
     f.regen = (tuning().path_regen > 0 || s.mesh_path) && !s.unbiased && !lane_is_pixel;
     if (s.use_path && !s.mesh_path && !lane_is_pixel && tuning().path_regen < 0 && !s.unbiased) {
@@ -441,6 +447,11 @@ void shard_plan(Shard<R>& s)
         f.op = PathOp::tangents;
         f.np = DRT_NP_TANGENT;
         f.nc = s.n_dirs <= 2 ? 2 : (s.n_dirs <= 4 ? 4 : 8);
+    }
+    if (s.sets && !s.mesh_path) {   // the parameter-set form, at the width the host staged its tables for
+        f.op = PathOp::param_sets;
+        f.np = DRT_NP_SETS;
+        f.nc = s.sets->width;
     }
     f.loss = s.loss_l2;
     // the slots' roles as the scene's records give them: for the form the headline runs -- diffuse, f32, lockstep, parameters in columns
@@ -499,8 +510,8 @@ void shard_plan(Shard<R>& s)
         cap = s.total_paths;               // no per-path memory: one batch covers the frame
     if (tuning().batch_paths > 0)
         cap = (uint64_t)tuning().batch_paths;
-    if (s.neq)
-        cap = s.total_paths;               // k_normal_eq reads every range of every pixel of the shard: one batch (render_impl refuses frames beyond 2^31 paths)
+    if (s.neq || s.sets)
+        cap = s.total_paths;               // k_normal_eq / k_sets_finish reads every range of every pixel of the shard: one batch (render_impl refuses frames beyond 2^31 paths)
     if (cap > s.total_paths) cap = s.total_paths;
     if (cap < 1) cap = 1;
     if (cap > 0x7FFFFFFFull) cap = 0x7FFFFFFFull;
@@ -589,6 +600,11 @@ int shard_buffers(Shard<R>& s)
             const uint64_t items = ((uint64_t)s.Pb + s.neq_vw - 1) / s.neq_vw;
             s.neq_blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((items + DRT_BLOCK - 1) / DRT_BLOCK, (uint64_t)ctx->n_cu * 4));
             if ((rc = ensure(ctx, ctx->neq_part, (size_t)3 * s.neq_blocks * DRT_NEQ_VALUES(DRT_FAST_PARAMS) * sizeof(double))) != DRT_OK) return rc;
+        }
+        if (s.sets) {
+            // k_sets_finish: k_normal_eq's grid rule, a pixel per thread
+            s.neq_blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(((uint64_t)s.Pb + DRT_BLOCK - 1) / DRT_BLOCK, (uint64_t)ctx->n_cu * 4));
+            if ((rc = ensure(ctx, ctx->neq_part, (size_t)s.neq_blocks * DRT_SETS_VALUES * sizeof(double))) != DRT_OK) return rc;
         }
         if (s.mesh_path) {   // the traversal stack's entries beyond the ones in LDS, per thread of the grid (one area per k_path stream)
             const size_t threads = ((s.path_waves + DRT_BLOCK / DRT_WAVE - 1) / (DRT_BLOCK / DRT_WAVE)) * DRT_BLOCK;
@@ -746,8 +762,8 @@ int path_batch(Shard<R>& s)
     pa.ct_step_f = (float)(2. * pa.tan_half * pa.inv_H);
     pa.gimg_param = s.gimg_param;
     pa.gen_rows = s.gen_rows; pa.gen_clog2 = s.gen_clog2;
-    if (s.path.op == PathOp::tangents)
-        pa.set_dirs_out((uint32_t)s.n_dirs);       // (the K-direction form: the directions whose sums leave the kernel)
+    if (s.path.op == PathOp::tangents || s.path.op == PathOp::param_sets)
+        pa.set_dirs_out((uint32_t)s.n_dirs);       // (the K-direction / parameter-set form: the directions / sets whose sums leave the kernel)
     // the general form's vertex history: a word per four vertices and thread, in dynamic shared memory
     const bool gen = s.path_gen;
     // (the first words in LDS, as many as leave the kernel's blocks per CU alone: four in the lockstep k_path -- 16 vertices --,
@@ -850,7 +866,10 @@ int path_batch(Shard<R>& s)
     //  block with any amount of dynamic LDS the CU has, for library and hiprtc kernels alike: tests/test_gpu_tangents.py fills both)
     const unsigned dirs_bytes = form.op == PathOp::tangents
         ? dirs_table_words((uint32_t)std::min(ctx->n_params, DRT_PATH_LDS_PARAMS), (uint32_t)form.nc) * (unsigned)sizeof(R) : 0u;
-    const unsigned lds_bytes = form.op == PathOp::unbiased ? 0u : (form.op == PathOp::tangents ? dirs_bytes : hist_bytes);
+    // (the parameter-set form's: stage_sets -- 17.5 KB in f32, 35 KB in f64 at 136 parameters x 8 sets)
+    const unsigned sets_bytes = form.op == PathOp::param_sets
+        ? sets_table_words((uint32_t)std::min(ctx->n_params, DRT_PATH_LDS_PARAMS), (uint32_t)form.nc) * (unsigned)sizeof(R) : 0u;
+    const unsigned lds_bytes = form.op == PathOp::unbiased ? 0u : (form.op == PathOp::tangents ? dirs_bytes : (form.op == PathOp::param_sets ? sets_bytes : hist_bytes));
     if (jit)
         HIPCHK(ctx, hipModuleLaunchKernel(jit, (unsigned)gpath, 1, 1, DRT_BLOCK, 1, 1, lds_bytes, ks, args, nullptr));
     else
@@ -903,6 +922,20 @@ int path_batch(Shard<R>& s)
             DRT_TIMED(s, DRT_K_GRADREDUCE,
                       hipLaunchKernelGGL(k_normal_eq_finish, dim3(3 * DRT_NEQ_VALUES(npw)), dim3(DRT_BLOCK), 0, ctx->stream, (const double*)part,
                                          (int)s.neq_blocks, npw, n_out, q.d_A, q.d_b, q.d_loss));
+            st->units[DRT_K_GRADREDUCE] += (uint64_t)a.Pb;
+            st->path_bytes += (uint64_t)pa.n_ranges * a.Pb * (uint64_t)s.jac_rows() * sizeof(double);
+        }
+        if (s.sets) {
+            // the sets' images and losses: per-pixel means and squared residuals reduced per block, then over the blocks (timed in the reduction's slot)
+            const ParamSetsRequest& q = *s.sets;
+            double* part = (double*)ctx->neq_part.p;
+            DRT_TIMED(s, DRT_K_GRADREDUCE,
+                      hipLaunchKernelGGL(k_sets_finish, dim3(s.neq_blocks), dim3(DRT_BLOCK), 0, ctx->stream, pa, (const double*)gpix, s.n_dirs, q.d_target,
+                                         q.d_images, q.d_images64, q.d_loss ? part : (double*)nullptr));
+            if (q.d_loss)
+                DRT_TIMED(s, DRT_K_GRADREDUCE,
+                          hipLaunchKernelGGL(k_sets_loss_finish, dim3(DRT_SETS_VALUES), dim3(DRT_BLOCK), 0, ctx->stream, (const double*)part, (int)s.neq_blocks,
+                                             s.n_dirs * 3, q.d_loss));
             st->units[DRT_K_GRADREDUCE] += (uint64_t)a.Pb;
             st->path_bytes += (uint64_t)pa.n_ranges * a.Pb * (uint64_t)s.jac_rows() * sizeof(double);
         }
@@ -1206,10 +1239,17 @@ int render_impl(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_p
     s.neq = tangent ? tangent->neq : nullptr;
     s.fwd_tangent = tangent != nullptr && !s.neq;
     s.keep_sums = s.fwd_tangent && tangent->keep_sums;
-    s.n_dirs = s.neq ? tangent->n_dirs : 0;
+    s.sets = tangent ? tangent->sets : nullptr;
+    s.fwd_tangent = s.fwd_tangent && !s.sets;
+    s.keep_sums = s.keep_sums && !s.sets;
+    s.n_dirs = s.neq ? tangent->n_dirs : (s.sets ? s.sets->n_sets : 0);
     if (s.fwd_tangent || s.n_dirs > 0)
         s.d_params = (const R*)tangent->d_params;
     shard_plan(s);
+    if (s.sets && (!s.use_path || s.mesh_path || !s.path_finish || s.path.op != PathOp::param_sets))
+        return fail(ctx, DRT_ERR_UNSUPPORTED, "param sets: they come from the one-launch path kernel's parameter-set form over the whole shard in one batch, "
+                                              "which this render does not take (a DRT_HIP_* setting that forces the queue wavefront or a batch size, paths "
+                                              "that end at depth 0, or a scene its intersection program does not cover)");
     if (s.fwd_tangent && s.D > 0 && (!s.use_path || s.mesh_path))
         return fail(ctx, DRT_ERR_UNSUPPORTED, s.mesh_path || ctx->has_mesh
                         ? "render_tangent: no tangent image of a scene that holds a triangle mesh"

@@ -13,6 +13,7 @@
 //
 //   drt::hip::render_tangent(scene, cam, tracer, spp, {{param, direction}, ...}, img, tangent_img [, options])
 //   drt::hip::render_tangents(scene, cam, tracer, spp, {direction, ...}, img, tangent_imgs [, options])      up to 8 directions, one render
+//   drt::hip::render_param_sets(scene, cam, tracer, spp, {set, ...}, target, imgs, &losses [, options])      up to 8 parameter sets, one trace
 //   drt::hip::normal_equations_along(scene, cam, tracer, spp, {direction, ...}, options, target_or_residual) Gauss-Newton in their span
 //   drt::hip::render(scene of Dual<U>, ...)
 //
@@ -995,6 +996,62 @@ inline NormalEquationsAlong<T> normal_equations_along(const Scene<T>& scene, con
     if (tangent_imgs)
         detail::from_buffer(trgb.data(), npix * K, tangent_imgs);
     return ne;
+}
+
+// ---- one frame under several parameter sets in one trace (drt_hip_render_param_sets) ------------------------------------
+// A parameter set as render_tangent takes a direction: (handle, value) pairs over the scene's current values; handles not listed keep
+// the value they have in the scene
+template <typename T>
+using ParamSet = std::vector<std::pair<Vector<T, 3, true>, Vector<T, 3>>>;
+
+// What a frame looks like, and what its loss is, under each of up to DRT_HIP_MAX_PARAM_SETS parameter sets: imgs[k * width * height +
+// pixel] is what render() gives with sets[k] installed (nullptr: no images), losses[k * 3 + ch] the sum over the pixels of
+// (mean_k - target)^2 where `target` (width x height) is given, empty otherwise.  The scene's own values are not changed.
+template <typename T>
+inline Stats render_param_sets(const Scene<T>& scene, const Camera<T>& cam, const Pathtracer<T>& tracer, std::size_t spp,
+                               const std::vector<ParamSet<T>>& sets, const Vector<T, 3>* target, Vector<T, 3>* imgs,
+                               std::vector<double>* losses, const Options& opt = Options())
+{
+    const char* who = "drt::hip::render_param_sets";
+    if (opt.backward || opt.unbiased || opt.sample_loss_l2)
+        throw std::runtime_error(std::string(who) + ": a forward render takes no reverse-mode option (backward, unbiased, sample_loss_l2)");
+    if (opt.devices.size() > 1)
+        throw std::runtime_error(std::string(who) + ": one device (render shards on plain contexts and add them)");
+    if (!imgs && !(losses && target))
+        throw std::runtime_error(std::string(who) + ": no output requested (images, or losses with a target)");
+    if (losses && !target)
+        throw std::runtime_error(std::string(who) + ": losses need a target");
+    FlatScene<T> flat = flatten(scene);
+    const std::size_t n = flat.handles.size() * 3, K = sets.size();
+    std::vector<double> values(K * n);
+    for (std::size_t k = 0; k < K; ++k) {
+        std::copy(flat.params.begin(), flat.params.begin() + (std::ptrdiff_t)n, values.begin() + (std::ptrdiff_t)(k * n));
+        for (const auto& t : sets[k]) {
+            const int index = detail::param_index(flat, t.first, (std::string(who) + ": a listed parameter is not used by the scene").c_str());
+            for (int c = 0; c < 3; ++c)
+                values[k * n + (std::size_t)index * 3 + c] = double(real(t.second[c]));
+        }
+    }
+    const drt_camera_desc cd = describe(cam);
+    const std::size_t npix = cam.width() * cam.height();
+    std::vector<float> tgt, out;
+    if (target)
+        tgt = detail::to_floats(target, npix);
+    if (imgs)
+        out.assign((K ? K : 1) * npix * 3, 0.f);
+    if (losses)
+        losses->assign(K * 3, 0.0);
+    const drt_render_params rp = detail::render_params(tracer.absorb(), tracer.min_bounces(), spp, opt, detail::f64_flag(opt));
+    drt_hip_stats st{};
+    {
+        detail::Session s = detail::Session::on_first_device(opt, flat);
+        s.ctx.check(drt_hip_render_param_sets(s.ctx.get(), &cd, &rp, (int32_t)K, values.data(), target ? tgt.data() : nullptr,
+                                              imgs ? out.data() : nullptr, (losses && K) ? losses->data() : nullptr, nullptr, &st),
+                    "drt_hip_render_param_sets");
+    }
+    if (imgs)
+        detail::from_buffer(out.data(), npix * K, imgs);
+    return detail::to_stats(st);
 }
 
 // A Scene<Dual<U>> for the device: the real parts as the scene, the dual parts of its PARAMETERS as the direction (n_params x 3).

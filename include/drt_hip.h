@@ -474,6 +474,36 @@ int drt_hip_render_normal_equations_along(drt_hip_ctx* ctx, const drt_camera_des
                                           float* out_rgb /* may be NULL */, double* out_A /* 3 x K x K */, double* out_b /* 3 x K */,
                                           double* out_loss /* 3, may be NULL */, float* out_tangents /* n_dirs x H x W x 3, may be NULL */,
                                           drt_hip_stats* stats);
+/* ONE frame under n_sets parameter vectors in one trace: out_images[k] (H x W x 3 floats) is what drt_hip_update_params(param_sets[k])
+ * followed by drt_hip_render returns -- a parameter is a colour or an emission, nothing that decides where a path goes sees its value, so
+ * the sets share the ray, the RNG key, the hit and the BxDF sample and each keeps its own throughput and radiance, moved by the forward
+ * render's own operations.  With target_rgb,
+ *   out_loss[k][ch] = sum over the pixels of this call's shard of (mean_k - target)^2        (n_sets x 3 doubles)
+ * reduced in fp64 without atomics: the same call returns the same bits.  A line search, the dampings of a Levenberg-Marquardt step, a
+ * finite-difference probe or a population of candidates costs one trace per seed.  1 <= n_sets <= DRT_HIP_MAX_PARAM_SETS; the kernel is
+ * instantiated for 2, 4 and 8 sets and a call's count is padded up with copies of the context's own parameters, which are never written
+ * out: the image of a set depends neither on its companions nor on n_sets, bit for bit.  A set holds the caller's parameters
+ * (n_params x 3 doubles); the colour constant a mirror material appends keeps the scene's own value in every set.  The context's own
+ * parameters are not changed.  out_rgb, where given, is the plain image of the context's own parameters from the same trace; it takes
+ * one of the kernel's sets, so out_rgb beside 8 sets is refused (DRT_ERR_UNSUPPORTED) -- drt_hip_render gives that image.
+ * Shards, DRT_RENDER_DEVICE_OUT (target_rgb, out_images, out_loss and out_rgb are then device pointers; param_sets is host memory
+ * always), _F64, _SYNC, _TIMING, one batch per shard, lockstep under the roulette, the 2^31-sample limit: as drt_hip_render_tangents.  The
+ * reduction is timed in the gradient-reduction slot of drt_hip_stats.
+ * DRT_ERR_INVALID: n_sets outside 1 ... DRT_HIP_MAX_PARAM_SETS, NULL param_sets, a value that is not finite, neither out_images nor
+ * out_loss, out_loss without target_rgb, asynchronous frames in flight, DRT_RENDER_BACKWARD.  DRT_ERR_UNSUPPORTED: a scene that holds a
+ * triangle mesh, a group context, bounces_per_launch >= 1, DRT_RENDER_UNFUSED, _UNBIASED, _LOSS_L2, _ALLREDUCE*, more than 136
+ * parameters, a render forced into several batches or onto the queue wavefront.  The message of either says "param sets"; the context
+ * stays usable. */
+#define DRT_HIP_MAX_PARAM_SETS 8
+int drt_hip_render_param_sets(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_params* rp, int32_t n_sets,
+                              const double* param_sets /* n_sets x n_params x 3 */, const float* target_rgb /* H x W x 3, may be NULL */,
+                              float* out_images /* n_sets x H x W x 3, may be NULL */, double* out_loss /* n_sets x 3, may be NULL */,
+                              float* out_rgb /* may be NULL */, drt_hip_stats* stats);
+/* ... the images as the means the device formed, in double: host buffers only */
+int drt_hip_render_param_sets_double(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_params* rp, int32_t n_sets,
+                                     const double* param_sets /* n_sets x n_params x 3 */, const float* target_rgb /* H x W x 3, may be NULL */,
+                                     double* out_images /* n_sets x H x W x 3, may be NULL */, double* out_loss /* n_sets x 3, may be NULL */,
+                                     float* out_rgb /* may be NULL */, drt_hip_stats* stats);
 /* stream the context launches on (a hipStream_t), for event timing / interop */
 void* drt_hip_stream(drt_hip_ctx* ctx);
 int drt_hip_synchronize(drt_hip_ctx* ctx);

@@ -14,7 +14,7 @@ the noisy objective sits ~9 % below the true albedo at 16 spp.  The per-pixel ad
 (the ABI's adjoint_rgb seeds every sample of a pixel alike); the reference's per-sample `loss_func(radiance).backward()` is
 the same thing for a loss that is linear in the radiance.
 
-    python tools/fit_albedo.py [--size 128] [--spp 16] [--steps 60] [--async] [--oracle] [--gauss-newton [--one-render]]
+    python tools/fit_albedo.py [--size 128] [--spp 16] [--steps 60] [--async] [--oracle] [--gauss-newton [--one-render] [--lambda-sets N]]
 
 --async: the same loop through drt_hip_render_async / drt_hip_wait (frame i + 1 needs the parameters of step i, so frames
 cannot overlap: what is measured is the call overhead).  --oracle: the CPU restatement instead of the device (checker;
@@ -41,6 +41,10 @@ Here the same covariance is divided by a J^T J that the pixels' variance inflate
 measured on the device at the defaults, red settles at 0.286 (6 steps, the last two 0.2866 and 0.2857), so this form exits with
 status 1 at the defaults; it is for frames with enough samples that the bias is below what the caller needs.
 --oracle runs the same loop on the CPU restatement, J assembled from oracle.render(backward=True, grad_image_param=p).
+--lambda-sets N (N <= 7): after the two normal-equation renders the candidates for lambda x {1, 1/3, 4, 1/9, 16, 1/27, 64}[:N] are
+evaluated in ONE drt_hip_render_param_sets call per seed (one trace for all N: a parameter does not decide where a path goes), the
+smallest two-seed loss sum r_A r_B wins and is accepted if it is below the current one (lambda becomes the winner's / 3; else the
+largest tried x 4).  A step is still four renders, of which two are traces of N candidates.
 
 --gauss-newton --scene cornell_shapes: ALL parameters of a scene past the eight the normal equations take (ten: an albedo per shape, the
 unused `white`, the emission), from a perturbed start, through drt_hip_render_normal_equations_along -- unit-vector directions in blocks
@@ -87,7 +91,22 @@ ALONG_STEPS = 4       # block Gauss-Seidel steps over cornell_shapes by default 
 GN_STEPS = 5          # Gauss-Newton steps the tool takes by default: what the CPU loop (--oracle) needs at 128 x 128 x 16 (HISTORY.md has its trace)
 
 
-def fit_gauss_newton(render, p_index, start, steps, one_render=False, lam=1e-3, log=None):
+LAMBDA_FACTORS = (1.0, 1.0 / 3.0, 4.0, 1.0 / 9.0, 16.0, 1.0 / 27.0, 64.0)
+
+
+def best_of_lambdas(render, params, lam, n_sets, sa, sb, candidate, lo=0.0, hi=1.0):
+    """the candidates params + step(lambda f) for the first n_sets factors, evaluated in one render_param_sets call per seed
+    -> (best candidate, its lambda, its two-seed loss, the largest lambda tried)"""
+    lams = [lam * f for f in LAMBDA_FACTORS[:n_sets]]
+    cands = np.stack([np.clip(candidate(l), lo, hi) for l in lams])
+    ia = render.param_sets(cands, sa).astype(np.float64) - render.target
+    ib = render.param_sets(cands, sb).astype(np.float64) - render.target
+    losses = (ia * ib).sum((1, 2, 3))
+    i = int(np.argmin(losses))
+    return cands[i], lams[i], float(losses[i]), max(lams)
+
+
+def fit_gauss_newton(render, p_index, start, steps, one_render=False, lam=1e-3, log=None, lambda_sets=0):
     """render as in fit(), plus render.normal_equations(params, seed, residual=None, target=None) -> (A [3,P,P], b [3,P], loss [3], image).
     Levenberg-Marquardt on parameter p_index, per channel.  -> (fitted rgb, history of rgb per step)"""
     params = render.params0.copy()
@@ -109,6 +128,22 @@ def fit_gauss_newton(render, p_index, start, steps, one_render=False, lam=1e-3, 
             r = img.astype(np.float64) - render.target
             A, b, _, img_b = render.normal_equations(params, 1001 + 2 * k, residual=r.astype(np.float32))
             loss = float((r * (img_b.astype(np.float64) - render.target)).sum())
+            if lambda_sets > 0:
+                def candidate(l):
+                    c = params.copy()
+                    c[p_index] = params[p_index] + lm_step(A, b, l)
+                    return c
+                hi = np.maximum(1.0, params)
+                hi[p_index] = 1.0
+                cand, lam_c, loss_c, lam_max = best_of_lambdas(render, params, lam, lambda_sets, 1000 + 2 * k, 1001 + 2 * k, candidate, 0.0, hi)
+                if loss_c < loss:
+                    params, lam, verdict, loss = cand, max(lam_c / 3.0, 1e-9), "accepted", loss_c      # (logged: the loss the step ends on, as in fit_gauss_newton_along)
+                else:
+                    lam, verdict = lam_max * 4.0, "rejected"
+                hist.append(params[p_index].copy())
+                if log:
+                    log(f"step {k:3d}  loss {loss:.6f}  lambda {lam:.2e}  {verdict} (best of {lambda_sets})  red = ({params[p_index][0]:.4f}, {params[p_index][1]:.4f}, {params[p_index][2]:.4f})")
+                continue
             cand = params.copy()
             cand[p_index] = np.clip(params[p_index] + lm_step(A, b, lam), 0.0, 1.0)
             ca, _ = render(cand, 1000 + 2 * k, False, None)
@@ -169,7 +204,7 @@ def eval_loss(render, params, seeds=(9001, 9002), spp=128):
     return float((ra * (b.astype(np.float64) - render.target)).sum())
 
 
-def fit_gauss_newton_along(render, blocks, start, steps, lam=1e-3, lo=0.0, hi=None, log=None):
+def fit_gauss_newton_along(render, blocks, start, steps, lam=1e-3, lo=0.0, hi=None, log=None, lambda_sets=0):
     """render as in fit(), plus render.normal_equations_along(params, seed, V, residual) -> (A [3,K,K], b [3,K], image).  `blocks`: lists
     of directions [K, P, 3]; per step every block in turn takes a two-seed Levenberg-Marquardt step along its directions (block
     Gauss-Seidel; a lambda per block).  4 renders per block and step.  -> (fitted params, history of the two-seed loss per step)"""
@@ -184,6 +219,16 @@ def fit_gauss_newton_along(render, blocks, start, steps, lam=1e-3, lo=0.0, hi=No
             r = img.astype(np.float64) - render.target
             A, b, img_b = render.normal_equations_along(params, sb, V, r.astype(np.float32))
             loss = float((r * (img_b.astype(np.float64) - render.target)).sum())
+            if lambda_sets > 0:
+                cand, lam_c, loss_c, lam_max = best_of_lambdas(render, params, lams[bi], lambda_sets, sa, sb,
+                                                               lambda l: params + np.einsum("kc,kpc->pc", lm_solve(A, b, l), V), lo, hi)
+                if loss_c < loss:
+                    params, lams[bi], verdict, loss = cand, max(lam_c / 3.0, 1e-9), "accepted", loss_c
+                else:
+                    lams[bi], verdict = lam_max * 4.0, "rejected"
+                if log:
+                    log(f"step {k:3d} block {bi}  loss {loss:.6f}  lambda {lams[bi]:.2e}  {verdict} (best of {lambda_sets})")
+                continue
             x = lm_solve(A, b, lams[bi])
             cand = np.clip(params + np.einsum("kc,kpc->pc", x, V), lo, hi)
             ca, _ = render(cand, sa, False, None)
@@ -229,7 +274,7 @@ def perturbed_start(params0, seed=7, amount=0.2):
     return np.clip(p, 0.02, np.maximum(1.0, params0 + amount))
 
 
-def fit_scene(render, steps, subspace=None, log=None):
+def fit_scene(render, steps, subspace=None, log=None, lambda_sets=0):
     """the Levenberg-Marquardt fit of every parameter of render.scene (or of one tint over its albedos) beside Adam with the same number of
     renders, from the same perturbed start -> dict of figures"""
     P = len(render.params0)
@@ -245,7 +290,7 @@ def fit_scene(render, steps, subspace=None, log=None):
     else:
         blocks, start, free = unit_blocks(P), perturbed_start(render.params0), range(P)
     calls0 = render.calls
-    fitted, hist = fit_gauss_newton_along(render, blocks, start, steps, hi=hi, log=log)
+    fitted, hist = fit_gauss_newton_along(render, blocks, start, steps, hi=hi, log=log, lambda_sets=lambda_sets)
     gn_renders = render.calls - calls0
     calls0 = render.calls
     adam, ahist = fit_adam_all(render, free, start, gn_renders // 2, render.spp, render.target.size, hi=hi, log=log)
@@ -275,7 +320,7 @@ class DeviceRender:
         if not use_async:
             for im in self.img:
                 self.r.pin_host(im)
-        self.calls = 0
+        self.calls = self.traces_of_sets = 0
         self.target, _ = self(self.params0, 1, False, None, spp=256)
         self.target = self.target.astype(np.float64)
         self.calls = 0
@@ -304,6 +349,13 @@ class DeviceRender:
         o = self.r.render_normal_equations_along(self.cam, rp, V, residual=residual)
         return o["A"], o["b"], o["image"]
 
+    def param_sets(self, sets, seed):
+        """the frame under every row of `sets` [N, P, 3] in one trace: [N, H, W, 3]"""
+        rp = self.pkg.RenderParams(spp=self.spp, min_bounces=self.depth, absorb=1.0, seed=seed)
+        self.calls += 1
+        self.traces_of_sets += 1
+        return self.r.render_param_sets(self.cam, rp, sets)["images"]
+
     def close(self):
         self.r.close()
 
@@ -316,7 +368,7 @@ class OracleRender:
 
     def __init__(self, pkg, oracle, size, spp, depth, scene="cornell"):
         self.pkg, self.oracle = pkg, oracle
-        self.calls = 0
+        self.calls = self.traces_of_sets = 0
         self.scene = pkg.scene_by_name(scene)
         self.cam = pkg.cornell_camera(size, size)
         self.spp, self.depth = spp, depth
@@ -357,6 +409,17 @@ class OracleRender:
         r = np.asarray(residual, np.float64)
         return np.einsum("kxyc,lxyc->ckl", T, T), np.einsum("kxyc,xyc->ck", T, r), img
 
+    def param_sets(self, sets, seed):
+        """the restatement in place of drt_hip_render_param_sets: a render per set, counted as the one trace it stands for"""
+        self.calls += 1
+        self.traces_of_sets += 1
+        rp = self.pkg.RenderParams(spp=self.spp, min_bounces=self.depth, absorb=1.0, seed=seed)
+        out = []
+        for p in sets:
+            self.scene.params = [tuple(q) for q in p]
+            out.append(self.oracle.render(self.scene, self.cam, rp)["image"])
+        return np.stack(out)
+
     def close(self):
         pass
 
@@ -372,12 +435,16 @@ def main():
     ap.add_argument("--steps", type=int, default=None, help="default: 60 (Adam), %d (--gauss-newton)" % GN_STEPS)
     ap.add_argument("--gauss-newton", dest="gauss_newton", action="store_true")
     ap.add_argument("--one-render", dest="one_render", action="store_true")
+    ap.add_argument("--lambda-sets", dest="lambda_sets", type=int, default=0,
+                    help="with --gauss-newton: try this many dampings (<= 7) per step in one render_param_sets call per seed")
     ap.add_argument("--async", dest="use_async", action="store_true")
     ap.add_argument("--oracle", action="store_true")
     ap.add_argument("--quiet", action="store_true")
     ap.add_argument("--scene", default="cornell", help="cornell: the red albedo (the loops above); cornell_shapes: every parameter, with --gauss-newton")
     ap.add_argument("--subspace", choices=("tint",), default=None, help="with --scene cornell_shapes: one tint over the albedos instead of every parameter")
     a = ap.parse_args()
+    if a.lambda_sets and (not a.gauss_newton or a.one_render or not 1 <= a.lambda_sets <= len(LAMBDA_FACTORS)):
+        ap.error("--lambda-sets N (1 ... 7) goes with --gauss-newton (not --one-render)")
     import __graft_entry__ as e
     pkg = e.load_package()
     if a.oracle:
@@ -388,7 +455,9 @@ def main():
         if not a.gauss_newton:
             ap.error("--scene other than cornell goes with --gauss-newton")
         t0 = time.time()
-        f = fit_scene(render, a.steps or ALONG_STEPS, a.subspace, log=None if a.quiet else print)
+        f = fit_scene(render, a.steps or ALONG_STEPS, a.subspace, log=None if a.quiet else print, lambda_sets=a.lambda_sets)
+        if a.lambda_sets:
+            print(f"--lambda-sets {a.lambda_sets}: {render.traces_of_sets} of the renders were traces of {a.lambda_sets} candidates")
         print(f"{a.scene}{' (tint)' if a.subspace else ''}: two-seed loss at the start {f['start_loss']:.5f}; Levenberg-Marquardt {f['gn_steps']} steps, "
               f"{f['gn_renders']} renders: loss {f['gn_loss']:.5f}, max parameter error {f['gn_error']:.4f}; Adam {f['adam_steps']} steps, "
               f"{f['adam_renders']} renders: loss {f['adam_loss']:.5f}, max parameter error {f['adam_error']:.4f}  ({time.time() - t0:.2f} s)")
@@ -397,8 +466,11 @@ def main():
         a.steps = GN_STEPS if a.gauss_newton else 60
     if a.gauss_newton:
         t0 = time.time()
-        rgb, hist = fit_gauss_newton(render, 0, np.array([0.2, 0.2, 0.2]), a.steps, a.one_render, log=None if a.quiet else print)
+        rgb, hist = fit_gauss_newton(render, 0, np.array([0.2, 0.2, 0.2]), a.steps, a.one_render, log=None if a.quiet else print,
+                                     lambda_sets=a.lambda_sets)
         dt = time.time() - t0
+        if a.lambda_sets:
+            print(f"--lambda-sets {a.lambda_sets}: {render.traces_of_sets} of the renders below were traces of {a.lambda_sets} candidates each")
         err = np.abs(rgb - np.array([0.5, 0.0, 0.0])).max()
         n = a.steps if a.one_render else 4 * a.steps
         print(f"fitted red = ({rgb[0]:.4f}, {rgb[1]:.4f}, {rgb[2]:.4f})  max error {err:.4f}  "
