@@ -979,6 +979,32 @@ class HipRenderer:
         self._check(rc, "drt_hip_render_gradient_image")
         return img, gimg, stats.as_dict()
 
+    @staticmethod
+    def _host_flags(rp: RenderParams, f64: bool = False, timing: bool = False) -> int:
+        """the flag word of a call that returns through host buffers"""
+        return (rp.flags & ~(RENDER_DEVICE_OUT | RENDER_SYNC)) | (RENDER_F64 if f64 else 0) | (RENDER_TIMING if timing else 0)
+
+    @staticmethod
+    def _device_flags(rp: RenderParams, f64: bool = False, timing: bool = False, sync: bool = False) -> int:
+        """the flag word of a call on device pointers, enqueued on the context's stream"""
+        return ((rp.flags | RENDER_DEVICE_OUT) & ~RENDER_SYNC) | (RENDER_F64 if f64 else 0) | (RENDER_TIMING if timing else 0) | \
+               (RENDER_SYNC if sync else 0)
+
+    @staticmethod
+    def _image_arg(a, cam: Camera):
+        """an optional float32 [H,W,3] image -> (array, pointer), or (None, None)"""
+        if a is None:
+            return None, None
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        assert a.shape == (cam.height, cam.width, 3), a.shape
+        return a, a.ctypes.data_as(C.c_void_p)
+
+    def _begin(self, cam: Camera, rp: RenderParams, flags: int):
+        """what every call passes -> (camera, render parameters with `flags`, a statistics record) as the ABI takes them"""
+        d = rp.to_desc()
+        d.flags = flags
+        return cam.to_desc(), d, HipStats()
+
     def render_tangent(self, cam: Camera, rp: RenderParams, tangent: np.ndarray, f64: bool = False, timing: bool = False):
         """Forward mode (drt_hip_render_tangent): the image and its derivative along `tangent` (shape (n_params, 3)), the
         Jacobian-vector product J v -- per pixel, the mean over its samples of d radiance / d eps at params + eps * tangent.
@@ -987,12 +1013,9 @@ class HipRenderer:
         assert self.scene is not None
         v = np.ascontiguousarray(tangent, dtype=np.float64)
         assert v.shape == (self.scene.n_params, 3), v.shape
-        d = rp.to_desc()
-        d.flags = (rp.flags & ~(RENDER_DEVICE_OUT | RENDER_SYNC)) | (RENDER_F64 if f64 else 0) | (RENDER_TIMING if timing else 0)
+        cd, d, stats = self._begin(cam, rp, self._host_flags(rp, f64, timing))
         img = np.zeros((cam.height, cam.width, 3), dtype=np.float64 if f64 else np.float32)
         timg = np.zeros((cam.height, cam.width, 3), dtype=np.float64 if f64 else np.float32)
-        stats = HipStats()
-        cd = cam.to_desc()
         fn = self.lib.drt_hip_render_tangent_double if f64 else self.lib.drt_hip_render_tangent
         rc = fn(self.ctx, C.byref(cd), C.byref(d), v.ctypes.data_as(C.c_void_p), img.ctypes.data_as(C.c_void_p),
                 timg.ctypes.data_as(C.c_void_p), C.byref(stats))
@@ -1002,14 +1025,10 @@ class HipRenderer:
     def render_tangent_device(self, cam: Camera, rp: RenderParams, tangent: np.ndarray, out_rgb_ptr: int, out_tangent_ptr: int,
                               timing: bool = False, want_stats: Optional[bool] = None) -> dict:
         """drt_hip_render_tangent on device pointers (float32 [H,W,3] each; out_rgb_ptr may be 0), enqueued on the context's stream."""
-        if want_stats is None:
-            want_stats = timing
+        want_stats = timing if want_stats is None else want_stats
         v = np.ascontiguousarray(tangent, dtype=np.float64)
         assert self.scene is not None and v.shape == (self.scene.n_params, 3), v.shape
-        d = rp.to_desc()
-        d.flags = ((rp.flags | RENDER_DEVICE_OUT) & ~RENDER_SYNC) | (RENDER_TIMING if timing else 0)
-        stats = HipStats()
-        cd = cam.to_desc()
+        cd, d, stats = self._begin(cam, rp, self._device_flags(rp, timing=timing))
         rc = self.lib.drt_hip_render_tangent(self.ctx, C.byref(cd), C.byref(d), v.ctypes.data_as(C.c_void_p), C.c_void_p(out_rgb_ptr or None),
                                              C.c_void_p(out_tangent_ptr), C.byref(stats) if want_stats else None)
         self._check(rc, "drt_hip_render_tangent")
@@ -1023,24 +1042,14 @@ class HipRenderer:
             "jacobian" [P,H,W,3] float32 or None, "stats"}"""
         assert self.scene is not None
         P = self.scene.n_params
-        d = rp.to_desc()
-        d.flags = (rp.flags & ~(RENDER_DEVICE_OUT | RENDER_SYNC)) | (RENDER_F64 if f64 else 0) | (RENDER_TIMING if timing else 0)
-
-        def image(a):
-            if a is None:
-                return None, None
-            a = np.ascontiguousarray(a, dtype=np.float32)
-            assert a.shape == (cam.height, cam.width, 3), a.shape
-            return a, a.ctypes.data_as(C.c_void_p)
-        target, t_ptr = image(target)
-        residual, r_ptr = image(residual)
+        cd, d, stats = self._begin(cam, rp, self._host_flags(rp, f64, timing))
+        target, t_ptr = self._image_arg(target, cam)
+        residual, r_ptr = self._image_arg(residual, cam)
         img = np.zeros((cam.height, cam.width, 3), dtype=np.float32)
         A = np.zeros((3, P, P), dtype=np.float64)
         b = np.zeros((3, P), dtype=np.float64)
         loss = np.zeros(3, dtype=np.float64)
         jac = np.zeros((P, cam.height, cam.width, 3), dtype=np.float32) if jacobian else None
-        stats = HipStats()
-        cd = cam.to_desc()
         rc = self.lib.drt_hip_render_normal_equations(self.ctx, C.byref(cd), C.byref(d), t_ptr, r_ptr, img.ctypes.data_as(C.c_void_p),
                                                       A.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p), loss.ctypes.data_as(C.c_void_p),
                                                       jac.ctypes.data_as(C.c_void_p) if jacobian else None, C.byref(stats))
@@ -1052,14 +1061,9 @@ class HipRenderer:
                                        f64: bool = False, timing: bool = False, sync: bool = False, want_stats: Optional[bool] = None) -> dict:
         """drt_hip_render_normal_equations on device pointers (images float32, A [3,P,P] / b [3,P] / loss [3] float64), enqueued on
         the context's stream; exactly one of target_ptr and residual_ptr."""
-        if want_stats is None:
-            want_stats = timing
+        want_stats = timing if want_stats is None else want_stats
         assert self.scene is not None
-        d = rp.to_desc()
-        d.flags = ((rp.flags | RENDER_DEVICE_OUT) & ~RENDER_SYNC) | (RENDER_F64 if f64 else 0) | (RENDER_TIMING if timing else 0) | \
-                  (RENDER_SYNC if sync else 0)
-        stats = HipStats()
-        cd = cam.to_desc()
+        cd, d, stats = self._begin(cam, rp, self._device_flags(rp, f64, timing, sync))
         rc = self.lib.drt_hip_render_normal_equations(self.ctx, C.byref(cd), C.byref(d), C.c_void_p(target_ptr or None),
                                                       C.c_void_p(residual_ptr or None), C.c_void_p(out_rgb_ptr or None), C.c_void_p(out_A_ptr or None),
                                                       C.c_void_p(out_b_ptr or None), C.c_void_p(out_loss_ptr or None),
@@ -1081,12 +1085,9 @@ class HipRenderer:
         -> (image [H,W,3], tangent images [K,H,W,3], stats dict), float32 (with f64=True: the device's float64 sums, rounded)."""
         v = self._directions(tangents)
         K = v.shape[0]
-        d = rp.to_desc()
-        d.flags = (rp.flags & ~(RENDER_DEVICE_OUT | RENDER_SYNC)) | (RENDER_F64 if f64 else 0) | (RENDER_TIMING if timing else 0)
+        cd, d, stats = self._begin(cam, rp, self._host_flags(rp, f64, timing))
         img = np.zeros((cam.height, cam.width, 3), dtype=np.float32)
         timg = np.zeros((max(K, 1), cam.height, cam.width, 3), dtype=np.float32)
-        stats = HipStats()
-        cd = cam.to_desc()
         rc = self.lib.drt_hip_render_tangents(self.ctx, C.byref(cd), C.byref(d), K, v.ctypes.data_as(C.c_void_p), img.ctypes.data_as(C.c_void_p),
                                               timg.ctypes.data_as(C.c_void_p), C.byref(stats))
         self._check(rc, "drt_hip_render_tangents")
@@ -1095,14 +1096,9 @@ class HipRenderer:
     def render_tangents_device(self, cam: Camera, rp: RenderParams, tangents: np.ndarray, out_rgb_ptr: int, out_tangents_ptr: int,
                                f64: bool = False, timing: bool = False, sync: bool = False, want_stats: Optional[bool] = None) -> dict:
         """drt_hip_render_tangents on device pointers (float32 [H,W,3] and [K,H,W,3]; out_rgb_ptr may be 0), enqueued on the context's stream."""
-        if want_stats is None:
-            want_stats = timing
+        want_stats = timing if want_stats is None else want_stats
         v = self._directions(tangents)
-        d = rp.to_desc()
-        d.flags = ((rp.flags | RENDER_DEVICE_OUT) & ~RENDER_SYNC) | (RENDER_F64 if f64 else 0) | (RENDER_TIMING if timing else 0) | \
-                  (RENDER_SYNC if sync else 0)
-        stats = HipStats()
-        cd = cam.to_desc()
+        cd, d, stats = self._begin(cam, rp, self._device_flags(rp, f64, timing, sync))
         rc = self.lib.drt_hip_render_tangents(self.ctx, C.byref(cd), C.byref(d), v.shape[0], v.ctypes.data_as(C.c_void_p),
                                               C.c_void_p(out_rgb_ptr or None), C.c_void_p(out_tangents_ptr or None),
                                               C.byref(stats) if want_stats else None)
@@ -1118,24 +1114,14 @@ class HipRenderer:
             "tangents" [K,H,W,3] float32 or None, "stats"}"""
         v = self._directions(tangents)
         K = v.shape[0]
-        d = rp.to_desc()
-        d.flags = (rp.flags & ~(RENDER_DEVICE_OUT | RENDER_SYNC)) | (RENDER_F64 if f64 else 0) | (RENDER_TIMING if timing else 0)
-
-        def image(a):
-            if a is None:
-                return None, None
-            a = np.ascontiguousarray(a, dtype=np.float32)
-            assert a.shape == (cam.height, cam.width, 3), a.shape
-            return a, a.ctypes.data_as(C.c_void_p)
-        target, t_ptr = image(target)
-        residual, r_ptr = image(residual)
+        cd, d, stats = self._begin(cam, rp, self._host_flags(rp, f64, timing))
+        target, t_ptr = self._image_arg(target, cam)
+        residual, r_ptr = self._image_arg(residual, cam)
         img = np.zeros((cam.height, cam.width, 3), dtype=np.float32)
         A = np.zeros((3, max(K, 1), max(K, 1)), dtype=np.float64)
         b = np.zeros((3, max(K, 1)), dtype=np.float64)
         loss = np.zeros(3, dtype=np.float64)
         timg = np.zeros((max(K, 1), cam.height, cam.width, 3), dtype=np.float32) if images else None
-        stats = HipStats()
-        cd = cam.to_desc()
         rc = self.lib.drt_hip_render_normal_equations_along(self.ctx, C.byref(cd), C.byref(d), K, v.ctypes.data_as(C.c_void_p), t_ptr, r_ptr,
                                                             img.ctypes.data_as(C.c_void_p), A.ctypes.data_as(C.c_void_p),
                                                             b.ctypes.data_as(C.c_void_p), loss.ctypes.data_as(C.c_void_p),
@@ -1149,14 +1135,9 @@ class HipRenderer:
                                              want_stats: Optional[bool] = None) -> dict:
         """drt_hip_render_normal_equations_along on device pointers (images float32, A [3,K,K] / b [3,K] / loss [3] float64), enqueued
         on the context's stream; the directions are host memory; exactly one of target_ptr and residual_ptr."""
-        if want_stats is None:
-            want_stats = timing
+        want_stats = timing if want_stats is None else want_stats
         v = self._directions(tangents)
-        d = rp.to_desc()
-        d.flags = ((rp.flags | RENDER_DEVICE_OUT) & ~RENDER_SYNC) | (RENDER_F64 if f64 else 0) | (RENDER_TIMING if timing else 0) | \
-                  (RENDER_SYNC if sync else 0)
-        stats = HipStats()
-        cd = cam.to_desc()
+        cd, d, stats = self._begin(cam, rp, self._device_flags(rp, f64, timing, sync))
         rc = self.lib.drt_hip_render_normal_equations_along(self.ctx, C.byref(cd), C.byref(d), v.shape[0], v.ctypes.data_as(C.c_void_p),
                                                             C.c_void_p(target_ptr or None), C.c_void_p(residual_ptr or None),
                                                             C.c_void_p(out_rgb_ptr or None), C.c_void_p(out_A_ptr or None),
@@ -1176,8 +1157,7 @@ class HipRenderer:
         K = v.shape[0]
         if not images and target is None:
             raise ValueError("param sets: no output requested (images=False without a target)")
-        d = rp.to_desc()
-        d.flags = (rp.flags & ~(RENDER_DEVICE_OUT | RENDER_SYNC)) | (RENDER_F64 if f64 else 0) | (RENDER_TIMING if timing else 0)
+        cd, d, stats = self._begin(cam, rp, self._host_flags(rp, f64, timing))
         t_ptr = None
         if target is not None:
             target = np.ascontiguousarray(target, dtype=np.float32)
@@ -1186,8 +1166,6 @@ class HipRenderer:
             t_ptr = target.ctypes.data_as(C.c_void_p)
         imgs = np.zeros((K, cam.height, cam.width, 3), dtype=np.float64 if double else np.float32) if images else None
         loss = np.zeros((K, 3), dtype=np.float64) if target is not None else None
-        stats = HipStats()
-        cd = cam.to_desc()
         fn = self.lib.drt_hip_render_param_sets_double if double else self.lib.drt_hip_render_param_sets
         rc = fn(self.ctx, C.byref(cd), C.byref(d), K, v.ctypes.data_as(C.c_void_p), t_ptr,
                 imgs.ctypes.data_as(C.c_void_p) if images else None, loss.ctypes.data_as(C.c_void_p) if loss is not None else None,
@@ -1200,15 +1178,10 @@ class HipRenderer:
                                  want_stats: Optional[bool] = None) -> dict:
         """drt_hip_render_param_sets on device pointers (images float32 [K,H,W,3], target float32 [H,W,3], loss float64 [K,3]), enqueued
         on the context's stream; the sets are host memory."""
-        if want_stats is None:
-            want_stats = timing
+        want_stats = timing if want_stats is None else want_stats
         assert self.scene is not None
         v = check_param_sets(sets, self.scene.n_params)
-        d = rp.to_desc()
-        d.flags = ((rp.flags | RENDER_DEVICE_OUT) & ~RENDER_SYNC) | (RENDER_F64 if f64 else 0) | (RENDER_TIMING if timing else 0) | \
-                  (RENDER_SYNC if sync else 0)
-        stats = HipStats()
-        cd = cam.to_desc()
+        cd, d, stats = self._begin(cam, rp, self._device_flags(rp, f64, timing, sync))
         rc = self.lib.drt_hip_render_param_sets(self.ctx, C.byref(cd), C.byref(d), v.shape[0], v.ctypes.data_as(C.c_void_p),
                                                 C.c_void_p(target_ptr or None), C.c_void_p(out_images_ptr or None),
                                                 C.c_void_p(out_loss_ptr or None), C.c_void_p(out_rgb_ptr or None),

@@ -15,8 +15,7 @@ struct TimedLaunch {
     hipEvent_t e0, e1;
 };
 
-// A forward-mode render (drt_hip_render_tangent), as render_common / render_launch / render_impl are told about it
-// ... and the normal equations of a frame (drt_hip_render_normal_equations): the path kernel's Jacobian form, then k_normal_eq.  All pointers
+// The normal equations of a frame (drt_hip_render_normal_equations): the path kernel's Jacobian form, then k_normal_eq.  All pointers
 // are the device's; exactly one of d_target / d_residual is set
 struct NormalEqRequest {
     const float* d_target = nullptr;
@@ -33,14 +32,21 @@ struct ParamSetsRequest {
     double* d_images64 = nullptr;         // ... the means in double (drt_hip_render_param_sets_double), or none
     double* d_loss = nullptr;             // n_sets x 3, or none (needs d_target)
 };
+// A render on one of the path kernel's special forms, as render_common / render_launch / render_impl are told about it: which form, and what
+// that form reads.  render_impl decodes it, in one place
 struct TangentRequest {
-    const void* d_params = nullptr;       // [the scene's parameters | the direction] in the render's compute type: the path kernel's `params`
+    enum class Kind {
+        forward,                          // forward mode along one direction (drt_hip_render_tangent): d_params, keep_sums
+        jacobian,                         // the normal equations of a frame (drt_hip_render_normal_equations): neq
+        directions,                       // ... in the span of K directions (drt_hip_render_tangents / _normal_equations_along): d_params, neq, n_dirs
+        param_sets,                       // one frame under K parameter sets (drt_hip_render_param_sets): d_params, sets
+    } kind = Kind::forward;
+    const void* d_params = nullptr;       // the path kernel's `params`, in the render's compute type: [the scene's parameters | row_1 | ... | row_K],
+                                          // the rows padded up to an instantiated width K (stage_rows, drt_hip.hip)
     bool keep_sums = false;               // the pixels' sums of both images also stay in `film` / `gfilm`, in double (drt_hip_render_tangent_double)
-    const NormalEqRequest* neq = nullptr; // not a forward-mode render at all: the normal equations (d_params, keep_sums unused)
-    const ParamSetsRequest* sets = nullptr;   // not a forward-mode render either: d_params holds [parameters | P_1 | ... | P_K]
-    int n_dirs = 0;                       // > 0, with neq: the K-direction forward form (drt_hip_render_tangents / _normal_equations_along) -- d_params holds
-                                          // [parameters | v_1 | ... | v_K], K = n_dirs padded up to an instantiated width with zero directions, and the
-                                          // rows k_normal_eq reduces are the n_dirs directions instead of the parameters
+    const NormalEqRequest* neq = nullptr;
+    int n_dirs = 0;                       // the rows k_normal_eq reduces are these directions instead of the parameters
+    const ParamSetsRequest* sets = nullptr;
 };
 
 // One render call between its phases: launch (everything enqueued, gradients in ctx->grad[ctx->slot]) -> reduce (the

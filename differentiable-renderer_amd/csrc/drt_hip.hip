@@ -253,16 +253,105 @@ int drt_hip_render_gradient_image(drt_hip_ctx* ctx, const drt_camera_desc* cam, 
 
 } // extern "C"
 
-// ---- forward mode: the derivative of the render along one direction of parameter space (Dual<T> of the reference, dual.hpp) ----
-// dst = [the scene's parameters | the direction] in compute type R; internal constants (a mirror's colour) have direction 0
+// ---- the renders that exist on the one-launch path kernel's special forms only: forward mode along one direction, the Jacobian form,
+// K directions, K parameter sets.  What they share: the rows behind the kernel's `params`, the refusals, the K images' way back ----
+// dst = [the scene's parameters | row_1 | ... | row_K] in compute type R.  Rows at and above n_rows (padding up to the kernel's width) and the
+// internal constants (a mirror's colour) of every row are zero -- directions -- or, with pad_own, the context's own parameters -- sets
 template <typename R>
-__global__ void __launch_bounds__(DRT_BLOCK) k_stage_tangent(const R* __restrict__ params, int n_all, const double* __restrict__ h_dir, int n_user,
-                                                             R* __restrict__ dst)
+__global__ void __launch_bounds__(DRT_BLOCK) k_stage_rows(const R* __restrict__ params, int n_all, const double* __restrict__ h_rows, int n_user,
+                                                          int n_rows, int K, bool pad_own, R* __restrict__ dst)
 {
     for (int i = blockIdx.x * DRT_BLOCK + threadIdx.x; i < n_all; i += gridDim.x * DRT_BLOCK) {
-        dst[i] = params[i];
-        dst[n_all + i] = i < n_user ? (R)h_dir[i] : R(0);
+        const R own = params[i], pad = pad_own ? own : R(0);
+        dst[i] = own;
+        for (int k = 0; k < K; ++k)
+            dst[(size_t)(1 + k) * n_all + i] = (k < n_rows && i < n_user) ? (R)h_rows[(size_t)k * n_user + i] : pad;
     }
+}
+
+// the caller's n_rows x n_user rows -> pinned memory -> ctx->tangent.p = [parameters | row_1 | ... | row_K], in stream order.  Two pinned
+// copies used in turn: the one this call rewrites was read by the launch of the call before the previous one, and its event says so
+static int stage_rows(drt_hip_ctx* ctx, const drt_render_params* rp, const double* rows, int n_rows, int K, bool pad_own)
+{
+    const int n_user = ctx->n_user_params * 3, n_all = ctx->n_params * 3;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const int hb = (int)(ctx->tangent_calls++ & 1);
+    const size_t need = (size_t)n_rows * (size_t)(n_user ? n_user : 1);
+    if (!ctx->ev_tangent[hb])
+        HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_tangent[hb], hipEventDisableTiming));
+    else
+        HIPCHK(ctx, hipEventSynchronize(ctx->ev_tangent[hb]));
+    if (ctx->h_tangent_cap[hb] < need) {
+        if (ctx->h_tangent[hb])
+            (void)hipHostFree(ctx->h_tangent[hb]);
+        ctx->h_tangent[hb] = nullptr;
+        ctx->h_tangent_cap[hb] = 0;
+        HIPCHK(ctx, hipHostMalloc((void**)&ctx->h_tangent[hb], need * sizeof(double)));
+        ctx->h_tangent_cap[hb] = need;
+    }
+    memcpy(ctx->h_tangent[hb], rows, (size_t)n_rows * (size_t)n_user * sizeof(double));
+    int rc;
+    if ((rc = ensure(ctx, ctx->tangent, (size_t)(n_all ? n_all : 1) * (size_t)(1 + K) * sizeof(double))) != DRT_OK) return rc;
+    if (n_all > 0) {
+        const unsigned blocks = (unsigned)((n_all + DRT_BLOCK - 1) / DRT_BLOCK);
+        if (rp->flags & DRT_RENDER_F64)
+            hipLaunchKernelGGL(k_stage_rows<double>, dim3(blocks), dim3(DRT_BLOCK), 0, ctx->stream, (const double*)ctx->d_params_d, n_all,
+                               (const double*)ctx->h_tangent[hb], n_user, n_rows, K, pad_own, (double*)ctx->tangent.p);
+        else
+            hipLaunchKernelGGL(k_stage_rows<float>, dim3(blocks), dim3(DRT_BLOCK), 0, ctx->stream, (const float*)ctx->d_params_f, n_all,
+                               (const double*)ctx->h_tangent[hb], n_user, n_rows, K, pad_own, (float*)ctx->tangent.p);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    HIPCHK(ctx, hipEventRecord(ctx->ev_tangent[hb], ctx->stream));
+    return DRT_OK;
+}
+
+// who is asking, and the few words of the shared refusals that are its own
+struct PathFormCaller {
+    const char* who;            // every message's first words
+    const char* group_hint;     // what to do on a group context instead
+    const char* what;           // "... -- `what` on the one-launch path kernel, one context"
+    int cap;                    // the most parameters (internal constants included) its form of the kernel takes ...
+    const char* above_cap;      // ... and what it says above that
+};
+
+// a refusal in the caller's name
+static int refuse(drt_hip_ctx* ctx, const PathFormCaller& c, int code, const std::string& what)
+{
+    return fail(ctx, code, (std::string(c.who) + ": " + what).c_str());
+}
+
+// The refusals the Jacobian, K-direction and parameter-set forms share, in the order they have always come in: the context, the scene and the
+// camera (refuse_before); the entry point's own checks; then what the one-launch path kernel over the whole shard in one batch cannot do
+// (refuse_after).  (drt_hip_render_tangent is older, renders in batches and speaks its own words: it keeps its own ladder.)
+static int refuse_before(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_params* rp, const PathFormCaller& c)
+{
+    if (!ctx->members.empty())
+        return refuse(ctx, c, DRT_ERR_UNSUPPORTED, std::string("not on a group context (") + c.group_hint + ")");
+    if (!ctx->has_scene)
+        return fail(ctx, DRT_ERR_NO_SCENE, "render before upload_scene");
+    if (!cam || !rp || cam->width <= 0 || cam->height <= 0)
+        return refuse(ctx, c, DRT_ERR_INVALID, "bad camera or render parameters");
+    return DRT_OK;
+}
+
+static int refuse_after(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_params* rp, const PathFormCaller& c)
+{
+    for (int i = 0; i < DRT_HIP_FRAMES_IN_FLIGHT; ++i)
+        if (ctx->in_flight[i])
+            return refuse(ctx, c, DRT_ERR_INVALID, "asynchronous frames are in flight -- drt_hip_wait for them first");
+    if (rp->flags & (DRT_RENDER_UNFUSED | DRT_RENDER_UNBIASED | DRT_RENDER_LOSS_L2 | DRT_RENDER_ALLREDUCE | DRT_RENDER_ALLREDUCE_ASYNC))
+        return refuse(ctx, c, DRT_ERR_UNSUPPORTED, std::string("not with DRT_RENDER_UNFUSED, _UNBIASED, _LOSS_L2 or _ALLREDUCE* -- ") + c.what +
+                                                   " on the one-launch path kernel, one context");
+    if (ctx->has_mesh)
+        return refuse(ctx, c, DRT_ERR_UNSUPPORTED, "not of a scene that holds a triangle mesh");
+    if (rp->bounces_per_launch >= 1)
+        return refuse(ctx, c, DRT_ERR_UNSUPPORTED, "they come from the one-launch path kernel -- not with bounces_per_launch >= 1");
+    if (ctx->n_params > c.cap)
+        return refuse(ctx, c, DRT_ERR_UNSUPPORTED, c.above_cap);
+    if ((uint64_t)cam->width * (uint64_t)cam->height * (uint64_t)(rp->spp > 0 ? rp->spp : 1) > 0x7FFFFFFFull)
+        return refuse(ctx, c, DRT_ERR_UNSUPPORTED, "more than 2^31 camera samples in one frame (the shard renders in one batch)");
+    return DRT_OK;
 }
 
 static int render_tangent_common(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_params* rp, const double* param_tangent,
@@ -278,8 +367,7 @@ static int render_tangent_common(drt_hip_ctx* ctx, const drt_camera_desc* cam, c
         return fail(ctx, DRT_ERR_INVALID, "render_tangent: NULL render parameters, tangent or output");
     if (rp->flags & (DRT_RENDER_BACKWARD | DRT_RENDER_UNBIASED | DRT_RENDER_LOSS_L2 | DRT_RENDER_ALLREDUCE | DRT_RENDER_ALLREDUCE_ASYNC))
         return fail(ctx, DRT_ERR_INVALID, "render_tangent: forward mode takes no reverse-mode flag (DRT_RENDER_BACKWARD, _UNBIASED, _LOSS_L2, _ALLREDUCE*)");
-    const int n_user = ctx->n_user_params * 3, n_all = ctx->n_params * 3;
-    for (int i = 0; i < n_user; ++i)
+    for (int i = 0; i < ctx->n_user_params * 3; ++i)
         if (!std::isfinite(param_tangent[i]))
             return fail(ctx, DRT_ERR_INVALID, "render_tangent: the tangent holds a value that is not finite");
     for (int i = 0; i < DRT_HIP_FRAMES_IN_FLIGHT; ++i)
@@ -292,38 +380,10 @@ static int render_tangent_common(drt_hip_ctx* ctx, const drt_camera_desc* cam, c
                                               "or DRT_RENDER_UNFUSED");
     if (ctx->n_params > DRT_PATH_LDS_PARAMS)
         return fail(ctx, DRT_ERR_UNSUPPORTED, "render_tangent: a tangent of more parameters than the path kernels stage (136)");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    // the direction -> pinned memory -> [parameters | direction] on the device, in stream order (the copy this call rewrites was read
-    // by the launch of the call before the previous one)
-    const int hb = (int)(ctx->tangent_calls++ & 1);
-    const size_t need = (size_t)(n_user ? n_user : 1);
-    if (!ctx->ev_tangent[hb])
-        HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_tangent[hb], hipEventDisableTiming));
-    else
-        HIPCHK(ctx, hipEventSynchronize(ctx->ev_tangent[hb]));
-    if (ctx->h_tangent_cap[hb] < need) {
-        if (ctx->h_tangent[hb])
-            (void)hipHostFree(ctx->h_tangent[hb]);
-        ctx->h_tangent[hb] = nullptr;
-        ctx->h_tangent_cap[hb] = 0;
-        HIPCHK(ctx, hipHostMalloc((void**)&ctx->h_tangent[hb], need * sizeof(double)));
-        ctx->h_tangent_cap[hb] = need;
-    }
-    memcpy(ctx->h_tangent[hb], param_tangent, (size_t)n_user * sizeof(double));
     int rc;
-    if ((rc = ensure(ctx, ctx->tangent, (size_t)(n_all ? n_all : 1) * 2 * sizeof(double))) != DRT_OK) return rc;
-    if (n_all > 0) {
-        const unsigned blocks = (unsigned)((n_all + DRT_BLOCK - 1) / DRT_BLOCK);
-        if (rp->flags & DRT_RENDER_F64)
-            hipLaunchKernelGGL(k_stage_tangent<double>, dim3(blocks), dim3(DRT_BLOCK), 0, ctx->stream, (const double*)ctx->d_params_d, n_all,
-                               (const double*)ctx->h_tangent[hb], n_user, (double*)ctx->tangent.p);
-        else
-            hipLaunchKernelGGL(k_stage_tangent<float>, dim3(blocks), dim3(DRT_BLOCK), 0, ctx->stream, (const float*)ctx->d_params_f, n_all,
-                               (const double*)ctx->h_tangent[hb], n_user, (float*)ctx->tangent.p);
-        HIPCHK(ctx, hipGetLastError());
-    }
-    HIPCHK(ctx, hipEventRecord(ctx->ev_tangent[hb], ctx->stream));
+    if ((rc = stage_rows(ctx, rp, param_tangent, 1, 1, false)) != DRT_OK) return rc;
     TangentRequest req;
+    req.kind = TangentRequest::Kind::forward;
     req.d_params = ctx->tangent.p;
     req.keep_sums = keep_sums;
     return render_common(ctx, cam, rp, nullptr, out_rgb, nullptr, stats, -1, out_tangent_rgb, &req);
@@ -472,35 +532,21 @@ int drt_hip_render_normal_equations(drt_hip_ctx* ctx, const drt_camera_desc* cam
 {
     if (!ctx)
         return DRT_ERR_INVALID;
-    if (!ctx->members.empty())
-        return fail(ctx, DRT_ERR_UNSUPPORTED, "normal equations: not on a group context (render the shards on plain contexts and add them)");
-    if (!ctx->has_scene)
-        return fail(ctx, DRT_ERR_NO_SCENE, "render before upload_scene");
-    if (!cam || !rp || cam->width <= 0 || cam->height <= 0)
-        return fail(ctx, DRT_ERR_INVALID, "normal equations: bad camera or render parameters");
+    const PathFormCaller me = {"normal equations", "render the shards on plain contexts and add them", "the biased operator", DRT_FAST_PARAMS,
+                               ctx->n_user_params > DRT_FAST_PARAMS
+        ? "more than DRT_FAST_PARAMS = 8 parameters (the Jacobian is the path kernel's gradient "
+          "columns, which stop there; J^T J v by drt_hip_render_tangent + drt_hip_render is the matrix-free route)"
+        : "the scene's parameters and the constant a mirror material adds take more than DRT_FAST_PARAMS = 8 "
+          "gradient columns of the path kernel (a mirror costs one: at most 7 parameters beside it)"};
+    int rc;
+    if ((rc = refuse_before(ctx, cam, rp, me)) != DRT_OK) return rc;
     if ((target_rgb != nullptr) == (residual_rgb != nullptr))
-        return fail(ctx, DRT_ERR_INVALID, "normal equations: exactly one of target_rgb and residual_rgb");
+        return refuse(ctx, me, DRT_ERR_INVALID, "exactly one of target_rgb and residual_rgb");
     if (!out_A || !out_b)
-        return fail(ctx, DRT_ERR_INVALID, "normal equations: NULL out_A or out_b");
-    for (int i = 0; i < DRT_HIP_FRAMES_IN_FLIGHT; ++i)
-        if (ctx->in_flight[i])
-            return fail(ctx, DRT_ERR_INVALID, "normal equations: asynchronous frames are in flight -- drt_hip_wait for them first");
-    if (rp->flags & (DRT_RENDER_UNFUSED | DRT_RENDER_UNBIASED | DRT_RENDER_LOSS_L2 | DRT_RENDER_ALLREDUCE | DRT_RENDER_ALLREDUCE_ASYNC))
-        return fail(ctx, DRT_ERR_UNSUPPORTED, "normal equations: not with DRT_RENDER_UNFUSED, _UNBIASED, _LOSS_L2 or _ALLREDUCE* -- the biased operator on the "
-                                              "one-launch path kernel, one context");
-    if (ctx->has_mesh)
-        return fail(ctx, DRT_ERR_UNSUPPORTED, "normal equations: not of a scene that holds a triangle mesh");
-    if (rp->bounces_per_launch >= 1)
-        return fail(ctx, DRT_ERR_UNSUPPORTED, "normal equations: they come from the one-launch path kernel -- not with bounces_per_launch >= 1");
-    if (ctx->n_params > DRT_FAST_PARAMS)
-        return fail(ctx, DRT_ERR_UNSUPPORTED, ctx->n_user_params > DRT_FAST_PARAMS
-            ? "normal equations: more than DRT_FAST_PARAMS = 8 parameters (the Jacobian is the path kernel's gradient "
-              "columns, which stop there; J^T J v by drt_hip_render_tangent + drt_hip_render is the matrix-free route)"
-            : "normal equations: the scene's parameters and the constant a mirror material adds take more than DRT_FAST_PARAMS = 8 "
-              "gradient columns of the path kernel (a mirror costs one: at most 7 parameters beside it)");
-    if ((uint64_t)cam->width * (uint64_t)cam->height * (uint64_t)(rp->spp > 0 ? rp->spp : 1) > 0x7FFFFFFFull)
-        return fail(ctx, DRT_ERR_UNSUPPORTED, "normal equations: more than 2^31 camera samples in one frame (the shard renders in one batch)");
+        return refuse(ctx, me, DRT_ERR_INVALID, "NULL out_A or out_b");
+    if ((rc = refuse_after(ctx, cam, rp, me)) != DRT_OK) return rc;
     TangentRequest req;
+    req.kind = TangentRequest::Kind::jacobian;
     return normal_equations_run(ctx, cam, rp, target_rgb, residual_rgb, out_rgb, out_A, out_b, out_loss, out_jacobian, stats,
                                 (size_t)ctx->n_user_params, req, "normal equations");
 }
@@ -509,93 +555,34 @@ int drt_hip_render_normal_equations(drt_hip_ctx* ctx, const drt_camera_desc* cam
 } // extern "C"
 
 // ---- J V for up to DRT_HIP_MAX_DIRS directions in one render, and the normal equations in their span ----
-// dst = [the scene's parameters | v_1 | ... | v_K] in compute type R: directions at and above n_dirs are zero (padding up to the
-// kernel's width), and so are internal constants (a mirror's colour)
-template <typename R>
-__global__ void __launch_bounds__(DRT_BLOCK) k_stage_tangents(const R* __restrict__ params, int n_all, const double* __restrict__ h_dirs, int n_user,
-                                                              int n_dirs, int K, R* __restrict__ dst)
-{
-    for (int i = blockIdx.x * DRT_BLOCK + threadIdx.x; i < n_all; i += gridDim.x * DRT_BLOCK) {
-        dst[i] = params[i];
-        for (int k = 0; k < K; ++k)
-            dst[(size_t)(1 + k) * n_all + i] = (k < n_dirs && i < n_user) ? (R)h_dirs[(size_t)k * n_user + i] : R(0);
-    }
-}
-
 static int render_tangents_common(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_params* rp, int32_t n_dirs,
                                   const double* param_tangents, const float* target_rgb, const float* residual_rgb, float* out_rgb,
                                   double* out_A, double* out_b, double* out_loss, float* out_tangents, drt_hip_stats* stats, bool along)
 {
     if (!ctx)
         return DRT_ERR_INVALID;
-    const std::string who = along ? "normal equations along" : "tangents";
-    const auto no = [&](int code, const char* what) { return fail(ctx, code, (who + ": " + what).c_str()); };
-    if (!ctx->members.empty())
-        return no(DRT_ERR_UNSUPPORTED, "not on a group context (render the shards on plain contexts)");
-    if (!ctx->has_scene)
-        return fail(ctx, DRT_ERR_NO_SCENE, "render before upload_scene");
-    if (!cam || !rp || cam->width <= 0 || cam->height <= 0)
-        return no(DRT_ERR_INVALID, "bad camera or render parameters");
-    if (n_dirs < 1 || n_dirs > DRT_HIP_MAX_DIRS)
-        return no(DRT_ERR_INVALID, "n_dirs outside 1 ... DRT_HIP_MAX_DIRS = 8");
-    if (!param_tangents || (along ? (!out_A || !out_b) : !out_tangents))
-        return no(DRT_ERR_INVALID, "NULL directions or output");
-    if (along && (target_rgb != nullptr) == (residual_rgb != nullptr))
-        return no(DRT_ERR_INVALID, "exactly one of target_rgb and residual_rgb");
-    const int n_user = ctx->n_user_params * 3, n_all = ctx->n_params * 3;
-    for (size_t i = 0; i < (size_t)n_dirs * (size_t)n_user; ++i)
-        if (!std::isfinite(param_tangents[i]))
-            return no(DRT_ERR_INVALID, "a direction holds a value that is not finite");
-    for (int i = 0; i < DRT_HIP_FRAMES_IN_FLIGHT; ++i)
-        if (ctx->in_flight[i])
-            return no(DRT_ERR_INVALID, "asynchronous frames are in flight -- drt_hip_wait for them first");
-    if (rp->flags & (DRT_RENDER_UNFUSED | DRT_RENDER_UNBIASED | DRT_RENDER_LOSS_L2 | DRT_RENDER_ALLREDUCE | DRT_RENDER_ALLREDUCE_ASYNC))
-        return no(DRT_ERR_UNSUPPORTED, "not with DRT_RENDER_UNFUSED, _UNBIASED, _LOSS_L2 or _ALLREDUCE* -- forward mode on the one-launch path kernel, one context");
-    if (ctx->has_mesh)
-        return no(DRT_ERR_UNSUPPORTED, "not of a scene that holds a triangle mesh");
-    if (rp->bounces_per_launch >= 1)
-        return no(DRT_ERR_UNSUPPORTED, "they come from the one-launch path kernel -- not with bounces_per_launch >= 1");
-    if (ctx->n_params > DRT_PATH_LDS_PARAMS)
-        return no(DRT_ERR_UNSUPPORTED, "more parameters than the path kernels stage (136)");
-    if ((uint64_t)cam->width * (uint64_t)cam->height * (uint64_t)(rp->spp > 0 ? rp->spp : 1) > 0x7FFFFFFFull)
-        return no(DRT_ERR_UNSUPPORTED, "more than 2^31 camera samples in one frame (the shard renders in one batch)");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    // the directions -> pinned memory -> [parameters | v_1 | ... | v_K] on the device, in stream order: drt_hip_render_tangent's
-    // double buffer and events (the copy this call rewrites was read by the launch of the call before the previous one)
-    const int K = n_dirs <= 2 ? 2 : (n_dirs <= 4 ? 4 : 8);
-    const int hb = (int)(ctx->tangent_calls++ & 1);
-    const size_t need = (size_t)n_dirs * (size_t)(n_user ? n_user : 1);
-    if (!ctx->ev_tangent[hb])
-        HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_tangent[hb], hipEventDisableTiming));
-    else
-        HIPCHK(ctx, hipEventSynchronize(ctx->ev_tangent[hb]));
-    if (ctx->h_tangent_cap[hb] < need) {
-        if (ctx->h_tangent[hb])
-            (void)hipHostFree(ctx->h_tangent[hb]);
-        ctx->h_tangent[hb] = nullptr;
-        ctx->h_tangent_cap[hb] = 0;
-        HIPCHK(ctx, hipHostMalloc((void**)&ctx->h_tangent[hb], need * sizeof(double)));
-        ctx->h_tangent_cap[hb] = need;
-    }
-    memcpy(ctx->h_tangent[hb], param_tangents, (size_t)n_dirs * (size_t)n_user * sizeof(double));
+    const PathFormCaller me = {along ? "normal equations along" : "tangents", "render the shards on plain contexts", "forward mode", DRT_PATH_LDS_PARAMS,
+                               "more parameters than the path kernels stage (136)"};
     int rc;
-    if ((rc = ensure(ctx, ctx->tangent, (size_t)(n_all ? n_all : 1) * (size_t)(1 + K) * sizeof(double))) != DRT_OK) return rc;
-    if (n_all > 0) {
-        const unsigned blocks = (unsigned)((n_all + DRT_BLOCK - 1) / DRT_BLOCK);
-        if (rp->flags & DRT_RENDER_F64)
-            hipLaunchKernelGGL(k_stage_tangents<double>, dim3(blocks), dim3(DRT_BLOCK), 0, ctx->stream, (const double*)ctx->d_params_d, n_all,
-                               (const double*)ctx->h_tangent[hb], n_user, (int)n_dirs, K, (double*)ctx->tangent.p);
-        else
-            hipLaunchKernelGGL(k_stage_tangents<float>, dim3(blocks), dim3(DRT_BLOCK), 0, ctx->stream, (const float*)ctx->d_params_f, n_all,
-                               (const double*)ctx->h_tangent[hb], n_user, (int)n_dirs, K, (float*)ctx->tangent.p);
-        HIPCHK(ctx, hipGetLastError());
-    }
-    HIPCHK(ctx, hipEventRecord(ctx->ev_tangent[hb], ctx->stream));
+    if ((rc = refuse_before(ctx, cam, rp, me)) != DRT_OK) return rc;
+    if (n_dirs < 1 || n_dirs > DRT_HIP_MAX_DIRS)
+        return refuse(ctx, me, DRT_ERR_INVALID, "n_dirs outside 1 ... DRT_HIP_MAX_DIRS = 8");
+    if (!param_tangents || (along ? (!out_A || !out_b) : !out_tangents))
+        return refuse(ctx, me, DRT_ERR_INVALID, "NULL directions or output");
+    if (along && (target_rgb != nullptr) == (residual_rgb != nullptr))
+        return refuse(ctx, me, DRT_ERR_INVALID, "exactly one of target_rgb and residual_rgb");
+    for (size_t i = 0; i < (size_t)n_dirs * (size_t)ctx->n_user_params * 3; ++i)
+        if (!std::isfinite(param_tangents[i]))
+            return refuse(ctx, me, DRT_ERR_INVALID, "a direction holds a value that is not finite");
+    if ((rc = refuse_after(ctx, cam, rp, me)) != DRT_OK) return rc;
+    // (directions at and above n_dirs, up to the kernel's width, are zero)
+    if ((rc = stage_rows(ctx, rp, param_tangents, n_dirs, n_dirs <= 2 ? 2 : (n_dirs <= 4 ? 4 : 8), false)) != DRT_OK) return rc;
     TangentRequest req;
+    req.kind = TangentRequest::Kind::directions;
     req.d_params = ctx->tangent.p;
     req.n_dirs = n_dirs;
     return normal_equations_run(ctx, cam, rp, target_rgb, residual_rgb, out_rgb, out_A, out_b, out_loss, out_tangents, stats, (size_t)n_dirs, req,
-                                who.c_str());
+                                me.who);
 }
 
 extern "C" {
@@ -616,101 +603,43 @@ int drt_hip_render_normal_equations_along(drt_hip_ctx* ctx, const drt_camera_des
 } // extern "C"
 
 // ---- one frame under up to DRT_HIP_MAX_PARAM_SETS parameter sets in one trace ----
-// dst = [the scene's parameters | P_1 | ... | P_K] in compute type R: sets at and above n_sets are the context's own parameters (padding up
-// to the kernel's width; the last one is the plain image's), and so are internal constants (a mirror's colour) in every set
-template <typename R>
-__global__ void __launch_bounds__(DRT_BLOCK) k_stage_param_sets(const R* __restrict__ params, int n_all, const double* __restrict__ h_sets, int n_user,
-                                                                int n_sets, int K, R* __restrict__ dst)
-{
-    for (int i = blockIdx.x * DRT_BLOCK + threadIdx.x; i < n_all; i += gridDim.x * DRT_BLOCK) {
-        dst[i] = params[i];
-        for (int k = 0; k < K; ++k)
-            dst[(size_t)(1 + k) * n_all + i] = (k < n_sets && i < n_user) ? (R)h_sets[(size_t)k * n_user + i] : params[i];
-    }
-}
-
 static int render_param_sets_common(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_params* rp, int32_t n_sets,
                                     const double* param_sets, const float* target_rgb, float* out_images, double* out_images64,
                                     double* out_loss, float* out_rgb, drt_hip_stats* stats)
 {
     if (!ctx)
         return DRT_ERR_INVALID;
-    const auto no = [&](int code, const char* what) { return fail(ctx, code, (std::string("param sets: ") + what).c_str()); };
-    if (!ctx->members.empty())
-        return no(DRT_ERR_UNSUPPORTED, "not on a group context (render the shards on plain contexts)");
-    if (!ctx->has_scene)
-        return fail(ctx, DRT_ERR_NO_SCENE, "render before upload_scene");
-    if (!cam || !rp || cam->width <= 0 || cam->height <= 0)
-        return no(DRT_ERR_INVALID, "bad camera or render parameters");
+    const PathFormCaller me = {"param sets", "render the shards on plain contexts", "a forward render", DRT_PATH_LDS_PARAMS,
+                               "more parameters than the path kernels stage (136)"};
+    int rc;
+    if ((rc = refuse_before(ctx, cam, rp, me)) != DRT_OK) return rc;
     if (n_sets < 1 || n_sets > DRT_HIP_MAX_PARAM_SETS)
-        return no(DRT_ERR_INVALID, "n_sets outside 1 ... DRT_HIP_MAX_PARAM_SETS = 8");
+        return refuse(ctx, me, DRT_ERR_INVALID, "n_sets outside 1 ... DRT_HIP_MAX_PARAM_SETS = 8");
     if (!param_sets)
-        return no(DRT_ERR_INVALID, "NULL param_sets");
+        return refuse(ctx, me, DRT_ERR_INVALID, "NULL param_sets");
     if (!out_images && !out_images64 && !out_loss)
-        return no(DRT_ERR_INVALID, "no output requested (out_images and out_loss are both NULL)");
+        return refuse(ctx, me, DRT_ERR_INVALID, "no output requested (out_images and out_loss are both NULL)");
     if (out_loss && !target_rgb)
-        return no(DRT_ERR_INVALID, "out_loss needs target_rgb");
+        return refuse(ctx, me, DRT_ERR_INVALID, "out_loss needs target_rgb");
     if (rp->flags & DRT_RENDER_BACKWARD)
-        return no(DRT_ERR_INVALID, "a forward render: no DRT_RENDER_BACKWARD");
-    const bool dev = (rp->flags & DRT_RENDER_DEVICE_OUT) != 0;
-    const int n_user = ctx->n_user_params * 3, n_all = ctx->n_params * 3;
-    for (size_t i = 0; i < (size_t)n_sets * (size_t)n_user; ++i)
+        return refuse(ctx, me, DRT_ERR_INVALID, "a forward render: no DRT_RENDER_BACKWARD");
+    for (size_t i = 0; i < (size_t)n_sets * (size_t)ctx->n_user_params * 3; ++i)
         if (!std::isfinite(param_sets[i]))
-            return no(DRT_ERR_INVALID, "a set holds a value that is not finite");
-    const size_t npix = (size_t)cam->width * (size_t)cam->height;
-    if (!dev && target_rgb)
-        for (size_t i = 0; i < npix * 3; ++i)
+            return refuse(ctx, me, DRT_ERR_INVALID, "a set holds a value that is not finite");
+    if (!(rp->flags & DRT_RENDER_DEVICE_OUT) && target_rgb)
+        for (size_t i = 0; i < (size_t)cam->width * (size_t)cam->height * 3; ++i)
             if (!std::isfinite(target_rgb[i]))
-                return no(DRT_ERR_INVALID, "the target image holds a value that is not finite");
-    for (int i = 0; i < DRT_HIP_FRAMES_IN_FLIGHT; ++i)
-        if (ctx->in_flight[i])
-            return no(DRT_ERR_INVALID, "asynchronous frames are in flight -- drt_hip_wait for them first");
-    if (rp->flags & (DRT_RENDER_UNFUSED | DRT_RENDER_UNBIASED | DRT_RENDER_LOSS_L2 | DRT_RENDER_ALLREDUCE | DRT_RENDER_ALLREDUCE_ASYNC))
-        return no(DRT_ERR_UNSUPPORTED, "not with DRT_RENDER_UNFUSED, _UNBIASED, _LOSS_L2 or _ALLREDUCE* -- a forward render on the one-launch path kernel, one context");
-    if (ctx->has_mesh)
-        return no(DRT_ERR_UNSUPPORTED, "not of a scene that holds a triangle mesh");
-    if (rp->bounces_per_launch >= 1)
-        return no(DRT_ERR_UNSUPPORTED, "they come from the one-launch path kernel -- not with bounces_per_launch >= 1");
-    if (ctx->n_params > DRT_PATH_LDS_PARAMS)
-        return no(DRT_ERR_UNSUPPORTED, "more parameters than the path kernels stage (136)");
-    if ((uint64_t)cam->width * (uint64_t)cam->height * (uint64_t)(rp->spp > 0 ? rp->spp : 1) > 0x7FFFFFFFull)
-        return no(DRT_ERR_UNSUPPORTED, "more than 2^31 camera samples in one frame (the shard renders in one batch)");
+                return refuse(ctx, me, DRT_ERR_INVALID, "the target image holds a value that is not finite");
+    if ((rc = refuse_after(ctx, cam, rp, me)) != DRT_OK) return rc;
     // (the plain image is the kernel's last set, the context's own parameters: one set more)
     const int n_int = n_sets + (out_rgb ? 1 : 0);
     if (n_int > DRT_HIP_MAX_PARAM_SETS)
-        return no(DRT_ERR_UNSUPPORTED, "out_rgb beside 8 sets (the plain image takes one of the kernel's eight: drt_hip_render gives it)");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    // the sets -> pinned memory -> [parameters | P_1 | ... | P_K] on the device, in stream order: drt_hip_render_tangent's double buffer
-    // and events (the copy this call rewrites was read by the launch of the call before the previous one)
+        return refuse(ctx, me, DRT_ERR_UNSUPPORTED, "out_rgb beside 8 sets (the plain image takes one of the kernel's eight: drt_hip_render gives it)");
+    // (sets at and above n_sets, up to the kernel's width, are the context's own parameters; the last one is the plain image's)
     const int K = n_int <= 2 ? 2 : (n_int <= 4 ? 4 : 8);
-    const int hb = (int)(ctx->tangent_calls++ & 1);
-    const size_t need = (size_t)n_sets * (size_t)(n_user ? n_user : 1);
-    if (!ctx->ev_tangent[hb])
-        HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_tangent[hb], hipEventDisableTiming));
-    else
-        HIPCHK(ctx, hipEventSynchronize(ctx->ev_tangent[hb]));
-    if (ctx->h_tangent_cap[hb] < need) {
-        if (ctx->h_tangent[hb])
-            (void)hipHostFree(ctx->h_tangent[hb]);
-        ctx->h_tangent[hb] = nullptr;
-        ctx->h_tangent_cap[hb] = 0;
-        HIPCHK(ctx, hipHostMalloc((void**)&ctx->h_tangent[hb], need * sizeof(double)));
-        ctx->h_tangent_cap[hb] = need;
-    }
-    memcpy(ctx->h_tangent[hb], param_sets, (size_t)n_sets * (size_t)n_user * sizeof(double));
-    int rc;
-    if ((rc = ensure(ctx, ctx->tangent, (size_t)(n_all ? n_all : 1) * (size_t)(1 + K) * sizeof(double))) != DRT_OK) return rc;
-    if (n_all > 0) {
-        const unsigned blocks = (unsigned)((n_all + DRT_BLOCK - 1) / DRT_BLOCK);
-        if (rp->flags & DRT_RENDER_F64)
-            hipLaunchKernelGGL(k_stage_param_sets<double>, dim3(blocks), dim3(DRT_BLOCK), 0, ctx->stream, (const double*)ctx->d_params_d, n_all,
-                               (const double*)ctx->h_tangent[hb], n_user, (int)n_sets, K, (double*)ctx->tangent.p);
-        else
-            hipLaunchKernelGGL(k_stage_param_sets<float>, dim3(blocks), dim3(DRT_BLOCK), 0, ctx->stream, (const float*)ctx->d_params_f, n_all,
-                               (const double*)ctx->h_tangent[hb], n_user, (int)n_sets, K, (float*)ctx->tangent.p);
-        HIPCHK(ctx, hipGetLastError());
-    }
-    HIPCHK(ctx, hipEventRecord(ctx->ev_tangent[hb], ctx->stream));
+    if ((rc = stage_rows(ctx, rp, param_sets, n_sets, K, true)) != DRT_OK) return rc;
+    const bool dev = (rp->flags & DRT_RENDER_DEVICE_OUT) != 0;
+    const size_t npix = (size_t)cam->width * (size_t)cam->height;
     // the caller's images: device pointers as they are; host buffers through buffers of the context's own
     ParamSetsRequest q;
     q.n_sets = n_sets;
@@ -742,6 +671,7 @@ static int render_param_sets_common(drt_hip_ctx* ctx, const drt_camera_desc* cam
     if (q.d_loss)
         HIPCHK(ctx, hipMemsetAsync(q.d_loss, 0, (size_t)n_sets * 3 * sizeof(double), ctx->stream));
     TangentRequest req;
+    req.kind = TangentRequest::Kind::param_sets;
     req.d_params = ctx->tangent.p;
     req.sets = &q;
     if ((rc = render_common(ctx, cam, rp, nullptr, out_rgb, nullptr, stats, -1, nullptr, &req)) != DRT_OK)

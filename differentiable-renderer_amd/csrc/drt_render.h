@@ -61,7 +61,7 @@ static int render_launch(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt
     j.adjoint_rgb = adjoint_rgb; j.out_rgb = out_rgb; j.out_param_grad = out_param_grad; j.out_gimg = out_gimg;
     j.stats = stats;
     j.gimg_param = gimg_param;
-    j.tangent = tangent != nullptr && !tangent->neq && !tangent->sets;
+    j.tangent = tangent != nullptr && tangent->kind == TangentRequest::Kind::forward;
     j.n_shards = n_shards; j.shard = n_shards > 1 ? rp->shard : 0; j.band = band;
     j.backward = (rp->flags & DRT_RENDER_BACKWARD) != 0;
     j.dev_out = (rp->flags & DRT_RENDER_DEVICE_OUT) != 0;

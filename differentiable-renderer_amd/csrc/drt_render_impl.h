@@ -1234,36 +1234,39 @@ int render_impl(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_p
     s.st = st; s.n_local_pixels = n_local_pixels; s.D = depth_cap; s.film = film; s.gimg_param = gimg_param; s.gfilm = gfilm;
     s.d_out_gimg = d_out_gimg;
     s.d_scene = sizeof(R) == 4 ? (const DevScene<R>*)ctx->d_scene_f : (const DevScene<R>*)ctx->d_scene_d;
-    s.d_params = sizeof(R) == 4 ? (const R*)ctx->d_params_f : (const R*)ctx->d_params_d;
     memcpy(&s.bvh, sizeof(R) == 4 ? (const void*)&ctx->bvh_f : (const void*)&ctx->bvh_d, sizeof s.bvh);
-    s.neq = tangent ? tangent->neq : nullptr;
-    s.fwd_tangent = tangent != nullptr && !s.neq;
-    s.keep_sums = s.fwd_tangent && tangent->keep_sums;
-    s.sets = tangent ? tangent->sets : nullptr;
-    s.fwd_tangent = s.fwd_tangent && !s.sets;
-    s.keep_sums = s.keep_sums && !s.sets;
-    s.n_dirs = s.neq ? tangent->n_dirs : (s.sets ? s.sets->n_sets : 0);
-    if (s.fwd_tangent || s.n_dirs > 0)
-        s.d_params = (const R*)tangent->d_params;
+    // the request, decoded: what the shard is told, and what the plan below has to come to for the request's form
+    using Kind = TangentRequest::Kind;
+    const bool forward = tangent && tangent->kind == Kind::forward, jacobian = tangent && tangent->kind == Kind::jacobian,
+               directions = tangent && tangent->kind == Kind::directions, param_sets = tangent && tangent->kind == Kind::param_sets;
+    s.fwd_tangent = forward;
+    s.keep_sums = forward && tangent->keep_sums;
+    s.neq = jacobian || directions ? tangent->neq : nullptr;
+    s.sets = param_sets ? tangent->sets : nullptr;
+    s.n_dirs = directions ? tangent->n_dirs : (param_sets ? tangent->sets->n_sets : 0);
+    s.d_params = forward || directions || param_sets ? (const R*)tangent->d_params
+                                                     : (sizeof(R) == 4 ? (const R*)ctx->d_params_f : (const R*)ctx->d_params_d);
     shard_plan(s);
-    if (s.sets && (!s.use_path || s.mesh_path || !s.path_finish || s.path.op != PathOp::param_sets))
-        return fail(ctx, DRT_ERR_UNSUPPORTED, "param sets: they come from the one-launch path kernel's parameter-set form over the whole shard in one batch, "
-                                              "which this render does not take (a DRT_HIP_* setting that forces the queue wavefront or a batch size, paths "
-                                              "that end at depth 0, or a scene its intersection program does not cover)");
-    if (s.fwd_tangent && s.D > 0 && (!s.use_path || s.mesh_path))
+    if (forward && s.D > 0 && (!s.use_path || s.mesh_path))
         return fail(ctx, DRT_ERR_UNSUPPORTED, s.mesh_path || ctx->has_mesh
                         ? "render_tangent: no tangent image of a scene that holds a triangle mesh"
                         : "render_tangent: the tangent image comes from the one-launch path kernel, which this render does not take "
                           "(bounces_per_launch >= 1, DRT_RENDER_UNFUSED, a DRT_HIP_* setting that forces the queue wavefront, or a scene its "
                           "intersection program does not cover)");
-    if (s.neq && s.n_dirs > 0 && (!s.use_path || s.mesh_path || !s.path_finish || s.path.op != PathOp::tangents))
-        return fail(ctx, DRT_ERR_UNSUPPORTED, "tangents / normal equations along: they come from the one-launch path kernel's K-direction form over the whole "
-                                              "shard in one batch, which this render does not take (a DRT_HIP_* setting that forces the queue wavefront or a "
-                                              "batch size, more than 2^31 camera samples, or a scene its intersection program does not cover)");
-    if (s.neq && s.n_dirs <= 0 && (!s.use_path || s.mesh_path || !s.path_finish || s.path.op != PathOp::jacobian))
-        return fail(ctx, DRT_ERR_UNSUPPORTED, "normal equations: they come from the one-launch path kernel's Jacobian form over the whole shard in one "
-                                              "batch, which this render does not take (a DRT_HIP_* setting that forces the queue wavefront or a batch size, "
-                                              "more than 2^31 camera samples, or a scene its intersection program does not cover)");
+    if (jacobian || directions || param_sets) {
+        const PathOp op = jacobian ? PathOp::jacobian : (directions ? PathOp::tangents : PathOp::param_sets);
+        if (!s.use_path || s.mesh_path || !s.path_finish || s.path.op != op)
+            return fail(ctx, DRT_ERR_UNSUPPORTED,
+                        jacobian ? "normal equations: they come from the one-launch path kernel's Jacobian form over the whole shard in one "
+                                   "batch, which this render does not take (a DRT_HIP_* setting that forces the queue wavefront or a batch size, "
+                                   "more than 2^31 camera samples, or a scene its intersection program does not cover)"
+                        : directions ? "tangents / normal equations along: they come from the one-launch path kernel's K-direction form over the whole "
+                                       "shard in one batch, which this render does not take (a DRT_HIP_* setting that forces the queue wavefront or a "
+                                       "batch size, more than 2^31 camera samples, or a scene its intersection program does not cover)"
+                                     : "param sets: they come from the one-launch path kernel's parameter-set form over the whole shard in one batch, "
+                                       "which this render does not take (a DRT_HIP_* setting that forces the queue wavefront or a batch size, paths "
+                                       "that end at depth 0, or a scene its intersection program does not cover)");
+    }
     if (!ctx->user_header.empty()) {
         // caller-defined shape kinds live in the one-launch path kernel hiprtc compiles for the scene, nowhere else
         if (ctx->jit_mode <= 0)
