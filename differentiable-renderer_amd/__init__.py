@@ -45,6 +45,7 @@ K_RAYGEN, K_INTERSECT, K_SHADE, K_FILM, K_BACKWARD, K_GRADREDUCE, K_INTERSECT_ME
 KERNEL_NAMES = ["raygen", "intersect", "shade", "film", "backward", "gradreduce", "intersect_mesh", "path"]
 MAX_DIRS = 8                 # DRT_HIP_MAX_DIRS: directions per render_tangents / render_normal_equations_along call
 MAX_PARAM_SETS = 8           # DRT_HIP_MAX_PARAM_SETS: parameter sets per render_param_sets call
+MAX_SETS_ALONG = 4           # DRT_HIP_MAX_SETS_ALONG: parameter sets with a direction each per render_param_sets_along call
 ABI_VERSION = 8
 UNIQUE_ID_BYTES = 128
 
@@ -734,12 +735,31 @@ def check_param_sets(sets, n_params: int) -> np.ndarray:
     return v
 
 
+def check_param_sets_along(sets, tangents, n_params: int):
+    """K parameter sets and their K directions as drt_hip_render_param_sets_along takes them: float64 [K, n_params, 3] each,
+    1 <= K <= MAX_SETS_ALONG, finite values.  Raises ValueError otherwise (what the library would refuse, said before the call)."""
+    v = np.ascontiguousarray(sets, dtype=np.float64)
+    t = np.ascontiguousarray(tangents, dtype=np.float64)
+    if v.ndim != 3 or v.shape[1:] != (n_params, 3):
+        raise ValueError(f"param sets along: expected sets of shape [n_sets, {n_params}, 3], got {list(v.shape)}")
+    if t.shape != v.shape:
+        raise ValueError(f"param sets along: expected directions of shape {list(v.shape)}, got {list(t.shape)}")
+    if not 1 <= v.shape[0] <= MAX_SETS_ALONG:
+        raise ValueError(f"param sets along: n_sets = {v.shape[0]} outside 1 ... MAX_SETS_ALONG = {MAX_SETS_ALONG}")
+    if not np.isfinite(v).all():
+        raise ValueError("param sets along: a set holds a value that is not finite")
+    if not np.isfinite(t).all():
+        raise ValueError("param sets along: a direction holds a value that is not finite")
+    return v, t
+
+
 _ABI_SYMBOLS = ["drt_hip_abi_version", "drt_hip_device_count", "drt_hip_create", "drt_hip_create_group",
                 "drt_hip_group_size", "drt_hip_device_pci_bus_id", "drt_hip_destroy",
                 "drt_hip_comm_unique_id", "drt_hip_comm_init_rank", "drt_hip_comm_size", "drt_hip_comm_destroy",
                 "drt_hip_upload_scene", "drt_hip_update_params", "drt_hip_set_specialisation", "drt_hip_render", "drt_hip_render_async", "drt_hip_wait",
                 "drt_hip_render_gradient_image", "drt_hip_render_tangent", "drt_hip_render_tangent_double", "drt_hip_render_normal_equations", "drt_hip_render_tangents",
-                "drt_hip_render_normal_equations_along", "drt_hip_render_param_sets", "drt_hip_render_param_sets_double", "drt_hip_pin_host", "drt_hip_unpin_host", "drt_hip_stream",
+                "drt_hip_render_normal_equations_along", "drt_hip_render_param_sets", "drt_hip_render_param_sets_double",
+                "drt_hip_render_param_sets_along", "drt_hip_render_param_sets_along_double", "drt_hip_pin_host", "drt_hip_unpin_host", "drt_hip_stream",
                 "drt_hip_synchronize", "drt_hip_last_error", "drt_hip_kernel_name"]
 
 
@@ -787,6 +807,10 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.drt_hip_render_param_sets.argtypes = [C.c_void_p, C.POINTER(CameraDesc), C.POINTER(RenderParamsDesc), C.c_int32, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(HipStats)]
     lib.drt_hip_render_param_sets_double.argtypes = lib.drt_hip_render_param_sets.argtypes
+    lib.drt_hip_render_param_sets_along.argtypes = [C.c_void_p, C.POINTER(CameraDesc), C.POINTER(RenderParamsDesc), C.c_int32, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.POINTER(HipStats)]
+    lib.drt_hip_render_param_sets_along_double.argtypes = lib.drt_hip_render_param_sets_along.argtypes
     lib.drt_hip_pin_host.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
     lib.drt_hip_unpin_host.argtypes = [C.c_void_p, C.c_void_p]
     lib.drt_hip_stream.argtypes = [C.c_void_p]
@@ -1187,6 +1211,55 @@ class HipRenderer:
                                                 C.c_void_p(out_loss_ptr or None), C.c_void_p(out_rgb_ptr or None),
                                                 C.byref(stats) if want_stats else None)
         self._check(rc, "drt_hip_render_param_sets")
+        return stats.as_dict() if want_stats else {}
+
+    def render_param_sets_along(self, cam: Camera, rp: RenderParams, sets: np.ndarray, tangents: np.ndarray,
+                                target: Optional[np.ndarray] = None, f64: bool = False, double: bool = False, images: bool = True,
+                                timing: bool = False) -> dict:
+        """drt_hip_render_param_sets_along: the frame under the K <= MAX_SETS_ALONG parameter vectors `sets`, each with its own direction
+        `tangents[k]` ([K, n_params, 3] both), in ONE trace; the context's own parameters stay what they are.
+        -> {"images", "tangents" [K,H,W,3] float32 (double=True: float64, the means as the device formed them) or None,
+            "loss" = sum r_k^2, "dloss" = sum 2 r_k (J d_k) ([K,3] float64 over this shard's pixels, r_k = mean_k - target; None without a
+            target), "curv" = sum (J d_k)^2 [K,3] float64, "stats"}"""
+        assert self.scene is not None
+        v, t = check_param_sets_along(sets, tangents, self.scene.n_params)
+        K = v.shape[0]
+        cd, d, stats = self._begin(cam, rp, self._host_flags(rp, f64, timing))
+        t_ptr = None
+        if target is not None:
+            target = np.ascontiguousarray(target, dtype=np.float32)
+            if target.shape != (cam.height, cam.width, 3):
+                raise ValueError(f"param sets along: expected a target of shape {[cam.height, cam.width, 3]}, got {list(target.shape)}")
+            t_ptr = target.ctypes.data_as(C.c_void_p)
+        dt = np.float64 if double else np.float32
+        imgs = np.zeros((K, cam.height, cam.width, 3), dtype=dt) if images else None
+        timgs = np.zeros((K, cam.height, cam.width, 3), dtype=dt) if images else None
+        loss = np.zeros((K, 3), dtype=np.float64) if target is not None else None
+        dloss = np.zeros((K, 3), dtype=np.float64) if target is not None else None
+        curv = np.zeros((K, 3), dtype=np.float64)
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+        fn = self.lib.drt_hip_render_param_sets_along_double if double else self.lib.drt_hip_render_param_sets_along
+        rc = fn(self.ctx, C.byref(cd), C.byref(d), K, ptr(v), ptr(t), t_ptr, ptr(imgs), ptr(timgs), ptr(loss), ptr(dloss), ptr(curv),
+                C.byref(stats))
+        self._check(rc, "drt_hip_render_param_sets_along")
+        return {"images": imgs, "tangents": timgs, "loss": loss, "dloss": dloss, "curv": curv, "stats": stats.as_dict()}
+
+    def render_param_sets_along_device(self, cam: Camera, rp: RenderParams, sets: np.ndarray, tangents: np.ndarray, out_images_ptr: int = 0,
+                                       out_tangents_ptr: int = 0, out_loss_ptr: int = 0, out_dloss_ptr: int = 0, out_curv_ptr: int = 0,
+                                       target_ptr: int = 0, f64: bool = False, timing: bool = False, sync: bool = False,
+                                       want_stats: Optional[bool] = None) -> dict:
+        """drt_hip_render_param_sets_along on device pointers (images float32 [K,H,W,3], target float32 [H,W,3], sums float64 [K,3]),
+        enqueued on the context's stream; the sets and directions are host memory."""
+        want_stats = timing if want_stats is None else want_stats
+        assert self.scene is not None
+        v, t = check_param_sets_along(sets, tangents, self.scene.n_params)
+        cd, d, stats = self._begin(cam, rp, self._device_flags(rp, f64, timing, sync))
+        rc = self.lib.drt_hip_render_param_sets_along(self.ctx, C.byref(cd), C.byref(d), v.shape[0], v.ctypes.data_as(C.c_void_p),
+                                                      t.ctypes.data_as(C.c_void_p), C.c_void_p(target_ptr or None),
+                                                      C.c_void_p(out_images_ptr or None), C.c_void_p(out_tangents_ptr or None),
+                                                      C.c_void_p(out_loss_ptr or None), C.c_void_p(out_dloss_ptr or None),
+                                                      C.c_void_p(out_curv_ptr or None), C.byref(stats) if want_stats else None)
+        self._check(rc, "drt_hip_render_param_sets_along")
         return stats.as_dict() if want_stats else {}
 
     def render_device(self, cam: Camera, rp: RenderParams, out_rgb_ptr: int, out_grad_ptr: int,

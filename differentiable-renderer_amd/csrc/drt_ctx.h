@@ -31,6 +31,12 @@ struct ParamSetsRequest {
     float* d_images = nullptr;            // n_sets x H x W x 3, or none
     double* d_images64 = nullptr;         // ... the means in double (drt_hip_render_param_sets_double), or none
     double* d_loss = nullptr;             // n_sets x 3, or none (needs d_target)
+    // drt_hip_render_param_sets_along: every set has a direction -- k_sets_along_finish in place of k_sets_finish
+    bool along = false;
+    float* d_tangents = nullptr;          // n_sets x H x W x 3: the derivative of image k along direction k, or none
+    double* d_tangents64 = nullptr;       // ... in double, or none
+    double* d_dloss = nullptr;            // n_sets x 3: 2 <r_k, J d_k>, or none (needs d_target)
+    double* d_curv = nullptr;             // n_sets x 3: |J d_k|^2, or none
 };
 // A render on one of the path kernel's special forms, as render_common / render_launch / render_impl are told about it: which form, and what
 // that form reads.  render_impl decodes it, in one place
@@ -40,6 +46,7 @@ struct TangentRequest {
         jacobian,                         // the normal equations of a frame (drt_hip_render_normal_equations): neq
         directions,                       // ... in the span of K directions (drt_hip_render_tangents / _normal_equations_along): d_params, neq, n_dirs
         param_sets,                       // one frame under K parameter sets (drt_hip_render_param_sets): d_params, sets
+        param_sets_along,                 // ... each with a direction (drt_hip_render_param_sets_along): d_params, sets (sets->along)
     } kind = Kind::forward;
     const void* d_params = nullptr;       // the path kernel's `params`, in the render's compute type: [the scene's parameters | row_1 | ... | row_K],
                                           // the rows padded up to an instantiated width K (stage_rows, drt_hip.hip)

@@ -595,6 +595,83 @@ struct Tangents<R, DRT_NP_SETS, NC> {
     }
 };
 
+// ---- ... each set with a DIRECTION of its own (NP = DRT_NP_SETS_ALONG, NC = K in {2, 4}; drt_hip_render_param_sets_along) ---------
+// The product of the two forms above: one ray, one key, one hit, one m_k, and per set k the forward-mode form's state on set k's own
+// operands -- the throughput T_k WITHOUT its zero factors, their counts zc_k (per set: the sets differ in which channels are zero), the sums
+// S_k of d_k / c_k and Z_k of d_k over the zero channels, the radiance L_k (T_k masked by zc_k: a channel that met a zero is dark) and the
+// derivative dL_k of the current path along d_k.  Every per-set operation is the single-direction form's (Tangents<R, DRT_NP_TANGENT, 0>) on
+// that set's operands in its order: set k's sums see neither its companions nor the width.  Tables in dynamic shared memory, per set k and
+// sized by the SCENE's parameter count n, in units of R --
+//     colnz_k[n + 1], dlog_k[n + 1], dzero_k[n + 1]     rows of four: P_k with zero channels replaced by 1 | zero-count increments (pid_pack),
+//                                                       d_k / P_k, and d_k where the channel is zero; row n: the rest row (1, 1, 1), zeros
+//     par_k[3 n], dir_k[3 n]                            P_k and d_k themselves, for the lights (an emission is used as it is, zeros included)
+// staged from [params | P_1 | d_1 | ... | P_K | d_K] behind the kernel's `params`.  Lockstep form only (a lane is a pixel): at the end of its
+// sample range a lane writes 6 sums per set in the Jacobian form's layout, gpix[range][6 k + ch][pixel] (radiance) and
+// gpix[range][6 k + 3 + ch][pixel] (derivative), for k below the caller's count (PathArgs::dirs_out()).
+#define DRT_NP_SETS_ALONG (-4)
+// blocks per CU (= waves per SIMD) of the f32 forms: the most that stay free of scratch (the compiler's report, DESIGN.md 9b: 121-128 registers
+// at K = 2, 169-175 at K = 4; a block more spills 88 and 8 bytes per lane).  K = 8 was built and is not kept: 301 registers at one block per
+// CU in f32, and its glossy f64 form spills at any budget
+#ifndef DRT_SETS_ALONG2_MIN_BLOCKS
+#define DRT_SETS_ALONG2_MIN_BLOCKS 4
+#endif
+#ifndef DRT_SETS_ALONG4_MIN_BLOCKS
+#define DRT_SETS_ALONG4_MIN_BLOCKS 2
+#endif
+__host__ __device__ inline uint32_t sets_along_set_words(uint32_t n) { return 3u * (n + 1u) * 4u + 6u * n; }
+__host__ __device__ inline uint32_t sets_along_table_words(uint32_t n, uint32_t K) { return K * sets_along_set_words(n); }
+template <typename R, int K, typename SL>
+__device__ inline void stage_sets_along(R* __restrict__ tab, const SL& lds, const R* __restrict__ params)
+{
+    // (after stage_path_scene's barrier)
+    const int n = lds.sc.n_params < DRT_PATH_LDS_PARAMS ? lds.sc.n_params : DRT_PATH_LDS_PARAMS;
+    const int stride = (n + 1) * 4, words = (int)sets_along_set_words((uint32_t)n);
+    for (int i = threadIdx.x; i < K * (n + 1); i += blockDim.x) {
+        const int k = i / (n + 1), p = i - k * (n + 1);
+        const bool in = p < n;
+        const R* P = params + ((size_t)(1 + 2 * k) * lds.sc.n_params + p) * 3;
+        const R* D = params + ((size_t)(2 + 2 * k) * lds.sc.n_params + p) * 3;
+        R* set = tab + (size_t)k * words;
+        uint32_t zinc = 0;
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            const R c = in ? P[ch] : R(1);
+            const R v = in ? D[ch] : R(0);
+            const bool zero = abs_r(c) < R(1e-18);
+            set[p * 4 + ch] = zero ? R(1) : c;
+            set[stride + p * 4 + ch] = zero ? R(0) : v / c;
+            set[2 * stride + p * 4 + ch] = zero ? v : R(0);
+            zinc |= zero ? 1u << (8 * ch) : 0u;
+            if (in) {
+                set[3 * stride + p * 3 + ch] = c;
+                set[3 * stride + 3 * n + p * 3 + ch] = v;
+            }
+        }
+        set[p * 4 + 3] = pid_pack(R(0), zinc);
+        set[stride + p * 4 + 3] = R(0);
+        set[2 * stride + p * 4 + 3] = R(0);
+    }
+    __syncthreads();
+}
+
+template <typename R, int NC>
+struct Tangents<R, DRT_NP_SETS_ALONG, NC> {
+    V3<R> T[NC], L[NC];             // per set: prefix throughput (zero factors left out) and radiance of the current path
+    V3<R> S[NC], Z[NC], dL[NC];     // ... sums of d / c and of d (zero channels) over its vertices, its derivative along the set's direction
+    uint32_t zc[NC];                // ... zero factors met per channel, 8 bits each
+    const R* tab;                   // the block's tables (see above)
+    uint32_t rest, stride, words;   // the rest row = the scene's parameter count; words of one table of rows, of one set
+    __device__ inline void new_path()
+    {
+#pragma unroll
+        for (int k = 0; k < NC; ++k) {
+            T[k] = mk<R>(R(1), R(1), R(1));
+            L[k] = S[k] = Z[k] = dL[k] = mk<R>(R(0), R(0), R(0));
+            zc[k] = 0;
+        }
+    }
+};
+
 // what a block of a general-form kernel keeps in LDS, and the two ends of its life
 template <typename R>
 struct GenBlock {
@@ -690,6 +767,25 @@ __device__ inline void add_emission(const SL& lds, const TangentLds<R>& tl, cons
             const R* e = er + (uint32_t)k * tg.stride;
             const V3<R> Ek = mk<R>(e[0], e[1], e[2]) * inv_pk;
             tg.L[k] = tg.L[k] + tg.T[k] * Ek;
+        }
+    } else if constexpr (NP == DRT_NP_SETS_ALONG) {
+        // K sets, a direction each: the single-direction forward case below, once per set on the set's own emission, its tangent, T, zc, S, Z
+        const uint32_t er = 3u * tg.stride + (eid < tg.rest ? eid : 0u) * 3u;
+#pragma unroll
+        for (int k = 0; k < NC; ++k) {
+            const R* e = tg.tab + (uint32_t)k * tg.words + er;
+            const R* vd = e + 3u * tg.rest;
+            const V3<R> Tk = tg.T[k];
+            const V3<R> Ek = mk<R>(e[0], e[1], e[2]) * inv_pk;
+            const uint32_t zx = tg.zc[k] & 0xFFu, zy = tg.zc[k] & 0xFF00u, zz = tg.zc[k] & 0xFF0000u;
+            const V3<R> Tr = mk<R>(zx ? R(0) : Tk.x, zy ? R(0) : Tk.y, zz ? R(0) : Tk.z);
+            tg.L[k] = tg.L[k] + Tr * Ek;
+            const V3<R> Ed = mk<R>(vd[0], vd[1], vd[2]) * inv_pk;
+            const V3<R> d0 = mk<R>(fma_r(Ek.x, tg.S[k].x, Ed.x), fma_r(Ek.y, tg.S[k].y, Ed.y), fma_r(Ek.z, tg.S[k].z, Ed.z));
+            const V3<R> d1 = Ek * tg.Z[k];
+            tg.dL[k] = mk<R>(fma_r(Tk.x, zx == 0u ? d0.x : (zx == 0x1u ? d1.x : R(0)), tg.dL[k].x),
+                             fma_r(Tk.y, zy == 0u ? d0.y : (zy == 0x100u ? d1.y : R(0)), tg.dL[k].y),
+                             fma_r(Tk.z, zz == 0u ? d0.z : (zz == 0x10000u ? d1.z : R(0)), tg.dL[k].z));
         }
     } else {
         const V3<R> E = load_param<R, (NP != 0)>(lds, params, (int)eid) * inv_pk;
@@ -896,6 +992,19 @@ __device__ inline void path_bounce(const PathArgs& a, const PathSceneLds<R>& lds
             const R* rec = tg.tab + (uint32_t)k * tg.stride + row;
             tg.T[k] = tg.T[k] * (mk<R>(rec[0], rec[1], rec[2]) * mm);
         }
+    } else if constexpr (NP == DRT_NP_SETS_ALONG) {
+        // K sets, a direction each: set k's three rows -- its colour, d / c, d (zero channels) -- move its T, zc, S and Z as the forward-mode
+        // form moves its own; a lane that stops reads the rest row and m = 1
+        const uint32_t row = (alive && cid < tg.rest ? cid : tg.rest) * 4u;
+        const R mm = alive ? mk_ : R(1);
+#pragma unroll
+        for (int k = 0; k < NC; ++k) {
+            const R *rec = tg.tab + (uint32_t)k * tg.words + row, *ds = rec + tg.stride, *dz = ds + tg.stride;
+            tg.T[k] = tg.T[k] * (mk<R>(rec[0], rec[1], rec[2]) * mm);
+            tg.zc[k] += pid_unpack(rec[3]);
+            tg.S[k] = mk<R>(tg.S[k].x + ds[0], tg.S[k].y + ds[1], tg.S[k].z + ds[2]);
+            tg.Z[k] = mk<R>(tg.Z[k].x + dz[0], tg.Z[k].y + dz[1], tg.Z[k].z + dz[2]);
+        }
     } else {
         const int cidx = DIR ? (alive ? (int)cid : DRT_PATH_LDS_PARAMS) : (REST ? (alive ? (int)cid : DRT_TANGENT_REST) : (has_bxdf ? (int)cid : 0));
         V3<R> col;
@@ -1027,6 +1136,8 @@ __device__ inline uint32_t path_camera(const PathArgs& a, const CameraLane<R>& c
 template <size_t RB, bool SPEC, int NP, int NSG, bool REGEN, int NCR = 0>
 constexpr int path_min_blocks()
 {
+    if (NP == DRT_NP_SETS_ALONG)   // K parameter sets with a direction each, lockstep: sixteen values and six fp64 sums per set beside the forward-only kernel's
+        return RB == 4 ? (DRT_NC_OF(NCR) <= 2 ? DRT_SETS_ALONG2_MIN_BLOCKS : DRT_SETS_ALONG4_MIN_BLOCKS) : (DRT_NC_OF(NCR) <= 2 && !SPEC ? 2 : 1);
     if (NP == DRT_NP_SETS)         // K parameter sets, lockstep: six values and three fp64 sums per set beside the forward-only kernel's
         return RB == 4 ? (DRT_NC_OF(NCR) <= 2 ? DRT_SETS2_MIN_BLOCKS : (DRT_NC_OF(NCR) <= 4 ? DRT_SETS4_MIN_BLOCKS : DRT_SETS8_MIN_BLOCKS))
                        : (DRT_NC_OF(NCR) <= 2 ? (SPEC ? 2 : 3) : (DRT_NC_OF(NCR) <= 4 ? 2 : 1));
@@ -1082,12 +1193,14 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
     static_assert(!(DIRS && REGEN), "the K-direction form is a lockstep form: a lane is a pixel");
     constexpr bool SETS = NP == DRT_NP_SETS;              // one path under NC parameter sets: tables in dynamic shared memory (see stage_sets)
     static_assert(!(SETS && (REGEN || NC < 1)), "the parameter-set form is a lockstep form of K >= 1 sets: a lane is a pixel");
+    constexpr bool ALONG = NP == DRT_NP_SETS_ALONG;       // ... each set with a direction of its own (see stage_sets_along)
+    static_assert(!(ALONG && (REGEN || NC < 1)), "the parameter-set form with directions is a lockstep form of K >= 1 sets: a lane is a pixel");
     __shared__ typename PickT<(DIR && !DIRS), DirLds<R>, NoLds>::T s_dir;
     if constexpr (GEN)
         gen_zero(s_gen);
     stage_path_scene(lds, sc, params);
     const TangentLds<R>& tl = s_tl;
-    if (NC > 0 && !GEN && !DIR && !SETS)
+    if (NC > 0 && !GEN && !DIR && !SETS && !ALONG)
         stage_tangents(s_tl, lds);
 
     const uint32_t lane = threadIdx.x & (DRT_WAVE - 1);
@@ -1100,7 +1213,7 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
 
     Tangents<R, NP, NC> tg;
     __shared__ R s_acc[NP > 0 ? NP * 3 : 1][DRT_BLOCK];
-    if constexpr (!SETS)
+    if constexpr (!SETS && !ALONG)
         tg.acc = &s_acc[0][threadIdx.x];
     if constexpr (GEN)
         gen_begin(s_gen, lds, sc, a, s_hist, reinterpret_cast<uint32_t*>(a.hist_ovf), tg);
@@ -1120,6 +1233,15 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
         tg.rest = (uint32_t)(lds.sc.n_params < DRT_PATH_LDS_PARAMS ? lds.sc.n_params : DRT_PATH_LDS_PARAMS);
         tg.stride = (tg.rest + 1u) * 4u;
         tg.new_path();
+    } else if constexpr (ALONG) {
+        extern __shared__ __attribute__((aligned(16))) unsigned char s_dirs[];
+        R* tab = reinterpret_cast<R*>(s_dirs);
+        stage_sets_along<R, NC>(tab, lds, params);
+        tg.tab = tab;
+        tg.rest = (uint32_t)(lds.sc.n_params < DRT_PATH_LDS_PARAMS ? lds.sc.n_params : DRT_PATH_LDS_PARAMS);
+        tg.stride = (tg.rest + 1u) * 4u;
+        tg.words = sets_along_set_words(tg.rest);
+        tg.new_path();
     } else if constexpr (DIR) {
         stage_dir(s_dir, lds, params);
         tg.dl = &s_dir;
@@ -1131,10 +1253,10 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
     }
     double fx = 0, fy = 0, fz = 0;                        // radiance sum of this lane's pixel over the range
     double tx = 0, ty = 0, tz = 0;                        // DIR: ... and the sum of its samples' derivatives
-    double tk[(DIRS || SETS) ? NC : 1][3];                // DIRS: ... per direction; SETS: the radiance sums per set
-    if constexpr (DIRS || SETS) {
+    double tk[(DIRS || SETS) ? NC : (ALONG ? 2 * NC : 1)][3];   // DIRS: ... per direction; SETS: the radiance sums per set; ALONG: radiance, derivative per set
+    if constexpr (DIRS || SETS || ALONG) {
 #pragma unroll
-        for (int k = 0; k < NC; ++k)
+        for (int k = 0; k < (ALONG ? 2 * NC : NC); ++k)
             tk[k][0] = tk[k][1] = tk[k][2] = 0.0;
     }
     uint32_t n_seg = 0, n_capped = 0;                     // wave-uniform counters
@@ -1214,6 +1336,13 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
             if (end_ids != DRT_ID_NONE)
                 add_emission<R, NP, NC, LOSS, PathSceneLds<R>, ROLES>(lds, tl, params, end_ids, end_inv_pk, T, g, L, tg);
         }
+        if constexpr (ALONG) {
+#pragma unroll
+            for (int k = 0; k < NC; ++k) {
+                tk[2 * k][0] += (double)tg.L[k].x; tk[2 * k][1] += (double)tg.L[k].y; tk[2 * k][2] += (double)tg.L[k].z;
+                tk[2 * k + 1][0] += (double)tg.dL[k].x; tk[2 * k + 1][1] += (double)tg.dL[k].y; tk[2 * k + 1][2] += (double)tg.dL[k].z;
+            }
+        } else
         if constexpr (SETS) {
 #pragma unroll
             for (int k = 0; k < NC; ++k) {
@@ -1378,6 +1507,16 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
 #pragma unroll
             for (int k = 0; k < NC; ++k)
                 if ((uint32_t)k < nd) {
+                    f[(size_t)(k * 3) * a.Pb] = tk[k][0]; f[(size_t)(k * 3 + 1) * a.Pb] = tk[k][1]; f[(size_t)(k * 3 + 2) * a.Pb] = tk[k][2];
+                }
+        }
+        if constexpr (ALONG) if (gimg_part && have) {
+            // K sets with a direction each: [range][6 k + ch][pixel] the radiance sums, [range][6 k + 3 + ch][pixel] the derivative sums
+            const uint32_t nd = a.dirs_out() < (uint32_t)NC ? a.dirs_out() : (uint32_t)NC;
+            double* f = gimg_part + ((size_t)range * (size_t)(nd * 6u)) * a.Pb + lp;
+#pragma unroll
+            for (int k = 0; k < 2 * NC; ++k)
+                if ((uint32_t)(k >> 1) < nd) {
                     f[(size_t)(k * 3) * a.Pb] = tk[k][0]; f[(size_t)(k * 3 + 1) * a.Pb] = tk[k][1]; f[(size_t)(k * 3 + 2) * a.Pb] = tk[k][2];
                 }
         }
@@ -2017,4 +2156,99 @@ k_sets_loss_finish(const double* __restrict__ part, int n_blocks, int n_values, 
     }
     if (threadIdx.x == 0 && v < n_values)
         out_loss[v] = red[0];
+}
+
+// ---- the images, losses, slopes and curvatures of a frame under K parameter sets with a direction each (drt_hip_render_param_sets_along) ----
+// Behind a launch of k_path's form of that name: spart[range][6 k + ch][pixel] holds, per pixel of the shard, set k's radiance sums over one
+// sample range and spart[range][6 k + 3 + ch][pixel] the sums of its derivative along d_k.  Per pixel, set and channel, in fp64: both sums
+// over the ranges in range order, the means m and t, the set's images (float and / or double, the layout of n_sets images) where the caller
+// wants them, and three running sums of the thread -- r r and 2 r t with the residual r = m - target (where there is a target), and t t:
+// the loss phi_k, its slope along d_k and the Gauss-Newton curvature |J d_k|^2 -- at most DRT_SETS_ALONG_VALUES = 9 DRT_HIP_MAX_SETS_ALONG of
+// them, value (3 k + ch) * 3 + {0, 1, 2}.  Then thread -> wave (shuffles) -> block (LDS) in a fixed order, one partial per block;
+// k_sets_along_sums adds the blocks in a fixed order.  No atomics: the same call gives the same bits.  k_sets_finish's structure and grid rule.
+#define DRT_SETS_ALONG_VALUES 36
+__global__ void __launch_bounds__(DRT_BLOCK)
+k_sets_along_finish(PathArgs a, const double* __restrict__ spart, int n_sets, const float* __restrict__ target, float* __restrict__ out_img,
+                    double* __restrict__ out_img64, float* __restrict__ out_tan, double* __restrict__ out_tan64, double* __restrict__ part)
+{
+    const size_t Pb = a.Pb, rows = (size_t)n_sets * 6, npix = (size_t)a.W * (size_t)a.H;
+    const double inv = 1.0 / (double)a.spp;
+    double acc[DRT_SETS_ALONG_VALUES];
+#pragma unroll
+    for (int v = 0; v < DRT_SETS_ALONG_VALUES; ++v)
+        acc[v] = 0.0;
+    for (uint32_t j = blockIdx.x * DRT_BLOCK + threadIdx.x; j < a.Pb; j += gridDim.x * DRT_BLOCK) {
+        const size_t gp = path_global_pixel(a, a.p0 + j);
+        double tg[3] = {0.0, 0.0, 0.0};
+        if (target) {
+            tg[0] = (double)target[gp * 3]; tg[1] = (double)target[gp * 3 + 1]; tg[2] = (double)target[gp * 3 + 2];
+        }
+#pragma unroll
+        for (int v = 0; v < DRT_SETS_ALONG_VALUES / 3; ++v)          // v = 3 k + ch
+            if (v < n_sets * 3) {
+                const size_t row = (size_t)(v / 3) * 6 + (size_t)(v % 3);
+                double sm = 0.0, st = 0.0;
+                for (uint32_t q = 0; q < a.n_ranges; ++q) {
+                    sm += spart[((size_t)q * rows + row) * Pb + j];
+                    st += spart[((size_t)q * rows + row + 3) * Pb + j];
+                }
+                const double m = sm * inv, t = st * inv;
+                const size_t at = ((size_t)(v / 3) * npix + gp) * 3 + (size_t)(v % 3);
+                if (out_img) out_img[at] = (float)m;
+                if (out_img64) out_img64[at] = m;
+                if (out_tan) out_tan[at] = (float)t;
+                if (out_tan64) out_tan64[at] = t;
+                if (target) {
+                    const double r = m - tg[v % 3];
+                    acc[v * 3] += r * r;
+                    acc[v * 3 + 1] += 2.0 * r * t;
+                }
+                acc[v * 3 + 2] += t * t;
+            }
+    }
+    if (!part)
+        return;
+    __shared__ double red[DRT_BLOCK / DRT_WAVE][DRT_SETS_ALONG_VALUES];
+    const int wv = threadIdx.x / DRT_WAVE;
+#pragma unroll
+    for (int v = 0; v < DRT_SETS_ALONG_VALUES; ++v) {
+        double s = acc[v];
+#pragma unroll
+        for (int o2 = DRT_WAVE / 2; o2 > 0; o2 >>= 1)
+            s += __shfl_down(s, o2);
+        if ((threadIdx.x & (DRT_WAVE - 1)) == 0)
+            red[wv][v] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < DRT_SETS_ALONG_VALUES) {
+        double s = 0;
+        for (int ww = 0; ww < DRT_BLOCK / DRT_WAVE; ++ww)
+            s += red[ww][threadIdx.x];
+        part[(size_t)blockIdx.x * DRT_SETS_ALONG_VALUES + threadIdx.x] = s;
+    }
+}
+
+// ... its second stage: block v adds value v's partials over k_sets_along_finish's blocks -- a strided sum per thread, then an LDS tree, both
+// in a fixed order -- into out_loss / out_dloss / out_curv [set][channel], whichever the caller gave
+__global__ void __launch_bounds__(DRT_BLOCK)
+k_sets_along_sums(const double* __restrict__ part, int n_blocks, int n_values, double* __restrict__ out_loss, double* __restrict__ out_dloss,
+                  double* __restrict__ out_curv)
+{
+    __shared__ double red[DRT_BLOCK];
+    const int v = (int)blockIdx.x;
+    double s = 0;
+    for (int b = threadIdx.x; b < n_blocks; b += DRT_BLOCK)
+        s += part[(size_t)b * DRT_SETS_ALONG_VALUES + v];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int off = DRT_BLOCK / 2; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off)
+            red[threadIdx.x] += red[threadIdx.x + off];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0 && v < n_values) {
+        double* out = v % 3 == 0 ? out_loss : (v % 3 == 1 ? out_dloss : out_curv);
+        if (out)
+            out[v / 3] = red[0];
+    }
 }

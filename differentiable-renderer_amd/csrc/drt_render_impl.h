@@ -151,10 +151,11 @@ inline int np_width(int n_params, int general)
 }
 
 // ---- which instantiation of the one-launch path kernels a render runs (shard_plan decides it, path_batch launches it) ----
-enum class PathOp { biased, unbiased, mesh, tangent, jacobian, tangents, param_sets };   // k_path (the gradient image included), k_path_unbiased, k_path_mesh, k_path's forward-mode form,
+enum class PathOp { biased, unbiased, mesh, tangent, jacobian, tangents, param_sets, param_sets_along };   // k_path (the gradient image included), k_path_unbiased, k_path_mesh, k_path's forward-mode form,
                                                                     // its Jacobian form (lockstep, parameters in columns: DRT_NC_JACOBIAN),
                                                                     // its K-direction forward form (lockstep, nc = K),
-                                                                    // its parameter-set form (lockstep, np = DRT_NP_SETS, nc = K)
+                                                                    // its parameter-set form (lockstep, np = DRT_NP_SETS, nc = K),
+                                                                    // ... with a direction per set (lockstep, np = DRT_NP_SETS_ALONG, nc = K)
 enum class PathProg { cornell, sorted, scene };  // closest-hit program: the reference's kinds compiled in (SigCornell), kinds read at
                                                  // run time (SigNone), or compiled by hiprtc for the scene's own KindSig (drt_jit.h)
 struct PathForm {
@@ -196,7 +197,7 @@ struct Shard {
     int neq_vw = 1;                 // ... pixels per lane (2: 16-byte loads, an even number of pixels)
     int n_dirs = 0;                 // ... > 0: its rows are directions -- k_path's K-direction forward form in place of the Jacobian form
     const ParamSetsRequest* sets = nullptr;   // drt_hip_render_param_sets: the parameter-set form, then k_sets_finish (n_dirs: the caller's sets)
-    int jac_rows() const { return (neq || sets) ? (n_dirs > 0 ? n_dirs : ctx->n_params) * 3 : 3; }   // rows a pixel's sums have in `gpix`
+    int jac_rows() const { return (neq || sets) ? (n_dirs > 0 ? n_dirs : ctx->n_params) * (sets && sets->along ? 6 : 3) : 3; }   // rows a pixel's sums have in `gpix`
     bool pixel_sums() const { return gimg_param >= 0 || fwd_tangent || neq || sets; }   // the lanes' per-pixel sums leave the path kernel (gimg_part)
     // the scene in compute type R
     const DevScene<R>* d_scene;
@@ -346,6 +347,10 @@ const void* library_path_kernel(const PathForm& f)
         return f.regen ? nullptr : with_int<2, 4, 8>(f.nc, [&](auto k) {
             return spec_sig([](auto spec, auto sg) { return (const void*)k_path<R, decltype(spec)::value, DRT_NP_SETS, decltype(k)::value, decltype(sg), false>; });
         });
+    if (f.op == PathOp::param_sets_along)  // ... each set with a direction: lockstep, every program
+        return f.regen ? nullptr : with_int<2, 4>(f.nc, [&](auto k) {
+            return spec_sig([](auto spec, auto sg) { return (const void*)k_path<R, decltype(spec)::value, DRT_NP_SETS_ALONG, decltype(k)::value, decltype(sg), false>; });
+        });
     if (f.op == PathOp::tangents)  // ... along K directions: lockstep, every program
         return f.regen ? nullptr : with_int<2, 4, 8>(f.nc, [&](auto k) {
             return spec_sig([](auto spec, auto sg) { return (const void*)k_path<R, decltype(spec)::value, DRT_NP_TANGENT, decltype(k)::value, decltype(sg), false>; });
@@ -452,6 +457,10 @@ void shard_plan(Shard<R>& s)
         f.op = PathOp::param_sets;
         f.np = DRT_NP_SETS;
         f.nc = s.sets->width;
+        if (s.sets->along) {
+            f.op = PathOp::param_sets_along;
+            f.np = DRT_NP_SETS_ALONG;
+        }
     }
     f.loss = s.loss_l2;
     // the slots' roles as the scene's records give them: for the form the headline runs -- diffuse, f32, lockstep, parameters in columns
@@ -604,7 +613,7 @@ int shard_buffers(Shard<R>& s)
         if (s.sets) {
             // k_sets_finish: k_normal_eq's grid rule, a pixel per thread
             s.neq_blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(((uint64_t)s.Pb + DRT_BLOCK - 1) / DRT_BLOCK, (uint64_t)ctx->n_cu * 4));
-            if ((rc = ensure(ctx, ctx->neq_part, (size_t)s.neq_blocks * DRT_SETS_VALUES * sizeof(double))) != DRT_OK) return rc;
+            if ((rc = ensure(ctx, ctx->neq_part, (size_t)s.neq_blocks * (s.sets->along ? DRT_SETS_ALONG_VALUES : DRT_SETS_VALUES) * sizeof(double))) != DRT_OK) return rc;
         }
         if (s.mesh_path) {   // the traversal stack's entries beyond the ones in LDS, per thread of the grid (one area per k_path stream)
             const size_t threads = ((s.path_waves + DRT_BLOCK / DRT_WAVE - 1) / (DRT_BLOCK / DRT_WAVE)) * DRT_BLOCK;
@@ -762,7 +771,7 @@ int path_batch(Shard<R>& s)
     pa.ct_step_f = (float)(2. * pa.tan_half * pa.inv_H);
     pa.gimg_param = s.gimg_param;
     pa.gen_rows = s.gen_rows; pa.gen_clog2 = s.gen_clog2;
-    if (s.path.op == PathOp::tangents || s.path.op == PathOp::param_sets)
+    if (s.path.op == PathOp::tangents || s.path.op == PathOp::param_sets || s.path.op == PathOp::param_sets_along)
         pa.set_dirs_out((uint32_t)s.n_dirs);       // (the K-direction / parameter-set form: the directions / sets whose sums leave the kernel)
     // the general form's vertex history: a word per four vertices and thread, in dynamic shared memory
     const bool gen = s.path_gen;
@@ -869,7 +878,11 @@ int path_batch(Shard<R>& s)
     // (the parameter-set form's: stage_sets -- 17.5 KB in f32, 35 KB in f64 at 136 parameters x 8 sets)
     const unsigned sets_bytes = form.op == PathOp::param_sets
         ? sets_table_words((uint32_t)std::min(ctx->n_params, DRT_PATH_LDS_PARAMS), (uint32_t)form.nc) * (unsigned)sizeof(R) : 0u;
-    const unsigned lds_bytes = form.op == PathOp::unbiased ? 0u : (form.op == PathOp::tangents ? dirs_bytes : (form.op == PathOp::param_sets ? sets_bytes : hist_bytes));
+    // (... with a direction per set: stage_sets_along -- 39 KB in f32, 79 KB in f64 at 136 parameters x 4 sets)
+    const unsigned along_bytes = form.op == PathOp::param_sets_along
+        ? sets_along_table_words((uint32_t)std::min(ctx->n_params, DRT_PATH_LDS_PARAMS), (uint32_t)form.nc) * (unsigned)sizeof(R) : 0u;
+    const unsigned lds_bytes = form.op == PathOp::unbiased ? 0u : (form.op == PathOp::tangents ? dirs_bytes : (form.op == PathOp::param_sets ? sets_bytes :
+                               (form.op == PathOp::param_sets_along ? along_bytes : hist_bytes)));
     if (jit)
         HIPCHK(ctx, hipModuleLaunchKernel(jit, (unsigned)gpath, 1, 1, DRT_BLOCK, 1, 1, lds_bytes, ks, args, nullptr));
     else
@@ -925,6 +938,22 @@ int path_batch(Shard<R>& s)
             st->units[DRT_K_GRADREDUCE] += (uint64_t)a.Pb;
             st->path_bytes += (uint64_t)pa.n_ranges * a.Pb * (uint64_t)s.jac_rows() * sizeof(double);
         }
+        if (s.sets && s.sets->along) {
+            // the sets' images, derivative images, losses, slopes and curvatures: per-pixel means and products reduced per block, then over the
+            // blocks (timed in the reduction's slot)
+            const ParamSetsRequest& q = *s.sets;
+            const bool sums = q.d_loss || q.d_dloss || q.d_curv;
+            double* part = (double*)ctx->neq_part.p;
+            DRT_TIMED(s, DRT_K_GRADREDUCE,
+                      hipLaunchKernelGGL(k_sets_along_finish, dim3(s.neq_blocks), dim3(DRT_BLOCK), 0, ctx->stream, pa, (const double*)gpix, s.n_dirs, q.d_target,
+                                         q.d_images, q.d_images64, q.d_tangents, q.d_tangents64, sums ? part : (double*)nullptr));
+            if (sums)
+                DRT_TIMED(s, DRT_K_GRADREDUCE,
+                          hipLaunchKernelGGL(k_sets_along_sums, dim3(DRT_SETS_ALONG_VALUES), dim3(DRT_BLOCK), 0, ctx->stream, (const double*)part, (int)s.neq_blocks,
+                                             s.n_dirs * 9, q.d_loss, q.d_dloss, q.d_curv));
+            st->units[DRT_K_GRADREDUCE] += (uint64_t)a.Pb;
+            st->path_bytes += (uint64_t)pa.n_ranges * a.Pb * (uint64_t)s.jac_rows() * sizeof(double);
+        } else
         if (s.sets) {
             // the sets' images and losses: per-pixel means and squared residuals reduced per block, then over the blocks (timed in the reduction's slot)
             const ParamSetsRequest& q = *s.sets;
@@ -1238,7 +1267,8 @@ int render_impl(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_p
     // the request, decoded: what the shard is told, and what the plan below has to come to for the request's form
     using Kind = TangentRequest::Kind;
     const bool forward = tangent && tangent->kind == Kind::forward, jacobian = tangent && tangent->kind == Kind::jacobian,
-               directions = tangent && tangent->kind == Kind::directions, param_sets = tangent && tangent->kind == Kind::param_sets;
+               directions = tangent && tangent->kind == Kind::directions, sets_along = tangent && tangent->kind == Kind::param_sets_along,
+               param_sets = (tangent && tangent->kind == Kind::param_sets) || sets_along;
     s.fwd_tangent = forward;
     s.keep_sums = forward && tangent->keep_sums;
     s.neq = jacobian || directions ? tangent->neq : nullptr;
@@ -1254,7 +1284,7 @@ int render_impl(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_p
                           "(bounces_per_launch >= 1, DRT_RENDER_UNFUSED, a DRT_HIP_* setting that forces the queue wavefront, or a scene its "
                           "intersection program does not cover)");
     if (jacobian || directions || param_sets) {
-        const PathOp op = jacobian ? PathOp::jacobian : (directions ? PathOp::tangents : PathOp::param_sets);
+        const PathOp op = jacobian ? PathOp::jacobian : (directions ? PathOp::tangents : (sets_along ? PathOp::param_sets_along : PathOp::param_sets));
         if (!s.use_path || s.mesh_path || !s.path_finish || s.path.op != op)
             return fail(ctx, DRT_ERR_UNSUPPORTED,
                         jacobian ? "normal equations: they come from the one-launch path kernel's Jacobian form over the whole shard in one "
@@ -1263,6 +1293,9 @@ int render_impl(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_p
                         : directions ? "tangents / normal equations along: they come from the one-launch path kernel's K-direction form over the whole "
                                        "shard in one batch, which this render does not take (a DRT_HIP_* setting that forces the queue wavefront or a "
                                        "batch size, more than 2^31 camera samples, or a scene its intersection program does not cover)"
+                        : sets_along ? "param sets along: they come from the one-launch path kernel's parameter-set form with directions over the whole "
+                                       "shard in one batch, which this render does not take (a DRT_HIP_* setting that forces the queue wavefront or a "
+                                       "batch size, paths that end at depth 0, or a scene its intersection program does not cover)"
                                      : "param sets: they come from the one-launch path kernel's parameter-set form over the whole shard in one batch, "
                                        "which this render does not take (a DRT_HIP_* setting that forces the queue wavefront or a batch size, paths "
                                        "that end at depth 0, or a scene its intersection program does not cover)");

@@ -14,6 +14,7 @@
 //   drt::hip::render_tangent(scene, cam, tracer, spp, {{param, direction}, ...}, img, tangent_img [, options])
 //   drt::hip::render_tangents(scene, cam, tracer, spp, {direction, ...}, img, tangent_imgs [, options])      up to 8 directions, one render
 //   drt::hip::render_param_sets(scene, cam, tracer, spp, {set, ...}, target, imgs, &losses [, options])      up to 8 parameter sets, one trace
+//   drt::hip::render_param_sets_along(scene, cam, tracer, spp, {set, ...}, target [, imgs, tangent_imgs, options])   up to 4 sets with a direction each: loss, slope, curvature
 //   drt::hip::normal_equations_along(scene, cam, tracer, spp, {direction, ...}, options, target_or_residual) Gauss-Newton in their span
 //   drt::hip::render(scene of Dual<U>, ...)
 //
@@ -1052,6 +1053,84 @@ inline Stats render_param_sets(const Scene<T>& scene, const Camera<T>& cam, cons
     if (imgs)
         detail::from_buffer(out.data(), npix * K, imgs);
     return detail::to_stats(st);
+}
+
+// ---- ... each set with a direction of its own (drt_hip_render_param_sets_along) ----------------------------------------------
+// A parameter set with its direction: (handle, value, direction) triples over the scene's current values; handles not listed keep the
+// value they have in the scene and get direction 0
+template <typename T>
+struct ParamAlong {
+    Vector<T, 3, true> handle;
+    Vector<T, 3> value, direction;
+};
+template <typename T>
+using ParamSetAlong = std::vector<ParamAlong<T>>;
+
+// Value, slope and Gauss-Newton curvature of the loss under each of up to DRT_HIP_MAX_SETS_ALONG parameter sets, each along its own
+// direction, from one trace: with r_k = mean_k - target and t_k = J(P_k) d_k, per set and channel (index k * 3 + ch)
+//     losses = sum r_k^2      slopes = sum 2 r_k t_k      curvatures = sum t_k^2
+// losses and slopes are empty without a target.  imgs / tangent_imgs (nullptr: none): [k * width * height + pixel] what render() and
+// render_tangent() give with sets[k] installed.  The scene's own values are not changed.
+template <typename T>
+struct SetsAlong {
+    std::vector<double> losses, slopes, curvatures;
+    Stats stats;
+};
+
+template <typename T>
+inline SetsAlong<T> render_param_sets_along(const Scene<T>& scene, const Camera<T>& cam, const Pathtracer<T>& tracer, std::size_t spp,
+                                            const std::vector<ParamSetAlong<T>>& sets, const Vector<T, 3>* target, Vector<T, 3>* imgs = nullptr,
+                                            Vector<T, 3>* tangent_imgs = nullptr, const Options& opt = Options())
+{
+    const char* who = "drt::hip::render_param_sets_along";
+    if (opt.backward || opt.unbiased || opt.sample_loss_l2)
+        throw std::runtime_error(std::string(who) + ": a forward render takes no reverse-mode option (backward, unbiased, sample_loss_l2)");
+    if (opt.devices.size() > 1)
+        throw std::runtime_error(std::string(who) + ": one device (render shards on plain contexts and add them)");
+    FlatScene<T> flat = flatten(scene);
+    const std::size_t n = flat.handles.size() * 3, K = sets.size();
+    std::vector<double> values(K * n), dirs(K * n, 0.0);
+    for (std::size_t k = 0; k < K; ++k) {
+        std::copy(flat.params.begin(), flat.params.begin() + (std::ptrdiff_t)n, values.begin() + (std::ptrdiff_t)(k * n));
+        for (const auto& t : sets[k]) {
+            const int index = detail::param_index(flat, t.handle, (std::string(who) + ": a listed parameter is not used by the scene").c_str());
+            for (int c = 0; c < 3; ++c) {
+                values[k * n + (std::size_t)index * 3 + c] = double(real(t.value[c]));
+                dirs[k * n + (std::size_t)index * 3 + c] = double(real(t.direction[c]));
+            }
+        }
+    }
+    const drt_camera_desc cd = describe(cam);
+    const std::size_t npix = cam.width() * cam.height();
+    std::vector<float> tgt, out, tout;
+    if (target)
+        tgt = detail::to_floats(target, npix);
+    if (imgs)
+        out.assign((K ? K : 1) * npix * 3, 0.f);
+    if (tangent_imgs)
+        tout.assign((K ? K : 1) * npix * 3, 0.f);
+    SetsAlong<T> r;
+    if (target) {
+        r.losses.assign(K * 3, 0.0);
+        r.slopes.assign(K * 3, 0.0);
+    }
+    r.curvatures.assign(K * 3, 0.0);
+    const drt_render_params rp = detail::render_params(tracer.absorb(), tracer.min_bounces(), spp, opt, detail::f64_flag(opt));
+    drt_hip_stats st{};
+    {
+        detail::Session s = detail::Session::on_first_device(opt, flat);
+        s.ctx.check(drt_hip_render_param_sets_along(s.ctx.get(), &cd, &rp, (int32_t)K, values.data(), dirs.data(), target ? tgt.data() : nullptr,
+                                                    imgs ? out.data() : nullptr, tangent_imgs ? tout.data() : nullptr,
+                                                    (target && K) ? r.losses.data() : nullptr, (target && K) ? r.slopes.data() : nullptr,
+                                                    K ? r.curvatures.data() : nullptr, &st),
+                    "drt_hip_render_param_sets_along");
+    }
+    if (imgs)
+        detail::from_buffer(out.data(), npix * K, imgs);
+    if (tangent_imgs)
+        detail::from_buffer(tout.data(), npix * K, tangent_imgs);
+    r.stats = detail::to_stats(st);
+    return r;
 }
 
 // A Scene<Dual<U>> for the device: the real parts as the scene, the dual parts of its PARAMETERS as the direction (n_params x 3).

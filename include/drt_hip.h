@@ -504,6 +504,38 @@ int drt_hip_render_param_sets_double(drt_hip_ctx* ctx, const drt_camera_desc* ca
                                      const double* param_sets /* n_sets x n_params x 3 */, const float* target_rgb /* H x W x 3, may be NULL */,
                                      double* out_images /* n_sets x H x W x 3, may be NULL */, double* out_loss /* n_sets x 3, may be NULL */,
                                      float* out_rgb /* may be NULL */, drt_hip_stats* stats);
+/* ... each set with a DIRECTION of its own, in one trace: what a strong-Wolfe line search, a cubic step picker or a Levenberg-Marquardt
+ * gain ratio needs per candidate P_k -- out_images[k] as above, out_tangents[k] = J(P_k) d_k (what drt_hip_update_params(param_sets[k]) +
+ * drt_hip_render_tangent(param_tangents[k]) returns, by the forward-mode form's own operations on set k's operands), and with the residual
+ * r_k = mean_k - target over the pixels of this call's shard, n_sets x 3 doubles each,
+ *   out_loss[k][ch]  = sum r_k^2          out_dloss[k][ch] = sum 2 r_k (J d_k)          out_curv[k][ch] = sum (J d_k)^2
+ * the value, the slope along d_k and the Gauss-Newton curvature of the loss, reduced in fp64 without atomics: the same call returns the
+ * same bits.  1 <= n_sets <= DRT_HIP_MAX_SETS_ALONG; the kernel is instantiated for 2 and 4 sets and a call's count is padded up with
+ * copies of the context's own parameters and zero directions, which are never written out: a set's results depend neither on its companions
+ * nor on n_sets, bit for bit.  A channel of a set that is exactly zero is handled as the forward-mode form handles it.  The colour constant a
+ * mirror material appends keeps the scene's own value and a zero tangent in every set.  The context's own parameters are not changed.
+ * There is no out_rgb: drt_hip_render gives that image.  out_loss and out_dloss need target_rgb; out_curv does not.  Everything else --
+ * shards, DRT_RENDER_DEVICE_OUT (target_rgb and every out_* are then device pointers; param_sets and param_tangents are host memory always),
+ * _F64, _SYNC, _TIMING, one batch per shard, lockstep under the roulette, the 2^31-sample limit, the slot the reduction is timed in -- as
+ * drt_hip_render_param_sets.
+ * DRT_ERR_INVALID: n_sets outside 1 ... DRT_HIP_MAX_SETS_ALONG, NULL param_sets or param_tangents, a value that is not finite, no output
+ * requested, out_loss or out_dloss without target_rgb, asynchronous frames in flight, DRT_RENDER_BACKWARD.  DRT_ERR_UNSUPPORTED: what
+ * drt_hip_render_param_sets refuses.  The message of either says "param sets along"; the context stays usable. */
+#define DRT_HIP_MAX_SETS_ALONG 4
+int drt_hip_render_param_sets_along(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_params* rp, int32_t n_sets,
+                                    const double* param_sets /* n_sets x n_params x 3 */, const double* param_tangents /* n_sets x n_params x 3 */,
+                                    const float* target_rgb /* H x W x 3, may be NULL */, float* out_images /* n_sets x H x W x 3, may be NULL */,
+                                    float* out_tangents /* n_sets x H x W x 3, may be NULL */, double* out_loss /* n_sets x 3, may be NULL */,
+                                    double* out_dloss /* n_sets x 3, may be NULL */, double* out_curv /* n_sets x 3, may be NULL */,
+                                    drt_hip_stats* stats);
+/* ... the images as the means the device formed, in double: host buffers only */
+int drt_hip_render_param_sets_along_double(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_params* rp, int32_t n_sets,
+                                           const double* param_sets /* n_sets x n_params x 3 */,
+                                           const double* param_tangents /* n_sets x n_params x 3 */,
+                                           const float* target_rgb /* H x W x 3, may be NULL */, double* out_images /* n_sets x H x W x 3, may be NULL */,
+                                           double* out_tangents /* n_sets x H x W x 3, may be NULL */, double* out_loss /* n_sets x 3, may be NULL */,
+                                           double* out_dloss /* n_sets x 3, may be NULL */, double* out_curv /* n_sets x 3, may be NULL */,
+                                           drt_hip_stats* stats);
 /* stream the context launches on (a hipStream_t), for event timing / interop */
 void* drt_hip_stream(drt_hip_ctx* ctx);
 int drt_hip_synchronize(drt_hip_ctx* ctx);

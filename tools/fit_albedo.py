@@ -46,6 +46,13 @@ evaluated in ONE drt_hip_render_param_sets call per seed (one trace for all N: a
 smallest two-seed loss sum r_A r_B wins and is accepted if it is below the current one (lambda becomes the winner's / 3; else the
 largest tried x 4).  A step is still four renders, of which two are traces of N candidates.
 
+--line-search N (N <= 4, with --scene cornell_shapes): the block's Gauss-Newton direction delta (the step of the current lambda) is kept and its
+LENGTH is searched: the N step lengths alpha x {1, 1/2, 2, 1/4}[:N] are evaluated as params + alpha delta with direction delta in ONE
+drt_hip_render_param_sets_along call per seed -- images and their derivatives along delta from one trace --, which gives per step length
+the two-seed loss phi = sum r_A r_B and its slope phi' = sum (t_A r_B + r_A t_B).  Where two neighbouring step lengths bracket a minimum
+(phi' < 0 then phi' > 0) the step is the minimiser of the cubic through both (phi, phi') pairs; else the best candidate, accepted if it is
+below the current loss.  A step is still four renders per block, of which two are traces of N candidates.
+
 --gauss-newton --scene cornell_shapes: ALL parameters of a scene past the eight the normal equations take (ten: an albedo per shape, the
 unused `white`, the emission), from a perturbed start, through drt_hip_render_normal_equations_along -- unit-vector directions in blocks
 of at most eight (8 + 2), block Gauss-Seidel: per step every block in turn takes the two-seed Levenberg-Marquardt step above (its own
@@ -104,6 +111,43 @@ def best_of_lambdas(render, params, lam, n_sets, sa, sb, candidate, lo=0.0, hi=1
     losses = (ia * ib).sum((1, 2, 3))
     i = int(np.argmin(losses))
     return cands[i], lams[i], float(losses[i]), max(lams)
+
+
+STEP_LENGTHS = (1.0, 0.5, 2.0, 0.25)
+
+
+def cubic_minimiser(a0, f0, g0, a1, f1, g1):
+    """the minimiser of the cubic through (a0, f0, slope g0) and (a1, f1, slope g1), g0 < 0 < g1, inside [a0, a1] (Nocedal & Wright 3.59)"""
+    d1 = g0 + g1 - 3.0 * (f0 - f1) / (a0 - a1)
+    rad = d1 * d1 - g0 * g1
+    d2 = np.sqrt(rad) if rad > 0 else 0.0
+    a = a1 - (a1 - a0) * (g1 + d2 - d1) / (g1 - g0 + 2.0 * d2)
+    t = (a - a0) / (a1 - a0)
+    h00, h10, h01, h11 = 2 * t ** 3 - 3 * t ** 2 + 1, t ** 3 - 2 * t ** 2 + t, -2 * t ** 3 + 3 * t ** 2, t ** 3 - t ** 2
+    return float(a), float(h00 * f0 + h10 * (a1 - a0) * g0 + h01 * f1 + h11 * (a1 - a0) * g1)
+
+
+def line_search(render, params, delta, n, sa, sb, lo, hi):
+    """n step lengths along delta in one render_param_sets_along call per seed -> (step length, its two-seed loss, "cubic" | "best")"""
+    # (no clipping inside the search -- a clipped candidate's derivative would not be the loss's along delta: the lengths shrink instead)
+    moving = np.abs(delta) > 0
+    room = np.where(delta > 0, hi - params, params - lo)
+    scale = min(1.0, float((room[moving] / np.abs(delta[moving])).min()) / max(STEP_LENGTHS[:n])) if moving.any() else 1.0
+    alphas = np.sort(np.array(STEP_LENGTHS[:n]) * scale)
+    cands = np.stack([params + a * delta for a in alphas])
+    dirs = np.stack([delta] * n)
+    ia, ta = render.sets_along(cands, dirs, sa)
+    ib, tb = render.sets_along(cands, dirs, sb)
+    ra, rb = ia.astype(np.float64) - render.target, ib.astype(np.float64) - render.target
+    phi = (ra * rb).sum((1, 2, 3))
+    slope = (ta.astype(np.float64) * rb + ra * tb.astype(np.float64)).sum((1, 2, 3))
+    for i in range(n - 1):
+        if slope[i] < 0 < slope[i + 1]:
+            a, f = cubic_minimiser(alphas[i], phi[i], slope[i], alphas[i + 1], phi[i + 1], slope[i + 1])
+            if f <= min(phi[i], phi[i + 1]):
+                return a, f, "cubic"
+    i = int(np.argmin(phi))
+    return float(alphas[i]), float(phi[i]), "best"
 
 
 def fit_gauss_newton(render, p_index, start, steps, one_render=False, lam=1e-3, log=None, lambda_sets=0):
@@ -204,7 +248,7 @@ def eval_loss(render, params, seeds=(9001, 9002), spp=128):
     return float((ra * (b.astype(np.float64) - render.target)).sum())
 
 
-def fit_gauss_newton_along(render, blocks, start, steps, lam=1e-3, lo=0.0, hi=None, log=None, lambda_sets=0):
+def fit_gauss_newton_along(render, blocks, start, steps, lam=1e-3, lo=0.0, hi=None, log=None, lambda_sets=0, line_search_n=0):
     """render as in fit(), plus render.normal_equations_along(params, seed, V, residual) -> (A [3,K,K], b [3,K], image).  `blocks`: lists
     of directions [K, P, 3]; per step every block in turn takes a two-seed Levenberg-Marquardt step along its directions (block
     Gauss-Seidel; a lambda per block).  4 renders per block and step.  -> (fitted params, history of the two-seed loss per step)"""
@@ -219,6 +263,16 @@ def fit_gauss_newton_along(render, blocks, start, steps, lam=1e-3, lo=0.0, hi=No
             r = img.astype(np.float64) - render.target
             A, b, img_b = render.normal_equations_along(params, sb, V, r.astype(np.float32))
             loss = float((r * (img_b.astype(np.float64) - render.target)).sum())
+            if line_search_n > 0:
+                delta = np.einsum("kc,kpc->pc", lm_solve(A, b, lams[bi]), V)
+                alpha, loss_c, how = line_search(render, params, delta, line_search_n, sa, sb, lo, hi)
+                if loss_c < loss:
+                    params, lams[bi], verdict, loss = np.clip(params + alpha * delta, lo, hi), max(lams[bi] / 3.0, 1e-9), "accepted", loss_c
+                else:
+                    lams[bi], verdict = lams[bi] * 4.0, "rejected"
+                if log:
+                    log(f"step {k:3d} block {bi}  loss {loss:.6f}  lambda {lams[bi]:.2e}  {verdict} (step length {alpha:.3f}, {how} of {line_search_n})")
+                continue
             if lambda_sets > 0:
                 cand, lam_c, loss_c, lam_max = best_of_lambdas(render, params, lams[bi], lambda_sets, sa, sb,
                                                                lambda l: params + np.einsum("kc,kpc->pc", lm_solve(A, b, l), V), lo, hi)
@@ -274,7 +328,7 @@ def perturbed_start(params0, seed=7, amount=0.2):
     return np.clip(p, 0.02, np.maximum(1.0, params0 + amount))
 
 
-def fit_scene(render, steps, subspace=None, log=None, lambda_sets=0):
+def fit_scene(render, steps, subspace=None, log=None, lambda_sets=0, line_search_n=0):
     """the Levenberg-Marquardt fit of every parameter of render.scene (or of one tint over its albedos) beside Adam with the same number of
     renders, from the same perturbed start -> dict of figures"""
     P = len(render.params0)
@@ -290,7 +344,7 @@ def fit_scene(render, steps, subspace=None, log=None, lambda_sets=0):
     else:
         blocks, start, free = unit_blocks(P), perturbed_start(render.params0), range(P)
     calls0 = render.calls
-    fitted, hist = fit_gauss_newton_along(render, blocks, start, steps, hi=hi, log=log, lambda_sets=lambda_sets)
+    fitted, hist = fit_gauss_newton_along(render, blocks, start, steps, hi=hi, log=log, lambda_sets=lambda_sets, line_search_n=line_search_n)
     gn_renders = render.calls - calls0
     calls0 = render.calls
     adam, ahist = fit_adam_all(render, free, start, gn_renders // 2, render.spp, render.target.size, hi=hi, log=log)
@@ -355,6 +409,14 @@ class DeviceRender:
         self.calls += 1
         self.traces_of_sets += 1
         return self.r.render_param_sets(self.cam, rp, sets)["images"]
+
+    def sets_along(self, sets, dirs, seed):
+        """the frame and its derivative along dirs[k] under every row of `sets` [N, P, 3] in one trace: two of [N, H, W, 3]"""
+        rp = self.pkg.RenderParams(spp=self.spp, min_bounces=self.depth, absorb=1.0, seed=seed)
+        self.calls += 1
+        self.traces_of_sets += 1
+        o = self.r.render_param_sets_along(self.cam, rp, sets, dirs)
+        return o["images"], o["tangents"]
 
     def close(self):
         self.r.close()
@@ -437,6 +499,9 @@ def main():
     ap.add_argument("--one-render", dest="one_render", action="store_true")
     ap.add_argument("--lambda-sets", dest="lambda_sets", type=int, default=0,
                     help="with --gauss-newton: try this many dampings (<= 7) per step in one render_param_sets call per seed")
+    ap.add_argument("--line-search", dest="line_search", type=int, default=0,
+                    help="with --gauss-newton --scene cornell_shapes: search the step LENGTH over this many candidates (<= 4) in one "
+                         "render_param_sets_along call per seed")
     ap.add_argument("--async", dest="use_async", action="store_true")
     ap.add_argument("--oracle", action="store_true")
     ap.add_argument("--quiet", action="store_true")
@@ -445,6 +510,8 @@ def main():
     a = ap.parse_args()
     if a.lambda_sets and (not a.gauss_newton or a.one_render or not 1 <= a.lambda_sets <= len(LAMBDA_FACTORS)):
         ap.error("--lambda-sets N (1 ... 7) goes with --gauss-newton (not --one-render)")
+    if a.line_search and (not a.gauss_newton or a.scene == "cornell" or a.oracle or a.lambda_sets or not 1 <= a.line_search <= len(STEP_LENGTHS)):
+        ap.error("--line-search N (1 ... 4) goes with --gauss-newton --scene cornell_shapes on the device (not --oracle, not --lambda-sets)")
     import __graft_entry__ as e
     pkg = e.load_package()
     if a.oracle:
@@ -455,7 +522,9 @@ def main():
         if not a.gauss_newton:
             ap.error("--scene other than cornell goes with --gauss-newton")
         t0 = time.time()
-        f = fit_scene(render, a.steps or ALONG_STEPS, a.subspace, log=None if a.quiet else print, lambda_sets=a.lambda_sets)
+        f = fit_scene(render, a.steps or ALONG_STEPS, a.subspace, log=None if a.quiet else print, lambda_sets=a.lambda_sets, line_search_n=a.line_search)
+        if a.line_search:
+            print(f"--line-search {a.line_search}: {render.traces_of_sets} of the renders were traces of {a.line_search} step lengths")
         if a.lambda_sets:
             print(f"--lambda-sets {a.lambda_sets}: {render.traces_of_sets} of the renders were traces of {a.lambda_sets} candidates")
         print(f"{a.scene}{' (tint)' if a.subspace else ''}: two-seed loss at the start {f['start_loss']:.5f}; Levenberg-Marquardt {f['gn_steps']} steps, "
