@@ -179,11 +179,26 @@ __device__ inline void stage_path_scene(PathSceneLds<R>& lds, const DevScene<R>*
 //                                     : (n_p == 1 and zc_ch == 1 ? T_ch : 0)     (d/dc of c^n at 0: 1 for n = 1, else 0)
 // Evaluated where a path meets a light: once per sample.  Same sums as the reference's backward functors
 // (vector.hpp:418-484) in closed form; the image is unchanged bit for bit (a channel without zero factors sees the very
-// same multiplications), gradients to f32 rounding.  |c| < 1e-18 counts as zero (its quotient would overflow).
+// same multiplications), gradients to f32 rounding.  |c| < DRT_ZERO_CHANNEL = 1e-18 counts as zero (its quotient would overflow).
 // Row DRT_TANGENT_REST is for a lane whose path does NOT go on from the vertex: colour (1, 1, 1), increments 0.  The lockstep kernel
 // freezes such a lane by pointing its table index there (the index is a select anyway) and its multiplicand m_k at 1: T * (1 * 1) and
 // counters + 0 are exact, so the lane keeps its bits -- one select on the index and one on m_k instead of three on the factor and one per counter.
 #define DRT_TANGENT_REST DRT_FAST_PARAMS
+// The zero-channel rule of every table below, once: |c| < DRT_ZERO_CHANNEL counts as zero, and a table entry (c, v) -- a colour channel and
+// its tangent -- splits into the colour with zero replaced by 1, v / c (0 at a zero), v where the channel is zero (else 0), and the zero bit
+// (the three values go straight to their table words, in this order: the staging prologues keep their instruction streams).
+#define DRT_ZERO_CHANNEL 1e-18
+template <typename R>
+__device__ inline bool zero_channel(R c) { return abs_r(c) < R(DRT_ZERO_CHANNEL); }
+template <typename R>
+__device__ inline bool zero_split(R c, R v, R& colnz, R& dlog, R& dzero)
+{
+    const bool zero = zero_channel(c);
+    colnz = zero ? R(1) : c;
+    dlog = zero ? R(0) : v / c;
+    dzero = zero ? v : R(0);
+    return zero;
+}
 #ifndef DRT_FREEZE_BY_ROW
 #define DRT_FREEZE_BY_ROW 1
 #endif
@@ -205,7 +220,7 @@ __device__ inline void stage_tangents(TangentLds<R>& tl, const SL& lds)
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) {
             const R c = in ? lds.params[p * 3 + ch] : R(1);
-            const bool zero = abs_r(c) < R(1e-18);
+            const bool zero = zero_channel(c);
             tl.colnz[p][ch] = zero ? R(1) : c;
             tl.invc[p][ch] = zero ? R(0) : R(1) / c;
             zinc |= zero ? 1u << (8 * ch) : 0u;
@@ -326,7 +341,7 @@ __device__ inline void stage_gen(GenLds<R>& gl, const SL& lds, const DevScene<R>
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) {
             const R c = in ? lds.params[p * 3 + ch] : R(1);
-            const bool zero = abs_r(c) < R(1e-18);
+            const bool zero = zero_channel(c);
             gl.colnz[p][ch] = zero ? R(1) : c;
             gl.invc[p][ch] = zero ? R(0) : R(1) / c;
             zinc |= zero ? 1u << (8 * ch) : 0u;
@@ -454,10 +469,7 @@ __device__ inline void stage_dir(DirLds<R>& dl, const SL& lds, const R* __restri
         for (int ch = 0; ch < 3; ++ch) {
             const R c = in ? lds.params[p * 3 + ch] : R(1);
             const R v = in ? params[(lds.sc.n_params + p) * 3 + ch] : R(0);
-            const bool zero = abs_r(c) < R(1e-18);
-            dl.colnz[p][ch] = zero ? R(1) : c;
-            dl.dlog[p][ch] = zero ? R(0) : v / c;
-            dl.dzero[p][ch] = zero ? v : R(0);
+            const bool zero = zero_split(c, v, dl.colnz[p][ch], dl.dlog[p][ch], dl.dzero[p][ch]);
             zinc |= zero ? 1u << (8 * ch) : 0u;
             if (p < DRT_PATH_LDS_PARAMS)
                 dl.dir[p * 3 + ch] = v;
@@ -504,7 +516,9 @@ __device__ inline void stage_dirs(R* __restrict__ tab, const SL& lds, const R* _
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) {
             const R c = in ? lds.params[p * 3 + ch] : R(1);
-            const bool zero = abs_r(c) < R(1e-18);
+            // (the rule alone, not zero_split(): the colour row is shared by the K directions and written once, and the split called per
+            //  direction moved these kernels' instruction streams)
+            const bool zero = zero_channel(c);
             tab[p * 4 + ch] = zero ? R(1) : c;
             zinc |= zero ? 1u << (8 * ch) : 0u;
             for (int k = 0; k < K; ++k) {
@@ -637,10 +651,7 @@ __device__ inline void stage_sets_along(R* __restrict__ tab, const SL& lds, cons
         for (int ch = 0; ch < 3; ++ch) {
             const R c = in ? P[ch] : R(1);
             const R v = in ? D[ch] : R(0);
-            const bool zero = abs_r(c) < R(1e-18);
-            set[p * 4 + ch] = zero ? R(1) : c;
-            set[stride + p * 4 + ch] = zero ? R(0) : v / c;
-            set[2 * stride + p * 4 + ch] = zero ? v : R(0);
+            const bool zero = zero_split(c, v, set[p * 4 + ch], set[stride + p * 4 + ch], set[2 * stride + p * 4 + ch]);
             zinc |= zero ? 1u << (8 * ch) : 0u;
             if (in) {
                 set[3 * stride + p * 3 + ch] = c;
@@ -671,6 +682,51 @@ struct Tangents<R, DRT_NP_SETS_ALONG, NC> {
         }
     }
 };
+
+// ---- the forward-mode step, once: what the single-direction form, every direction of the K-direction form and every set of the sets-along
+// form do to their own operands (so a direction's or a set's sums equal the single-direction form's bit for bit: one function, not three
+// copies).  Operand-level: none of them knows which form calls it.
+// ... per bounce, from the rows of v / c and of v (zero channels) of the colour the path scattered on
+template <typename R>
+__device__ inline void tangent_advance(const R* ds, const R* dz, V3<R>& S, V3<R>& Z)
+{
+    S = mk<R>(S.x + ds[0], S.y + ds[1], S.z + ds[2]);
+    Z = mk<R>(Z.x + dz[0], Z.y + dz[1], Z.z + dz[2]);
+}
+// ... at a light of emission E (already / p_k) whose tangent is vd: dL += T (E S + vd / p_k) where no factor of the channel is zero,
+// T E Z where exactly one is (T leaves the zero factors out), else nothing
+template <typename R>
+__device__ inline void tangent_emit(V3<R> T, uint32_t zc, V3<R> E, const R* vd, R inv_pk, V3<R> S, V3<R> Z, V3<R>& dL)
+{
+    const V3<R> Ed = mk<R>(vd[0], vd[1], vd[2]) * inv_pk;
+    const V3<R> d0 = mk<R>(fma_r(E.x, S.x, Ed.x), fma_r(E.y, S.y, Ed.y), fma_r(E.z, S.z, Ed.z));
+    const V3<R> d1 = E * Z;
+    const uint32_t zx = zc & 0xFFu, zy = zc & 0xFF00u, zz = zc & 0xFF0000u;
+    dL = mk<R>(fma_r(T.x, zx == 0u ? d0.x : (zx == 0x1u ? d1.x : R(0)), dL.x),
+               fma_r(T.y, zy == 0u ? d0.y : (zy == 0x100u ? d1.y : R(0)), dL.y),
+               fma_r(T.z, zz == 0u ? d0.z : (zz == 0x10000u ? d1.z : R(0)), dL.z));
+}
+
+// ---- the three forms whose tables live in dynamic shared memory (K directions, K sets, K sets with a direction each): the form's
+// staging, then the thread's view of the block's tables (after stage_path_scene's barrier)
+template <typename R, int NP, int NC, typename SL>
+__device__ inline void path_tables_begin(Tangents<R, NP, NC>& tg, const SL& lds, const R* __restrict__ params)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char s_dirs[];
+    R* tab = reinterpret_cast<R*>(s_dirs);
+    if constexpr (NP == DRT_NP_SETS_ALONG)
+        stage_sets_along<R, NC>(tab, lds, params);
+    else if constexpr (NP == DRT_NP_SETS)
+        stage_sets<R, NC>(tab, lds, params);
+    else
+        stage_dirs<R, NC>(tab, lds, params);
+    tg.tab = tab;
+    tg.rest = (uint32_t)(lds.sc.n_params < DRT_PATH_LDS_PARAMS ? lds.sc.n_params : DRT_PATH_LDS_PARAMS);
+    tg.stride = (tg.rest + 1u) * 4u;
+    if constexpr (NP == DRT_NP_SETS_ALONG)
+        tg.words = sets_along_set_words(tg.rest);
+    tg.new_path();
+}
 
 // what a block of a general-form kernel keeps in LDS, and the two ends of its life
 template <typename R>
@@ -769,7 +825,9 @@ __device__ inline void add_emission(const SL& lds, const TangentLds<R>& tl, cons
             tg.L[k] = tg.L[k] + tg.T[k] * Ek;
         }
     } else if constexpr (NP == DRT_NP_SETS_ALONG) {
-        // K sets, a direction each: the single-direction forward case below, once per set on the set's own emission, its tangent, T, zc, S, Z
+        // K sets, a direction each: the single-direction forward case below (tangent_emit), once per set on the set's own emission, its tangent,
+        // T, zc, S, Z.  (The radiance add's dark channels share their three masks with the tangent add: written here, not taken from a function
+        // shared with the general branch below -- that moved these kernels' instruction streams)
         const uint32_t er = 3u * tg.stride + (eid < tg.rest ? eid : 0u) * 3u;
 #pragma unroll
         for (int k = 0; k < NC; ++k) {
@@ -780,12 +838,7 @@ __device__ inline void add_emission(const SL& lds, const TangentLds<R>& tl, cons
             const uint32_t zx = tg.zc[k] & 0xFFu, zy = tg.zc[k] & 0xFF00u, zz = tg.zc[k] & 0xFF0000u;
             const V3<R> Tr = mk<R>(zx ? R(0) : Tk.x, zy ? R(0) : Tk.y, zz ? R(0) : Tk.z);
             tg.L[k] = tg.L[k] + Tr * Ek;
-            const V3<R> Ed = mk<R>(vd[0], vd[1], vd[2]) * inv_pk;
-            const V3<R> d0 = mk<R>(fma_r(Ek.x, tg.S[k].x, Ed.x), fma_r(Ek.y, tg.S[k].y, Ed.y), fma_r(Ek.z, tg.S[k].z, Ed.z));
-            const V3<R> d1 = Ek * tg.Z[k];
-            tg.dL[k] = mk<R>(fma_r(Tk.x, zx == 0u ? d0.x : (zx == 0x1u ? d1.x : R(0)), tg.dL[k].x),
-                             fma_r(Tk.y, zy == 0u ? d0.y : (zy == 0x100u ? d1.y : R(0)), tg.dL[k].y),
-                             fma_r(Tk.z, zz == 0u ? d0.z : (zz == 0x10000u ? d1.z : R(0)), tg.dL[k].z));
+            tangent_emit(Tk, tg.zc[k], Ek, vd, inv_pk, tg.S[k], tg.Z[k], tg.dL[k]);
         }
     } else {
         const V3<R> E = load_param<R, (NP != 0)>(lds, params, (int)eid) * inv_pk;
@@ -794,30 +847,15 @@ __device__ inline void add_emission(const SL& lds, const TangentLds<R>& tl, cons
             Tr = mk<R>((tg.zc & 0xFFu) ? R(0) : T.x, (tg.zc & 0xFF00u) ? R(0) : T.y, (tg.zc & 0xFF0000u) ? R(0) : T.z);
         L = L + Tr * E;
         if constexpr (NP == DRT_NP_TANGENT && NC > 0) {
-            // K directions: the single-direction case below, once per direction
+            // K directions: the single-direction case below (tangent_emit), once per direction
             const R* dir = tg.tab + (1u + 2u * NC) * tg.stride + (eid < tg.rest ? eid : 0u) * 3u;
-            const uint32_t zx = tg.zc & 0xFFu, zy = tg.zc & 0xFF00u, zz = tg.zc & 0xFF0000u;
 #pragma unroll
-            for (int k = 0; k < NC; ++k) {
-                const R* vd = dir + (uint32_t)k * 3u * tg.rest;
-                const V3<R> Ed = mk<R>(vd[0], vd[1], vd[2]) * inv_pk;
-                const V3<R> d0 = mk<R>(fma_r(E.x, tg.S[k].x, Ed.x), fma_r(E.y, tg.S[k].y, Ed.y), fma_r(E.z, tg.S[k].z, Ed.z));
-                const V3<R> d1 = E * tg.Z[k];
-                tg.dL[k] = mk<R>(fma_r(T.x, zx == 0u ? d0.x : (zx == 0x1u ? d1.x : R(0)), tg.dL[k].x),
-                                 fma_r(T.y, zy == 0u ? d0.y : (zy == 0x100u ? d1.y : R(0)), tg.dL[k].y),
-                                 fma_r(T.z, zz == 0u ? d0.z : (zz == 0x10000u ? d1.z : R(0)), tg.dL[k].z));
-            }
+            for (int k = 0; k < NC; ++k)
+                tangent_emit(T, tg.zc, E, dir + (uint32_t)k * 3u * tg.rest, inv_pk, tg.S[k], tg.Z[k], tg.dL[k]);
         } else
         if constexpr (NP == DRT_NP_TANGENT) {
             // forward mode: T (e S + e') where no factor of the channel is zero, T e Z where exactly one is
-            const R* vd = tg.dl->dir + (eid < DRT_PATH_LDS_PARAMS ? eid : 0u) * 3u;
-            const V3<R> Ed = mk<R>(vd[0], vd[1], vd[2]) * inv_pk;
-            const V3<R> d0 = mk<R>(fma_r(E.x, tg.S.x, Ed.x), fma_r(E.y, tg.S.y, Ed.y), fma_r(E.z, tg.S.z, Ed.z));
-            const V3<R> d1 = E * tg.Z;
-            const uint32_t zx = tg.zc & 0xFFu, zy = tg.zc & 0xFF00u, zz = tg.zc & 0xFF0000u;
-            tg.dL = mk<R>(fma_r(T.x, zx == 0u ? d0.x : (zx == 0x1u ? d1.x : R(0)), tg.dL.x),
-                          fma_r(T.y, zy == 0u ? d0.y : (zy == 0x100u ? d1.y : R(0)), tg.dL.y),
-                          fma_r(T.z, zz == 0u ? d0.z : (zz == 0x10000u ? d1.z : R(0)), tg.dL.z));
+            tangent_emit(T, tg.zc, E, tg.dl->dir + (eid < DRT_PATH_LDS_PARAMS ? eid : 0u) * 3u, inv_pk, tg.S, tg.Z, tg.dL);
         } else
         if constexpr (NP == DRT_NP_ANY) {
             // any number of parameters: the light's own row, then every vertex of the path's history adds to its colour's row
@@ -1002,8 +1040,7 @@ __device__ inline void path_bounce(const PathArgs& a, const PathSceneLds<R>& lds
             const R *rec = tg.tab + (uint32_t)k * tg.words + row, *ds = rec + tg.stride, *dz = ds + tg.stride;
             tg.T[k] = tg.T[k] * (mk<R>(rec[0], rec[1], rec[2]) * mm);
             tg.zc[k] += pid_unpack(rec[3]);
-            tg.S[k] = mk<R>(tg.S[k].x + ds[0], tg.S[k].y + ds[1], tg.S[k].z + ds[2]);
-            tg.Z[k] = mk<R>(tg.Z[k].x + dz[0], tg.Z[k].y + dz[1], tg.Z[k].z + dz[2]);
+            tangent_advance(ds, dz, tg.S[k], tg.Z[k]);
         }
     } else {
         const int cidx = DIR ? (alive ? (int)cid : DRT_PATH_LDS_PARAMS) : (REST ? (alive ? (int)cid : DRT_TANGENT_REST) : (has_bxdf ? (int)cid : 0));
@@ -1017,8 +1054,7 @@ __device__ inline void path_bounce(const PathArgs& a, const PathSceneLds<R>& lds
 #pragma unroll
             for (int k = 0; k < NC; ++k) {
                 const R *ds = tg.tab + (1u + 2u * k) * tg.stride + row, *dz = ds + tg.stride;
-                tg.S[k] = mk<R>(tg.S[k].x + ds[0], tg.S[k].y + ds[1], tg.S[k].z + ds[2]);
-                tg.Z[k] = mk<R>(tg.Z[k].x + dz[0], tg.Z[k].y + dz[1], tg.Z[k].z + dz[2]);
+                tangent_advance(ds, dz, tg.S[k], tg.Z[k]);
             }
         } else
         if constexpr (DIR) {
@@ -1026,8 +1062,7 @@ __device__ inline void path_bounce(const PathArgs& a, const PathSceneLds<R>& lds
             const R *rec = tg.dl->colnz[row], *ds = tg.dl->dlog[row], *dz = tg.dl->dzero[row];
             col = mk<R>(rec[0], rec[1], rec[2]);
             tg.zc += pid_unpack(rec[3]);
-            tg.S = mk<R>(tg.S.x + ds[0], tg.S.y + ds[1], tg.S.z + ds[2]);
-            tg.Z = mk<R>(tg.Z.x + dz[0], tg.Z.y + dz[1], tg.Z.z + dz[2]);
+            tangent_advance(ds, dz, tg.S, tg.Z);
         } else
         if constexpr (NP == DRT_NP_ANY) {
             const R* rec = tg.gl->colnz[cidx < DRT_PATH_LDS_PARAMS ? cidx : 0];
@@ -1217,32 +1252,9 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
         tg.acc = &s_acc[0][threadIdx.x];
     if constexpr (GEN)
         gen_begin(s_gen, lds, sc, a, s_hist, reinterpret_cast<uint32_t*>(a.hist_ovf), tg);
-    else if constexpr (DIRS) {
-        extern __shared__ __attribute__((aligned(16))) unsigned char s_dirs[];
-        R* tab = reinterpret_cast<R*>(s_dirs);
-        stage_dirs<R, NC>(tab, lds, params);
-        tg.tab = tab;
-        tg.rest = (uint32_t)(lds.sc.n_params < DRT_PATH_LDS_PARAMS ? lds.sc.n_params : DRT_PATH_LDS_PARAMS);
-        tg.stride = (tg.rest + 1u) * 4u;
-        tg.new_path();
-    } else if constexpr (SETS) {
-        extern __shared__ __attribute__((aligned(16))) unsigned char s_dirs[];
-        R* tab = reinterpret_cast<R*>(s_dirs);
-        stage_sets<R, NC>(tab, lds, params);
-        tg.tab = tab;
-        tg.rest = (uint32_t)(lds.sc.n_params < DRT_PATH_LDS_PARAMS ? lds.sc.n_params : DRT_PATH_LDS_PARAMS);
-        tg.stride = (tg.rest + 1u) * 4u;
-        tg.new_path();
-    } else if constexpr (ALONG) {
-        extern __shared__ __attribute__((aligned(16))) unsigned char s_dirs[];
-        R* tab = reinterpret_cast<R*>(s_dirs);
-        stage_sets_along<R, NC>(tab, lds, params);
-        tg.tab = tab;
-        tg.rest = (uint32_t)(lds.sc.n_params < DRT_PATH_LDS_PARAMS ? lds.sc.n_params : DRT_PATH_LDS_PARAMS);
-        tg.stride = (tg.rest + 1u) * 4u;
-        tg.words = sets_along_set_words(tg.rest);
-        tg.new_path();
-    } else if constexpr (DIR) {
+    else if constexpr (DIRS || SETS || ALONG)
+        path_tables_begin(tg, lds, params);
+    else if constexpr (DIR) {
         stage_dir(s_dir, lds, params);
         tg.dl = &s_dir;
         tg.new_path();
@@ -1253,6 +1265,8 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
     }
     double fx = 0, fy = 0, fz = 0;                        // radiance sum of this lane's pixel over the range
     double tx = 0, ty = 0, tz = 0;                        // DIR: ... and the sum of its samples' derivatives
+    constexpr int TK = ALONG ? 2 : 1;                     // rows of three sums a direction / a set has (the write-out below)
+    // (tk's size and zeroing stay spelled per form: as TK * NC and one loop over it they moved 16 kernels' instruction streams)
     double tk[(DIRS || SETS) ? NC : (ALONG ? 2 * NC : 1)][3];   // DIRS: ... per direction; SETS: the radiance sums per set; ALONG: radiance, derivative per set
     if constexpr (DIRS || SETS || ALONG) {
 #pragma unroll
@@ -1500,23 +1514,14 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
             double* f = gimg_part + ((size_t)range * 3) * a.Pb + lp;
             f[0] = (double)tg.gsum.x; f[(size_t)a.Pb] = (double)tg.gsum.y; f[(size_t)a.Pb * 2] = (double)tg.gsum.z;
         }
-        if constexpr (DIRS || SETS) if (gimg_part && have) {
-            // K directions / K sets: the pixel's sums in the Jacobian form's layout, [range][3 k + ch][pixel], for those the caller gave
+        if constexpr (DIRS || SETS || ALONG) if (gimg_part && have) {
+            // K directions / K sets: the pixel's sums in the Jacobian form's layout, [range][3 k + ch][pixel], for those the caller gave; with a
+            // direction per set, 6 rows a set: [range][6 k + ch][pixel] the radiance sums, [range][6 k + 3 + ch][pixel] the derivative sums
             const uint32_t nd = a.dirs_out() < (uint32_t)NC ? a.dirs_out() : (uint32_t)NC;
-            double* f = gimg_part + ((size_t)range * (size_t)(nd * 3u)) * a.Pb + lp;
+            double* f = gimg_part + ((size_t)range * (size_t)(nd * (3u * TK))) * a.Pb + lp;
 #pragma unroll
-            for (int k = 0; k < NC; ++k)
-                if ((uint32_t)k < nd) {
-                    f[(size_t)(k * 3) * a.Pb] = tk[k][0]; f[(size_t)(k * 3 + 1) * a.Pb] = tk[k][1]; f[(size_t)(k * 3 + 2) * a.Pb] = tk[k][2];
-                }
-        }
-        if constexpr (ALONG) if (gimg_part && have) {
-            // K sets with a direction each: [range][6 k + ch][pixel] the radiance sums, [range][6 k + 3 + ch][pixel] the derivative sums
-            const uint32_t nd = a.dirs_out() < (uint32_t)NC ? a.dirs_out() : (uint32_t)NC;
-            double* f = gimg_part + ((size_t)range * (size_t)(nd * 6u)) * a.Pb + lp;
-#pragma unroll
-            for (int k = 0; k < 2 * NC; ++k)
-                if ((uint32_t)(k >> 1) < nd) {
+            for (int k = 0; k < TK * NC; ++k)
+                if ((uint32_t)(k / TK) < nd) {
                     f[(size_t)(k * 3) * a.Pb] = tk[k][0]; f[(size_t)(k * 3 + 1) * a.Pb] = tk[k][1]; f[(size_t)(k * 3 + 2) * a.Pb] = tk[k][2];
                 }
         }
@@ -1935,6 +1940,51 @@ k_path_finish(PathArgs a, const double* __restrict__ fpart, float* __restrict__ 
     }
 }
 
+// ---- the two stages of a frame-wide sum in fp64 behind the forms below: no atomics, every addition in a fixed order, so the same call
+// gives the same bits
+// first stage: the thread's NV running sums -> wave (shuffles) -> block (LDS); thread v < NV writes the block's sum of value v to
+// part[at + v]  (base and offset apart, as the kernels wrote it: added up before the call the address costs them their instruction streams)
+template <int NV>
+__device__ inline void block_sums(const double (&acc)[NV], double* __restrict__ part, size_t at)
+{
+    __shared__ double red[DRT_BLOCK / DRT_WAVE][NV];
+    const int wv = threadIdx.x / DRT_WAVE;
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+        double s = acc[v];
+#pragma unroll
+        for (int o2 = DRT_WAVE / 2; o2 > 0; o2 >>= 1)
+            s += __shfl_down(s, o2);
+        if ((threadIdx.x & (DRT_WAVE - 1)) == 0)
+            red[wv][v] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < NV) {
+        double s = 0;
+        for (int ww = 0; ww < DRT_BLOCK / DRT_WAVE; ++ww)
+            s += red[ww][threadIdx.x];
+        part[at + threadIdx.x] = s;
+    }
+}
+
+// second stage: one value's partials over the first stage's n_blocks blocks, block b's from part_of(b) -- a strided sum per thread, then an
+// LDS tree over the kernel's red[DRT_BLOCK]; the sum is red[0].  (The array and the index are the caller's: with an array of its own and
+// the partials as pointer + stride, k_sets_along_sums and k_normal_eq_finish changed their register counts)
+template <typename F>
+__device__ inline void add_blocks(double* red, int n_blocks, F part_of)
+{
+    double s = 0;
+    for (int b = threadIdx.x; b < n_blocks; b += DRT_BLOCK)
+        s += part_of(b);
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int off = DRT_BLOCK / 2; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off)
+            red[threadIdx.x] += red[threadIdx.x + off];
+        __syncthreads();
+    }
+}
+
 // ---- the Gauss-Newton normal equations of a frame (drt_hip_render_normal_equations) -------------------------------------
 // Behind a launch of k_path's Jacobian form: jpart[range][3 p + ch][pixel] holds, per pixel of the shard, the sums over one sample range of
 // d radiance_ch / d c_{p,ch} (a radiance channel depends on the same channel of every parameter only: T_ch = prod c_{p_j,ch} m_j), fpart the
@@ -2014,6 +2064,8 @@ k_normal_eq(PathArgs a, const double* __restrict__ jpart, const double* __restri
             acc[k] += r * r;
         }
     }
+    // (block_sums(), written out: through the function this kernel's resource report moves -- 96 -> 95 and 90 -> 88 SGPRs at width 4, 36 -> 39
+    //  and 35 -> 37 SGPR spills at width 8 -- and a memory-bound kernel's time is not argued from a report)
     __shared__ double red[DRT_BLOCK / DRT_WAVE][NV];
     const int wv = threadIdx.x / DRT_WAVE;
 #pragma unroll
@@ -2044,16 +2096,7 @@ k_normal_eq_finish(const double* __restrict__ part, int n_blocks, int np_w, int 
     __shared__ double red[DRT_BLOCK];
     const int nv = DRT_NEQ_VALUES(np_w);
     const int ch = (int)blockIdx.x / nv, k = (int)blockIdx.x - ch * nv;
-    double v = 0;
-    for (int b = threadIdx.x; b < n_blocks; b += DRT_BLOCK)
-        v += part[((size_t)ch * n_blocks + b) * nv + k];
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int off = DRT_BLOCK / 2; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off)
-            red[threadIdx.x] += red[threadIdx.x + off];
-        __syncthreads();
-    }
+    add_blocks(red, n_blocks, [&](int b) { return part[((size_t)ch * n_blocks + b) * nv + k]; });
     if (threadIdx.x != 0)
         return;
     const int n_tri = np_w * (np_w + 1) / 2;
@@ -2117,24 +2160,7 @@ k_sets_finish(PathArgs a, const double* __restrict__ spart, int n_sets, const fl
     }
     if (!part)
         return;
-    __shared__ double red[DRT_BLOCK / DRT_WAVE][DRT_SETS_VALUES];
-    const int wv = threadIdx.x / DRT_WAVE;
-#pragma unroll
-    for (int v = 0; v < DRT_SETS_VALUES; ++v) {
-        double s = acc[v];
-#pragma unroll
-        for (int o2 = DRT_WAVE / 2; o2 > 0; o2 >>= 1)
-            s += __shfl_down(s, o2);
-        if ((threadIdx.x & (DRT_WAVE - 1)) == 0)
-            red[wv][v] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < DRT_SETS_VALUES) {
-        double s = 0;
-        for (int ww = 0; ww < DRT_BLOCK / DRT_WAVE; ++ww)
-            s += red[ww][threadIdx.x];
-        part[(size_t)blockIdx.x * DRT_SETS_VALUES + threadIdx.x] = s;
-    }
+    block_sums(acc, part, (size_t)blockIdx.x * DRT_SETS_VALUES);
 }
 
 // ... its second stage: block v adds value v's partials over k_sets_finish's blocks -- a strided sum per thread, then an LDS tree, both
@@ -2144,16 +2170,7 @@ k_sets_loss_finish(const double* __restrict__ part, int n_blocks, int n_values, 
 {
     __shared__ double red[DRT_BLOCK];
     const int v = (int)blockIdx.x;
-    double s = 0;
-    for (int b = threadIdx.x; b < n_blocks; b += DRT_BLOCK)
-        s += part[(size_t)b * DRT_SETS_VALUES + v];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int off = DRT_BLOCK / 2; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off)
-            red[threadIdx.x] += red[threadIdx.x + off];
-        __syncthreads();
-    }
+    add_blocks(red, n_blocks, [&](int b) { return part[(size_t)b * DRT_SETS_VALUES + v]; });
     if (threadIdx.x == 0 && v < n_values)
         out_loss[v] = red[0];
 }
@@ -2208,24 +2225,7 @@ k_sets_along_finish(PathArgs a, const double* __restrict__ spart, int n_sets, co
     }
     if (!part)
         return;
-    __shared__ double red[DRT_BLOCK / DRT_WAVE][DRT_SETS_ALONG_VALUES];
-    const int wv = threadIdx.x / DRT_WAVE;
-#pragma unroll
-    for (int v = 0; v < DRT_SETS_ALONG_VALUES; ++v) {
-        double s = acc[v];
-#pragma unroll
-        for (int o2 = DRT_WAVE / 2; o2 > 0; o2 >>= 1)
-            s += __shfl_down(s, o2);
-        if ((threadIdx.x & (DRT_WAVE - 1)) == 0)
-            red[wv][v] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < DRT_SETS_ALONG_VALUES) {
-        double s = 0;
-        for (int ww = 0; ww < DRT_BLOCK / DRT_WAVE; ++ww)
-            s += red[ww][threadIdx.x];
-        part[(size_t)blockIdx.x * DRT_SETS_ALONG_VALUES + threadIdx.x] = s;
-    }
+    block_sums(acc, part, (size_t)blockIdx.x * DRT_SETS_ALONG_VALUES);
 }
 
 // ... its second stage: block v adds value v's partials over k_sets_along_finish's blocks -- a strided sum per thread, then an LDS tree, both
@@ -2236,16 +2236,7 @@ k_sets_along_sums(const double* __restrict__ part, int n_blocks, int n_values, d
 {
     __shared__ double red[DRT_BLOCK];
     const int v = (int)blockIdx.x;
-    double s = 0;
-    for (int b = threadIdx.x; b < n_blocks; b += DRT_BLOCK)
-        s += part[(size_t)b * DRT_SETS_ALONG_VALUES + v];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int off = DRT_BLOCK / 2; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off)
-            red[threadIdx.x] += red[threadIdx.x + off];
-        __syncthreads();
-    }
+    add_blocks(red, n_blocks, [&](int b) { return part[(size_t)b * DRT_SETS_ALONG_VALUES + v]; });
     if (threadIdx.x == 0 && v < n_values) {
         double* out = v % 3 == 0 ? out_loss : (v % 3 == 1 ? out_dloss : out_curv);
         if (out)

@@ -297,6 +297,20 @@ inline std::string path_kernel_name(const drt_hip_ctx* ctx, const PathForm& f)
     return name;
 }
 
+// The dynamic shared memory a launch of the form takes: the tables of the three K-wide forms, sized by the scene's own parameter count
+// (stage_dirs: up to 100.6 KB in f64 -- this runtime launches a block with any amount of dynamic LDS the CU has, for library and hiprtc
+// kernels alike: tests/test_gpu_tangents.py fills both; stage_sets: 17.5 KB in f32, 35 KB in f64 at 136 parameters x 8 sets;
+// stage_sets_along: 39 KB in f32, 79 KB in f64 at 136 parameters x 4 sets), else the general form's history words (none: 0)
+template <typename R>
+unsigned path_dynamic_lds(const PathForm& f, int n_params, unsigned hist_bytes)
+{
+    const uint32_t n = (uint32_t)std::min(n_params, DRT_PATH_LDS_PARAMS), K = (uint32_t)f.nc;
+    if (f.op == PathOp::tangents) return dirs_table_words(n, K) * (unsigned)sizeof(R);
+    if (f.op == PathOp::param_sets) return sets_table_words(n, K) * (unsigned)sizeof(R);
+    if (f.op == PathOp::param_sets_along) return sets_along_table_words(n, K) * (unsigned)sizeof(R);
+    return f.op == PathOp::unbiased ? 0u : hist_bytes;
+}
+
 // The form's instantiation the library carries -- exactly the ones it launches -- or nullptr: the form exists only through
 // hiprtc (LOSS, the scene's own program)
 template <typename R>
@@ -343,17 +357,16 @@ const void* library_path_kernel(const PathForm& f)
         }
         return nullptr;
     }
-    if (f.op == PathOp::param_sets)  // one path under K parameter sets: lockstep, every program
-        return f.regen ? nullptr : with_int<2, 4, 8>(f.nc, [&](auto k) {
-            return spec_sig([](auto spec, auto sg) { return (const void*)k_path<R, decltype(spec)::value, DRT_NP_SETS, decltype(k)::value, decltype(sg), false>; });
-        });
-    if (f.op == PathOp::param_sets_along)  // ... each set with a direction: lockstep, every program
-        return f.regen ? nullptr : with_int<2, 4>(f.nc, [&](auto k) {
-            return spec_sig([](auto spec, auto sg) { return (const void*)k_path<R, decltype(spec)::value, DRT_NP_SETS_ALONG, decltype(k)::value, decltype(sg), false>; });
-        });
-    if (f.op == PathOp::tangents)  // ... along K directions: lockstep, every program
-        return f.regen ? nullptr : with_int<2, 4, 8>(f.nc, [&](auto k) {
-            return spec_sig([](auto spec, auto sg) { return (const void*)k_path<R, decltype(spec)::value, DRT_NP_TANGENT, decltype(k)::value, decltype(sg), false>; });
+    // one path under K parameter sets, each set with a direction, along K directions -- the op names its NP tag --: lockstep, every program,
+    // widths 2, 4 and 8; with a direction per set 2 and 4 (drt_path.h: K = 8 is not kept)
+    if (const int tag = f.op == PathOp::param_sets ? DRT_NP_SETS : (f.op == PathOp::param_sets_along ? DRT_NP_SETS_ALONG : (f.op == PathOp::tangents ? DRT_NP_TANGENT : 0)))
+        return f.regen ? nullptr : with_int<DRT_NP_SETS, DRT_NP_SETS_ALONG, DRT_NP_TANGENT>(tag, [&](auto np) {
+            return with_int<2, 4, 8>(f.nc, [&](auto k) {
+                if constexpr (decltype(np)::value == DRT_NP_SETS_ALONG && decltype(k)::value > 4)
+                    return (const void*)nullptr;
+                else
+                    return spec_sig([](auto spec, auto sg) { return (const void*)k_path<R, decltype(spec)::value, decltype(np)::value, decltype(k)::value, decltype(sg), false>; });
+            });
         });
     if (f.op == PathOp::tangent)   // forward mode: both forms, every program
         return spec_sig([&f](auto spec, auto sg) {
@@ -871,18 +884,7 @@ int path_batch(Shard<R>& s)
     void* args_unb[] = {&pa, &d_scene, &d_params, &d_adjoint, &gpart, &fpart, &counts, &ptotal};
     void* args_mesh[] = {&pa, &d_scene, &d_params, &d_adjoint, &s.bvh, &ovf, &ovf_stride, &gpart, &fpart, &counts, &ptotal, &gpix};
     void** args = form.op == PathOp::unbiased ? args_unb : (form.op == PathOp::mesh ? args_mesh : args_path);
-    // (the K-direction form's tables, sized by the scene's own parameter count: stage_dirs.  Up to 100.6 KB in f64; this runtime launches a
-    //  block with any amount of dynamic LDS the CU has, for library and hiprtc kernels alike: tests/test_gpu_tangents.py fills both)
-    const unsigned dirs_bytes = form.op == PathOp::tangents
-        ? dirs_table_words((uint32_t)std::min(ctx->n_params, DRT_PATH_LDS_PARAMS), (uint32_t)form.nc) * (unsigned)sizeof(R) : 0u;
-    // (the parameter-set form's: stage_sets -- 17.5 KB in f32, 35 KB in f64 at 136 parameters x 8 sets)
-    const unsigned sets_bytes = form.op == PathOp::param_sets
-        ? sets_table_words((uint32_t)std::min(ctx->n_params, DRT_PATH_LDS_PARAMS), (uint32_t)form.nc) * (unsigned)sizeof(R) : 0u;
-    // (... with a direction per set: stage_sets_along -- 39 KB in f32, 79 KB in f64 at 136 parameters x 4 sets)
-    const unsigned along_bytes = form.op == PathOp::param_sets_along
-        ? sets_along_table_words((uint32_t)std::min(ctx->n_params, DRT_PATH_LDS_PARAMS), (uint32_t)form.nc) * (unsigned)sizeof(R) : 0u;
-    const unsigned lds_bytes = form.op == PathOp::unbiased ? 0u : (form.op == PathOp::tangents ? dirs_bytes : (form.op == PathOp::param_sets ? sets_bytes :
-                               (form.op == PathOp::param_sets_along ? along_bytes : hist_bytes)));
+    const unsigned lds_bytes = path_dynamic_lds<R>(form, ctx->n_params, hist_bytes);
     if (jit)
         HIPCHK(ctx, hipModuleLaunchKernel(jit, (unsigned)gpath, 1, 1, DRT_BLOCK, 1, 1, lds_bytes, ks, args, nullptr));
     else

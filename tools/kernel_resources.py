@@ -3,7 +3,13 @@
 VGPRs, SGPRs, scratch, LDS, occupancy (-Rpass-analysis=kernel-resource-usage), plus -- for the
 kernels named on the command line -- an instruction-class histogram of their ISA.
 
-  python tools/kernel_resources.py [--keep DIR] [substring of a demangled kernel name ...]
+  python tools/kernel_resources.py [--keep DIR] [--against DIR] [substring of a demangled kernel name ...]
+
+--against DIR (the --keep directory of another build, usually the parent commit's): after the report, one line per kernel saying whether
+its resource figures and its instruction stream are the `same` as in that build or which `differs`, then a count of each.  The stream is
+compared as text, without comments, blank lines, debug directives, the compilation-unit id symbol and the function's number in its local
+labels (.LBB<n>_, .Lfunc_begin<n>, .Lfunc_end<n>, .Ltmp<n>).  The exit status is 1 if a kernel appeared, vanished or changed a figure, or
+if a figure was not found in either build.
 """
 import collections
 import os
@@ -43,15 +49,85 @@ def classify(op):
     return "other"
 
 
+FIGURES = ("NumVgprs", "NumAgprs", "TotalNumSgprs", "ScratchSize", "LDSByteSize", "Occupancy", "sgpr_spill_count", "vgpr_spill_count")
+
+
+def parse_asm(path):
+    """{mangled name: (figures, instruction stream)} of the kernels in an assembly file: the figures from the kernel's `; Kernel info:`
+    comment and its metadata record, the stream from its label to its .amdhsa_kernel block."""
+    bodies, figures, kernels = {}, collections.defaultdict(dict), []
+    body = info = meta = None
+    for line in open(path):
+        m = re.match(r"(\S+):\s+; @(\S+)$", line)
+        if m and m.group(1) == m.group(2):
+            body = bodies[m.group(1)] = []
+            last = m.group(1)
+            continue
+        m = re.match(r"\s+\.amdhsa_kernel (\S+)", line)
+        if m:
+            kernels.append(m.group(1))
+            body = None
+        if body is not None:
+            code = line.split(";")[0].strip()
+            if code and not code.startswith((".loc", ".file", ".cfi_")):
+                code = re.sub(r"\.L(func_begin|func_end|tmp)\d+", r".L\1", re.sub(r"\.LBB\d+_", ".LBB_", code))
+                body.append(re.sub(r"__hip_cuid_\w+", "__hip_cuid", code))
+        if line.startswith("; Kernel info:"):
+            info = figures[last]
+        elif info is not None:
+            m = re.match(r"; (\w+):? *[:=] *(\d+)", line)
+            if m:
+                info[m.group(1)] = m.group(2)
+            elif not line.startswith(";"):
+                info = None
+        if line.startswith("  - ."):              # a kernel's metadata record: its fields in name order
+            meta = {}
+        m = re.match(r"\s+(?:- )?\.(name|sgpr_spill_count|vgpr_spill_count):\s+(\S+)", line)
+        if m and meta is not None:
+            meta[m.group(1)] = m.group(2)
+            if len(meta) == 3:
+                figures[meta.pop("name")].update(meta)
+                meta = None
+    return {k: (tuple(figures[k].get(f, "?") for f in FIGURES), bodies[k]) for k in kernels}
+
+
+def compare(asm, parent_asm):
+    new, old = parse_asm(asm), parse_asm(parent_asm)
+    names = sorted(set(new) | set(old))
+    count = collections.Counter()
+    print(f"\nagainst {parent_asm}\n{'kernel':110s} {'figures':>8s} {'stream':>8s}")
+    for k, dn in zip(names, demangle(names)):
+        if k not in old or k not in new:
+            verdict = ("appeared", "") if k in new else ("vanished", "")
+            count[verdict[0]] += 1
+        else:
+            verdict = tuple("same" if new[k][i] == old[k][i] else "differs" for i in (0, 1))
+            if "?" in new[k][0] + old[k][0]:          # a figure the parser did not find is no agreement
+                verdict = ("unknown", verdict[1])
+            count["figures " + verdict[0]] += 1
+            count["stream " + verdict[1]] += 1
+        print(f"{short(dn)[:110]:110s} {verdict[0]:>8s} {verdict[1]:>8s}")
+        if verdict[0] == "differs":
+            print("    " + ", ".join(f"{f} {o} -> {n}" for f, o, n in zip(FIGURES, old[k][0], new[k][0]) if o != n))
+    print(f"\n{len(new)} kernels ({len(old)} there): " + ", ".join(f"{v} {c}" for c, v in sorted(count.items())))
+    return 1 if count["appeared"] or count["vanished"] or count["figures differs"] or count["figures unknown"] else 0
+
+
 def main():
     args = sys.argv[1:]
-    keep = None
-    if args and args[0] == "--keep":
-        keep = args[1]
+    keep = against = None
+    while args and args[0] in ("--keep", "--against"):
+        if len(args) < 2:
+            sys.exit(f"{args[0]} needs a directory")
+        if args[0] == "--keep":
+            keep = args[1]
+        else:
+            against = args[1]
         args = args[2:]
     d = keep or tempfile.mkdtemp(prefix="drt_isa_")
     os.makedirs(d, exist_ok=True)
     asm = os.path.join(d, "drt.s")
+    subprocess.run([sys.executable, os.path.join(os.path.dirname(SRC), "embed_sources.py")], check=True)   # (drt_jit_sources.inc, which drt_hip.hip includes)
     cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-fno-slp-vectorize", "-std=c++17", "-fPIC", "-I" + os.path.join(ROOT, "include"),
            "--cuda-device-only", "-S", "-o", asm, SRC, "-Rpass-analysis=kernel-resource-usage"] + \
           [a for a in os.environ.get("DRT_EXTRA_FLAGS", "").split() if a]
@@ -77,8 +153,9 @@ def main():
         k["short"] = short(dn)
         print(f"{k['short'][:78]:78s} {k.get('VGPRs', '?'):>5s} {k.get('AGPRs', '?'):>5s} {k.get('TotalSGPRs', k.get('SGPRs', '?')):>5s} "
               f"{k.get('ScratchSize [bytes/lane]', '?'):>8s} {k.get('LDS Size [bytes/block]', '?'):>7s} {k.get('Occupancy [waves/SIMD]', '?'):>4s} {k.get('SGPRs Spill', '?'):>10s}")
+    status = compare(asm, os.path.join(against, "drt.s")) if against else 0
     if not args:
-        return
+        return status
     text = open(asm).read()
     for k in kernels:
         if not any(a in k["short"] for a in args):
@@ -96,7 +173,8 @@ def main():
         for c, n in hist.most_common():
             print(f"  {c:12s} {n}")
     print(f"\nassembly kept in {asm}")
+    return status
 
 
 if __name__ == "__main__":
-    main()
+    sys.exit(main())
