@@ -722,35 +722,31 @@ class DrtHipError(RuntimeError):
     pass
 
 
-def check_param_sets(sets, n_params: int) -> np.ndarray:
-    """K parameter sets as drt_hip_render_param_sets takes them: float64 [K, n_params, 3], 1 <= K <= MAX_PARAM_SETS, finite values.
-    Raises ValueError otherwise (what the library would refuse, said before the call)."""
+def check_param_sets(sets, n_params: int, tangents=None):
+    """K parameter sets as drt_hip_render_param_sets takes them: float64 [K, n_params, 3], 1 <= K <= MAX_PARAM_SETS, finite values -- or,
+    with `tangents`, the sets and their K directions as drt_hip_render_param_sets_along takes them: the same shape each,
+    1 <= K <= MAX_SETS_ALONG -> (sets, directions).  Raises ValueError otherwise (what the library would refuse, said before the call)."""
+    along = tangents is not None
+    who, cap, cap_name = ("param sets along", MAX_SETS_ALONG, "MAX_SETS_ALONG") if along else ("param sets", MAX_PARAM_SETS, "MAX_PARAM_SETS")
     v = np.ascontiguousarray(sets, dtype=np.float64)
     if v.ndim != 3 or v.shape[1:] != (n_params, 3):
-        raise ValueError(f"param sets: expected shape [n_sets, {n_params}, 3], got {list(v.shape)}")
-    if not 1 <= v.shape[0] <= MAX_PARAM_SETS:
-        raise ValueError(f"param sets: n_sets = {v.shape[0]} outside 1 ... MAX_PARAM_SETS = {MAX_PARAM_SETS}")
+        raise ValueError(f"{who}: expected {'sets of ' if along else ''}shape [n_sets, {n_params}, 3], got {list(v.shape)}")
+    if along:
+        t = np.ascontiguousarray(tangents, dtype=np.float64)
+        if t.shape != v.shape:
+            raise ValueError(f"{who}: expected directions of shape {list(v.shape)}, got {list(t.shape)}")
+    if not 1 <= v.shape[0] <= cap:
+        raise ValueError(f"{who}: n_sets = {v.shape[0]} outside 1 ... {cap_name} = {cap}")
     if not np.isfinite(v).all():
-        raise ValueError("param sets: a set holds a value that is not finite")
-    return v
+        raise ValueError(f"{who}: a set holds a value that is not finite")
+    if along and not np.isfinite(t).all():
+        raise ValueError(f"{who}: a direction holds a value that is not finite")
+    return (v, t) if along else v
 
 
 def check_param_sets_along(sets, tangents, n_params: int):
-    """K parameter sets and their K directions as drt_hip_render_param_sets_along takes them: float64 [K, n_params, 3] each,
-    1 <= K <= MAX_SETS_ALONG, finite values.  Raises ValueError otherwise (what the library would refuse, said before the call)."""
-    v = np.ascontiguousarray(sets, dtype=np.float64)
-    t = np.ascontiguousarray(tangents, dtype=np.float64)
-    if v.ndim != 3 or v.shape[1:] != (n_params, 3):
-        raise ValueError(f"param sets along: expected sets of shape [n_sets, {n_params}, 3], got {list(v.shape)}")
-    if t.shape != v.shape:
-        raise ValueError(f"param sets along: expected directions of shape {list(v.shape)}, got {list(t.shape)}")
-    if not 1 <= v.shape[0] <= MAX_SETS_ALONG:
-        raise ValueError(f"param sets along: n_sets = {v.shape[0]} outside 1 ... MAX_SETS_ALONG = {MAX_SETS_ALONG}")
-    if not np.isfinite(v).all():
-        raise ValueError("param sets along: a set holds a value that is not finite")
-    if not np.isfinite(t).all():
-        raise ValueError("param sets along: a direction holds a value that is not finite")
-    return v, t
+    """check_param_sets for sets with a direction each -> (sets, directions)"""
+    return check_param_sets(sets, n_params, np.asarray(tangents, dtype=np.float64))
 
 
 _ABI_SYMBOLS = ["drt_hip_abi_version", "drt_hip_device_count", "drt_hip_create", "drt_hip_create_group",
@@ -1170,24 +1166,33 @@ class HipRenderer:
         self._check(rc, "drt_hip_render_normal_equations_along")
         return stats.as_dict() if want_stats else {}
 
+    @staticmethod
+    def _target_arg(target, cam: Camera, who: str):
+        """an optional target image of the parameter-set renders -> (float32 [H,W,3] array, pointer), or (None, None)"""
+        if target is None:
+            return None, None
+        target = np.ascontiguousarray(target, dtype=np.float32)
+        if target.shape != (cam.height, cam.width, 3):
+            raise ValueError(f"{who}: expected a target of shape {[cam.height, cam.width, 3]}, got {list(target.shape)}")
+        return target, target.ctypes.data_as(C.c_void_p)
+
+    def _begin_sets(self, cam: Camera, rp: RenderParams, flags: int, sets, *tangents):
+        """what the four parameter-set calls start with -> (the checked sets -- with `tangents`: (sets, directions) --, then what _begin gives)"""
+        assert self.scene is not None
+        n = self.scene.n_params
+        return (check_param_sets_along(sets, *tangents, n) if tangents else check_param_sets(sets, n),) + self._begin(cam, rp, flags)
+
     def render_param_sets(self, cam: Camera, rp: RenderParams, sets: np.ndarray, target: Optional[np.ndarray] = None, f64: bool = False,
                           images: bool = True, timing: bool = False, double: bool = False) -> dict:
         """drt_hip_render_param_sets: the frame under the K <= MAX_PARAM_SETS parameter vectors `sets` ([K, n_params, 3]) in ONE trace;
         the context's own parameters stay what they are.  `target` (float32 [H,W,3]) asks for the losses.
         -> {"images" [K,H,W,3] float32 (double=True: float64, the means as the device formed them) or None,
             "loss" [K,3] float64 = sum over this shard's pixels of (mean_k - target)^2, or None, "stats"}"""
-        assert self.scene is not None
-        v = check_param_sets(sets, self.scene.n_params)
+        v, cd, d, stats = self._begin_sets(cam, rp, self._host_flags(rp, f64, timing), sets)
         K = v.shape[0]
         if not images and target is None:
             raise ValueError("param sets: no output requested (images=False without a target)")
-        cd, d, stats = self._begin(cam, rp, self._host_flags(rp, f64, timing))
-        t_ptr = None
-        if target is not None:
-            target = np.ascontiguousarray(target, dtype=np.float32)
-            if target.shape != (cam.height, cam.width, 3):
-                raise ValueError(f"param sets: expected a target of shape {[cam.height, cam.width, 3]}, got {list(target.shape)}")
-            t_ptr = target.ctypes.data_as(C.c_void_p)
+        target, t_ptr = self._target_arg(target, cam, "param sets")
         imgs = np.zeros((K, cam.height, cam.width, 3), dtype=np.float64 if double else np.float32) if images else None
         loss = np.zeros((K, 3), dtype=np.float64) if target is not None else None
         fn = self.lib.drt_hip_render_param_sets_double if double else self.lib.drt_hip_render_param_sets
@@ -1203,9 +1208,7 @@ class HipRenderer:
         """drt_hip_render_param_sets on device pointers (images float32 [K,H,W,3], target float32 [H,W,3], loss float64 [K,3]), enqueued
         on the context's stream; the sets are host memory."""
         want_stats = timing if want_stats is None else want_stats
-        assert self.scene is not None
-        v = check_param_sets(sets, self.scene.n_params)
-        cd, d, stats = self._begin(cam, rp, self._device_flags(rp, f64, timing, sync))
+        v, cd, d, stats = self._begin_sets(cam, rp, self._device_flags(rp, f64, timing, sync), sets)
         rc = self.lib.drt_hip_render_param_sets(self.ctx, C.byref(cd), C.byref(d), v.shape[0], v.ctypes.data_as(C.c_void_p),
                                                 C.c_void_p(target_ptr or None), C.c_void_p(out_images_ptr or None),
                                                 C.c_void_p(out_loss_ptr or None), C.c_void_p(out_rgb_ptr or None),
@@ -1221,16 +1224,9 @@ class HipRenderer:
         -> {"images", "tangents" [K,H,W,3] float32 (double=True: float64, the means as the device formed them) or None,
             "loss" = sum r_k^2, "dloss" = sum 2 r_k (J d_k) ([K,3] float64 over this shard's pixels, r_k = mean_k - target; None without a
             target), "curv" = sum (J d_k)^2 [K,3] float64, "stats"}"""
-        assert self.scene is not None
-        v, t = check_param_sets_along(sets, tangents, self.scene.n_params)
+        (v, t), cd, d, stats = self._begin_sets(cam, rp, self._host_flags(rp, f64, timing), sets, tangents)
         K = v.shape[0]
-        cd, d, stats = self._begin(cam, rp, self._host_flags(rp, f64, timing))
-        t_ptr = None
-        if target is not None:
-            target = np.ascontiguousarray(target, dtype=np.float32)
-            if target.shape != (cam.height, cam.width, 3):
-                raise ValueError(f"param sets along: expected a target of shape {[cam.height, cam.width, 3]}, got {list(target.shape)}")
-            t_ptr = target.ctypes.data_as(C.c_void_p)
+        target, t_ptr = self._target_arg(target, cam, "param sets along")
         dt = np.float64 if double else np.float32
         imgs = np.zeros((K, cam.height, cam.width, 3), dtype=dt) if images else None
         timgs = np.zeros((K, cam.height, cam.width, 3), dtype=dt) if images else None
@@ -1251,9 +1247,7 @@ class HipRenderer:
         """drt_hip_render_param_sets_along on device pointers (images float32 [K,H,W,3], target float32 [H,W,3], sums float64 [K,3]),
         enqueued on the context's stream; the sets and directions are host memory."""
         want_stats = timing if want_stats is None else want_stats
-        assert self.scene is not None
-        v, t = check_param_sets_along(sets, tangents, self.scene.n_params)
-        cd, d, stats = self._begin(cam, rp, self._device_flags(rp, f64, timing, sync))
+        (v, t), cd, d, stats = self._begin_sets(cam, rp, self._device_flags(rp, f64, timing, sync), sets, tangents)
         rc = self.lib.drt_hip_render_param_sets_along(self.ctx, C.byref(cd), C.byref(d), v.shape[0], v.ctypes.data_as(C.c_void_p),
                                                       t.ctypes.data_as(C.c_void_p), C.c_void_p(target_ptr or None),
                                                       C.c_void_p(out_images_ptr or None), C.c_void_p(out_tangents_ptr or None),

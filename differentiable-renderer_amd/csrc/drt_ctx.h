@@ -45,8 +45,8 @@ struct TangentRequest {
         forward,                          // forward mode along one direction (drt_hip_render_tangent): d_params, keep_sums
         jacobian,                         // the normal equations of a frame (drt_hip_render_normal_equations): neq
         directions,                       // ... in the span of K directions (drt_hip_render_tangents / _normal_equations_along): d_params, neq, n_dirs
-        param_sets,                       // one frame under K parameter sets (drt_hip_render_param_sets): d_params, sets
-        param_sets_along,                 // ... each with a direction (drt_hip_render_param_sets_along): d_params, sets (sets->along)
+        param_sets,                       // one frame under K parameter sets (drt_hip_render_param_sets; with sets->along each has a direction:
+                                          // drt_hip_render_param_sets_along): d_params, sets
     } kind = Kind::forward;
     const void* d_params = nullptr;       // the path kernel's `params`, in the render's compute type: [the scene's parameters | row_1 | ... | row_K],
                                           // the rows padded up to an instantiated width K (stage_rows, drt_hip.hip)

@@ -256,37 +256,29 @@ int drt_hip_render_gradient_image(drt_hip_ctx* ctx, const drt_camera_desc* cam, 
 // ---- the renders that exist on the one-launch path kernel's special forms only: forward mode along one direction, the Jacobian form,
 // K directions, K parameter sets.  What they share: the rows behind the kernel's `params`, the refusals, the K images' way back ----
 // dst = [the scene's parameters | row_1 | ... | row_K] in compute type R.  Rows at and above n_rows (padding up to the kernel's width) and the
-// internal constants (a mirror's colour) of every row are zero -- directions -- or, with pad_own, the context's own parameters -- sets
+// internal constants (a mirror's colour) of every row are padded by one of three rules
+enum class RowPad : int {
+    zero,                       // directions
+    own,                        // sets: the context's own parameters
+    own_even,                   // rows in PAIRS (a set, then its direction: drt_hip_render_param_sets_along): even rows like sets, odd rows like directions
+};
 template <typename R>
 __global__ void __launch_bounds__(DRT_BLOCK) k_stage_rows(const R* __restrict__ params, int n_all, const double* __restrict__ h_rows, int n_user,
-                                                          int n_rows, int K, bool pad_own, R* __restrict__ dst)
-{
-    for (int i = blockIdx.x * DRT_BLOCK + threadIdx.x; i < n_all; i += gridDim.x * DRT_BLOCK) {
-        const R own = params[i], pad = pad_own ? own : R(0);
-        dst[i] = own;
-        for (int k = 0; k < K; ++k)
-            dst[(size_t)(1 + k) * n_all + i] = (k < n_rows && i < n_user) ? (R)h_rows[(size_t)k * n_user + i] : pad;
-    }
-}
-
-// ... for rows that come in PAIRS (a parameter set, then its direction: drt_hip_render_param_sets_along): even rows are padded like sets,
-// odd rows like directions
-template <typename R>
-__global__ void __launch_bounds__(DRT_BLOCK) k_stage_row_pairs(const R* __restrict__ params, int n_all, const double* __restrict__ h_rows, int n_user,
-                                                               int n_rows, int K, R* __restrict__ dst)
+                                                          int n_rows, int K, RowPad pad, R* __restrict__ dst)
 {
     for (int i = blockIdx.x * DRT_BLOCK + threadIdx.x; i < n_all; i += gridDim.x * DRT_BLOCK) {
         const R own = params[i];
         dst[i] = own;
         for (int k = 0; k < K; ++k)
-            dst[(size_t)(1 + k) * n_all + i] = (k < n_rows && i < n_user) ? (R)h_rows[(size_t)k * n_user + i] : ((k & 1) ? R(0) : own);
+            dst[(size_t)(1 + k) * n_all + i] = (k < n_rows && i < n_user) ? (R)h_rows[(size_t)k * n_user + i]
+                                               : ((pad == RowPad::own || (pad == RowPad::own_even && !(k & 1))) ? own : R(0));
     }
 }
 
 // the caller's n_rows x n_user rows -> pinned memory -> ctx->tangent.p = [parameters | row_1 | ... | row_K], in stream order.  Two pinned
 // copies used in turn: the one this call rewrites was read by the launch of the call before the previous one, and its event says so
 // (rows2: the rows come in pairs -- row 2 k from `rows`, row 2 k + 1 from `rows2`, n_rows and K counting both)
-static int stage_rows(drt_hip_ctx* ctx, const drt_render_params* rp, const double* rows, int n_rows, int K, bool pad_own, const double* rows2 = nullptr)
+static int stage_rows(drt_hip_ctx* ctx, const drt_render_params* rp, const double* rows, int n_rows, int K, RowPad pad, const double* rows2 = nullptr)
 {
     const int n_user = ctx->n_user_params * 3, n_all = ctx->n_params * 3;
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -313,20 +305,12 @@ static int stage_rows(drt_hip_ctx* ctx, const drt_render_params* rp, const doubl
     if ((rc = ensure(ctx, ctx->tangent, (size_t)(n_all ? n_all : 1) * (size_t)(1 + K) * sizeof(double))) != DRT_OK) return rc;
     if (n_all > 0) {
         const unsigned blocks = (unsigned)((n_all + DRT_BLOCK - 1) / DRT_BLOCK);
-        if (rows2) {
-            if (rp->flags & DRT_RENDER_F64)
-                hipLaunchKernelGGL(k_stage_row_pairs<double>, dim3(blocks), dim3(DRT_BLOCK), 0, ctx->stream, (const double*)ctx->d_params_d, n_all,
-                                   (const double*)ctx->h_tangent[hb], n_user, n_rows, K, (double*)ctx->tangent.p);
-            else
-                hipLaunchKernelGGL(k_stage_row_pairs<float>, dim3(blocks), dim3(DRT_BLOCK), 0, ctx->stream, (const float*)ctx->d_params_f, n_all,
-                                   (const double*)ctx->h_tangent[hb], n_user, n_rows, K, (float*)ctx->tangent.p);
-        } else
         if (rp->flags & DRT_RENDER_F64)
             hipLaunchKernelGGL(k_stage_rows<double>, dim3(blocks), dim3(DRT_BLOCK), 0, ctx->stream, (const double*)ctx->d_params_d, n_all,
-                               (const double*)ctx->h_tangent[hb], n_user, n_rows, K, pad_own, (double*)ctx->tangent.p);
+                               (const double*)ctx->h_tangent[hb], n_user, n_rows, K, pad, (double*)ctx->tangent.p);
         else
             hipLaunchKernelGGL(k_stage_rows<float>, dim3(blocks), dim3(DRT_BLOCK), 0, ctx->stream, (const float*)ctx->d_params_f, n_all,
-                               (const double*)ctx->h_tangent[hb], n_user, n_rows, K, pad_own, (float*)ctx->tangent.p);
+                               (const double*)ctx->h_tangent[hb], n_user, n_rows, K, pad, (float*)ctx->tangent.p);
         HIPCHK(ctx, hipGetLastError());
     }
     HIPCHK(ctx, hipEventRecord(ctx->ev_tangent[hb], ctx->stream));
@@ -408,7 +392,7 @@ static int render_tangent_common(drt_hip_ctx* ctx, const drt_camera_desc* cam, c
     if (ctx->n_params > DRT_PATH_LDS_PARAMS)
         return fail(ctx, DRT_ERR_UNSUPPORTED, "render_tangent: a tangent of more parameters than the path kernels stage (136)");
     int rc;
-    if ((rc = stage_rows(ctx, rp, param_tangent, 1, 1, false)) != DRT_OK) return rc;
+    if ((rc = stage_rows(ctx, rp, param_tangent, 1, 1, RowPad::zero)) != DRT_OK) return rc;
     TangentRequest req;
     req.kind = TangentRequest::Kind::forward;
     req.d_params = ctx->tangent.p;
@@ -603,7 +587,7 @@ static int render_tangents_common(drt_hip_ctx* ctx, const drt_camera_desc* cam, 
             return refuse(ctx, me, DRT_ERR_INVALID, "a direction holds a value that is not finite");
     if ((rc = refuse_after(ctx, cam, rp, me)) != DRT_OK) return rc;
     // (directions at and above n_dirs, up to the kernel's width, are zero)
-    if ((rc = stage_rows(ctx, rp, param_tangents, n_dirs, n_dirs <= 2 ? 2 : (n_dirs <= 4 ? 4 : 8), false)) != DRT_OK) return rc;
+    if ((rc = stage_rows(ctx, rp, param_tangents, n_dirs, n_dirs <= 2 ? 2 : (n_dirs <= 4 ? 4 : 8), RowPad::zero)) != DRT_OK) return rc;
     TangentRequest req;
     req.kind = TangentRequest::Kind::directions;
     req.d_params = ctx->tangent.p;
@@ -629,30 +613,73 @@ int drt_hip_render_normal_equations_along(drt_hip_ctx* ctx, const drt_camera_des
 
 } // extern "C"
 
-// ---- one frame under up to DRT_HIP_MAX_PARAM_SETS parameter sets in one trace ----
-static int render_param_sets_common(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_params* rp, int32_t n_sets,
-                                    const double* param_sets, const float* target_rgb, float* out_images, double* out_images64,
-                                    double* out_loss, float* out_rgb, drt_hip_stats* stats)
+// ---- one frame under several parameter sets in one trace: up to DRT_HIP_MAX_PARAM_SETS of them, or up to DRT_HIP_MAX_SETS_ALONG with a
+// direction each -- value, slope and Gauss-Newton curvature of the loss per set ----
+// the two forms: who is asking, the most sets it takes, and its own words where the forms' refusals differ
+struct SetsForm {
+    bool along;
+    PathFormCaller me;
+    int most;
+    const char *outside, *null_input, *no_output, *needs_target;
+};
+static const SetsForm plain_sets = {false,
+                                    {"param sets", "render the shards on plain contexts", "a forward render", DRT_PATH_LDS_PARAMS,
+                                     "more parameters than the path kernels stage (136)"},
+                                    DRT_HIP_MAX_PARAM_SETS, "n_sets outside 1 ... DRT_HIP_MAX_PARAM_SETS = 8", "NULL param_sets",
+                                    "no output requested (out_images and out_loss are both NULL)", "out_loss needs target_rgb"};
+static const SetsForm sets_along = {true,
+                                    {"param sets along", "render the shards on plain contexts", "a forward render", DRT_PATH_LDS_PARAMS,
+                                     "more parameters than the path kernels stage (136)"},
+                                    DRT_HIP_MAX_SETS_ALONG, "n_sets outside 1 ... DRT_HIP_MAX_SETS_ALONG = 4", "NULL param_sets or param_tangents",
+                                    "no output requested (out_images, out_tangents, out_loss, out_dloss and out_curv are all NULL)",
+                                    "out_loss and out_dloss need target_rgb"};
+
+// this shard's rows of n_sets images, from `from` bytes into ctx->neq_jac to the caller's buffer: a copy per band (the render has waited
+// for its stream)
+static int fetch_set_images(drt_hip_ctx* ctx, const drt_camera_desc* cam, int n_sets, void* out, size_t from, size_t el)
+{
+    const RenderJob& j = ctx->job;
+    const size_t row = (size_t)cam->width * 3 * el, img = (size_t)cam->height * row;
+    hipError_t e = hipSuccess;
+    for (size_t k = 0; k < (size_t)n_sets; ++k)
+        for_each_band(cam->height, j.band, j.n_shards, j.shard, [&](int y0, int y1) {
+            const size_t at = k * img + (size_t)y0 * row;
+            if (e == hipSuccess)
+                e = hipMemcpy((uint8_t*)out + at, (const uint8_t*)ctx->neq_jac.p + from + at, (size_t)(y1 - y0) * row, hipMemcpyDeviceToHost);
+        });
+    HIPCHK(ctx, e);
+    return DRT_OK;
+}
+
+// the one call behind the four entry points.  The plain form has no param_tangents, out_tangents, out_dloss and out_curv; the form with
+// directions has no out_rgb.  `wide`: the images are double (host buffers only)
+static int render_sets_common(drt_hip_ctx* ctx, const SetsForm& form, const drt_camera_desc* cam, const drt_render_params* rp, int32_t n_sets,
+                              const double* param_sets, const double* param_tangents, const float* target_rgb, void* out_images, void* out_tangents,
+                              bool wide, double* out_loss, double* out_dloss, double* out_curv, float* out_rgb, drt_hip_stats* stats)
 {
     if (!ctx)
         return DRT_ERR_INVALID;
-    const PathFormCaller me = {"param sets", "render the shards on plain contexts", "a forward render", DRT_PATH_LDS_PARAMS,
-                               "more parameters than the path kernels stage (136)"};
+    const PathFormCaller& me = form.me;
+    if (wide && rp && (rp->flags & DRT_RENDER_DEVICE_OUT))
+        return refuse(ctx, me, DRT_ERR_INVALID, "the double images come through host buffers only (no DRT_RENDER_DEVICE_OUT)");
     int rc;
     if ((rc = refuse_before(ctx, cam, rp, me)) != DRT_OK) return rc;
-    if (n_sets < 1 || n_sets > DRT_HIP_MAX_PARAM_SETS)
-        return refuse(ctx, me, DRT_ERR_INVALID, "n_sets outside 1 ... DRT_HIP_MAX_PARAM_SETS = 8");
-    if (!param_sets)
-        return refuse(ctx, me, DRT_ERR_INVALID, "NULL param_sets");
-    if (!out_images && !out_images64 && !out_loss)
-        return refuse(ctx, me, DRT_ERR_INVALID, "no output requested (out_images and out_loss are both NULL)");
-    if (out_loss && !target_rgb)
-        return refuse(ctx, me, DRT_ERR_INVALID, "out_loss needs target_rgb");
+    if (n_sets < 1 || n_sets > form.most)
+        return refuse(ctx, me, DRT_ERR_INVALID, form.outside);
+    if (!param_sets || (form.along && !param_tangents))
+        return refuse(ctx, me, DRT_ERR_INVALID, form.null_input);
+    if (!out_images && !out_tangents && !out_loss && !out_dloss && !out_curv)
+        return refuse(ctx, me, DRT_ERR_INVALID, form.no_output);
+    if ((out_loss || out_dloss) && !target_rgb)
+        return refuse(ctx, me, DRT_ERR_INVALID, form.needs_target);
     if (rp->flags & DRT_RENDER_BACKWARD)
         return refuse(ctx, me, DRT_ERR_INVALID, "a forward render: no DRT_RENDER_BACKWARD");
-    for (size_t i = 0; i < (size_t)n_sets * (size_t)ctx->n_user_params * 3; ++i)
+    for (size_t i = 0; i < (size_t)n_sets * (size_t)ctx->n_user_params * 3; ++i) {
         if (!std::isfinite(param_sets[i]))
             return refuse(ctx, me, DRT_ERR_INVALID, "a set holds a value that is not finite");
+        if (form.along && !std::isfinite(param_tangents[i]))
+            return refuse(ctx, me, DRT_ERR_INVALID, "a direction holds a value that is not finite");
+    }
     if (!(rp->flags & DRT_RENDER_DEVICE_OUT) && target_rgb)
         for (size_t i = 0; i < (size_t)cam->width * (size_t)cam->height * 3; ++i)
             if (!std::isfinite(target_rgb[i]))
@@ -662,139 +689,23 @@ static int render_param_sets_common(drt_hip_ctx* ctx, const drt_camera_desc* cam
     const int n_int = n_sets + (out_rgb ? 1 : 0);
     if (n_int > DRT_HIP_MAX_PARAM_SETS)
         return refuse(ctx, me, DRT_ERR_UNSUPPORTED, "out_rgb beside 8 sets (the plain image takes one of the kernel's eight: drt_hip_render gives it)");
-    // (sets at and above n_sets, up to the kernel's width, are the context's own parameters; the last one is the plain image's)
+    // (sets at and above n_sets, up to the kernel's width, are the context's own parameters -- the last one is the plain image's --, with a
+    //  zero direction; a mirror's internal constant keeps the scene's value and a zero tangent in every set)
     const int K = n_int <= 2 ? 2 : (n_int <= 4 ? 4 : 8);
-    if ((rc = stage_rows(ctx, rp, param_sets, n_sets, K, true)) != DRT_OK) return rc;
+    if ((rc = form.along ? stage_rows(ctx, rp, param_sets, 2 * n_sets, 2 * K, RowPad::own_even, param_tangents)
+                         : stage_rows(ctx, rp, param_sets, n_sets, K, RowPad::own)) != DRT_OK) return rc;
     const bool dev = (rp->flags & DRT_RENDER_DEVICE_OUT) != 0;
     const size_t npix = (size_t)cam->width * (size_t)cam->height;
     // the caller's images: device pointers as they are; host buffers through buffers of the context's own
     ParamSetsRequest q;
     q.n_sets = n_sets;
     q.width = K;
-    const size_t n_img = (size_t)n_sets * npix * 3;
+    q.along = form.along;
+    const size_t el = wide ? sizeof(double) : sizeof(float), n_img = (size_t)n_sets * npix * 3 * el, ns3 = (size_t)n_sets * 3;
     if (dev) {
         q.d_target = target_rgb;
-        q.d_images = out_images;
-        q.d_loss = out_loss;
-    } else {
-        if (target_rgb) {
-            if ((rc = ensure(ctx, ctx->neq_in, npix * 3 * sizeof(float))) != DRT_OK) return rc;
-            HIPCHK(ctx, hipMemcpyAsync(ctx->neq_in.p, target_rgb, npix * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-            q.d_target = (const float*)ctx->neq_in.p;
-        }
-        if (out_images || out_images64) {
-            if ((rc = ensure(ctx, ctx->neq_jac, n_img * (out_images64 ? sizeof(double) : sizeof(float)))) != DRT_OK) return rc;
-            if (out_images64)
-                q.d_images64 = (double*)ctx->neq_jac.p;
-            else
-                q.d_images = (float*)ctx->neq_jac.p;
-        }
-        if (out_loss) {
-            if ((rc = ensure(ctx, ctx->neq_out, (size_t)DRT_SETS_VALUES * sizeof(double))) != DRT_OK) return rc;
-            q.d_loss = (double*)ctx->neq_out.p;
-        }
-    }
-    // (a shard without rows launches nothing: its sums are zero)
-    if (q.d_loss)
-        HIPCHK(ctx, hipMemsetAsync(q.d_loss, 0, (size_t)n_sets * 3 * sizeof(double), ctx->stream));
-    TangentRequest req;
-    req.kind = TangentRequest::Kind::param_sets;
-    req.d_params = ctx->tangent.p;
-    req.sets = &q;
-    if ((rc = render_common(ctx, cam, rp, nullptr, out_rgb, nullptr, stats, -1, nullptr, &req)) != DRT_OK)
-        return rc;
-    if (dev)
-        return DRT_OK;
-    // host buffers: the render has waited for its stream; the losses, and the images' rows of this shard
-    if (out_loss)
-        HIPCHK(ctx, hipMemcpy(out_loss, ctx->neq_out.p, (size_t)n_sets * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    if (out_images || out_images64) {
-        const RenderJob& j = ctx->job;
-        const size_t el = out_images64 ? sizeof(double) : sizeof(float), row = (size_t)cam->width * 3 * el;
-        uint8_t* dst = out_images64 ? (uint8_t*)out_images64 : (uint8_t*)out_images;
-        hipError_t e = hipSuccess;
-        for (size_t k = 0; k < (size_t)n_sets; ++k)
-            for_each_band(cam->height, j.band, j.n_shards, j.shard, [&](int y0, int y1) {
-                const size_t at = k * npix * 3 * el + (size_t)y0 * row;
-                if (e == hipSuccess)
-                    e = hipMemcpy(dst + at, (const uint8_t*)ctx->neq_jac.p + at, (size_t)(y1 - y0) * row, hipMemcpyDeviceToHost);
-            });
-        HIPCHK(ctx, e);
-    }
-    return DRT_OK;
-}
-
-extern "C" {
-
-int drt_hip_render_param_sets(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_params* rp, int32_t n_sets,
-                              const double* param_sets, const float* target_rgb, float* out_images, double* out_loss, float* out_rgb,
-                              drt_hip_stats* stats)
-{
-    return render_param_sets_common(ctx, cam, rp, n_sets, param_sets, target_rgb, out_images, nullptr, out_loss, out_rgb, stats);
-}
-
-int drt_hip_render_param_sets_double(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_params* rp, int32_t n_sets,
-                                     const double* param_sets, const float* target_rgb, double* out_images, double* out_loss, float* out_rgb,
-                                     drt_hip_stats* stats)
-{
-    if (ctx && rp && (rp->flags & DRT_RENDER_DEVICE_OUT))
-        return fail(ctx, DRT_ERR_INVALID, "param sets: the double images come through host buffers only (no DRT_RENDER_DEVICE_OUT)");
-    return render_param_sets_common(ctx, cam, rp, n_sets, param_sets, target_rgb, nullptr, out_images, out_loss, out_rgb, stats);
-}
-
-} // extern "C"
-
-// ---- ... each set with a direction of its own: value, slope and Gauss-Newton curvature of the loss per set, in one trace ----
-static int render_param_sets_along_common(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_params* rp, int32_t n_sets,
-                                          const double* param_sets, const double* param_tangents, const float* target_rgb, float* out_images,
-                                          float* out_tangents, double* out_images64, double* out_tangents64, double* out_loss, double* out_dloss,
-                                          double* out_curv, drt_hip_stats* stats)
-{
-    if (!ctx)
-        return DRT_ERR_INVALID;
-    const PathFormCaller me = {"param sets along", "render the shards on plain contexts", "a forward render", DRT_PATH_LDS_PARAMS,
-                               "more parameters than the path kernels stage (136)"};
-    int rc;
-    if ((rc = refuse_before(ctx, cam, rp, me)) != DRT_OK) return rc;
-    if (n_sets < 1 || n_sets > DRT_HIP_MAX_SETS_ALONG)
-        return refuse(ctx, me, DRT_ERR_INVALID, "n_sets outside 1 ... DRT_HIP_MAX_SETS_ALONG = 4");
-    if (!param_sets || !param_tangents)
-        return refuse(ctx, me, DRT_ERR_INVALID, "NULL param_sets or param_tangents");
-    if (!out_images && !out_images64 && !out_tangents && !out_tangents64 && !out_loss && !out_dloss && !out_curv)
-        return refuse(ctx, me, DRT_ERR_INVALID, "no output requested (out_images, out_tangents, out_loss, out_dloss and out_curv are all NULL)");
-    if ((out_loss || out_dloss) && !target_rgb)
-        return refuse(ctx, me, DRT_ERR_INVALID, "out_loss and out_dloss need target_rgb");
-    if (rp->flags & DRT_RENDER_BACKWARD)
-        return refuse(ctx, me, DRT_ERR_INVALID, "a forward render: no DRT_RENDER_BACKWARD");
-    for (size_t i = 0; i < (size_t)n_sets * (size_t)ctx->n_user_params * 3; ++i) {
-        if (!std::isfinite(param_sets[i]))
-            return refuse(ctx, me, DRT_ERR_INVALID, "a set holds a value that is not finite");
-        if (!std::isfinite(param_tangents[i]))
-            return refuse(ctx, me, DRT_ERR_INVALID, "a direction holds a value that is not finite");
-    }
-    if (!(rp->flags & DRT_RENDER_DEVICE_OUT) && target_rgb)
-        for (size_t i = 0; i < (size_t)cam->width * (size_t)cam->height * 3; ++i)
-            if (!std::isfinite(target_rgb[i]))
-                return refuse(ctx, me, DRT_ERR_INVALID, "the target image holds a value that is not finite");
-    if ((rc = refuse_after(ctx, cam, rp, me)) != DRT_OK) return rc;
-    // (sets at and above n_sets, up to the kernel's width, are the context's own parameters with a zero direction; a mirror's internal
-    //  constant keeps the scene's value and a zero tangent in every set)
-    const int K = n_sets <= 2 ? 2 : 4;
-    if ((rc = stage_rows(ctx, rp, param_sets, 2 * n_sets, 2 * K, true, param_tangents)) != DRT_OK) return rc;
-    const bool dev = (rp->flags & DRT_RENDER_DEVICE_OUT) != 0;
-    const size_t npix = (size_t)cam->width * (size_t)cam->height;
-    // the caller's images: device pointers as they are; host buffers through buffers of the context's own
-    ParamSetsRequest q;
-    q.n_sets = n_sets;
-    q.width = K;
-    q.along = true;
-    const bool wide = out_images64 || out_tangents64;
-    const size_t n_img = (size_t)n_sets * npix * 3, el = wide ? sizeof(double) : sizeof(float);
-    const size_t ns3 = (size_t)n_sets * 3;
-    if (dev) {
-        q.d_target = target_rgb;
-        q.d_images = out_images;
-        q.d_tangents = out_tangents;
+        q.d_images = (float*)out_images;
+        q.d_tangents = (float*)out_tangents;
         q.d_loss = out_loss;
         q.d_dloss = out_dloss;
         q.d_curv = out_curv;
@@ -804,17 +715,17 @@ static int render_param_sets_along_common(drt_hip_ctx* ctx, const drt_camera_des
             HIPCHK(ctx, hipMemcpyAsync(ctx->neq_in.p, target_rgb, npix * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
             q.d_target = (const float*)ctx->neq_in.p;
         }
-        if (out_images || out_images64 || out_tangents || out_tangents64) {
+        if (out_images || out_tangents) {
             // (the images, then the derivative images)
-            if ((rc = ensure(ctx, ctx->neq_jac, 2 * n_img * el)) != DRT_OK) return rc;
+            if ((rc = ensure(ctx, ctx->neq_jac, (form.along ? 2 : 1) * n_img)) != DRT_OK) return rc;
             uint8_t* base = (uint8_t*)ctx->neq_jac.p;
-            if (out_images64) q.d_images64 = (double*)base;
-            if (out_images) q.d_images = (float*)base;
-            if (out_tangents64) q.d_tangents64 = (double*)(base + n_img * el);
-            if (out_tangents) q.d_tangents = (float*)(base + n_img * el);
+            if (out_images && wide) q.d_images64 = (double*)base;
+            if (out_images && !wide) q.d_images = (float*)base;
+            if (out_tangents && wide) q.d_tangents64 = (double*)(base + n_img);
+            if (out_tangents && !wide) q.d_tangents = (float*)(base + n_img);
         }
         if (out_loss || out_dloss || out_curv) {
-            if ((rc = ensure(ctx, ctx->neq_out, (size_t)DRT_SETS_ALONG_VALUES * sizeof(double))) != DRT_OK) return rc;
+            if ((rc = ensure(ctx, ctx->neq_out, (size_t)(form.along ? DRT_SETS_ALONG_VALUES : DRT_SETS_VALUES) * sizeof(double))) != DRT_OK) return rc;
             double* sums = (double*)ctx->neq_out.p;
             if (out_loss) q.d_loss = sums;
             if (out_dloss) q.d_dloss = sums + ns3;
@@ -822,14 +733,13 @@ static int render_param_sets_along_common(drt_hip_ctx* ctx, const drt_camera_des
         }
     }
     // (a shard without rows launches nothing: its sums are zero)
-    if (q.d_loss) HIPCHK(ctx, hipMemsetAsync(q.d_loss, 0, ns3 * sizeof(double), ctx->stream));
-    if (q.d_dloss) HIPCHK(ctx, hipMemsetAsync(q.d_dloss, 0, ns3 * sizeof(double), ctx->stream));
-    if (q.d_curv) HIPCHK(ctx, hipMemsetAsync(q.d_curv, 0, ns3 * sizeof(double), ctx->stream));
+    for (double* sum : {q.d_loss, q.d_dloss, q.d_curv})
+        if (sum) HIPCHK(ctx, hipMemsetAsync(sum, 0, ns3 * sizeof(double), ctx->stream));
     TangentRequest req;
-    req.kind = TangentRequest::Kind::param_sets_along;
+    req.kind = TangentRequest::Kind::param_sets;
     req.d_params = ctx->tangent.p;
     req.sets = &q;
-    if ((rc = render_common(ctx, cam, rp, nullptr, nullptr, nullptr, stats, -1, nullptr, &req)) != DRT_OK)
+    if ((rc = render_common(ctx, cam, rp, nullptr, out_rgb, nullptr, stats, -1, nullptr, &req)) != DRT_OK)
         return rc;
     if (dev)
         return DRT_OK;
@@ -837,44 +747,43 @@ static int render_param_sets_along_common(drt_hip_ctx* ctx, const drt_camera_des
     if (out_loss) HIPCHK(ctx, hipMemcpy(out_loss, q.d_loss, ns3 * sizeof(double), hipMemcpyDeviceToHost));
     if (out_dloss) HIPCHK(ctx, hipMemcpy(out_dloss, q.d_dloss, ns3 * sizeof(double), hipMemcpyDeviceToHost));
     if (out_curv) HIPCHK(ctx, hipMemcpy(out_curv, q.d_curv, ns3 * sizeof(double), hipMemcpyDeviceToHost));
-    const RenderJob& j = ctx->job;
-    const size_t row = (size_t)cam->width * 3 * el;
-    auto fetch = [&](void* out, size_t from) -> int {
-        hipError_t e = hipSuccess;
-        for (size_t k = 0; k < (size_t)n_sets; ++k)
-            for_each_band(cam->height, j.band, j.n_shards, j.shard, [&](int y0, int y1) {
-                const size_t at = k * npix * 3 * el + (size_t)y0 * row;
-                if (e == hipSuccess)
-                    e = hipMemcpy((uint8_t*)out + at, (const uint8_t*)ctx->neq_jac.p + from + at, (size_t)(y1 - y0) * row, hipMemcpyDeviceToHost);
-            });
-        HIPCHK(ctx, e);
-        return DRT_OK;
-    };
-    if (out_images || out_images64)
-        if ((rc = fetch(wide ? (void*)out_images64 : (void*)out_images, 0)) != DRT_OK) return rc;
-    if (out_tangents || out_tangents64)
-        if ((rc = fetch(wide ? (void*)out_tangents64 : (void*)out_tangents, n_img * el)) != DRT_OK) return rc;
+    if (out_images && (rc = fetch_set_images(ctx, cam, n_sets, out_images, 0, el)) != DRT_OK) return rc;
+    if (out_tangents && (rc = fetch_set_images(ctx, cam, n_sets, out_tangents, n_img, el)) != DRT_OK) return rc;
     return DRT_OK;
 }
 
 extern "C" {
 
+int drt_hip_render_param_sets(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_params* rp, int32_t n_sets,
+                              const double* param_sets, const float* target_rgb, float* out_images, double* out_loss, float* out_rgb,
+                              drt_hip_stats* stats)
+{
+    return render_sets_common(ctx, plain_sets, cam, rp, n_sets, param_sets, nullptr, target_rgb, out_images, nullptr, false, out_loss, nullptr, nullptr,
+                              out_rgb, stats);
+}
+
+int drt_hip_render_param_sets_double(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_params* rp, int32_t n_sets,
+                                     const double* param_sets, const float* target_rgb, double* out_images, double* out_loss, float* out_rgb,
+                                     drt_hip_stats* stats)
+{
+    return render_sets_common(ctx, plain_sets, cam, rp, n_sets, param_sets, nullptr, target_rgb, out_images, nullptr, true, out_loss, nullptr, nullptr,
+                              out_rgb, stats);
+}
+
 int drt_hip_render_param_sets_along(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_params* rp, int32_t n_sets,
                                     const double* param_sets, const double* param_tangents, const float* target_rgb, float* out_images,
                                     float* out_tangents, double* out_loss, double* out_dloss, double* out_curv, drt_hip_stats* stats)
 {
-    return render_param_sets_along_common(ctx, cam, rp, n_sets, param_sets, param_tangents, target_rgb, out_images, out_tangents, nullptr, nullptr,
-                                          out_loss, out_dloss, out_curv, stats);
+    return render_sets_common(ctx, sets_along, cam, rp, n_sets, param_sets, param_tangents, target_rgb, out_images, out_tangents, false, out_loss,
+                              out_dloss, out_curv, nullptr, stats);
 }
 
 int drt_hip_render_param_sets_along_double(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_params* rp, int32_t n_sets,
                                            const double* param_sets, const double* param_tangents, const float* target_rgb, double* out_images,
                                            double* out_tangents, double* out_loss, double* out_dloss, double* out_curv, drt_hip_stats* stats)
 {
-    if (ctx && rp && (rp->flags & DRT_RENDER_DEVICE_OUT))
-        return fail(ctx, DRT_ERR_INVALID, "param sets along: the double images come through host buffers only (no DRT_RENDER_DEVICE_OUT)");
-    return render_param_sets_along_common(ctx, cam, rp, n_sets, param_sets, param_tangents, target_rgb, nullptr, nullptr, out_images, out_tangents,
-                                          out_loss, out_dloss, out_curv, stats);
+    return render_sets_common(ctx, sets_along, cam, rp, n_sets, param_sets, param_tangents, target_rgb, out_images, out_tangents, true, out_loss,
+                              out_dloss, out_curv, nullptr, stats);
 }
 
 // ---- asynchronous host-buffer renders ---------------------------------------------------------------

@@ -914,8 +914,10 @@ int path_batch(Shard<R>& s)
                                (const double*)nullptr, 0, 0, DRT_FAST_PARAMS * 3, (double*)nullptr, 0u, (const uint32_t*)counts,
                                0u, s.totals);
         }
+        // what the Jacobian, K-direction and parameter-set forms reduce from `gpix`: per block, then over the blocks (timed in the reduction's slot)
+        double* part = (double*)ctx->neq_part.p;
         if (s.neq) {
-            // the normal equations: per-pixel products reduced per block, then over the blocks (timed in the reduction's slot)
+            // the normal equations: per-pixel products
             const NormalEqRequest& q = *s.neq;
             uint32_t mask = 0;
             for (int p2 = 0; p2 < ctx->n_params && p2 < DRT_FAST_PARAMS; ++p2)
@@ -925,7 +927,6 @@ int path_batch(Shard<R>& s)
             if (s.n_dirs > 0)
                 mask = 0xFFu;
             const int npw = np_width(n_par, DRT_FAST_PARAMS);
-            double* part = (double*)ctx->neq_part.p;
             DRT_TIMED(s, DRT_K_GRADREDUCE, with_int<4, 8>(npw, [&](auto np) {
                 with_bool(s.neq_vw == 2, [&](auto wide) {
                     hipLaunchKernelGGL((k_normal_eq<decltype(np)::value, decltype(wide)::value ? 2 : 1>), dim3(s.neq_blocks, 3), dim3(DRT_BLOCK), 0, ctx->stream, pa,
@@ -937,36 +938,32 @@ int path_batch(Shard<R>& s)
             DRT_TIMED(s, DRT_K_GRADREDUCE,
                       hipLaunchKernelGGL(k_normal_eq_finish, dim3(3 * DRT_NEQ_VALUES(npw)), dim3(DRT_BLOCK), 0, ctx->stream, (const double*)part,
                                          (int)s.neq_blocks, npw, n_out, q.d_A, q.d_b, q.d_loss));
-            st->units[DRT_K_GRADREDUCE] += (uint64_t)a.Pb;
-            st->path_bytes += (uint64_t)pa.n_ranges * a.Pb * (uint64_t)s.jac_rows() * sizeof(double);
         }
-        if (s.sets && s.sets->along) {
-            // the sets' images, derivative images, losses, slopes and curvatures: per-pixel means and products reduced per block, then over the
-            // blocks (timed in the reduction's slot)
+        if (s.sets) {
+            // the sets' images and losses -- with directions: and derivative images, slopes and curvatures --: per-pixel means, squared
+            // residuals and products
             const ParamSetsRequest& q = *s.sets;
             const bool sums = q.d_loss || q.d_dloss || q.d_curv;
-            double* part = (double*)ctx->neq_part.p;
-            DRT_TIMED(s, DRT_K_GRADREDUCE,
-                      hipLaunchKernelGGL(k_sets_along_finish, dim3(s.neq_blocks), dim3(DRT_BLOCK), 0, ctx->stream, pa, (const double*)gpix, s.n_dirs, q.d_target,
-                                         q.d_images, q.d_images64, q.d_tangents, q.d_tangents64, sums ? part : (double*)nullptr));
-            if (sums)
+            double* spart = sums ? part : (double*)nullptr;
+            if (q.along) {
                 DRT_TIMED(s, DRT_K_GRADREDUCE,
-                          hipLaunchKernelGGL(k_sets_along_sums, dim3(DRT_SETS_ALONG_VALUES), dim3(DRT_BLOCK), 0, ctx->stream, (const double*)part, (int)s.neq_blocks,
-                                             s.n_dirs * 9, q.d_loss, q.d_dloss, q.d_curv));
-            st->units[DRT_K_GRADREDUCE] += (uint64_t)a.Pb;
-            st->path_bytes += (uint64_t)pa.n_ranges * a.Pb * (uint64_t)s.jac_rows() * sizeof(double);
-        } else
-        if (s.sets) {
-            // the sets' images and losses: per-pixel means and squared residuals reduced per block, then over the blocks (timed in the reduction's slot)
-            const ParamSetsRequest& q = *s.sets;
-            double* part = (double*)ctx->neq_part.p;
-            DRT_TIMED(s, DRT_K_GRADREDUCE,
-                      hipLaunchKernelGGL(k_sets_finish, dim3(s.neq_blocks), dim3(DRT_BLOCK), 0, ctx->stream, pa, (const double*)gpix, s.n_dirs, q.d_target,
-                                         q.d_images, q.d_images64, q.d_loss ? part : (double*)nullptr));
-            if (q.d_loss)
+                          hipLaunchKernelGGL(k_sets_along_finish, dim3(s.neq_blocks), dim3(DRT_BLOCK), 0, ctx->stream, pa, (const double*)gpix, s.n_dirs, q.d_target,
+                                             q.d_images, q.d_images64, q.d_tangents, q.d_tangents64, spart));
+                if (sums)
+                    DRT_TIMED(s, DRT_K_GRADREDUCE,
+                              hipLaunchKernelGGL(k_sets_along_sums, dim3(DRT_SETS_ALONG_VALUES), dim3(DRT_BLOCK), 0, ctx->stream, (const double*)part, (int)s.neq_blocks,
+                                                 s.n_dirs * 9, q.d_loss, q.d_dloss, q.d_curv));
+            } else {
                 DRT_TIMED(s, DRT_K_GRADREDUCE,
-                          hipLaunchKernelGGL(k_sets_loss_finish, dim3(DRT_SETS_VALUES), dim3(DRT_BLOCK), 0, ctx->stream, (const double*)part, (int)s.neq_blocks,
-                                             s.n_dirs * 3, q.d_loss));
+                          hipLaunchKernelGGL(k_sets_finish, dim3(s.neq_blocks), dim3(DRT_BLOCK), 0, ctx->stream, pa, (const double*)gpix, s.n_dirs, q.d_target,
+                                             q.d_images, q.d_images64, spart));
+                if (sums)
+                    DRT_TIMED(s, DRT_K_GRADREDUCE,
+                              hipLaunchKernelGGL(k_sets_loss_finish, dim3(DRT_SETS_VALUES), dim3(DRT_BLOCK), 0, ctx->stream, (const double*)part, (int)s.neq_blocks,
+                                                 s.n_dirs * 3, q.d_loss));
+            }
+        }
+        if (s.neq || s.sets) {
             st->units[DRT_K_GRADREDUCE] += (uint64_t)a.Pb;
             st->path_bytes += (uint64_t)pa.n_ranges * a.Pb * (uint64_t)s.jac_rows() * sizeof(double);
         }
@@ -1269,8 +1266,8 @@ int render_impl(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_p
     // the request, decoded: what the shard is told, and what the plan below has to come to for the request's form
     using Kind = TangentRequest::Kind;
     const bool forward = tangent && tangent->kind == Kind::forward, jacobian = tangent && tangent->kind == Kind::jacobian,
-               directions = tangent && tangent->kind == Kind::directions, sets_along = tangent && tangent->kind == Kind::param_sets_along,
-               param_sets = (tangent && tangent->kind == Kind::param_sets) || sets_along;
+               directions = tangent && tangent->kind == Kind::directions, param_sets = tangent && tangent->kind == Kind::param_sets,
+               sets_along = param_sets && tangent->sets->along;
     s.fwd_tangent = forward;
     s.keep_sums = forward && tangent->keep_sums;
     s.neq = jacobian || directions ? tangent->neq : nullptr;

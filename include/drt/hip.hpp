@@ -524,6 +524,78 @@ inline int param_index(const FlatScene<T>& flat, const Vector<T, 3, true>& handl
             return (int)p;
     throw std::runtime_error(message_if_unused);
 }
+
+// what the forward-mode entry points refuse before they flatten the scene, in the caller's words (`what`: "forward mode", "a forward render")
+inline void forward_only(const char* who, const Options& opt, const char* what)
+{
+    if (opt.backward || opt.unbiased || opt.sample_loss_l2)
+        throw std::runtime_error(std::string(who) + ": " + what + " takes no reverse-mode option (backward, unbiased, sample_loss_l2)");
+}
+inline void one_device(const char* who, const Options& opt)
+{
+    if (opt.devices.size() > 1)
+        throw std::runtime_error(std::string(who) + ": one device (render shards on plain contexts and add them)");
+}
+
+// K x n_params x 3 rows as the ABI takes them, from K lists of entries that name a handle and a value (entry(t) -> their addresses): every
+// row starts as `start` (n_params x 3; nullptr: zeros) and takes each listed value at its handle's place.  `add`: a handle listed twice
+// adds up -- what render_tangent documents for DIRECTIONS, and only they do it; a set's values and directions keep the last one listed
+template <typename T, typename List, typename Entry>
+inline std::vector<double> rows_of(const char* who, const FlatScene<T>& flat, const std::vector<List>& lists, const double* start, bool add, Entry entry)
+{
+    const std::size_t n = flat.handles.size() * 3;
+    const std::string unused = std::string(who) + ": a listed parameter is not used by the scene";
+    std::vector<double> v(lists.size() * n, 0.0);
+    for (std::size_t k = 0; k < lists.size(); ++k) {
+        if (start)
+            std::copy(start, start + n, v.begin() + (std::ptrdiff_t)(k * n));
+        for (const auto& t : lists[k]) {
+            const std::pair<const Vector<T, 3, true>*, const Vector<T, 3>*> e = entry(t);
+            const int index = param_index(flat, *e.first, unused.c_str());
+            for (int c = 0; c < 3; ++c) {
+                double& at = v[k * n + (std::size_t)index * 3 + c];
+                const double value = double(real((*e.second)[c]));
+                at = add ? at + value : value;
+            }
+        }
+    }
+    return v;
+}
+
+// One channel's Levenberg-Marquardt step: (A + lambda diag A) x = -b over the chosen `rows` of the P x P matrix A (row-major), by a
+// Cholesky factorisation.  -> x, x[i] for rows[i].  Throws `not_positive_definite` where the damped matrix is not.
+inline std::vector<double> damped_cholesky(const double* A, const double* b, std::size_t P, const std::vector<std::size_t>& rows, double lambda,
+                                           const char* not_positive_definite)
+{
+    const std::size_t n = rows.size();
+    std::vector<double> L(n * n), y(n), x(n);
+    // M = A + lambda diag A = L L^T (lower triangle, row by row)
+    for (std::size_t i = 0; i < n; ++i)
+        for (std::size_t j = 0; j <= i; ++j) {
+            double v = A[rows[i] * P + rows[j]] * (i == j ? 1.0 + lambda : 1.0);
+            for (std::size_t k = 0; k < j; ++k)
+                v -= L[i * n + k] * L[j * n + k];
+            if (i == j) {
+                if (!(v > 0.0))
+                    throw std::runtime_error(not_positive_definite);
+                L[i * n + i] = std::sqrt(v);
+            } else
+                L[i * n + j] = v / L[j * n + j];
+        }
+    for (std::size_t i = 0; i < n; ++i) {          // L y = -b
+        double v = -b[rows[i]];
+        for (std::size_t k = 0; k < i; ++k)
+            v -= L[i * n + k] * y[k];
+        y[i] = v / L[i * n + i];
+    }
+    for (std::size_t ii = n; ii-- > 0;) {           // L^T x = y
+        double v = y[ii];
+        for (std::size_t k = ii + 1; k < n; ++k)
+            v -= L[k * n + ii] * x[k];
+        x[ii] = v / L[ii * n + ii];
+    }
+    return x;
+}
 } // namespace detail
 
 // img: width*height row-major (render.cpp:66,82); adjoint: optional per-pixel seed, same layout.
@@ -703,8 +775,7 @@ inline Stats tangent_call(const char* who, const FlatScene<T>& flat, const drt_c
                           std::size_t spp, const std::vector<double>& v, std::vector<double>& img, std::vector<double>& timg,
                           const Options& opt)
 {
-    if (opt.backward || opt.unbiased || opt.sample_loss_l2)
-        throw std::runtime_error(std::string(who) + ": forward mode takes no reverse-mode option (backward, unbiased, sample_loss_l2)");
+    forward_only(who, opt, "forward mode");
     const std::size_t n = (std::size_t)cd.width * (std::size_t)cd.height * 3;
     const drt_render_params rp = render_params(absorb, min_bounces, spp, opt, f64_flag(opt));
     drt_hip_stats st{};
@@ -732,12 +803,8 @@ inline Stats render_tangent(const Scene<T>& scene, const Camera<T>& cam, const P
                             Vector<T, 3>* tangent_img, const Options& opt = Options())
 {
     FlatScene<T> flat = flatten(scene);
-    std::vector<double> v(flat.handles.size() * 3, 0.0);
-    for (const auto& t : tangents) {
-        const int index = detail::param_index(flat, t.first, "drt::hip::render_tangent: a listed parameter is not used by the scene");
-        for (int c = 0; c < 3; ++c)
-            v[(std::size_t)index * 3 + c] += double(real(t.second[c]));
-    }
+    const std::vector<double> v = detail::rows_of("drt::hip::render_tangent", flat, std::vector<std::decay_t<decltype(tangents)>>{tangents}, nullptr, true,
+                                                  [](const auto& t) { return std::make_pair(&t.first, &t.second); });
     std::vector<double> rgb, trgb;
     const Stats st = detail::tangent_call("drt::hip::render_tangent", flat, describe(cam), tracer.absorb(), tracer.min_bounces(), spp, v, rgb, trgb, opt);
     const std::size_t npix = cam.width() * cam.height();
@@ -770,36 +837,11 @@ struct NormalEquations {
         for (std::size_t p = 0; p < P; ++p)
             if (p >= requires_grad.size() || requires_grad[p])
                 rows.push_back(p);
-        const std::size_t n = rows.size();
-        std::vector<double> L(n * n), y(n);
-        for (int ch = 0; ch < 3; ++ch) {
-            const double* Ac = A.data() + (std::size_t)ch * P * P;
-            const double* bc = b.data() + (std::size_t)ch * P;
-            // M = A + lambda diag A = L L^T (lower triangle, row by row)
-            for (std::size_t i = 0; i < n; ++i)
-                for (std::size_t j = 0; j <= i; ++j) {
-                    double v = Ac[rows[i] * P + rows[j]] * (i == j ? 1.0 + lambda : 1.0);
-                    for (std::size_t k = 0; k < j; ++k)
-                        v -= L[i * n + k] * L[j * n + k];
-                    if (i == j) {
-                        if (!(v > 0.0))
-                            throw std::runtime_error("drt::hip::NormalEquations::solve: the damped matrix of a channel is not positive definite");
-                        L[i * n + i] = std::sqrt(v);
-                    } else
-                        L[i * n + j] = v / L[j * n + j];
-                }
-            for (std::size_t i = 0; i < n; ++i) {          // L y = -b
-                double v = -bc[rows[i]];
-                for (std::size_t k = 0; k < i; ++k)
-                    v -= L[i * n + k] * y[k];
-                y[i] = v / L[i * n + i];
-            }
-            for (std::size_t ii = n; ii-- > 0;) {           // L^T x = y
-                double v = y[ii];
-                for (std::size_t k = ii + 1; k < n; ++k)
-                    v -= L[k * n + ii] * step[rows[k] * 3 + (std::size_t)ch];
-                step[rows[ii] * 3 + (std::size_t)ch] = v / L[ii * n + ii];
-            }
+        for (std::size_t ch = 0; ch < 3; ++ch) {
+            const std::vector<double> x = detail::damped_cholesky(A.data() + ch * P * P, b.data() + ch * P, P, rows, lambda,
+                                                                  "drt::hip::NormalEquations::solve: the damped matrix of a channel is not positive definite");
+            for (std::size_t i = 0; i < rows.size(); ++i)
+                step[rows[i] * 3 + ch] = x[i];
         }
         return step;
     }
@@ -862,15 +904,7 @@ namespace detail {
 template <typename T>
 inline std::vector<double> directions_of(const char* who, const FlatScene<T>& flat, const std::vector<Direction<T>>& directions)
 {
-    const std::size_t n = flat.handles.size() * 3;
-    std::vector<double> v(directions.size() * n, 0.0);
-    for (std::size_t k = 0; k < directions.size(); ++k)
-        for (const auto& t : directions[k]) {
-            const int index = param_index(flat, t.first, (std::string(who) + ": a listed parameter is not used by the scene").c_str());
-            for (int c = 0; c < 3; ++c)
-                v[k * n + (std::size_t)index * 3 + c] += double(real(t.second[c]));
-        }
-    return v;
+    return rows_of(who, flat, directions, nullptr, true, [](const auto& t) { return std::make_pair(&t.first, &t.second); });
 }
 // the one call behind render_tangents and normal_equations_along: A, b, loss where `in` is given, the K images where `timg` is
 template <typename T>
@@ -878,10 +912,8 @@ inline Stats tangents_call(const char* who, const FlatScene<T>& flat, const drt_
                            std::size_t spp, std::size_t K, const std::vector<double>& v, const float* in, bool in_is_residual,
                            std::vector<float>& rgb, std::vector<float>* timg, double* A, double* b, double* loss, const Options& opt)
 {
-    if (opt.backward || opt.unbiased || opt.sample_loss_l2)
-        throw std::runtime_error(std::string(who) + ": forward mode takes no reverse-mode option (backward, unbiased, sample_loss_l2)");
-    if (opt.devices.size() > 1)
-        throw std::runtime_error(std::string(who) + ": one device (render shards on plain contexts and add them)");
+    forward_only(who, opt, "forward mode");
+    one_device(who, opt);
     const std::size_t n = (std::size_t)cd.width * (std::size_t)cd.height * 3;
     rgb.assign(n, 0.f);
     if (timg)
@@ -930,43 +962,20 @@ struct NormalEquationsAlong {
     Stats stats;
     std::vector<double> solve(double lambda) const
     {
-        // (NormalEquations::solve's Cholesky step, with the rows chosen per channel: those whose diagonal is positive)
+        // (NormalEquations::solve's step, with the rows chosen per channel: those whose diagonal is positive)
         const std::size_t K = n_dirs;
         std::vector<double> step(K * 3, 0.0);
-        for (int ch = 0; ch < 3; ++ch) {
-            const double* Ac = A.data() + (std::size_t)ch * K * K;
-            const double* bc = b.data() + (std::size_t)ch * K;
+        for (std::size_t ch = 0; ch < 3; ++ch) {
+            const double* Ac = A.data() + ch * K * K;
             std::vector<std::size_t> rows;
             for (std::size_t k = 0; k < K; ++k)
                 if (Ac[k * K + k] > 0.0)
                     rows.push_back(k);
-            const std::size_t n = rows.size();
-            std::vector<double> L(n * n), y(n);
-            for (std::size_t i = 0; i < n; ++i)
-                for (std::size_t j = 0; j <= i; ++j) {
-                    double v = Ac[rows[i] * K + rows[j]] * (i == j ? 1.0 + lambda : 1.0);
-                    for (std::size_t k = 0; k < j; ++k)
-                        v -= L[i * n + k] * L[j * n + k];
-                    if (i == j) {
-                        if (!(v > 0.0))
-                            throw std::runtime_error("drt::hip::NormalEquationsAlong::solve: the damped matrix of a channel is not positive definite "
-                                                     "(linearly dependent directions: give it lambda > 0)");
-                        L[i * n + i] = std::sqrt(v);
-                    } else
-                        L[i * n + j] = v / L[j * n + j];
-                }
-            for (std::size_t i = 0; i < n; ++i) {          // L y = -b
-                double v = -bc[rows[i]];
-                for (std::size_t k = 0; k < i; ++k)
-                    v -= L[i * n + k] * y[k];
-                y[i] = v / L[i * n + i];
-            }
-            for (std::size_t ii = n; ii-- > 0;) {           // L^T x = y
-                double v = y[ii];
-                for (std::size_t k = ii + 1; k < n; ++k)
-                    v -= L[k * n + ii] * step[rows[k] * 3 + (std::size_t)ch];
-                step[rows[ii] * 3 + (std::size_t)ch] = v / L[ii * n + ii];
-            }
+            const std::vector<double> x = detail::damped_cholesky(Ac, b.data() + ch * K, K, rows, lambda,
+                                                                  "drt::hip::NormalEquationsAlong::solve: the damped matrix of a channel is not positive "
+                                                                  "definite (linearly dependent directions: give it lambda > 0)");
+            for (std::size_t i = 0; i < rows.size(); ++i)
+                step[rows[i] * 3 + ch] = x[i];
         }
         return step;
     }
@@ -1005,6 +1014,37 @@ inline NormalEquationsAlong<T> normal_equations_along(const Scene<T>& scene, con
 template <typename T>
 using ParamSet = std::vector<std::pair<Vector<T, 3, true>, Vector<T, 3>>>;
 
+namespace detail {
+// the one call behind render_param_sets and render_param_sets_along: the target as floats, the image buffers, the caller's entry point
+// `abi(context, camera, render parameters, target, images, derivative images, statistics)` on the first device, the images back
+template <typename T, typename Abi>
+inline Stats sets_call(const char* abi_name, const FlatScene<T>& flat, const Camera<T>& cam, const Pathtracer<T>& tracer, std::size_t spp,
+                       std::size_t K, const Vector<T, 3>* target, Vector<T, 3>* imgs, Vector<T, 3>* tangent_imgs, const Options& opt, Abi abi)
+{
+    const drt_camera_desc cd = describe(cam);
+    const std::size_t npix = cam.width() * cam.height();
+    std::vector<float> tgt, out, tout;
+    if (target)
+        tgt = to_floats(target, npix);
+    if (imgs)
+        out.assign((K ? K : 1) * npix * 3, 0.f);
+    if (tangent_imgs)
+        tout.assign((K ? K : 1) * npix * 3, 0.f);
+    const drt_render_params rp = render_params(tracer.absorb(), tracer.min_bounces(), spp, opt, f64_flag(opt));
+    drt_hip_stats st{};
+    {
+        Session s = Session::on_first_device(opt, flat);
+        s.ctx.check(abi(s.ctx.get(), &cd, &rp, target ? tgt.data() : nullptr, imgs ? out.data() : nullptr, tangent_imgs ? tout.data() : nullptr, &st),
+                    abi_name);
+    }
+    if (imgs)
+        from_buffer(out.data(), npix * K, imgs);
+    if (tangent_imgs)
+        from_buffer(tout.data(), npix * K, tangent_imgs);
+    return to_stats(st);
+}
+} // namespace detail
+
 // What a frame looks like, and what its loss is, under each of up to DRT_HIP_MAX_PARAM_SETS parameter sets: imgs[k * width * height +
 // pixel] is what render() gives with sets[k] installed (nullptr: no images), losses[k * 3 + ch] the sum over the pixels of
 // (mean_k - target)^2 where `target` (width x height) is given, empty otherwise.  The scene's own values are not changed.
@@ -1014,45 +1054,24 @@ inline Stats render_param_sets(const Scene<T>& scene, const Camera<T>& cam, cons
                                std::vector<double>* losses, const Options& opt = Options())
 {
     const char* who = "drt::hip::render_param_sets";
-    if (opt.backward || opt.unbiased || opt.sample_loss_l2)
-        throw std::runtime_error(std::string(who) + ": a forward render takes no reverse-mode option (backward, unbiased, sample_loss_l2)");
-    if (opt.devices.size() > 1)
-        throw std::runtime_error(std::string(who) + ": one device (render shards on plain contexts and add them)");
+    detail::forward_only(who, opt, "a forward render");
+    detail::one_device(who, opt);
     if (!imgs && !(losses && target))
         throw std::runtime_error(std::string(who) + ": no output requested (images, or losses with a target)");
     if (losses && !target)
         throw std::runtime_error(std::string(who) + ": losses need a target");
     FlatScene<T> flat = flatten(scene);
-    const std::size_t n = flat.handles.size() * 3, K = sets.size();
-    std::vector<double> values(K * n);
-    for (std::size_t k = 0; k < K; ++k) {
-        std::copy(flat.params.begin(), flat.params.begin() + (std::ptrdiff_t)n, values.begin() + (std::ptrdiff_t)(k * n));
-        for (const auto& t : sets[k]) {
-            const int index = detail::param_index(flat, t.first, (std::string(who) + ": a listed parameter is not used by the scene").c_str());
-            for (int c = 0; c < 3; ++c)
-                values[k * n + (std::size_t)index * 3 + c] = double(real(t.second[c]));
-        }
-    }
-    const drt_camera_desc cd = describe(cam);
-    const std::size_t npix = cam.width() * cam.height();
-    std::vector<float> tgt, out;
-    if (target)
-        tgt = detail::to_floats(target, npix);
-    if (imgs)
-        out.assign((K ? K : 1) * npix * 3, 0.f);
+    const std::size_t K = sets.size();
+    const std::vector<double> values =
+        detail::rows_of(who, flat, sets, flat.params.data(), false, [](const auto& t) { return std::make_pair(&t.first, &t.second); });
     if (losses)
         losses->assign(K * 3, 0.0);
-    const drt_render_params rp = detail::render_params(tracer.absorb(), tracer.min_bounces(), spp, opt, detail::f64_flag(opt));
-    drt_hip_stats st{};
-    {
-        detail::Session s = detail::Session::on_first_device(opt, flat);
-        s.ctx.check(drt_hip_render_param_sets(s.ctx.get(), &cd, &rp, (int32_t)K, values.data(), target ? tgt.data() : nullptr,
-                                              imgs ? out.data() : nullptr, (losses && K) ? losses->data() : nullptr, nullptr, &st),
-                    "drt_hip_render_param_sets");
-    }
-    if (imgs)
-        detail::from_buffer(out.data(), npix * K, imgs);
-    return detail::to_stats(st);
+    return detail::sets_call("drt_hip_render_param_sets", flat, cam, tracer, spp, K, target, imgs, (Vector<T, 3>*)nullptr, opt,
+                             [&](drt_hip_ctx* ctx, const drt_camera_desc* cd, const drt_render_params* rp, const float* tgt, float* out, float*,
+                                 drt_hip_stats* st) {
+                                 return drt_hip_render_param_sets(ctx, cd, rp, (int32_t)K, values.data(), tgt, out,
+                                                                  (losses && K) ? losses->data() : nullptr, nullptr, st);
+                             });
 }
 
 // ---- ... each set with a direction of its own (drt_hip_render_param_sets_along) ----------------------------------------------
@@ -1083,53 +1102,27 @@ inline SetsAlong<T> render_param_sets_along(const Scene<T>& scene, const Camera<
                                             Vector<T, 3>* tangent_imgs = nullptr, const Options& opt = Options())
 {
     const char* who = "drt::hip::render_param_sets_along";
-    if (opt.backward || opt.unbiased || opt.sample_loss_l2)
-        throw std::runtime_error(std::string(who) + ": a forward render takes no reverse-mode option (backward, unbiased, sample_loss_l2)");
-    if (opt.devices.size() > 1)
-        throw std::runtime_error(std::string(who) + ": one device (render shards on plain contexts and add them)");
+    detail::forward_only(who, opt, "a forward render");
+    detail::one_device(who, opt);
     FlatScene<T> flat = flatten(scene);
-    const std::size_t n = flat.handles.size() * 3, K = sets.size();
-    std::vector<double> values(K * n), dirs(K * n, 0.0);
-    for (std::size_t k = 0; k < K; ++k) {
-        std::copy(flat.params.begin(), flat.params.begin() + (std::ptrdiff_t)n, values.begin() + (std::ptrdiff_t)(k * n));
-        for (const auto& t : sets[k]) {
-            const int index = detail::param_index(flat, t.handle, (std::string(who) + ": a listed parameter is not used by the scene").c_str());
-            for (int c = 0; c < 3; ++c) {
-                values[k * n + (std::size_t)index * 3 + c] = double(real(t.value[c]));
-                dirs[k * n + (std::size_t)index * 3 + c] = double(real(t.direction[c]));
-            }
-        }
-    }
-    const drt_camera_desc cd = describe(cam);
-    const std::size_t npix = cam.width() * cam.height();
-    std::vector<float> tgt, out, tout;
-    if (target)
-        tgt = detail::to_floats(target, npix);
-    if (imgs)
-        out.assign((K ? K : 1) * npix * 3, 0.f);
-    if (tangent_imgs)
-        tout.assign((K ? K : 1) * npix * 3, 0.f);
+    const std::size_t K = sets.size();
+    const std::vector<double> values =
+        detail::rows_of(who, flat, sets, flat.params.data(), false, [](const auto& t) { return std::make_pair(&t.handle, &t.value); });
+    const std::vector<double> dirs = detail::rows_of(who, flat, sets, nullptr, false, [](const auto& t) { return std::make_pair(&t.handle, &t.direction); });
     SetsAlong<T> r;
     if (target) {
         r.losses.assign(K * 3, 0.0);
         r.slopes.assign(K * 3, 0.0);
     }
     r.curvatures.assign(K * 3, 0.0);
-    const drt_render_params rp = detail::render_params(tracer.absorb(), tracer.min_bounces(), spp, opt, detail::f64_flag(opt));
-    drt_hip_stats st{};
-    {
-        detail::Session s = detail::Session::on_first_device(opt, flat);
-        s.ctx.check(drt_hip_render_param_sets_along(s.ctx.get(), &cd, &rp, (int32_t)K, values.data(), dirs.data(), target ? tgt.data() : nullptr,
-                                                    imgs ? out.data() : nullptr, tangent_imgs ? tout.data() : nullptr,
-                                                    (target && K) ? r.losses.data() : nullptr, (target && K) ? r.slopes.data() : nullptr,
-                                                    K ? r.curvatures.data() : nullptr, &st),
-                    "drt_hip_render_param_sets_along");
-    }
-    if (imgs)
-        detail::from_buffer(out.data(), npix * K, imgs);
-    if (tangent_imgs)
-        detail::from_buffer(tout.data(), npix * K, tangent_imgs);
-    r.stats = detail::to_stats(st);
+    r.stats = detail::sets_call("drt_hip_render_param_sets_along", flat, cam, tracer, spp, K, target, imgs, tangent_imgs, opt,
+                                [&](drt_hip_ctx* ctx, const drt_camera_desc* cd, const drt_render_params* rp, const float* tgt, float* out, float* tout,
+                                    drt_hip_stats* st) {
+                                    return drt_hip_render_param_sets_along(ctx, cd, rp, (int32_t)K, values.data(), dirs.data(), tgt, out, tout,
+                                                                           (target && K) ? r.losses.data() : nullptr,
+                                                                           (target && K) ? r.slopes.data() : nullptr,
+                                                                           K ? r.curvatures.data() : nullptr, st);
+                                });
     return r;
 }
 

@@ -1,6 +1,6 @@
-"""Every refusal of the five families of entry points that run on the one-launch path kernel's special forms -- drt_hip_render_tangent /
-_double, _render_normal_equations, _render_tangents, _render_normal_equations_along, _render_param_sets / _double -- with its status and
-its COMPLETE message, compared with ==.  The other GPU files match a word or two of each message; this one pins the bytes, so that the
+"""Every refusal of the six families of entry points that run on the one-launch path kernel's special forms -- drt_hip_render_tangent /
+_double, _render_normal_equations, _render_tangents, _render_normal_equations_along, _render_param_sets / _double, _render_param_sets_along /
+_double -- with its status and its COMPLETE message, compared with ==.  The other GPU files match a word or two of each message; this one pins the bytes, so that the
 checks the families share can live in one place without a caller seeing a difference.
 
 All calls go straight through the C ABI (the Python mirror refuses some shapes and values before the call).  The frame is the 16 x 12
@@ -26,11 +26,15 @@ ARGS = {
     "render_normal_equations_along": ("n", "dirs", "target", "residual", "rgb", "A", "b", "loss", "jac"),
     "render_param_sets": ("n", "dirs", "target", "jac", "loss", "rgb"),
     "render_param_sets_double": ("n", "dirs", "target", "jac64", "loss", "rgb"),
+    "render_param_sets_along": ("n", "dirs", "dirs2", "target", "jac", "timgs", "loss", "dloss", "curv"),
+    "render_param_sets_along_double": ("n", "dirs", "dirs2", "target", "jac64", "timgs64", "loss", "dloss", "curv"),
 }
-# what a call passes unless its row says otherwise (a valid call of each entry point); "dirs" are the directions / the sets
+# what a call passes unless its row says otherwise (a valid call of each entry point); "dirs" are the directions / the sets, "dirs2" the
+# directions of the sets
 DEFAULTS = {"n": 2, "residual": None, "rgb": None}
 NE, ALONG, TS, PS, PSD, RT, RTD = ("render_normal_equations", "render_normal_equations_along", "render_tangents", "render_param_sets",
                                   "render_param_sets_double", "render_tangent", "render_tangent_double")
+PSA, PSAD = "render_param_sets_along", "render_param_sets_along_double"
 FLAGS = ("RENDER_UNFUSED", "RENDER_UNBIASED", "RENDER_LOSS_L2", "RENDER_ALLREDUCE", "RENDER_ALLREDUCE_ASYNC")
 TOO_MANY_SAMPLES = (1 << 31) // (W * H) + 1          # W x H x spp just above 2^31 - 1
 
@@ -46,8 +50,7 @@ RT_BPL = ("render_tangent: the tangent image comes from the one-launch path kern
 NE_FLAGS = ("normal equations: not with DRT_RENDER_UNFUSED, _UNBIASED, _LOSS_L2 or _ALLREDUCE* -- the biased operator on the "
             "one-launch path kernel, one context")
 FWD_FLAGS = "not with DRT_RENDER_UNFUSED, _UNBIASED, _LOSS_L2 or _ALLREDUCE* -- forward mode on the one-launch path kernel, one context"
-PS_FLAGS = ("param sets: not with DRT_RENDER_UNFUSED, _UNBIASED, _LOSS_L2 or _ALLREDUCE* -- a forward render on the one-launch path "
-            "kernel, one context")
+SETS_FLAGS = "not with DRT_RENDER_UNFUSED, _UNBIASED, _LOSS_L2 or _ALLREDUCE* -- a forward render on the one-launch path kernel, one context"
 NE_CAP_USER = ("normal equations: more than DRT_FAST_PARAMS = 8 parameters (the Jacobian is the path kernel's gradient "
                "columns, which stop there; J^T J v by drt_hip_render_tangent + drt_hip_render is the matrix-free route)")
 NE_CAP_MIRROR = ("normal equations: the scene's parameters and the constant a mirror material adds take more than DRT_FAST_PARAMS = 8 "
@@ -56,7 +59,7 @@ BAD_CAMERA = "bad camera or render parameters"
 
 # (where, entry point, how to provoke, status, complete message).  `where`: the context and scene the row runs on.  `how`: arguments
 # replaced ("cam": a camera, or None for NULL; "rp": a dict of RenderParams fields, or None for NULL; "flags": or-ed into rp.flags;
-# "bad": a value stored into "dirs"; "bad_target": a value stored into the target)
+# "bad": a value stored into "dirs"; "bad2": into "dirs2", at the same index; "bad_target": a value stored into the target)
 ROWS = []
 
 
@@ -69,18 +72,21 @@ for fn, who, group_hint in ((NE, "normal equations", " (render the shards on pla
                             (TS, "tangents", " (render the shards on plain contexts)"),
                             (ALONG, "normal equations along", " (render the shards on plain contexts)"),
                             (PS, "param sets", " (render the shards on plain contexts)"),
-                            (PSD, "param sets", " (render the shards on plain contexts)")):
+                            (PSD, "param sets", " (render the shards on plain contexts)"),
+                            (PSA, "param sets along", " (render the shards on plain contexts)"),
+                            (PSAD, "param sets along", " (render the shards on plain contexts)")):
     row("group", fn, {}, "DRT_ERR_UNSUPPORTED", f"{who}: not on a group context{group_hint}")
     row("empty", fn, {}, "DRT_ERR_NO_SCENE", "render before upload_scene")
     for how in ({"cam": None}, {"rp": None}, {"cam": (0, H)}, {"cam": (W, -1)}):
         row("cornell", fn, how, "DRT_ERR_INVALID", f"{who}: {BAD_CAMERA}")
     row("inflight", fn, {}, "DRT_ERR_INVALID", f"{who}: {INFLIGHT}")
     for flag in FLAGS:
-        row("cornell", fn, {"flags": flag}, "DRT_ERR_UNSUPPORTED", NE_FLAGS if fn == NE else PS_FLAGS if fn in (PS, PSD) else f"{who}: {FWD_FLAGS}")
+        row("cornell", fn, {"flags": flag}, "DRT_ERR_UNSUPPORTED", NE_FLAGS if fn == NE else f"{who}: {SETS_FLAGS if fn in (PS, PSD, PSA, PSAD) else FWD_FLAGS}")
     row("mesh", fn, {}, "DRT_ERR_UNSUPPORTED", f"{who}: {MESH}")
     row("cornell", fn, {"rp": {"bounces_per_launch": 1}}, "DRT_ERR_UNSUPPORTED", f"{who}: {BPL}")
     row("many137", fn, {}, "DRT_ERR_UNSUPPORTED", NE_CAP_USER if fn == NE else f"{who}: {CAP136}")
-    row("cornell", fn, {"rp": {"spp": TOO_MANY_SAMPLES}, "target": None, "loss": None} if fn in (PS, PSD) else {"rp": {"spp": TOO_MANY_SAMPLES}},
+    row("cornell", fn, {"rp": {"spp": TOO_MANY_SAMPLES}, "target": None, "loss": None} if fn in (PS, PSD)
+        else {"rp": {"spp": TOO_MANY_SAMPLES}, "target": None, "loss": None, "dloss": None} if fn in (PSA, PSAD) else {"rp": {"spp": TOO_MANY_SAMPLES}},
         "DRT_ERR_UNSUPPORTED", f"{who}: {SAMPLES}")
 
 # ---- paths that end at depth 0 never reach the path kernel: refused once the shard is planned, in the form's words
@@ -95,6 +101,11 @@ for fn in (TS, ALONG):
 for fn in (PS, PSD):
     row("cornell", fn, DEPTH0, "DRT_ERR_UNSUPPORTED",
         "param sets: they come from the one-launch path kernel's parameter-set form over the whole shard in one batch, "
+        "which this render does not take (a DRT_HIP_* setting that forces the queue wavefront or a batch size, paths "
+        "that end at depth 0, or a scene its intersection program does not cover)")
+for fn in (PSA, PSAD):
+    row("cornell", fn, DEPTH0, "DRT_ERR_UNSUPPORTED",
+        "param sets along: they come from the one-launch path kernel's parameter-set form with directions over the whole shard in one batch, "
         "which this render does not take (a DRT_HIP_* setting that forces the queue wavefront or a batch size, paths "
         "that end at depth 0, or a scene its intersection program does not cover)")
 
@@ -137,6 +148,26 @@ for fn in (PS, PSD):
 row("cornell", PSD, {"flags": "RENDER_DEVICE_OUT"}, "DRT_ERR_INVALID",
     "param sets: the double images come through host buffers only (no DRT_RENDER_DEVICE_OUT)")
 
+# ---- the parameter sets with a direction each: their own
+for fn in (PSA, PSAD):
+    for n in (0, 5, -1):
+        row("cornell", fn, {"n": n}, "DRT_ERR_INVALID", "param sets along: n_sets outside 1 ... DRT_HIP_MAX_SETS_ALONG = 4")
+    for array in ("dirs", "dirs2"):
+        row("cornell", fn, {array: None}, "DRT_ERR_INVALID", "param sets along: NULL param_sets or param_tangents")
+    row("cornell", fn, {"jac": None, "jac64": None, "timgs": None, "timgs64": None, "loss": None, "dloss": None, "curv": None}, "DRT_ERR_INVALID",
+        "param sets along: no output requested (out_images, out_tangents, out_loss, out_dloss and out_curv are all NULL)")
+    for other in ("dloss", "loss"):                      # out_loss alone, out_dloss alone
+        row("cornell", fn, {"target": None, other: None}, "DRT_ERR_INVALID", "param sets along: out_loss and out_dloss need target_rgb")
+    row("cornell", fn, {"flags": "RENDER_BACKWARD"}, "DRT_ERR_INVALID", "param sets along: a forward render: no DRT_RENDER_BACKWARD")
+    for bad in (np.nan, np.inf):
+        row("cornell", fn, {"bad": bad}, "DRT_ERR_INVALID", "param sets along: a set holds a value that is not finite")
+        row("cornell", fn, {"bad2": bad}, "DRT_ERR_INVALID", "param sets along: a direction holds a value that is not finite")
+        row("cornell", fn, {"bad_target": bad}, "DRT_ERR_INVALID", "param sets along: the target image holds a value that is not finite")
+    # (both arrays bad at the same index: the set is looked at first)
+    row("cornell", fn, {"bad": np.nan, "bad2": np.inf}, "DRT_ERR_INVALID", "param sets along: a set holds a value that is not finite")
+row("cornell", PSAD, {"flags": "RENDER_DEVICE_OUT"}, "DRT_ERR_INVALID",
+    "param sets along: the double images come through host buffers only (no DRT_RENDER_DEVICE_OUT)")
+
 # ---- forward mode along one direction: the oldest form, in its own words throughout
 for fn in (RT, RTD):
     row("group", fn, {}, "DRT_ERR_UNSUPPORTED", "render_tangent: not on a group context")
@@ -176,14 +207,19 @@ def provoke(pkg, r, fn, how):
     P = r.scene.n_params if r.scene is not None else 4
     a = dict(DEFAULTS)
     a["dirs"] = np.random.RandomState(5).uniform(0.1, 0.9, (9, P, 3))
+    a["dirs2"] = np.random.RandomState(7).uniform(-1, 1, (9, P, 3))
     a["target"] = np.random.RandomState(6).uniform(0, 1, (H, W, 3)).astype(np.float32)
     if "bad" in how:
         a["dirs"][1 if fn not in (RT, RTD) else 0, 2, 1] = how["bad"]
+    if "bad2" in how:
+        a["dirs2"][1, 2, 1] = how["bad2"]
     if "bad_target" in how:
         a["target"][3, 5, 1] = how["bad_target"]
     n_rows = max(P, 9)
     for name, shape, dtype in (("timg", (H, W, 3), np.float32), ("timg64", (H, W, 3), np.float64), ("rgb64", (H, W, 3), np.float64),
                                ("A", (3, n_rows, n_rows), np.float64), ("b", (3, n_rows), np.float64), ("loss", (n_rows, 3), np.float64),
+                               ("dloss", (n_rows, 3), np.float64), ("curv", (n_rows, 3), np.float64),
+                               ("timgs", (n_rows, H, W, 3), np.float32), ("timgs64", (n_rows, H, W, 3), np.float64),
                                ("jac", (n_rows, H, W, 3), np.float32), ("jac64", (n_rows, H, W, 3), np.float64)):
         a[name] = np.zeros(shape, dtype)
     spare_rgb = np.zeros((H, W, 3), np.float32)

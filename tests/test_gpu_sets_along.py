@@ -372,6 +372,41 @@ def test_device_pointers(pkg, hip):
         d.free()
 
 
+def test_three_shards_tile_the_whole(pkg, hip):
+    """7b: the counterpart of test_gpu_param_sets.py's shard check, on the scene whose internal constant (the mirror's) makes the staged rows
+    longer than the caller's: 13 rows in bands of 4 dealt to 3 shards (shard 0 has two bands, the last band is one row), K = 3 on the
+    width-4 kernel.  The shards' images and derivative images tile the unsharded call's exactly -- each shard writes its own rows and no
+    other --, and their sums add up to the unsharded call's within 1e-12 of the largest (fp64 summation order only)"""
+    scene = pkg.scene_by_name("cornell_mirror")
+    cam = pkg.cornell_camera(20, 13)
+    hip.upload_scene(scene)
+    P, D = three_sets(scene, 12)
+    target = np.random.RandomState(8).uniform(0, 1, (cam.height, cam.width, 3)).astype(np.float32)
+    rp = pkg.RenderParams(spp=3, seed=2, min_bounces=3, absorb=1.0)
+    for f64 in (False, True):
+        for double in (False, True):
+            whole = hip.render_param_sets_along(cam, rp, P, D, target=target, f64=f64, double=double)
+            assert np.abs(whole["images"]).max() > 0 and np.abs(whole["tangents"]).max() > 0
+            tiles = {key: np.zeros_like(whole[key]) for key in ("images", "tangents")}
+            sums = {key: np.zeros((3, 3)) for key in ("loss", "dloss", "curv")}
+            for shard in range(3):
+                part = hip.render_param_sets_along(cam, dataclasses.replace(rp, shard=shard, n_shards=3, band_rows=4), P, D, target=target,
+                                                   f64=f64, double=double)
+                rows = pkg.shard_rows(cam.height, 4, 3, shard)
+                others = np.setdiff1d(np.arange(cam.height), rows)
+                for key in tiles:
+                    assert part[key].dtype == whole[key].dtype and not part[key][:, others].any(), (key, shard)
+                    tiles[key][:, rows] = part[key][:, rows]
+                for key in sums:
+                    sums[key] += part[key]
+            for key in tiles:
+                assert np.array_equal(tiles[key], whole[key]), (key, f64, double)
+            for key in sums:
+                top = np.abs(whole[key]).max()
+                print(f"f64={f64} double={double} {key}: shards' sum differs by {np.abs(sums[key] - whole[key]).max() / top:.3e} of the largest")
+                assert top > 0 and np.abs(sums[key] - whole[key]).max() <= 1e-12 * top, key
+
+
 def test_refusals_leave_the_context_usable(pkg, hip):
     """8: every refusal with its status and its whole message -- the form's own and the ones it shares with "param sets", in the same
     words --; after EACH of them render(backward=True) returns the bits it returned before"""
