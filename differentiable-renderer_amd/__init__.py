@@ -46,6 +46,7 @@ KERNEL_NAMES = ["raygen", "intersect", "shade", "film", "backward", "gradreduce"
 MAX_DIRS = 8                 # DRT_HIP_MAX_DIRS: directions per render_tangents / render_normal_equations_along call
 MAX_PARAM_SETS = 8           # DRT_HIP_MAX_PARAM_SETS: parameter sets per render_param_sets call
 MAX_SETS_ALONG = 4           # DRT_HIP_MAX_SETS_ALONG: parameter sets with a direction each per render_param_sets_along call
+MAX_SETS_GRAD = 8            # DRT_HIP_MAX_SETS_GRAD: parameter sets with a summed gradient each per render_param_sets_grad call
 ABI_VERSION = 8
 UNIQUE_ID_BYTES = 128
 
@@ -722,12 +723,14 @@ class DrtHipError(RuntimeError):
     pass
 
 
-def check_param_sets(sets, n_params: int, tangents=None):
+def check_param_sets(sets, n_params: int, tangents=None, grad: bool = False):
     """K parameter sets as drt_hip_render_param_sets takes them: float64 [K, n_params, 3], 1 <= K <= MAX_PARAM_SETS, finite values -- or,
     with `tangents`, the sets and their K directions as drt_hip_render_param_sets_along takes them: the same shape each,
-    1 <= K <= MAX_SETS_ALONG -> (sets, directions).  Raises ValueError otherwise (what the library would refuse, said before the call)."""
+    1 <= K <= MAX_SETS_ALONG -> (sets, directions) -- or, with `grad`, the sets as drt_hip_render_param_sets_grad takes them:
+    1 <= K <= MAX_SETS_GRAD.  Raises ValueError otherwise (what the library would refuse, said before the call)."""
     along = tangents is not None
-    who, cap, cap_name = ("param sets along", MAX_SETS_ALONG, "MAX_SETS_ALONG") if along else ("param sets", MAX_PARAM_SETS, "MAX_PARAM_SETS")
+    who, cap, cap_name = ("param sets along", MAX_SETS_ALONG, "MAX_SETS_ALONG") if along else \
+                         (("param sets grad", MAX_SETS_GRAD, "MAX_SETS_GRAD") if grad else ("param sets", MAX_PARAM_SETS, "MAX_PARAM_SETS"))
     v = np.ascontiguousarray(sets, dtype=np.float64)
     if v.ndim != 3 or v.shape[1:] != (n_params, 3):
         raise ValueError(f"{who}: expected {'sets of ' if along else ''}shape [n_sets, {n_params}, 3], got {list(v.shape)}")
@@ -755,7 +758,7 @@ _ABI_SYMBOLS = ["drt_hip_abi_version", "drt_hip_device_count", "drt_hip_create",
                 "drt_hip_upload_scene", "drt_hip_update_params", "drt_hip_set_specialisation", "drt_hip_render", "drt_hip_render_async", "drt_hip_wait",
                 "drt_hip_render_gradient_image", "drt_hip_render_tangent", "drt_hip_render_tangent_double", "drt_hip_render_normal_equations", "drt_hip_render_tangents",
                 "drt_hip_render_normal_equations_along", "drt_hip_render_param_sets", "drt_hip_render_param_sets_double",
-                "drt_hip_render_param_sets_along", "drt_hip_render_param_sets_along_double", "drt_hip_pin_host", "drt_hip_unpin_host", "drt_hip_stream",
+                "drt_hip_render_param_sets_along", "drt_hip_render_param_sets_along_double", "drt_hip_render_param_sets_grad", "drt_hip_pin_host", "drt_hip_unpin_host", "drt_hip_stream",
                 "drt_hip_synchronize", "drt_hip_last_error", "drt_hip_kernel_name"]
 
 
@@ -807,6 +810,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                     C.POINTER(HipStats)]
     lib.drt_hip_render_param_sets_along_double.argtypes = lib.drt_hip_render_param_sets_along.argtypes
+    lib.drt_hip_render_param_sets_grad.argtypes = [C.c_void_p, C.POINTER(CameraDesc), C.POINTER(RenderParamsDesc), C.c_int32, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p, C.POINTER(HipStats)]
     lib.drt_hip_pin_host.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
     lib.drt_hip_unpin_host.argtypes = [C.c_void_p, C.c_void_p]
     lib.drt_hip_stream.argtypes = [C.c_void_p]
@@ -1176,11 +1181,11 @@ class HipRenderer:
             raise ValueError(f"{who}: expected a target of shape {[cam.height, cam.width, 3]}, got {list(target.shape)}")
         return target, target.ctypes.data_as(C.c_void_p)
 
-    def _begin_sets(self, cam: Camera, rp: RenderParams, flags: int, sets, *tangents):
-        """what the four parameter-set calls start with -> (the checked sets -- with `tangents`: (sets, directions) --, then what _begin gives)"""
+    def _begin_sets(self, cam: Camera, rp: RenderParams, flags: int, sets, *tangents, grad: bool = False):
+        """what the six parameter-set calls start with -> (the checked sets -- with `tangents`: (sets, directions) --, then what _begin gives)"""
         assert self.scene is not None
         n = self.scene.n_params
-        return (check_param_sets_along(sets, *tangents, n) if tangents else check_param_sets(sets, n),) + self._begin(cam, rp, flags)
+        return (check_param_sets_along(sets, *tangents, n) if tangents else check_param_sets(sets, n, grad=grad),) + self._begin(cam, rp, flags)
 
     def render_param_sets(self, cam: Camera, rp: RenderParams, sets: np.ndarray, target: Optional[np.ndarray] = None, f64: bool = False,
                           images: bool = True, timing: bool = False, double: bool = False) -> dict:
@@ -1254,6 +1259,40 @@ class HipRenderer:
                                                       C.c_void_p(out_loss_ptr or None), C.c_void_p(out_dloss_ptr or None),
                                                       C.c_void_p(out_curv_ptr or None), C.byref(stats) if want_stats else None)
         self._check(rc, "drt_hip_render_param_sets_along")
+        return stats.as_dict() if want_stats else {}
+
+    def render_param_sets_grad(self, cam: Camera, rp: RenderParams, sets: np.ndarray, adjoints: Optional[np.ndarray] = None,
+                               f64: bool = False, timing: bool = False) -> dict:
+        """drt_hip_render_param_sets_grad: the summed gradient of the frame under each of the K <= MAX_SETS_GRAD = 8 parameter vectors `sets`
+        ([K, n_params, 3]) in ONE trace, set k seeded with `adjoints[k]` (float32 [K,H,W,3]; None: every seed (1, 1, 1)); the context's
+        own parameters stay what they are.
+        -> {"grads" [K, n_params, 3] float64 = what update_params(sets[k]) + render(backward=True, adjoint=adjoints[k]) gives, "stats"}"""
+        v, cd, d, stats = self._begin_sets(cam, rp, self._host_flags(rp, f64, timing), sets, grad=True)
+        K = v.shape[0]
+        a_ptr = None
+        if adjoints is not None:
+            adjoints = np.ascontiguousarray(adjoints, dtype=np.float32)
+            if adjoints.shape != (K, cam.height, cam.width, 3):
+                raise ValueError(f"param sets grad: expected adjoints of shape {[K, cam.height, cam.width, 3]}, got {list(adjoints.shape)}")
+            if not np.isfinite(adjoints).all():
+                raise ValueError("param sets grad: an adjoint image holds a value that is not finite")
+            a_ptr = adjoints.ctypes.data_as(C.c_void_p)
+        grads = np.zeros((K, max(v.shape[1], 1), 3), dtype=np.float64)
+        rc = self.lib.drt_hip_render_param_sets_grad(self.ctx, C.byref(cd), C.byref(d), K, v.ctypes.data_as(C.c_void_p), a_ptr,
+                                                     grads.ctypes.data_as(C.c_void_p), C.byref(stats))
+        self._check(rc, "drt_hip_render_param_sets_grad")
+        return {"grads": grads[:, :v.shape[1]], "stats": stats.as_dict()}
+
+    def render_param_sets_grad_device(self, cam: Camera, rp: RenderParams, sets: np.ndarray, out_grads_ptr: int, adjoints_ptr: int = 0,
+                                      f64: bool = False, timing: bool = False, sync: bool = False, want_stats: Optional[bool] = None) -> dict:
+        """drt_hip_render_param_sets_grad on device pointers (adjoints float32 [K,H,W,3] or 0, gradients float64 [K, n_params, 3]), enqueued
+        on the context's stream; the sets are host memory."""
+        want_stats = timing if want_stats is None else want_stats
+        v, cd, d, stats = self._begin_sets(cam, rp, self._device_flags(rp, f64, timing, sync), sets, grad=True)
+        rc = self.lib.drt_hip_render_param_sets_grad(self.ctx, C.byref(cd), C.byref(d), v.shape[0], v.ctypes.data_as(C.c_void_p),
+                                                     C.c_void_p(adjoints_ptr or None), C.c_void_p(out_grads_ptr or None),
+                                                     C.byref(stats) if want_stats else None)
+        self._check(rc, "drt_hip_render_param_sets_grad")
         return stats.as_dict() if want_stats else {}
 
     def render_device(self, cam: Camera, rp: RenderParams, out_rgb_ptr: int, out_grad_ptr: int,

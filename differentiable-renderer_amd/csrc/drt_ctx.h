@@ -37,6 +37,10 @@ struct ParamSetsRequest {
     double* d_tangents64 = nullptr;       // ... in double, or none
     double* d_dloss = nullptr;            // n_sets x 3: 2 <r_k, J d_k>, or none (needs d_target)
     double* d_curv = nullptr;             // n_sets x 3: |J d_k|^2, or none
+    // drt_hip_render_param_sets_grad: every set's summed gradient and nothing else -- the path kernel's form of that name, then k_sets_grad_finish
+    bool grad = false;
+    const float* d_adjoints = nullptr;    // n_sets x H x W x 3: set k's seed image, or none (every seed (1, 1, 1))
+    double* d_grads = nullptr;            // n_sets x the caller's parameters x 3
 };
 // A render on one of the path kernel's special forms, as render_common / render_launch / render_impl are told about it: which form, and what
 // that form reads.  render_impl decodes it, in one place

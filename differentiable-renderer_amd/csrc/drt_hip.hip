@@ -615,12 +615,13 @@ int drt_hip_render_normal_equations_along(drt_hip_ctx* ctx, const drt_camera_des
 
 // ---- one frame under several parameter sets in one trace: up to DRT_HIP_MAX_PARAM_SETS of them, or up to DRT_HIP_MAX_SETS_ALONG with a
 // direction each -- value, slope and Gauss-Newton curvature of the loss per set ----
-// the two forms: who is asking, the most sets it takes, and its own words where the forms' refusals differ
+// the three forms: who is asking, the most sets it takes, and its own words where the forms' refusals differ
 struct SetsForm {
     bool along;
     PathFormCaller me;
     int most;
     const char *outside, *null_input, *no_output, *needs_target;
+    bool grad = false;          // drt_hip_render_param_sets_grad: reverse mode -- a seed image per set in, a summed gradient per set out, no images
 };
 static const SetsForm plain_sets = {false,
                                     {"param sets", "render the shards on plain contexts", "a forward render", DRT_PATH_LDS_PARAMS,
@@ -633,6 +634,11 @@ static const SetsForm sets_along = {true,
                                     DRT_HIP_MAX_SETS_ALONG, "n_sets outside 1 ... DRT_HIP_MAX_SETS_ALONG = 4", "NULL param_sets or param_tangents",
                                     "no output requested (out_images, out_tangents, out_loss, out_dloss and out_curv are all NULL)",
                                     "out_loss and out_dloss need target_rgb"};
+static const SetsForm sets_grad = {false,
+                                   {"param sets grad", "render the shards on plain contexts", "the biased operator's summed gradients", DRT_PATH_LDS_PARAMS,
+                                    "more parameters than the path kernels stage (136)"},
+                                   DRT_HIP_MAX_SETS_GRAD, "n_sets outside 1 ... DRT_HIP_MAX_SETS_GRAD = 8", "NULL param_sets or out_param_grads",
+                                   "", "", true};
 
 // this shard's rows of n_sets images, from `from` bytes into ctx->neq_jac to the caller's buffer: a copy per band (the render has waited
 // for its stream)
@@ -651,11 +657,13 @@ static int fetch_set_images(drt_hip_ctx* ctx, const drt_camera_desc* cam, int n_
     return DRT_OK;
 }
 
-// the one call behind the four entry points.  The plain form has no param_tangents, out_tangents, out_dloss and out_curv; the form with
-// directions has no out_rgb.  `wide`: the images are double (host buffers only)
+// the one call behind the five entry points.  The plain form has no param_tangents, out_tangents, out_dloss and out_curv; the form with
+// directions has no out_rgb; the gradient form has adjoints_rgb and out_param_grads and nothing else.  `wide`: the images are double (host
+// buffers only)
 static int render_sets_common(drt_hip_ctx* ctx, const SetsForm& form, const drt_camera_desc* cam, const drt_render_params* rp, int32_t n_sets,
                               const double* param_sets, const double* param_tangents, const float* target_rgb, void* out_images, void* out_tangents,
-                              bool wide, double* out_loss, double* out_dloss, double* out_curv, float* out_rgb, drt_hip_stats* stats)
+                              bool wide, double* out_loss, double* out_dloss, double* out_curv, float* out_rgb, drt_hip_stats* stats,
+                              const float* adjoints_rgb = nullptr, double* out_param_grads = nullptr)
 {
     if (!ctx)
         return DRT_ERR_INVALID;
@@ -666,13 +674,13 @@ static int render_sets_common(drt_hip_ctx* ctx, const SetsForm& form, const drt_
     if ((rc = refuse_before(ctx, cam, rp, me)) != DRT_OK) return rc;
     if (n_sets < 1 || n_sets > form.most)
         return refuse(ctx, me, DRT_ERR_INVALID, form.outside);
-    if (!param_sets || (form.along && !param_tangents))
+    if (!param_sets || (form.along && !param_tangents) || (form.grad && !out_param_grads))
         return refuse(ctx, me, DRT_ERR_INVALID, form.null_input);
-    if (!out_images && !out_tangents && !out_loss && !out_dloss && !out_curv)
+    if (!form.grad && !out_images && !out_tangents && !out_loss && !out_dloss && !out_curv)
         return refuse(ctx, me, DRT_ERR_INVALID, form.no_output);
     if ((out_loss || out_dloss) && !target_rgb)
         return refuse(ctx, me, DRT_ERR_INVALID, form.needs_target);
-    if (rp->flags & DRT_RENDER_BACKWARD)
+    if (!form.grad && (rp->flags & DRT_RENDER_BACKWARD))
         return refuse(ctx, me, DRT_ERR_INVALID, "a forward render: no DRT_RENDER_BACKWARD");
     for (size_t i = 0; i < (size_t)n_sets * (size_t)ctx->n_user_params * 3; ++i) {
         if (!std::isfinite(param_sets[i]))
@@ -684,6 +692,10 @@ static int render_sets_common(drt_hip_ctx* ctx, const SetsForm& form, const drt_
         for (size_t i = 0; i < (size_t)cam->width * (size_t)cam->height * 3; ++i)
             if (!std::isfinite(target_rgb[i]))
                 return refuse(ctx, me, DRT_ERR_INVALID, "the target image holds a value that is not finite");
+    if (!(rp->flags & DRT_RENDER_DEVICE_OUT) && adjoints_rgb)
+        for (size_t i = 0; i < (size_t)n_sets * (size_t)cam->width * (size_t)cam->height * 3; ++i)
+            if (!std::isfinite(adjoints_rgb[i]))
+                return refuse(ctx, me, DRT_ERR_INVALID, "an adjoint image holds a value that is not finite");
     if ((rc = refuse_after(ctx, cam, rp, me)) != DRT_OK) return rc;
     // (the plain image is the kernel's last set, the context's own parameters: one set more)
     const int n_int = n_sets + (out_rgb ? 1 : 0);
@@ -692,6 +704,14 @@ static int render_sets_common(drt_hip_ctx* ctx, const SetsForm& form, const drt_
     // (sets at and above n_sets, up to the kernel's width, are the context's own parameters -- the last one is the plain image's --, with a
     //  zero direction; a mirror's internal constant keeps the scene's value and a zero tangent in every set)
     const int K = n_int <= 2 ? 2 : (n_int <= 4 ? 4 : 8);
+    if (form.grad) {
+        // the form's own limit: a wave's fp64 table holds the K sets' rows, 3 per parameter that requires a gradient, once at least
+        const int rows = K * std::max(1, ctx->n_grad_slots) * 3;
+        if (rows > DRT_GEN_TABLE)
+            return refuse(ctx, me, DRT_ERR_UNSUPPORTED, "the kernel's width of " + std::to_string(K) + " sets x " + std::to_string(std::max(1, ctx->n_grad_slots) * 3) +
+                                                        " gradient rows = " + std::to_string(rows) + " rows, more than the " + std::to_string(DRT_GEN_TABLE) +
+                                                        " elements of a wave's gradient table (fewer sets per call, or fewer parameters that require a gradient)");
+    }
     if ((rc = form.along ? stage_rows(ctx, rp, param_sets, 2 * n_sets, 2 * K, RowPad::own_even, param_tangents)
                          : stage_rows(ctx, rp, param_sets, n_sets, K, RowPad::own)) != DRT_OK) return rc;
     const bool dev = (rp->flags & DRT_RENDER_DEVICE_OUT) != 0;
@@ -701,7 +721,26 @@ static int render_sets_common(drt_hip_ctx* ctx, const SetsForm& form, const drt_
     q.n_sets = n_sets;
     q.width = K;
     q.along = form.along;
+    q.grad = form.grad;
     const size_t el = wide ? sizeof(double) : sizeof(float), n_img = (size_t)n_sets * npix * 3 * el, ns3 = (size_t)n_sets * 3;
+    const size_t n_grads = (size_t)n_sets * (size_t)ctx->n_user_params * 3;
+    if (form.grad) {
+        // the seeds in, the gradients out: device pointers as they are; host buffers through buffers of the context's own
+        HIPCHK(ctx, hipSetDevice(ctx->device));
+        q.d_adjoints = adjoints_rgb;
+        q.d_grads = out_param_grads;
+        if (!dev) {
+            if (adjoints_rgb) {
+                if ((rc = ensure(ctx, ctx->neq_jac, (size_t)n_sets * npix * 3 * sizeof(float))) != DRT_OK) return rc;
+                HIPCHK(ctx, hipMemcpyAsync(ctx->neq_jac.p, adjoints_rgb, (size_t)n_sets * npix * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+                q.d_adjoints = (const float*)ctx->neq_jac.p;
+            }
+            if ((rc = ensure(ctx, ctx->neq_out, (n_grads ? n_grads : 1) * sizeof(double))) != DRT_OK) return rc;
+            q.d_grads = (double*)ctx->neq_out.p;
+        }
+        // (a shard without rows launches nothing: its sums are zero)
+        if (n_grads) HIPCHK(ctx, hipMemsetAsync(q.d_grads, 0, n_grads * sizeof(double), ctx->stream));
+    } else
     if (dev) {
         q.d_target = target_rgb;
         q.d_images = (float*)out_images;
@@ -739,11 +778,15 @@ static int render_sets_common(drt_hip_ctx* ctx, const SetsForm& form, const drt_
     req.kind = TangentRequest::Kind::param_sets;
     req.d_params = ctx->tangent.p;
     req.sets = &q;
-    if ((rc = render_common(ctx, cam, rp, nullptr, out_rgb, nullptr, stats, -1, nullptr, &req)) != DRT_OK)
+    // (the gradient form: DRT_RENDER_BACKWARD is implied -- the pipeline below is told a forward render: this form's seeds and sums go their own way)
+    drt_render_params r = *rp;
+    r.flags &= ~(uint32_t)DRT_RENDER_BACKWARD;
+    if ((rc = render_common(ctx, cam, &r, nullptr, out_rgb, nullptr, stats, -1, nullptr, &req)) != DRT_OK)
         return rc;
     if (dev)
         return DRT_OK;
     // host buffers: the render has waited for its stream; the sums, and the images' rows of this shard
+    if (form.grad && n_grads) HIPCHK(ctx, hipMemcpy(out_param_grads, q.d_grads, n_grads * sizeof(double), hipMemcpyDeviceToHost));
     if (out_loss) HIPCHK(ctx, hipMemcpy(out_loss, q.d_loss, ns3 * sizeof(double), hipMemcpyDeviceToHost));
     if (out_dloss) HIPCHK(ctx, hipMemcpy(out_dloss, q.d_dloss, ns3 * sizeof(double), hipMemcpyDeviceToHost));
     if (out_curv) HIPCHK(ctx, hipMemcpy(out_curv, q.d_curv, ns3 * sizeof(double), hipMemcpyDeviceToHost));
@@ -784,6 +827,13 @@ int drt_hip_render_param_sets_along_double(drt_hip_ctx* ctx, const drt_camera_de
 {
     return render_sets_common(ctx, sets_along, cam, rp, n_sets, param_sets, param_tangents, target_rgb, out_images, out_tangents, true, out_loss,
                               out_dloss, out_curv, nullptr, stats);
+}
+
+int drt_hip_render_param_sets_grad(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_params* rp, int32_t n_sets,
+                                   const double* param_sets, const float* adjoints_rgb, double* out_param_grads, drt_hip_stats* stats)
+{
+    return render_sets_common(ctx, sets_grad, cam, rp, n_sets, param_sets, nullptr, nullptr, nullptr, nullptr, false, nullptr, nullptr, nullptr, nullptr,
+                              stats, adjoints_rgb, out_param_grads);
 }
 
 // ---- asynchronous host-buffer renders ---------------------------------------------------------------

@@ -131,6 +131,17 @@ __device__ inline V3<R> load_param(const PathSceneLds<R>& lds, const R* __restri
         return mk<R>(lds.params[id * 3], lds.params[id * 3 + 1], lds.params[id * 3 + 2]);
     return mk<R>(params[id * 3], params[id * 3 + 1], params[id * 3 + 2]);
 }
+// ... of ONE parameter set (NP = DRT_NP_SETS_GRAD): the set's raw values, 3 per parameter, where add_emission's general branch reads a light's
+// emission -- handed to it in the scene's place, so the branch runs as it is on the set's own operands
+template <typename R>
+struct SetParams {
+    const R* p;
+};
+template <typename R, bool ALL_LDS = false>
+__device__ inline V3<R> load_param(const SetParams<R>& set, const R* __restrict__, int id)
+{
+    return mk<R>(set.p[id * 3], set.p[id * 3 + 1], set.p[id * 3 + 2]);
+}
 
 template <typename R>
 __device__ inline void stage_path_scene(PathSceneLds<R>& lds, const DevScene<R>* __restrict__ sc, const R* __restrict__ params)
@@ -329,6 +340,10 @@ template <typename R>
 struct GenLds {
     R colnz[DRT_PATH_LDS_PARAMS][4];   // colour, zero channels replaced by 1 | [3]: zero-count increments, 8 bits per channel (pid_pack)
     R invc[DRT_PATH_LDS_PARAMS][4];    // 1 / c per channel, 0 where the channel is zero | [3]: table row | zero-channel bits << 16 (pid_pack)
+    // The records of ONE parameter set (NP = DRT_NP_SETS_GRAD) live in tables sized by the scene's parameter count, not in a GenLds: this is
+    // the view through which the general form's own code (add_emission's branch, add_word) reads that set's invc rows.  ONLY invc[id], id below
+    // the scene's parameter count, may be read through it
+    static __device__ inline const GenLds* over_invc(const R* rows) { return reinterpret_cast<const GenLds*>(rows - DRT_PATH_LDS_PARAMS * 4); }
 };
 
 template <typename R, typename SL>
@@ -683,6 +698,99 @@ struct Tangents<R, DRT_NP_SETS_ALONG, NC> {
     }
 };
 
+// ---- REVERSE mode under K parameter sets: every set's summed gradient J(P_k)^T w_k in one trace (NP = DRT_NP_SETS_GRAD, NC = K in {2, 4, 8};
+// drt_hip_render_param_sets_grad) ----
+// The general gradient form (Tangents<R, DRT_NP_ANY>) remembers WHICH colour every vertex scattered on, and that history does not see a
+// parameter's value either: K sets share the ray, the key, the hit, m_k AND the history (`h`: cur, nv, the LDS words, the global overflow
+// column).  Per set k a lane keeps the throughput T_k without its zero factors, their counts zc_k (the sets differ in which channels are
+// zero) and the pixel's seed g_k (read once per pixel from adjoint + k W H 3): seven registers.  Where the path meets a light -- mid-path on
+// a shape with BxDF and emitter, or at its end -- set k runs add_emission's general branch AS IT IS on its own operands: `h` is pointed at
+// the set's zero counts, its invc rows (GenLds::over_invc), its raw parameters (SetParams: an emission is used as it is, zeros included) and
+// its rows of the wave's table, k R + slot with R = 3 rows per parameter that requires a gradient.  The table keeps its DRT_GEN_TABLE elements
+// for K R rows in the largest power-of-two number of copies that fits; K is the instantiated width, so a set's sums do not depend on how
+// many of the K the caller gave.  Padded sets (k at and above the caller's count, which rides in PathArgs::gimg_row) add nothing.  Tables in
+// dynamic shared memory BEHIND the history words (PathArgs::hist_lds of them per thread), per set k and sized by the SCENE's parameter count n,
+// in units of R --
+//     colnz_k[n + 1], invc_k[n + 1]      rows of four, as GenLds keeps them: P_k with zero channels replaced by 1 | zero-count increments, and
+//                                        1 / P_k | table row, zero-channel bits; row n of colnz: the rest row (1, 1, 1), zeros
+//     par_k[3 n] (padded to rows of four)  P_k itself, for the lights
+// staged from [params | P_1 | ... | P_K] behind the kernel's `params`.  Lockstep form only.  PathArgs::gen_rows counts ALL K R rows: the
+// block's row sums leave through gen_finish as the general form's do, and k_sets_grad_finish maps them back to out[k][parameter][channel].
+#define DRT_NP_SETS_GRAD (-5)
+// blocks per CU (= waves per SIMD) of the f32 forms: the most at which every instantiation stays free of scratch AND the static LDS plus the
+// largest tables (136 parameters) fit the CU (the compiler's report: DESIGN.md 9b).  The compiler takes 74-83 registers at K = 2, 103-105 at
+// K = 4 and 163-165 at K = 8 whatever the bound: the registers would allow 6-5, 4 and 3 blocks, the tables at 136 parameters 4, 3 and 2
+#ifndef DRT_SETS_GRAD2_MIN_BLOCKS
+#define DRT_SETS_GRAD2_MIN_BLOCKS 4
+#endif
+#ifndef DRT_SETS_GRAD4_MIN_BLOCKS
+#define DRT_SETS_GRAD4_MIN_BLOCKS 3
+#endif
+#ifndef DRT_SETS_GRAD8_MIN_BLOCKS
+#define DRT_SETS_GRAD8_MIN_BLOCKS 2
+#endif
+__host__ __device__ inline uint32_t sets_grad_set_words(uint32_t n) { return 2u * (n + 1u) * 4u + ((3u * n + 3u) & ~3u); }
+__host__ __device__ inline uint32_t sets_grad_table_words(uint32_t n, uint32_t K) { return K * sets_grad_set_words(n); }
+template <typename R, int K, typename SL>
+__device__ inline void stage_sets_grad(R* __restrict__ tab, const SL& lds, const DevScene<R>* __restrict__ sc, const R* __restrict__ params)
+{
+    // (after stage_path_scene's barrier; the records are stage_gen's, of set k's values)
+    const int n = lds.sc.n_params < DRT_PATH_LDS_PARAMS ? lds.sc.n_params : DRT_PATH_LDS_PARAMS;
+    const int stride = (n + 1) * 4, words = (int)sets_grad_set_words((uint32_t)n);
+    for (int i = threadIdx.x; i < K * (n + 1); i += blockDim.x) {
+        const int k = i / (n + 1), p = i - k * (n + 1);
+        const bool in = p < n;
+        const R* P = params + ((size_t)(1 + k) * lds.sc.n_params + p) * 3;
+        R* set = tab + (size_t)k * words;
+        uint32_t zinc = 0, zbits = 0;
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            const R c = in ? P[ch] : R(1);
+            const bool zero = zero_channel(c);
+            set[p * 4 + ch] = zero ? R(1) : c;
+            set[stride + p * 4 + ch] = zero ? R(0) : R(1) / c;
+            zinc |= zero ? 1u << (8 * ch) : 0u;
+            zbits |= zero ? 1u << ch : 0u;
+            if (in)
+                set[2 * stride + p * 3 + ch] = c;
+        }
+        const uint32_t slot = in ? (uint32_t)sc->grad_slot[p] : DRT_SLOT_NONE;
+        set[p * 4 + 3] = pid_pack(R(0), zinc);
+        set[stride + p * 4 + 3] = pid_pack(R(0), slot | zbits << 16);
+    }
+    __syncthreads();
+}
+
+template <typename R, int NC>
+struct Tangents<R, DRT_NP_SETS_GRAD, NC> {
+    typedef typename GenAcc<R>::T GT;
+    V3<R> T[NC], g[NC];             // per set: prefix throughput (zero factors left out); the pixel's seed
+    uint32_t zc[NC];                // ... zero factors met per channel, 8 bits each
+    Tangents<R, DRT_NP_ANY, 0> h;   // shared by the sets: the path's history; and the general form's view of ONE set, pointed at set k for its turn
+    const R* tab;                   // the block's tables (see above)
+    uint32_t rest, stride, words;   // the rest row = the scene's parameter count; words of one table of rows, of one set
+    GT* table;                      // the wave's table, at the lane's copy (set 0's first row)
+    uint32_t set_rows, n_sets;      // R: table rows of one set; the caller's sets
+    __device__ inline void new_path()
+    {
+#pragma unroll
+        for (int k = 0; k < NC; ++k) {
+            T[k] = mk<R>(R(1), R(1), R(1));
+            zc[k] = 0;
+        }
+        h.new_path();
+    }
+    // the general form's view, at set k
+    __device__ inline void point_at(int k)
+    {
+        const R* set = tab + (uint32_t)k * words;
+        h.zc = zc[k];
+        h.gl = GenLds<R>::over_invc(set + stride);
+        h.table = table + (((uint32_t)k * set_rows) << h.clog2);
+    }
+    __device__ inline SetParams<R> params_of(int k) const { return SetParams<R>{tab + (uint32_t)k * words + 2u * stride}; }
+};
+
 // ---- the forward-mode step, once: what the single-direction form, every direction of the K-direction form and every set of the sets-along
 // form do to their own operands (so a direction's or a set's sums equal the single-direction form's bit for bit: one function, not three
 // copies).  Operand-level: none of them knows which form calls it.
@@ -775,6 +883,31 @@ __device__ inline void gen_finish(const GenBlock<R>& gb, const PathArgs& a, doub
     }
 }
 
+// NP = DRT_NP_SETS_GRAD: the general form's block -- its zeroed tables, the shared history (gen_begin, on `h`) -- and the K sets' own tables in
+// dynamic shared memory behind the history words (after stage_path_scene's barrier)
+template <typename R, int NC, typename SL>
+__device__ inline void sets_grad_begin(GenBlock<R>& gb, const SL& lds, const DevScene<R>* __restrict__ sc, const R* __restrict__ params, const PathArgs& a,
+                                       Tangents<R, DRT_NP_SETS_GRAD, NC>& tg)
+{
+    // (the launch's one dynamic block: [hist_lds][DRT_BLOCK] history words, then the tables -- declared as path_tables_begin declares it, for its alignment)
+    extern __shared__ __attribute__((aligned(16))) unsigned char s_dirs[];
+    uint32_t* hist = reinterpret_cast<uint32_t*>(s_dirs);
+    gen_begin(gb, lds, sc, a, hist, reinterpret_cast<uint32_t*>(a.hist_ovf), tg.h);
+    R* tab = reinterpret_cast<R*>(hist + (size_t)a.hist_lds * DRT_BLOCK);
+    stage_sets_grad<R, NC>(tab, lds, sc, params);
+    tg.tab = tab;
+    tg.rest = (uint32_t)(lds.sc.n_params < DRT_PATH_LDS_PARAMS ? lds.sc.n_params : DRT_PATH_LDS_PARAMS);
+    tg.stride = (tg.rest + 1u) * 4u;
+    tg.words = sets_grad_set_words(tg.rest);
+    tg.table = tg.h.table;
+    tg.set_rows = a.gen_rows / (uint32_t)NC;
+    tg.n_sets = a.gimg_row < (uint32_t)NC ? a.gimg_row : (uint32_t)NC;
+#pragma unroll
+    for (int k = 0; k < NC; ++k)
+        tg.g[k] = mk<R>(R(1), R(1), R(1));
+    tg.new_path();
+}
+
 // ---- the roles of the fast path's parameter slots ------------------------------------------------------------------------
 // The reference's scene has three albedos that never emit and one emission that never scatters (render.cpp:26-29); a scene of the
 // ABI may use any parameter as both.  What the scene's records say about it (drt_hip_upload_scene: every material's colour parameter,
@@ -840,6 +973,16 @@ __device__ inline void add_emission(const SL& lds, const TangentLds<R>& tl, cons
             tg.L[k] = tg.L[k] + Tr * Ek;
             tangent_emit(Tk, tg.zc[k], Ek, vd, inv_pk, tg.S[k], tg.Z[k], tg.dL[k]);
         }
+    } else if constexpr (NP == DRT_NP_SETS_GRAD) {
+        // K sets, a gradient each: the general branch below, once per set the caller gave, on the set's own emission, T, zc, seed, invc rows and
+        // table rows (the radiance it also forms is not kept: this form has no image)
+#pragma unroll
+        for (int k = 0; k < NC; ++k)
+            if ((uint32_t)k < tg.n_sets) {
+                tg.point_at(k);
+                V3<R> Lk = mk<R>(R(0), R(0), R(0));
+                add_emission<R, DRT_NP_ANY, 0, false, SetParams<R>>(tg.params_of(k), tl, params, eid, inv_pk, tg.T[k], tg.g[k], Lk, tg.h);
+            }
     } else {
         const V3<R> E = load_param<R, (NP != 0)>(lds, params, (int)eid) * inv_pk;
         V3<R> Tr = T;
@@ -1042,6 +1185,18 @@ __device__ inline void path_bounce(const PathArgs& a, const PathSceneLds<R>& lds
             tg.zc[k] += pid_unpack(rec[3]);
             tangent_advance(ds, dz, tg.S[k], tg.Z[k]);
         }
+    } else if constexpr (NP == DRT_NP_SETS_GRAD) {
+        // K sets, a gradient each: set k's colour row moves its T and zc as the general form moves its own; a lane that stops reads the rest
+        // row and m = 1.  The vertex joins the ONE history the sets share
+        const uint32_t row = (alive && cid < tg.rest ? cid : tg.rest) * 4u;
+        const R mm = alive ? mk_ : R(1);
+#pragma unroll
+        for (int k = 0; k < NC; ++k) {
+            const R* rec = tg.tab + (uint32_t)k * tg.words + row;
+            tg.T[k] = tg.T[k] * (mk<R>(rec[0], rec[1], rec[2]) * mm);
+            tg.zc[k] += pid_unpack(rec[3]);
+        }
+        tg.h.template push<true>(live, alive ? cid : 0xFFu);
     } else {
         const int cidx = DIR ? (alive ? (int)cid : DRT_PATH_LDS_PARAMS) : (REST ? (alive ? (int)cid : DRT_TANGENT_REST) : (has_bxdf ? (int)cid : 0));
         V3<R> col;
@@ -1171,6 +1326,9 @@ __device__ inline uint32_t path_camera(const PathArgs& a, const CameraLane<R>& c
 template <size_t RB, bool SPEC, int NP, int NSG, bool REGEN, int NCR = 0>
 constexpr int path_min_blocks()
 {
+    if (NP == DRT_NP_SETS_GRAD)    // K parameter sets with a gradient each, lockstep: the general form + seven values per set (f64: what the largest tables leave)
+        return RB == 4 ? (DRT_NC_OF(NCR) <= 2 ? DRT_SETS_GRAD2_MIN_BLOCKS : (DRT_NC_OF(NCR) <= 4 ? DRT_SETS_GRAD4_MIN_BLOCKS : DRT_SETS_GRAD8_MIN_BLOCKS))
+                       : (DRT_NC_OF(NCR) <= 2 ? 2 : 1);
     if (NP == DRT_NP_SETS_ALONG)   // K parameter sets with a direction each, lockstep: sixteen values and six fp64 sums per set beside the forward-only kernel's
         return RB == 4 ? (DRT_NC_OF(NCR) <= 2 ? DRT_SETS_ALONG2_MIN_BLOCKS : DRT_SETS_ALONG4_MIN_BLOCKS) : (DRT_NC_OF(NCR) <= 2 && !SPEC ? 2 : 1);
     if (NP == DRT_NP_SETS)         // K parameter sets, lockstep: six values and three fp64 sums per set beside the forward-only kernel's
@@ -1221,7 +1379,9 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
     __shared__ double s_red[REGEN ? 1 : DRT_BLOCK / DRT_WAVE][DRT_FAST_PARAMS * 3];   // (REGEN: the block's gradient partials reuse the pixel sums' table)
     __shared__ TangentLds<R> s_tl;
     constexpr bool GEN = NP == DRT_NP_ANY;                // any number of parameters: history + per-wave tables (see Tangents<R, DRT_NP_ANY>)
-    __shared__ typename PickT<GEN, GenBlock<R>, NoLds>::T s_gen;
+    constexpr bool SGRAD = NP == DRT_NP_SETS_GRAD;        // one path under NC parameter sets, a summed gradient each: the general form's block, shared history (see Tangents<R, DRT_NP_SETS_GRAD>)
+    static_assert(!(SGRAD && (REGEN || NC < 1)), "the parameter-set gradient form is a lockstep form of K >= 1 sets: a lane is a pixel");
+    __shared__ typename PickT<(GEN || SGRAD), GenBlock<R>, NoLds>::T s_gen;
     extern __shared__ uint32_t s_hist[];                  // GEN: [a.hist_lds][DRT_BLOCK] history words
     constexpr bool DIR = NP == DRT_NP_TANGENT;            // forward mode: the derivative along one direction (see DirLds); `params` = [params | direction]
     constexpr bool DIRS = DIR && NC > 0;                  // ... along NC directions at once: tables in dynamic shared memory (see stage_dirs)
@@ -1231,11 +1391,11 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
     constexpr bool ALONG = NP == DRT_NP_SETS_ALONG;       // ... each set with a direction of its own (see stage_sets_along)
     static_assert(!(ALONG && (REGEN || NC < 1)), "the parameter-set form with directions is a lockstep form of K >= 1 sets: a lane is a pixel");
     __shared__ typename PickT<(DIR && !DIRS), DirLds<R>, NoLds>::T s_dir;
-    if constexpr (GEN)
+    if constexpr (GEN || SGRAD)
         gen_zero(s_gen);
     stage_path_scene(lds, sc, params);
     const TangentLds<R>& tl = s_tl;
-    if (NC > 0 && !GEN && !DIR && !SETS && !ALONG)
+    if (NC > 0 && !GEN && !DIR && !SETS && !ALONG && !SGRAD)
         stage_tangents(s_tl, lds);
 
     const uint32_t lane = threadIdx.x & (DRT_WAVE - 1);
@@ -1248,10 +1408,12 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
 
     Tangents<R, NP, NC> tg;
     __shared__ R s_acc[NP > 0 ? NP * 3 : 1][DRT_BLOCK];
-    if constexpr (!SETS && !ALONG)
+    if constexpr (!SETS && !ALONG && !SGRAD)
         tg.acc = &s_acc[0][threadIdx.x];
     if constexpr (GEN)
         gen_begin(s_gen, lds, sc, a, s_hist, reinterpret_cast<uint32_t*>(a.hist_ovf), tg);
+    else if constexpr (SGRAD)
+        sets_grad_begin(s_gen, lds, sc, params, a, tg);
     else if constexpr (DIRS || SETS || ALONG)
         path_tables_begin(tg, lds, params);
     else if constexpr (DIR) {
@@ -1283,6 +1445,15 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
         px = gpix - py * (uint32_t)a.W;
         if (NP != 0 && adjoint)
             g = mk<R>((R)adjoint[(size_t)gpix * 3], (R)adjoint[(size_t)gpix * 3 + 1], (R)adjoint[(size_t)gpix * 3 + 2]);
+        if constexpr (SGRAD) if (adjoint) {
+            // a seed per set: the caller's n_sets images, one behind the other
+#pragma unroll
+            for (int k = 0; k < NC; ++k)
+                if ((uint32_t)k < tg.n_sets) {
+                    const float* gk = adjoint + ((size_t)k * (size_t)a.W * (size_t)a.H + gpix) * 3;
+                    tg.g[k] = mk<R>((R)gk[0], (R)gk[1], (R)gk[2]);
+                }
+        }
     }
     // f32: the pixel's corner in double ONCE per lane; a sample then only adds its jitter (camera.hpp:53-58 in the form
     // cs = cs0 + u1 (2 aspect tan / W)): the sample's position inside the pixel is exact to ~2e-5 of a pixel and the
@@ -1552,7 +1723,7 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
             counts[(size_t)a.n_groups * a.n_ranges + w] = n_capped;
         }
     }
-    if constexpr (GEN)
+    if constexpr (GEN || SGRAD)
         gen_finish(s_gen, a, gpart);
     else
     if constexpr (NP > 0 && !JAC) {
@@ -2242,4 +2413,23 @@ k_sets_along_sums(const double* __restrict__ part, int n_blocks, int n_values, d
         if (out)
             out[v / 3] = red[0];
     }
+}
+
+// ---- the summed gradients of a frame under K parameter sets (drt_hip_render_param_sets_grad) ---------------------------------------
+// Behind a launch of k_path's form of that name: gpart[block][k R + row] holds the block's fp64 sums of set k's table rows (gen_finish), R =
+// set_rows = 3 per parameter that requires a gradient.  Block (k, parameter, channel) adds its row over k_path's blocks -- a strided sum per
+// thread, then an LDS tree, both in a fixed order -- into out[k][parameter][channel]; a parameter without a row (slot_map: DevScene::grad_slot)
+// gets zero.  No atomics: the same call gives the same bits.
+__global__ void __launch_bounds__(DRT_BLOCK)
+k_sets_grad_finish(const double* __restrict__ gpart, int n_blocks, int row_stride, int set_rows, int n_out, const unsigned short* __restrict__ slot_map,
+                   double* __restrict__ out)
+{
+    __shared__ double red[DRT_BLOCK];
+    const int k = (int)blockIdx.x / (n_out * 3), pc = (int)blockIdx.x - k * (n_out * 3);
+    const int slot = slot_map[pc / 3];
+    const bool none = slot == (int)DRT_SLOT_NONE || slot * 3 >= set_rows;
+    const int src = none ? 0 : k * set_rows + slot * 3 + pc % 3;
+    add_blocks(red, none ? 0 : n_blocks, [&](int b) { return gpart[(size_t)b * row_stride + src]; });
+    if (threadIdx.x == 0)
+        out[blockIdx.x] = red[0];
 }

@@ -151,11 +151,12 @@ inline int np_width(int n_params, int general)
 }
 
 // ---- which instantiation of the one-launch path kernels a render runs (shard_plan decides it, path_batch launches it) ----
-enum class PathOp { biased, unbiased, mesh, tangent, jacobian, tangents, param_sets, param_sets_along };   // k_path (the gradient image included), k_path_unbiased, k_path_mesh, k_path's forward-mode form,
+enum class PathOp { biased, unbiased, mesh, tangent, jacobian, tangents, param_sets, param_sets_along, param_sets_grad };   // k_path (the gradient image included), k_path_unbiased, k_path_mesh, k_path's forward-mode form,
                                                                     // its Jacobian form (lockstep, parameters in columns: DRT_NC_JACOBIAN),
                                                                     // its K-direction forward form (lockstep, nc = K),
                                                                     // its parameter-set form (lockstep, np = DRT_NP_SETS, nc = K),
                                                                     // ... with a direction per set (lockstep, np = DRT_NP_SETS_ALONG, nc = K)
+                                                                    // ... with a summed gradient per set (lockstep, np = DRT_NP_SETS_GRAD, nc = K)
 enum class PathProg { cornell, sorted, scene };  // closest-hit program: the reference's kinds compiled in (SigCornell), kinds read at
                                                  // run time (SigNone), or compiled by hiprtc for the scene's own KindSig (drt_jit.h)
 struct PathForm {
@@ -198,7 +199,8 @@ struct Shard {
     int n_dirs = 0;                 // ... > 0: its rows are directions -- k_path's K-direction forward form in place of the Jacobian form
     const ParamSetsRequest* sets = nullptr;   // drt_hip_render_param_sets: the parameter-set form, then k_sets_finish (n_dirs: the caller's sets)
     int jac_rows() const { return (neq || sets) ? (n_dirs > 0 ? n_dirs : ctx->n_params) * (sets && sets->along ? 6 : 3) : 3; }   // rows a pixel's sums have in `gpix`
-    bool pixel_sums() const { return gimg_param >= 0 || fwd_tangent || neq || sets; }   // the lanes' per-pixel sums leave the path kernel (gimg_part)
+    bool sets_grad() const { return sets && sets->grad; }   // drt_hip_render_param_sets_grad: gradient tables, no per-pixel sums
+    bool pixel_sums() const { return gimg_param >= 0 || fwd_tangent || neq || (sets && !sets->grad); }   // the lanes' per-pixel sums leave the path kernel (gimg_part)
     // the scene in compute type R
     const DevScene<R>* d_scene;
     const R* d_params;
@@ -308,6 +310,7 @@ unsigned path_dynamic_lds(const PathForm& f, int n_params, unsigned hist_bytes)
     if (f.op == PathOp::tangents) return dirs_table_words(n, K) * (unsigned)sizeof(R);
     if (f.op == PathOp::param_sets) return sets_table_words(n, K) * (unsigned)sizeof(R);
     if (f.op == PathOp::param_sets_along) return sets_along_table_words(n, K) * (unsigned)sizeof(R);
+    if (f.op == PathOp::param_sets_grad) return hist_bytes + sets_grad_table_words(n, K) * (unsigned)sizeof(R);   // (the history words, then the tables: 51 KB in f32, 98 KB in f64 at 136 parameters x 8 sets)
     return f.op == PathOp::unbiased ? 0u : hist_bytes;
 }
 
@@ -359,8 +362,9 @@ const void* library_path_kernel(const PathForm& f)
     }
     // one path under K parameter sets, each set with a direction, along K directions -- the op names its NP tag --: lockstep, every program,
     // widths 2, 4 and 8; with a direction per set 2 and 4 (drt_path.h: K = 8 is not kept)
-    if (const int tag = f.op == PathOp::param_sets ? DRT_NP_SETS : (f.op == PathOp::param_sets_along ? DRT_NP_SETS_ALONG : (f.op == PathOp::tangents ? DRT_NP_TANGENT : 0)))
-        return f.regen ? nullptr : with_int<DRT_NP_SETS, DRT_NP_SETS_ALONG, DRT_NP_TANGENT>(tag, [&](auto np) {
+    if (const int tag = f.op == PathOp::param_sets ? DRT_NP_SETS : (f.op == PathOp::param_sets_along ? DRT_NP_SETS_ALONG
+                        : (f.op == PathOp::param_sets_grad ? DRT_NP_SETS_GRAD : (f.op == PathOp::tangents ? DRT_NP_TANGENT : 0))))
+        return f.regen ? nullptr : with_int<DRT_NP_SETS, DRT_NP_SETS_ALONG, DRT_NP_SETS_GRAD, DRT_NP_TANGENT>(tag, [&](auto np) {
             return with_int<2, 4, 8>(f.nc, [&](auto k) {
                 if constexpr (decltype(np)::value == DRT_NP_SETS_ALONG && decltype(k)::value > 4)
                     return (const void*)nullptr;
@@ -474,6 +478,10 @@ void shard_plan(Shard<R>& s)
             f.op = PathOp::param_sets_along;
             f.np = DRT_NP_SETS_ALONG;
         }
+        if (s.sets->grad) {
+            f.op = PathOp::param_sets_grad;
+            f.np = DRT_NP_SETS_GRAD;
+        }
     }
     f.loss = s.loss_l2;
     // the slots' roles as the scene's records give them: for the form the headline runs -- diffuse, f32, lockstep, parameters in columns
@@ -575,7 +583,7 @@ void shard_plan(Shard<R>& s)
     const int tail_bounces = tail_bounces_now();
     s.tail_nb = s.shade_tail && (tail_bounces > 1 || (tail_bounces == 0 && s.unbiased)) ? 2 : 1;
     s.tail_ring = s.tail_nb > 1 ? 3 : 2;
-    s.overlap_ok = ctx->overlap_next && s.use_path && !s.timing && !s.pixel_sums() && ctx->path_stream[0] && ctx->ev_copied[0];
+    s.overlap_ok = ctx->overlap_next && s.use_path && !s.timing && !s.pixel_sums() && !s.sets && ctx->path_stream[0] && ctx->ev_copied[0];
     const bool odd = s.overlap_ok && (ctx->slot & 1);
     s.fpart_buf = odd ? &ctx->fpart2 : &ctx->fpart;
     s.gpart_buf = odd ? &ctx->gpart2 : &ctx->gpart;
@@ -594,6 +602,14 @@ void shard_plan(Shard<R>& s)
             ++s.gen_clog2;
         if (tuning().gen_copies_log2 >= 0 && (s.gen_rows << tuning().gen_copies_log2) <= DRT_GEN_TABLE)
             s.gen_clog2 = (uint32_t)tuning().gen_copies_log2;
+    }
+    if (s.use_path && s.sets_grad()) {
+        // the sets' gradients: K R rows -- K the kernel's width, R = 3 per parameter that requires a gradient -- in as many copies as the
+        // table holds (the entry point has refused K R > DRT_GEN_TABLE)
+        s.gen_rows = (uint32_t)s.sets->width * (uint32_t)std::max(1, ctx->n_grad_slots) * 3u;
+        s.gen_clog2 = 0;
+        while (s.gen_clog2 < 4 && (s.gen_rows << (s.gen_clog2 + 1)) <= DRT_GEN_TABLE)
+            ++s.gen_clog2;
     }
     s.n_fast = ctx->n_params < DRT_FAST_PARAMS ? ctx->n_params : DRT_FAST_PARAMS;
     const bool g_general = ctx->n_params > DRT_FAST_PARAMS;
@@ -679,14 +695,14 @@ int shard_buffers(Shard<R>& s)
     }
     if ((rc = ensure(ctx, *s.counts_buf, s.cw * sizeof(uint32_t))) != DRT_OK) return rc;
     if ((rc = ensure(ctx, ctx->segtotal[ctx->slot], DRT_TOTAL_WORDS * sizeof(unsigned long long))) != DRT_OK) return rc;
-    if (s.backward) {   // per-block partial sums: K6's persistent grid, the shade kernel's one block per 4 regions, or k_path's blocks
+    if (s.backward || s.sets_grad()) {   // per-block partial sums: K6's persistent grid, the shade kernel's one block per 4 regions, or k_path's blocks
         const size_t shade_blocks = (s.max_regions + DRT_BLOCK / DRT_WAVE - 1) / (DRT_BLOCK / DRT_WAVE);
         size_t blocks = std::max<size_t>(shade_blocks, (size_t)grid_for(ctx, N));
         const size_t path_blocks = (s.path_waves + DRT_BLOCK / DRT_WAVE - 1) / (DRT_BLOCK / DRT_WAVE);
         if (s.use_path && path_blocks > blocks)
             blocks = path_blocks;
         // rows per block: 24 for the register paths (<= 8 parameters), else one per parameter channel (LDS accumulators)
-        const size_t rows = s.path_gen ? (size_t)s.gen_rows
+        const size_t rows = (s.path_gen || s.sets_grad()) ? (size_t)s.gen_rows
                                        : (ctx->n_params <= DRT_FAST_PARAMS ? (size_t)DRT_FAST_PARAMS * 3
                                                                            : (size_t)std::min(ctx->n_params, DRT_LDS_PARAMS) * 3);
         if ((rc = ensure(ctx, *s.gpart_buf, blocks * rows * sizeof(double))) != DRT_OK) return rc;
@@ -787,7 +803,9 @@ int path_batch(Shard<R>& s)
     if (s.path.op == PathOp::tangents || s.path.op == PathOp::param_sets || s.path.op == PathOp::param_sets_along)
         pa.set_dirs_out((uint32_t)s.n_dirs);       // (the K-direction / parameter-set form: the directions / sets whose sums leave the kernel)
     // the general form's vertex history: a word per four vertices and thread, in dynamic shared memory
-    const bool gen = s.path_gen;
+    // (the parameter-set gradient form shares it: the general form's history, tables and block sums, K R rows of them)
+    const bool sets_grad = s.path.op == PathOp::param_sets_grad;
+    const bool gen = s.path_gen || sets_grad;
     // (the first words in LDS, as many as leave the kernel's blocks per CU alone: four in the lockstep k_path -- 16 vertices --,
     //  none in the regenerating forms, whose static LDS sits right under a block's share; the others in global memory)
     const uint32_t hist_words = gen ? (uint32_t)(a.depth_cap / 4) : 0u;
@@ -879,6 +897,8 @@ int path_batch(Shard<R>& s)
             row += ctx->requires_grad[(size_t)p2] ? 1u : 0u;
         pa.gimg_row = row;
     }
+    if (sets_grad)
+        pa.gimg_row = (uint32_t)s.n_dirs;      // (no gradient image in this form: the word carries the caller's set count)
     // the arguments of each operator: k_path_unbiased has no gradient image, k_path_mesh the BVH and its traversal stacks too
     void* args_path[] = {&pa, &d_scene, &d_params, &d_adjoint, &gpart, &fpart, &counts, &ptotal, &gpix};
     void* args_unb[] = {&pa, &d_scene, &d_params, &d_adjoint, &gpart, &fpart, &counts, &ptotal};
@@ -939,6 +959,15 @@ int path_batch(Shard<R>& s)
                       hipLaunchKernelGGL(k_normal_eq_finish, dim3(3 * DRT_NEQ_VALUES(npw)), dim3(DRT_BLOCK), 0, ctx->stream, (const double*)part,
                                          (int)s.neq_blocks, npw, n_out, q.d_A, q.d_b, q.d_loss));
         }
+        if (s.sets && s.sets->grad) {
+            // the sets' gradients: the blocks' row sums, added in a fixed order, to out[set][parameter][channel]
+            if (ctx->n_user_params > 0)
+            DRT_TIMED(s, DRT_K_GRADREDUCE,
+                      hipLaunchKernelGGL(k_sets_grad_finish, dim3((unsigned)(s.n_dirs * ctx->n_user_params * 3)), dim3(DRT_BLOCK), 0, ctx->stream,
+                                         (const double*)gpart, gpath, (int)s.gen_rows, (int)s.gen_rows / s.sets->width, ctx->n_user_params, slot_map,
+                                         s.sets->d_grads));
+            st->units[DRT_K_GRADREDUCE] += (uint64_t)gpath;
+        } else
         if (s.sets) {
             // the sets' images and losses -- with directions: and derivative images, slopes and curvatures --: per-pixel means, squared
             // residuals and products
@@ -963,7 +992,7 @@ int path_batch(Shard<R>& s)
                                                  s.n_dirs * 3, q.d_loss));
             }
         }
-        if (s.neq || s.sets) {
+        if (s.neq || (s.sets && !s.sets->grad)) {
             st->units[DRT_K_GRADREDUCE] += (uint64_t)a.Pb;
             st->path_bytes += (uint64_t)pa.n_ranges * a.Pb * (uint64_t)s.jac_rows() * sizeof(double);
         }
@@ -1267,12 +1296,14 @@ int render_impl(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_p
     using Kind = TangentRequest::Kind;
     const bool forward = tangent && tangent->kind == Kind::forward, jacobian = tangent && tangent->kind == Kind::jacobian,
                directions = tangent && tangent->kind == Kind::directions, param_sets = tangent && tangent->kind == Kind::param_sets,
-               sets_along = param_sets && tangent->sets->along;
+               sets_along = param_sets && tangent->sets->along, sets_grad = param_sets && tangent->sets->grad;
     s.fwd_tangent = forward;
     s.keep_sums = forward && tangent->keep_sums;
     s.neq = jacobian || directions ? tangent->neq : nullptr;
     s.sets = param_sets ? tangent->sets : nullptr;
     s.n_dirs = directions ? tangent->n_dirs : (param_sets ? tangent->sets->n_sets : 0);
+    if (sets_grad)
+        s.d_adjoint = tangent->sets->d_adjoints;
     s.d_params = forward || directions || param_sets ? (const R*)tangent->d_params
                                                      : (sizeof(R) == 4 ? (const R*)ctx->d_params_f : (const R*)ctx->d_params_d);
     shard_plan(s);
@@ -1283,7 +1314,7 @@ int render_impl(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_p
                           "(bounces_per_launch >= 1, DRT_RENDER_UNFUSED, a DRT_HIP_* setting that forces the queue wavefront, or a scene its "
                           "intersection program does not cover)");
     if (jacobian || directions || param_sets) {
-        const PathOp op = jacobian ? PathOp::jacobian : (directions ? PathOp::tangents : (sets_along ? PathOp::param_sets_along : PathOp::param_sets));
+        const PathOp op = jacobian ? PathOp::jacobian : (directions ? PathOp::tangents : (sets_along ? PathOp::param_sets_along : (sets_grad ? PathOp::param_sets_grad : PathOp::param_sets)));
         if (!s.use_path || s.mesh_path || !s.path_finish || s.path.op != op)
             return fail(ctx, DRT_ERR_UNSUPPORTED,
                         jacobian ? "normal equations: they come from the one-launch path kernel's Jacobian form over the whole shard in one "
@@ -1295,6 +1326,9 @@ int render_impl(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_p
                         : sets_along ? "param sets along: they come from the one-launch path kernel's parameter-set form with directions over the whole "
                                        "shard in one batch, which this render does not take (a DRT_HIP_* setting that forces the queue wavefront or a "
                                        "batch size, paths that end at depth 0, or a scene its intersection program does not cover)"
+                        : sets_grad ? "param sets grad: they come from the one-launch path kernel's parameter-set gradient form over the whole "
+                                      "shard in one batch, which this render does not take (a DRT_HIP_* setting that forces the queue wavefront or a "
+                                      "batch size, paths that end at depth 0, or a scene its intersection program does not cover)"
                                      : "param sets: they come from the one-launch path kernel's parameter-set form over the whole shard in one batch, "
                                        "which this render does not take (a DRT_HIP_* setting that forces the queue wavefront or a batch size, paths "
                                        "that end at depth 0, or a scene its intersection program does not cover)");

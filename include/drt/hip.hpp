@@ -15,6 +15,7 @@
 //   drt::hip::render_tangents(scene, cam, tracer, spp, {direction, ...}, img, tangent_imgs [, options])      up to 8 directions, one render
 //   drt::hip::render_param_sets(scene, cam, tracer, spp, {set, ...}, target, imgs, &losses [, options])      up to 8 parameter sets, one trace
 //   drt::hip::render_param_sets_along(scene, cam, tracer, spp, {set, ...}, target [, imgs, tangent_imgs, options])   up to 4 sets with a direction each: loss, slope, curvature
+//   drt::hip::render_param_sets_grad(scene, cam, tracer, spp, {set, ...} [, adjoints, options])     up to 8 sets with a summed gradient each, one trace
 //   drt::hip::normal_equations_along(scene, cam, tracer, spp, {direction, ...}, options, target_or_residual) Gauss-Newton in their span
 //   drt::hip::render(scene of Dual<U>, ...)
 //
@@ -1123,6 +1124,51 @@ inline SetsAlong<T> render_param_sets_along(const Scene<T>& scene, const Camera<
                                                                            (target && K) ? r.slopes.data() : nullptr,
                                                                            K ? r.curvatures.data() : nullptr, st);
                                 });
+    return r;
+}
+
+// ---- ... each set's summed gradient (drt_hip_render_param_sets_grad) -----------------------------------------------------------
+// The gradient of the frame under each of up to DRT_HIP_MAX_SETS_GRAD parameter sets, from one trace: grads[k] lists every parameter of
+// the scene with d <adjoint_k, radiance sum> / d parameter at sets[k] -- what render() with Options::backward leaves in the handles' grad()
+// with sets[k] installed and adjoints + k * width * height as the adjoint image, as the sum over the samples; zero for a handle that
+// requires no gradient.  `adjoints` (sets.size() x width x height; nullptr: every seed (1, 1, 1)).  Handles a set does not list keep the
+// scene's value; a listed handle the scene does not use throws.  The scene's own values and gradients are not changed.
+template <typename T>
+struct SetsGrad {
+    std::vector<ParamSet<T>> grads;     // per set: (handle, gradient) for every parameter of the scene, in the scene's order
+    Stats stats;
+};
+
+template <typename T>
+inline SetsGrad<T> render_param_sets_grad(const Scene<T>& scene, const Camera<T>& cam, const Pathtracer<T>& tracer, std::size_t spp,
+                                          const std::vector<ParamSet<T>>& sets, const Vector<T, 3>* adjoints = nullptr, const Options& opt = Options())
+{
+    const char* who = "drt::hip::render_param_sets_grad";
+    if (opt.unbiased || opt.sample_loss_l2)
+        throw std::runtime_error(std::string(who) + ": the biased operator's summed gradients (backward is implied; no unbiased, no sample_loss_l2)");
+    detail::one_device(who, opt);
+    FlatScene<T> flat = flatten(scene);
+    const std::size_t K = sets.size(), n = flat.handles.size(), npix = cam.width() * cam.height();
+    const std::vector<double> values =
+        detail::rows_of(who, flat, sets, flat.params.data(), false, [](const auto& t) { return std::make_pair(&t.first, &t.second); });
+    std::vector<float> seeds;
+    if (adjoints)
+        seeds = detail::to_floats(adjoints, npix * K);
+    std::vector<double> sums((K * n ? K * n : 1) * 3, 0.0);
+    Options forward = opt;
+    forward.backward = false;           // (implied by the call: the flag itself is the entry point's to add or not)
+    SetsGrad<T> r;
+    r.stats = detail::sets_call("drt_hip_render_param_sets_grad", flat, cam, tracer, spp, K, (const Vector<T, 3>*)nullptr, (Vector<T, 3>*)nullptr,
+                                (Vector<T, 3>*)nullptr, forward,
+                                [&](drt_hip_ctx* ctx, const drt_camera_desc* cd, const drt_render_params* rp, const float*, float*, float*,
+                                    drt_hip_stats* st) {
+                                    return drt_hip_render_param_sets_grad(ctx, cd, rp, (int32_t)K, values.data(), adjoints ? seeds.data() : nullptr,
+                                                                          sums.data(), st);
+                                });
+    r.grads.resize(K);
+    for (std::size_t k = 0; k < K; ++k)
+        for (std::size_t p = 0; p < n; ++p)
+            r.grads[k].emplace_back(flat.handles[p], Vector<T, 3>{T(sums[(k * n + p) * 3]), T(sums[(k * n + p) * 3 + 1]), T(sums[(k * n + p) * 3 + 2])});
     return r;
 }
 

@@ -536,6 +536,30 @@ int drt_hip_render_param_sets_along_double(drt_hip_ctx* ctx, const drt_camera_de
                                            double* out_tangents /* n_sets x H x W x 3, may be NULL */, double* out_loss /* n_sets x 3, may be NULL */,
                                            double* out_dloss /* n_sets x 3, may be NULL */, double* out_curv /* n_sets x 3, may be NULL */,
                                            drt_hip_stats* stats);
+/* ... each set's summed GRADIENT, in one trace: what K Adam chains, the accepted point of a line search, a population of candidates or a
+ * finite-difference check need at several points at once.  out_param_grads[k] is what drt_hip_update_params(param_sets[k]) followed by
+ * drt_hip_render(DRT_RENDER_BACKWARD, adjoints_rgb[k]) writes to out_param_grad: J(P_k)^T w_k as the SUM over this shard's samples, zeros for
+ * parameters with requires_grad == 0.  The sets share the path and its vertex history (neither sees a parameter's value); where the path
+ * meets a light every set runs the general gradient form's own code on its own operands, into its own rows of the wave's fp64 table, and
+ * k_sets_grad_finish adds the blocks in a fixed order without atomics: the same call returns the same bits.  1 <= n_sets <=
+ * DRT_HIP_MAX_SETS_GRAD; the kernel is instantiated for 2, 4 and 8 sets and a call's count is padded up with copies of the context's own
+ * parameters, which add nothing: a set's gradient depends neither on its companions nor on its position, and not on n_sets within a width,
+ * bit for bit.  The table has 408 elements per wave: width x 3 x (parameters that require a gradient) may not exceed it.  The colour
+ * constant a mirror material appends keeps the scene's value in every set and has no output row.  The context's own parameters are not
+ * changed.  adjoints_rgb == NULL seeds every pixel of every set with (1, 1, 1), as drt_hip_render does.  DRT_RENDER_BACKWARD is implied and
+ * may be set or not.  There are no images in this call: the adjoint exists before the trace, and drt_hip_render_param_sets on the other
+ * seed gives the images it comes from.  Everything else -- shards, DRT_RENDER_DEVICE_OUT (adjoints_rgb and out_param_grads are then device
+ * pointers; param_sets is host memory always), _F64, _SYNC, _TIMING, one batch per shard, lockstep under the roulette, the 2^31-sample
+ * limit, the slot the reduction is timed in -- as drt_hip_render_param_sets.
+ * DRT_ERR_INVALID: n_sets outside 1 ... DRT_HIP_MAX_SETS_GRAD, NULL param_sets or out_param_grads, a set or an adjoint value that is not
+ * finite (host buffers), asynchronous frames in flight, bad camera or render parameters.  DRT_ERR_UNSUPPORTED: what
+ * drt_hip_render_param_sets refuses, and more rows than the table holds.  The message of either says "param sets grad"; the context stays
+ * usable. */
+#define DRT_HIP_MAX_SETS_GRAD 8
+int drt_hip_render_param_sets_grad(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_params* rp, int32_t n_sets,
+                                   const double* param_sets /* n_sets x n_params x 3 */,
+                                   const float* adjoints_rgb /* n_sets x H x W x 3, may be NULL */,
+                                   double* out_param_grads /* n_sets x n_params x 3 */, drt_hip_stats* stats);
 /* stream the context launches on (a hipStream_t), for event timing / interop */
 void* drt_hip_stream(drt_hip_ctx* ctx);
 int drt_hip_synchronize(drt_hip_ctx* ctx);

@@ -15,6 +15,7 @@ the noisy objective sits ~9 % below the true albedo at 16 spp.  The per-pixel ad
 the same thing for a loss that is linear in the radiance.
 
     python tools/fit_albedo.py [--size 128] [--spp 16] [--steps 60] [--async] [--oracle] [--gauss-newton [--one-render] [--lambda-sets N]]
+    python tools/fit_albedo.py --scene cornell_shapes --multi-start N [--oracle]
 
 --async: the same loop through drt_hip_render_async / drt_hip_wait (frame i + 1 needs the parameters of step i, so frames
 cannot overlap: what is measured is the call overhead).  --oracle: the CPU restatement instead of the device (checker;
@@ -59,7 +60,13 @@ of at most eight (8 + 2), block Gauss-Seidel: per step every block in turn takes
 K x K system per channel; a row whose diagonal is zero -- `white`, a channel nothing depends on -- stays where it is), 4 renders per
 block.  --subspace tint fits ONE tint over the albedos instead (three directions d theta / d tint_ch, one block).  Printed beside it:
 Adam over the same parameters from the same start with the same number of renders, and both fits' loss on a fixed pair of evaluation
-seeds (sum of r_A r_B, the unbiased estimate of the squared error against the target)."""
+seeds (sum of r_A r_B, the unbiased estimate of the squared error against the target).
+
+--multi-start N (N <= 8, with --scene): N perturbed starts run as N Adam chains over every parameter, side by side.  Per step ONE
+drt_hip_render_param_sets call (seed A: the N images the adjoints 2 (image_k - target) / n come from) and ONE
+drt_hip_render_param_sets_grad call (seed B: the N gradients, each chain seeded with its own adjoint) -- two traces per step where N
+separate runs of the first-order loop need 2 N.  Printed: every chain's two-seed loss at its start and at its end, and the best.
+--oracle runs the same chains as a loop over the restatement."""
 import argparse
 import os
 import sys
@@ -322,6 +329,44 @@ def fit_adam_all(render, free, start, steps, spp, n_values, lr=0.05, decay=0.97,
     return params, hist
 
 
+MULTI_STEPS = 12      # Adam steps of --multi-start by default
+
+
+def fit_multi_start(render, free, starts, steps, spp, n_values, lr=0.05, decay=0.97, lo=0.0, hi=None, log=None):
+    """fit_adam_all for N chains at once: render.param_sets gives the N images of a step (seed A), render.sets_grad the N gradients (seed
+    B, chain k seeded with its own adjoint): two traces per step.  -> (fitted params [N, P, 3], history of the N one-seed losses)"""
+    params = np.array(starts, dtype=np.float64)
+    hi = np.full(params.shape[1:], 1.0) if hi is None else hi
+    m = np.zeros_like(params); v = np.zeros_like(params)
+    b1, b2, eps = 0.8, 0.99, 1e-8
+    mask = np.zeros(params.shape[1], bool)
+    mask[list(free)] = True
+    hist = []
+    for k in range(steps):
+        imgs = render.param_sets(params, 1000 + 2 * k)
+        r = imgs.astype(np.float64) - render.target
+        grads = render.sets_grad(params, (2.0 * r / n_values).astype(np.float32), 1001 + 2 * k)
+        g = np.where(mask[None, :, None], grads / spp, 0.0)
+        m = b1 * m + (1 - b1) * g
+        v = b2 * v + (1 - b2) * g * g
+        params = np.clip(params - lr * decay ** k * (m / (1 - b1 ** (k + 1))) / (np.sqrt(v / (1 - b2 ** (k + 1))) + eps), lo, hi)
+        hist.append((r ** 2).sum((1, 2, 3)))
+        if log and (k % 4 == 3 or k == steps - 1):
+            log(f"multi-start step {k:3d}  losses " + " ".join(f"{x:.6f}" for x in hist[-1]))
+    return params, hist
+
+
+def multi_start(render, n, steps, log=None):
+    """n perturbed starts (perturbed_start, seeds 7, 8, ...) as n Adam chains -> dict: the chains' two-seed losses at the start and at the end"""
+    P = len(render.params0)
+    hi = np.maximum(1.0, render.params0 + 0.5)
+    starts = np.stack([perturbed_start(render.params0, seed=7 + i) for i in range(n)])
+    calls0 = render.calls
+    fitted, hist = fit_multi_start(render, range(P), starts, steps, render.spp, render.target.size, hi=hi, log=log)
+    return {"renders": render.calls - calls0, "start_loss": [eval_loss(render, s) for s in starts], "loss": [eval_loss(render, f) for f in fitted],
+            "params": fitted, "hist": hist}
+
+
 def perturbed_start(params0, seed=7, amount=0.2):
     """every value moved by up to `amount`, kept inside (0, 1] for albedos (rows whose true value exceeds 1, the emission, only below by amount)"""
     p = params0 + np.random.RandomState(seed).uniform(-amount, amount, params0.shape)
@@ -418,6 +463,13 @@ class DeviceRender:
         o = self.r.render_param_sets_along(self.cam, rp, sets, dirs)
         return o["images"], o["tangents"]
 
+    def sets_grad(self, sets, adjoints, seed):
+        """the summed gradient under every row of `sets` [N, P, 3], row k seeded with adjoints[k], in one trace: [N, P, 3]"""
+        rp = self.pkg.RenderParams(spp=self.spp, min_bounces=self.depth, absorb=1.0, seed=seed)
+        self.calls += 1
+        self.traces_of_sets += 1
+        return self.r.render_param_sets_grad(self.cam, rp, sets, adjoints)["grads"]
+
     def close(self):
         self.r.close()
 
@@ -482,6 +534,17 @@ class OracleRender:
             out.append(self.oracle.render(self.scene, self.cam, rp)["image"])
         return np.stack(out)
 
+    def sets_grad(self, sets, adjoints, seed):
+        """the restatement in place of drt_hip_render_param_sets_grad: a backward render per set, counted as the one trace it stands for"""
+        self.calls += 1
+        self.traces_of_sets += 1
+        rp = self.pkg.RenderParams(spp=self.spp, min_bounces=self.depth, absorb=1.0, seed=seed)
+        out = []
+        for p, adj in zip(sets, adjoints):
+            self.scene.params = [tuple(q) for q in p]
+            out.append(self.oracle.render(self.scene, self.cam, rp, backward=True, adjoint=adj)["grads"])
+        return np.stack(out)
+
     def close(self):
         pass
 
@@ -502,6 +565,9 @@ def main():
     ap.add_argument("--line-search", dest="line_search", type=int, default=0,
                     help="with --gauss-newton --scene cornell_shapes: search the step LENGTH over this many candidates (<= 4) in one "
                          "render_param_sets_along call per seed")
+    ap.add_argument("--multi-start", dest="multi_start", type=int, default=0,
+                    help="with --scene: this many perturbed starts (<= 8) as Adam chains side by side, one render_param_sets and one "
+                         "render_param_sets_grad call per step")
     ap.add_argument("--async", dest="use_async", action="store_true")
     ap.add_argument("--oracle", action="store_true")
     ap.add_argument("--quiet", action="store_true")
@@ -512,12 +578,23 @@ def main():
         ap.error("--lambda-sets N (1 ... 7) goes with --gauss-newton (not --one-render)")
     if a.line_search and (not a.gauss_newton or a.scene == "cornell" or a.oracle or a.lambda_sets or not 1 <= a.line_search <= len(STEP_LENGTHS)):
         ap.error("--line-search N (1 ... 4) goes with --gauss-newton --scene cornell_shapes on the device (not --oracle, not --lambda-sets)")
+    if a.multi_start and (a.gauss_newton or a.use_async or a.lambda_sets or a.line_search or not 1 <= a.multi_start <= 8):
+        ap.error("--multi-start N (1 ... 8) is the first-order loop (not --gauss-newton, --async, --lambda-sets, --line-search)")
     import __graft_entry__ as e
     pkg = e.load_package()
     if a.oracle:
         render = OracleRender(pkg, e.load_oracle(), a.size, a.spp, a.depth, a.scene)
     else:
         render = DeviceRender(pkg, a.size, a.spp, a.depth, a.use_async, a.scene)
+    if a.multi_start:
+        t0 = time.time()
+        f = multi_start(render, a.multi_start, a.steps or MULTI_STEPS, log=None if a.quiet else print)
+        for i, (l0, l1) in enumerate(zip(f["start_loss"], f["loss"])):
+            print(f"chain {i}: two-seed loss {l0:.5f} at its start, {l1:.5f} after {a.steps or MULTI_STEPS} steps")
+        best = int(np.argmin(f["loss"]))
+        print(f"{a.scene}: {a.multi_start} Adam chains, {f['renders']} renders ({render.traces_of_sets} of them traces of {a.multi_start} sets: two per "
+              f"step where separate runs take {2 * a.multi_start}); best chain {best}: loss {f['loss'][best]:.5f}  ({time.time() - t0:.2f} s)")
+        return 0 if all(l1 < l0 for l0, l1 in zip(f["start_loss"], f["loss"])) else 1
     if a.scene != "cornell":
         if not a.gauss_newton:
             ap.error("--scene other than cornell goes with --gauss-newton")
