@@ -44,6 +44,7 @@ MAX_DEPTH = 64
 K_RAYGEN, K_INTERSECT, K_SHADE, K_FILM, K_BACKWARD, K_GRADREDUCE, K_INTERSECT_MESH, K_PATH, K_COUNT = 0, 1, 2, 3, 4, 5, 6, 7, 8
 KERNEL_NAMES = ["raygen", "intersect", "shade", "film", "backward", "gradreduce", "intersect_mesh", "path"]
 MAX_DIRS = 8                 # DRT_HIP_MAX_DIRS: directions per render_tangents / render_normal_equations_along call
+MAX_DIRS_CROSS = 8           # DRT_HIP_MAX_DIRS_CROSS: ... per render_normal_equations_cross call
 MAX_PARAM_SETS = 8           # DRT_HIP_MAX_PARAM_SETS: parameter sets per render_param_sets call
 MAX_SETS_ALONG = 4           # DRT_HIP_MAX_SETS_ALONG: parameter sets with a direction each per render_param_sets_along call
 MAX_SETS_GRAD = 8            # DRT_HIP_MAX_SETS_GRAD: parameter sets with a summed gradient each per render_param_sets_grad call
@@ -757,7 +758,7 @@ _ABI_SYMBOLS = ["drt_hip_abi_version", "drt_hip_device_count", "drt_hip_create",
                 "drt_hip_comm_unique_id", "drt_hip_comm_init_rank", "drt_hip_comm_size", "drt_hip_comm_destroy",
                 "drt_hip_upload_scene", "drt_hip_update_params", "drt_hip_set_specialisation", "drt_hip_render", "drt_hip_render_async", "drt_hip_wait",
                 "drt_hip_render_gradient_image", "drt_hip_render_tangent", "drt_hip_render_tangent_double", "drt_hip_render_normal_equations", "drt_hip_render_tangents",
-                "drt_hip_render_normal_equations_along", "drt_hip_render_param_sets", "drt_hip_render_param_sets_double",
+                "drt_hip_render_normal_equations_along", "drt_hip_render_normal_equations_cross", "drt_hip_render_param_sets", "drt_hip_render_param_sets_double",
                 "drt_hip_render_param_sets_along", "drt_hip_render_param_sets_along_double", "drt_hip_render_param_sets_grad", "drt_hip_pin_host", "drt_hip_unpin_host", "drt_hip_stream",
                 "drt_hip_synchronize", "drt_hip_last_error", "drt_hip_kernel_name"]
 
@@ -803,6 +804,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.drt_hip_render_normal_equations_along.argtypes = [C.c_void_p, C.POINTER(CameraDesc), C.POINTER(RenderParamsDesc), C.c_int32, C.c_void_p,
                                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                           C.POINTER(HipStats)]
+    lib.drt_hip_render_normal_equations_cross.argtypes = [C.c_void_p, C.POINTER(CameraDesc), C.POINTER(RenderParamsDesc), C.c_int32, C.c_void_p,
+                                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                          C.c_void_p, C.POINTER(HipStats)]
     lib.drt_hip_render_param_sets.argtypes = [C.c_void_p, C.POINTER(CameraDesc), C.POINTER(RenderParamsDesc), C.c_int32, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(HipStats)]
     lib.drt_hip_render_param_sets_double.argtypes = lib.drt_hip_render_param_sets.argtypes
@@ -1169,6 +1173,52 @@ class HipRenderer:
                                                             C.c_void_p(out_b_ptr or None), C.c_void_p(out_loss_ptr or None),
                                                             C.c_void_p(out_tangents_ptr or None), C.byref(stats) if want_stats else None)
         self._check(rc, "drt_hip_render_normal_equations_along")
+        return stats.as_dict() if want_stats else {}
+
+    def render_normal_equations_cross(self, cam: Camera, rp: RenderParams, tangents: np.ndarray, target: Optional[np.ndarray],
+                                      f64: bool = False, images: bool = False, variance: bool = False, timing: bool = False) -> dict:
+        """drt_hip_render_normal_equations_cross: the normal equations in the span of the K <= MAX_DIRS_CROSS directions `tangents`
+        ([K, n_params, 3]) with b and the loss unbiased from this ONE render (cross-sample products over each pixel's samples; spp >= 2);
+        `target` float32 [H,W,3].
+        -> {"image" [H,W,3] float32, "A" [3,K,K], "b" [3,K], "loss" [3], "bias" [3,K+1] (float64, sums over this shard's pixels; b + bias[:, :K]
+            and loss + bias[:, K] are render_normal_equations_along's plain values), "tangents" [K,H,W,3] float32 or None,
+            "variance" [H,W,3] float32 (the variance of each pixel's mean) or None, "stats"}"""
+        v = self._directions(tangents)
+        K = v.shape[0]
+        cd, d, stats = self._begin(cam, rp, self._host_flags(rp, f64, timing))
+        target, t_ptr = self._image_arg(target, cam)
+        img = np.zeros((cam.height, cam.width, 3), dtype=np.float32)
+        A = np.zeros((3, max(K, 1), max(K, 1)), dtype=np.float64)
+        b = np.zeros((3, max(K, 1)), dtype=np.float64)
+        loss = np.zeros(3, dtype=np.float64)
+        bias = np.zeros((3, max(K, 1) + 1), dtype=np.float64)
+        timg = np.zeros((max(K, 1), cam.height, cam.width, 3), dtype=np.float32) if images else None
+        vimg = np.zeros((cam.height, cam.width, 3), dtype=np.float32) if variance else None
+        rc = self.lib.drt_hip_render_normal_equations_cross(self.ctx, C.byref(cd), C.byref(d), K, v.ctypes.data_as(C.c_void_p), t_ptr,
+                                                            img.ctypes.data_as(C.c_void_p), A.ctypes.data_as(C.c_void_p),
+                                                            b.ctypes.data_as(C.c_void_p), loss.ctypes.data_as(C.c_void_p),
+                                                            bias.ctypes.data_as(C.c_void_p), timg.ctypes.data_as(C.c_void_p) if images else None,
+                                                            vimg.ctypes.data_as(C.c_void_p) if variance else None, C.byref(stats))
+        self._check(rc, "drt_hip_render_normal_equations_cross")
+        return {"image": img, "A": A[:, :K, :K], "b": b[:, :K], "loss": loss, "bias": bias[:, :K + 1], "tangents": timg[:K] if images else None,
+                "variance": vimg, "stats": stats.as_dict()}
+
+    def render_normal_equations_cross_device(self, cam: Camera, rp: RenderParams, tangents: np.ndarray, target_ptr: int, out_A_ptr: int,
+                                             out_b_ptr: int, out_loss_ptr: int, out_bias_ptr: int = 0, out_rgb_ptr: int = 0,
+                                             out_tangents_ptr: int = 0, out_variance_ptr: int = 0, f64: bool = False, timing: bool = False,
+                                             sync: bool = False, want_stats: Optional[bool] = None) -> dict:
+        """drt_hip_render_normal_equations_cross on device pointers (images float32, A [3,K,K] / b [3,K] / loss [3] / bias [3,K+1] float64),
+        enqueued on the context's stream; the directions are host memory."""
+        want_stats = timing if want_stats is None else want_stats
+        v = self._directions(tangents)
+        cd, d, stats = self._begin(cam, rp, self._device_flags(rp, f64, timing, sync))
+        rc = self.lib.drt_hip_render_normal_equations_cross(self.ctx, C.byref(cd), C.byref(d), v.shape[0], v.ctypes.data_as(C.c_void_p),
+                                                            C.c_void_p(target_ptr or None), C.c_void_p(out_rgb_ptr or None),
+                                                            C.c_void_p(out_A_ptr or None), C.c_void_p(out_b_ptr or None),
+                                                            C.c_void_p(out_loss_ptr or None), C.c_void_p(out_bias_ptr or None),
+                                                            C.c_void_p(out_tangents_ptr or None), C.c_void_p(out_variance_ptr or None),
+                                                            C.byref(stats) if want_stats else None)
+        self._check(rc, "drt_hip_render_normal_equations_cross")
         return stats.as_dict() if want_stats else {}
 
     @staticmethod

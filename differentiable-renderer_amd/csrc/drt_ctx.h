@@ -22,6 +22,11 @@ struct NormalEqRequest {
     const float* d_residual = nullptr;
     float* d_jacobian = nullptr;          // P x H x W x 3, or none
     double *d_A = nullptr, *d_b = nullptr, *d_loss = nullptr;
+    // drt_hip_render_normal_equations_cross: the K-direction form with the samples' cross moments, then k_cross_eq in place of k_normal_eq
+    // (d_target set; d_jacobian: the K derivative images)
+    bool cross = false;
+    double* d_bias = nullptr;             // 3 x (K + 1): what was subtracted from b and the loss
+    float* d_variance = nullptr;          // H x W x 3: the variance of the pixel's mean, or none
 };
 // ... and one frame under several parameter sets (drt_hip_render_param_sets): the path kernel's parameter-set form, then k_sets_finish.  All
 // pointers are the device's

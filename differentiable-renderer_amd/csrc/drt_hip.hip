@@ -403,13 +403,15 @@ static int render_tangent_common(drt_hip_ctx* ctx, const drt_camera_desc* cam, c
 // the call behind its refusals, for P rows -- the scene's parameters (the Jacobian form) or the directions of req (the K-direction forward
 // form): the caller's images to the device, the render, the sums and the P images back.  Without a target and a residual (the tangent
 // images alone) the reduction runs on a zero residual; without out_A its sums stay in the context.
+// (cross: drt_hip_render_normal_equations_cross -- the sums gain out_bias, 3 x (P + 1), behind the loss, the images out_variance behind the P)
 static int normal_equations_run(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_params* rp, const float* target_rgb,
                                 const float* residual_rgb, float* out_rgb, double* out_A, double* out_b, double* out_loss,
-                                float* out_jacobian, drt_hip_stats* stats, size_t P, TangentRequest& req, const char* who)
+                                float* out_jacobian, drt_hip_stats* stats, size_t P, TangentRequest& req, const char* who,
+                                bool cross = false, double* out_bias = nullptr, float* out_variance = nullptr)
 {
     const bool dev = (rp->flags & DRT_RENDER_DEVICE_OUT) != 0;
     const size_t npix = (size_t)cam->width * (size_t)cam->height;
-    const size_t nA = 3 * P * P, nb = 3 * P;
+    const size_t nA = 3 * P * P, nb = 3 * P, nbias = cross ? 3 * (P + 1) : 0;
     const float* src = target_rgb ? target_rgb : residual_rgb;
     if (!dev && src)
         for (size_t i = 0; i < npix * 3; ++i)
@@ -425,14 +427,18 @@ static int normal_equations_run(drt_hip_ctx* ctx, const drt_camera_desc* cam, co
             HIPCHK(ctx, hipMemsetAsync(ctx->neq_in.p, 0, npix * 3 * sizeof(float), ctx->stream));
     }
     if (!dev || !out_A) {
-        if ((rc = ensure(ctx, ctx->neq_out, (nA + nb + 3) * sizeof(double))) != DRT_OK) return rc;
+        if ((rc = ensure(ctx, ctx->neq_out, (nA + nb + 3 + nbias) * sizeof(double))) != DRT_OK) return rc;
         q.d_A = (double*)ctx->neq_out.p; q.d_b = q.d_A + nA; q.d_loss = q.d_b + nb;
+        if (cross) q.d_bias = q.d_loss + 3;
     }
+    q.cross = cross;
     if (dev) {
         if (out_A) {
             q.d_A = out_A; q.d_b = out_b; q.d_loss = out_loss;
+            if (cross) q.d_bias = out_bias;
         }
         q.d_jacobian = out_jacobian;
+        q.d_variance = out_variance;
         if (!rgb) {       // (the radiance sums are part of the pipeline: an image of the context's own)
             if ((rc = ensure(ctx, ctx->neq_rgb, npix * 3 * sizeof(float))) != DRT_OK) return rc;
             rgb = (float*)ctx->neq_rgb.p;
@@ -443,9 +449,10 @@ static int normal_equations_run(drt_hip_ctx* ctx, const drt_camera_desc* cam, co
         if (src)
             HIPCHK(ctx, hipMemcpyAsync(ctx->neq_in.p, src, npix * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
         src = (const float*)ctx->neq_in.p;
-        if (out_jacobian) {
-            if ((rc = ensure(ctx, ctx->neq_jac, (P ? P : 1) * npix * 3 * sizeof(float))) != DRT_OK) return rc;
-            q.d_jacobian = (float*)ctx->neq_jac.p;
+        if (out_jacobian || out_variance) {
+            if ((rc = ensure(ctx, ctx->neq_jac, ((P ? P : 1) + (out_variance ? 1 : 0)) * npix * 3 * sizeof(float))) != DRT_OK) return rc;
+            if (out_jacobian) q.d_jacobian = (float*)ctx->neq_jac.p;
+            if (out_variance) q.d_variance = (float*)ctx->neq_jac.p + (P ? P : 1) * npix * 3;
         }
         if (!rgb) {
             ctx->tangent_rgb32.resize(npix * 3);
@@ -457,6 +464,7 @@ static int normal_equations_run(drt_hip_ctx* ctx, const drt_camera_desc* cam, co
     if (nA) HIPCHK(ctx, hipMemsetAsync(q.d_A, 0, nA * sizeof(double), ctx->stream));
     if (nb) HIPCHK(ctx, hipMemsetAsync(q.d_b, 0, nb * sizeof(double), ctx->stream));
     if (q.d_loss) HIPCHK(ctx, hipMemsetAsync(q.d_loss, 0, 3 * sizeof(double), ctx->stream));
+    if (q.d_bias) HIPCHK(ctx, hipMemsetAsync(q.d_bias, 0, nbias * sizeof(double), ctx->stream));
     drt_render_params r = *rp;
     r.flags &= ~(uint32_t)DRT_RENDER_BACKWARD;       // (the Jacobian needs no seed and no summed gradient)
     req.neq = &q;
@@ -465,19 +473,21 @@ static int normal_equations_run(drt_hip_ctx* ctx, const drt_camera_desc* cam, co
     if (dev)
         return DRT_OK;
     // host buffers: the render has waited for its stream; a few hundred bytes of sums, and the Jacobian's rows of this shard where asked for
-    std::vector<double> sums(nA + nb + 3);
+    std::vector<double> sums(nA + nb + 3 + nbias);
     HIPCHK(ctx, hipMemcpy(sums.data(), ctx->neq_out.p, sums.size() * sizeof(double), hipMemcpyDeviceToHost));
     if (nA && out_A) memcpy(out_A, sums.data(), nA * sizeof(double));
     if (nb && out_b) memcpy(out_b, sums.data() + nA, nb * sizeof(double));
     if (out_loss) memcpy(out_loss, sums.data() + nA + nb, 3 * sizeof(double));
-    if (out_jacobian && P) {
+    if (out_bias && nbias) memcpy(out_bias, sums.data() + nA + nb + 3, nbias * sizeof(double));
+    if ((out_jacobian || out_variance) && P) {
         const RenderJob& j = ctx->job;
-        ctx->neq_host.resize(P * npix * 3);
+        ctx->neq_host.resize((P + (out_variance ? 1 : 0)) * npix * 3);
         HIPCHK(ctx, hipMemcpy(ctx->neq_host.data(), ctx->neq_jac.p, ctx->neq_host.size() * sizeof(float), hipMemcpyDeviceToHost));
         const size_t row = (size_t)cam->width * 3;
-        for (size_t p = 0; p < P; ++p)
+        // (image P: the variance image behind the P rows' images)
+        for (size_t p = out_jacobian ? 0 : P; p < P + (out_variance ? 1 : 0); ++p)
             for_each_band(cam->height, j.band, j.n_shards, j.shard, [&](int y0, int y1) {
-                memcpy(out_jacobian + p * npix * 3 + (size_t)y0 * row, ctx->neq_host.data() + p * npix * 3 + (size_t)y0 * row,
+                memcpy((p < P ? out_jacobian + p * npix * 3 : out_variance) + (size_t)y0 * row, ctx->neq_host.data() + p * npix * 3 + (size_t)y0 * row,
                        (size_t)(y1 - y0) * row * sizeof(float));
             });
     }
@@ -596,7 +606,46 @@ static int render_tangents_common(drt_hip_ctx* ctx, const drt_camera_desc* cam, 
                                 me.who);
 }
 
+// ---- ... and the cross-sample normal equations: b and the loss as U-statistics over each pixel's samples, unbiased from ONE render ----
+static int render_cross_common(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_params* rp, int32_t n_dirs,
+                               const double* param_tangents, const float* target_rgb, float* out_rgb, double* out_A, double* out_b,
+                               double* out_loss, double* out_bias, float* out_tangents, float* out_variance_rgb, drt_hip_stats* stats)
+{
+    if (!ctx)
+        return DRT_ERR_INVALID;
+    const PathFormCaller me = {"normal equations cross", "render the shards on plain contexts", "forward mode", DRT_PATH_LDS_PARAMS,
+                               "more parameters than the path kernels stage (136)"};
+    int rc;
+    if ((rc = refuse_before(ctx, cam, rp, me)) != DRT_OK) return rc;
+    if (rp->spp < 2)
+        return refuse(ctx, me, DRT_ERR_INVALID, "spp < 2 (the estimator needs a pair of samples per pixel)");
+    if (n_dirs < 1 || n_dirs > DRT_HIP_MAX_DIRS_CROSS)
+        return refuse(ctx, me, DRT_ERR_INVALID, "n_dirs outside 1 ... DRT_HIP_MAX_DIRS_CROSS = 8");
+    if (!param_tangents || !target_rgb || !out_A || !out_b || !out_loss)
+        return refuse(ctx, me, DRT_ERR_INVALID, "NULL directions, target_rgb, out_A, out_b or out_loss");
+    for (size_t i = 0; i < (size_t)n_dirs * (size_t)ctx->n_user_params * 3; ++i)
+        if (!std::isfinite(param_tangents[i]))
+            return refuse(ctx, me, DRT_ERR_INVALID, "a direction holds a value that is not finite");
+    if ((rc = refuse_after(ctx, cam, rp, me)) != DRT_OK) return rc;
+    // (directions at and above n_dirs, up to the kernel's width, are zero)
+    if ((rc = stage_rows(ctx, rp, param_tangents, n_dirs, n_dirs <= 2 ? 2 : (n_dirs <= 4 ? 4 : 8), RowPad::zero)) != DRT_OK) return rc;
+    TangentRequest req;
+    req.kind = TangentRequest::Kind::directions;
+    req.d_params = ctx->tangent.p;
+    req.n_dirs = n_dirs;
+    return normal_equations_run(ctx, cam, rp, target_rgb, nullptr, out_rgb, out_A, out_b, out_loss, out_tangents, stats, (size_t)n_dirs, req,
+                                me.who, true, out_bias, out_variance_rgb);
+}
+
 extern "C" {
+
+int drt_hip_render_normal_equations_cross(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_params* rp, int32_t n_dirs,
+                                          const double* param_tangents, const float* target_rgb, float* out_rgb, double* out_A, double* out_b,
+                                          double* out_loss, double* out_bias, float* out_tangents, float* out_variance_rgb, drt_hip_stats* stats)
+{
+    return render_cross_common(ctx, cam, rp, n_dirs, param_tangents, target_rgb, out_rgb, out_A, out_b, out_loss, out_bias, out_tangents,
+                               out_variance_rgb, stats);
+}
 
 int drt_hip_render_tangents(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_params* rp, int32_t n_dirs,
                             const double* param_tangents, float* out_rgb, float* out_tangents, drt_hip_stats* stats)

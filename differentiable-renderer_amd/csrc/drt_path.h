@@ -570,6 +570,32 @@ struct Tangents<R, DRT_NP_TANGENT, NC> {
     }
 };
 
+// ---- ... with the samples' CROSS moments (NP = DRT_NP_CROSS, NC = K in {2, 4, 8}; drt_hip_render_normal_equations_cross) ------------
+// The K-direction form above, unchanged in every operation on the path -- the same tables (stage_dirs), the same tangent_advance and
+// tangent_emit on the same operands, so the radiance and derivative sums keep the bits drt_hip_render_tangents gives -- plus, per lane and
+// after each sample, the raw moments an unbiased product of two pixel means needs (a U-statistic over the pixel's n samples):
+//     Q_k[ch] += dL_k[ch] L[ch]          S2[ch] += L[ch]^2          in fp64, from the sample's own values (exact products for f32 operands)
+// With T_k, m the pixel means and r = m - target:   mean over s != s' of t_{k,s} (L_s' - target) = T_k r - cov(t_k, L) / n, and of
+// (L_s - target)(L_s' - target) = r^2 - var(L) / n, with the sample covariance (Q_k - n T_k m) / (n - 1) and variance (S2 - n m^2) / (n - 1).
+// Raw moments add across sample ranges.  At the end of its range a lane writes gpix[range][row][pixel] with 6 nd + 3 rows: 3 nd derivative
+// sums, 3 nd of Q, 3 of S2 (nd = PathArgs::dirs_out(), the caller's directions); k_cross_eq (below) forms the corrections per pixel.
+#define DRT_NP_CROSS (-6)
+#define DRT_NP_IS_DIR(np) ((np) == DRT_NP_TANGENT || (np) == DRT_NP_CROSS)
+// blocks per CU (= waves per SIMD) of the f32 forms: the most that stay free of scratch (the compiler's report: DESIGN.md 9b)
+#ifndef DRT_CROSS2_MIN_BLOCKS
+#define DRT_CROSS2_MIN_BLOCKS 4
+#endif
+#ifndef DRT_CROSS4_MIN_BLOCKS
+#define DRT_CROSS4_MIN_BLOCKS 3      // (diffuse; the glossy form with the reference's kinds compiled in keeps 8 bytes of scratch at three: two)
+#endif
+#ifndef DRT_CROSS8_MIN_BLOCKS
+#define DRT_CROSS8_MIN_BLOCKS 2
+#endif
+template <typename R, int NC>
+struct Tangents<R, DRT_NP_CROSS, NC> : Tangents<R, DRT_NP_TANGENT, NC> {
+    double Q[NC][3], S2[3];         // the lane's moment sums over its sample range
+};
+
 // ---- ONE path under K parameter SETS (NP = DRT_NP_SETS, NC = K in {2, 4, 8}; drt_hip_render_param_sets) --------------------------
 // A parameter is a colour or an emission and nothing else: the closest hit, the BxDF sample, the roulette and the draw indices do not
 // see its value, so a path under parameter set A is the same path under set B.  K sets cost one ray, one key, one hit, one m_k and K
@@ -986,10 +1012,10 @@ __device__ inline void add_emission(const SL& lds, const TangentLds<R>& tl, cons
     } else {
         const V3<R> E = load_param<R, (NP != 0)>(lds, params, (int)eid) * inv_pk;
         V3<R> Tr = T;
-        if (NC > 0 || NP == DRT_NP_ANY || NP == DRT_NP_TANGENT)  // a channel that met a zero colour is dark
+        if (NC > 0 || NP == DRT_NP_ANY || DRT_NP_IS_DIR(NP))  // a channel that met a zero colour is dark
             Tr = mk<R>((tg.zc & 0xFFu) ? R(0) : T.x, (tg.zc & 0xFF00u) ? R(0) : T.y, (tg.zc & 0xFF0000u) ? R(0) : T.z);
         L = L + Tr * E;
-        if constexpr (NP == DRT_NP_TANGENT && NC > 0) {
+        if constexpr (DRT_NP_IS_DIR(NP) && NC > 0) {
             // K directions: the single-direction case below (tangent_emit), once per direction
             const R* dir = tg.tab + (1u + 2u * NC) * tg.stride + (eid < tg.rest ? eid : 0u) * 3u;
 #pragma unroll
@@ -1161,9 +1187,9 @@ __device__ inline void path_bounce(const PathArgs& a, const PathSceneLds<R>& lds
     // the throughput moves on only in lanes whose path goes on (the others stay frozen for the light's turn); with
     // gradients it leaves zero colour channels out and counts them, and counts the bounce for its colour (see Tangents)
     // (REST, the lockstep kernel's colour-column form: a lane that does not go on reads the table's row of ones and zero increments)
-    constexpr bool REST = FREEZE_BY_ROW && NC > 0 && NP != DRT_NP_ANY && NP != DRT_NP_TANGENT && NP != DRT_NP_SETS;
+    constexpr bool REST = FREEZE_BY_ROW && NC > 0 && NP != DRT_NP_ANY && !DRT_NP_IS_DIR(NP) && NP != DRT_NP_SETS;
     // (DIR, forward mode: the same by its own table's rest row, in every form)
-    constexpr bool DIR = NP == DRT_NP_TANGENT, BY_ROW = REST || DIR;
+    constexpr bool DIR = DRT_NP_IS_DIR(NP), BY_ROW = REST || DIR;
     if constexpr (NP == DRT_NP_SETS) {
         // K parameter sets: every set's throughput moves on by its own colour row; a lane that stops reads the rest row and m = 1
         const uint32_t row = (alive && cid < tg.rest ? cid : tg.rest) * 4u;
@@ -1237,7 +1263,7 @@ __device__ inline void path_bounce(const PathArgs& a, const PathSceneLds<R>& lds
                 tg.cnt[NC > 4 ? 1 : 0] += tl.inc[cidx][1];
             tg.zc += tl.inc[cidx][2];
         } else
-        if constexpr (NC > 0 && NP != DRT_NP_ANY && NP != DRT_NP_TANGENT && NP != DRT_NP_SETS) {
+        if constexpr (NC > 0 && NP != DRT_NP_ANY && !DRT_NP_IS_DIR(NP) && NP != DRT_NP_SETS) {
             tg.cnt[0] += alive ? tl.inc[cidx][0] : 0u;
             if (NC > 4)
                 tg.cnt[NC > 4 ? 1 : 0] += alive ? tl.inc[cidx][1] : 0u;
@@ -1334,6 +1360,9 @@ constexpr int path_min_blocks()
     if (NP == DRT_NP_SETS)         // K parameter sets, lockstep: six values and three fp64 sums per set beside the forward-only kernel's
         return RB == 4 ? (DRT_NC_OF(NCR) <= 2 ? DRT_SETS2_MIN_BLOCKS : (DRT_NC_OF(NCR) <= 4 ? DRT_SETS4_MIN_BLOCKS : DRT_SETS8_MIN_BLOCKS))
                        : (DRT_NC_OF(NCR) <= 2 ? (SPEC ? 2 : 3) : (DRT_NC_OF(NCR) <= 4 ? 2 : 1));
+    if (NP == DRT_NP_CROSS)        // K directions with the samples' cross moments, lockstep: 3 K + 3 more fp64 sums beside the K-direction form's
+        return RB == 4 ? (DRT_NC_OF(NCR) <= 2 ? DRT_CROSS2_MIN_BLOCKS : (DRT_NC_OF(NCR) <= 4 ? (SPEC ? 2 : DRT_CROSS4_MIN_BLOCKS) : DRT_CROSS8_MIN_BLOCKS))
+                       : (DRT_NC_OF(NCR) <= 2 ? 2 : 1);
     if (NP == DRT_NP_TANGENT && DRT_NC_OF(NCR) > 0)   // K directions, lockstep: f64 takes what a block per CU has
         return RB == 4 ? (DRT_NC_OF(NCR) <= 2 ? DRT_TANGENTS2_MIN_BLOCKS : (DRT_NC_OF(NCR) <= 4 ? DRT_TANGENTS4_MIN_BLOCKS : DRT_TANGENTS8_MIN_BLOCKS))
                        : (DRT_NC_OF(NCR) <= 2 ? 2 : 1);
@@ -1383,7 +1412,9 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
     static_assert(!(SGRAD && (REGEN || NC < 1)), "the parameter-set gradient form is a lockstep form of K >= 1 sets: a lane is a pixel");
     __shared__ typename PickT<(GEN || SGRAD), GenBlock<R>, NoLds>::T s_gen;
     extern __shared__ uint32_t s_hist[];                  // GEN: [a.hist_lds][DRT_BLOCK] history words
-    constexpr bool DIR = NP == DRT_NP_TANGENT;            // forward mode: the derivative along one direction (see DirLds); `params` = [params | direction]
+    constexpr bool CROSS = NP == DRT_NP_CROSS;            // the K-direction form + the samples' cross moments (see Tangents<R, DRT_NP_CROSS>)
+    static_assert(!(CROSS && (REGEN || NC < 1)), "the cross-moment form is a lockstep form of K >= 1 directions: a lane is a pixel");
+    constexpr bool DIR = DRT_NP_IS_DIR(NP);               // forward mode: the derivative along one direction (see DirLds); `params` = [params | direction]
     constexpr bool DIRS = DIR && NC > 0;                  // ... along NC directions at once: tables in dynamic shared memory (see stage_dirs)
     static_assert(!(DIRS && REGEN), "the K-direction form is a lockstep form: a lane is a pixel");
     constexpr bool SETS = NP == DRT_NP_SETS;              // one path under NC parameter sets: tables in dynamic shared memory (see stage_sets)
@@ -1434,6 +1465,12 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
 #pragma unroll
         for (int k = 0; k < (ALONG ? 2 * NC : NC); ++k)
             tk[k][0] = tk[k][1] = tk[k][2] = 0.0;
+    }
+    if constexpr (CROSS) {
+#pragma unroll
+        for (int k = 0; k < NC; ++k)
+            tg.Q[k][0] = tg.Q[k][1] = tg.Q[k][2] = 0.0;
+        tg.S2[0] = tg.S2[1] = tg.S2[2] = 0.0;
     }
     uint32_t n_seg = 0, n_capped = 0;                     // wave-uniform counters
 
@@ -1544,6 +1581,15 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
         } else
         if constexpr (DIR) {
             tx += (double)tg.dL.x; ty += (double)tg.dL.y; tz += (double)tg.dL.z;
+        }
+        if constexpr (CROSS) {
+            // the sample's products, from its own values: Q_k += dL_k L, S2 += L L
+            const double lx = (double)L.x, ly = (double)L.y, lz = (double)L.z;
+#pragma unroll
+            for (int k = 0; k < NC; ++k) {
+                tg.Q[k][0] += (double)tg.dL[k].x * lx; tg.Q[k][1] += (double)tg.dL[k].y * ly; tg.Q[k][2] += (double)tg.dL[k].z * lz;
+            }
+            tg.S2[0] += lx * lx; tg.S2[1] += ly * ly; tg.S2[2] += lz * lz;
         }
     }
     }
@@ -1685,7 +1731,7 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
             double* f = gimg_part + ((size_t)range * 3) * a.Pb + lp;
             f[0] = (double)tg.gsum.x; f[(size_t)a.Pb] = (double)tg.gsum.y; f[(size_t)a.Pb * 2] = (double)tg.gsum.z;
         }
-        if constexpr (DIRS || SETS || ALONG) if (gimg_part && have) {
+        if constexpr ((DIRS && !CROSS) || SETS || ALONG) if (gimg_part && have) {
             // K directions / K sets: the pixel's sums in the Jacobian form's layout, [range][3 k + ch][pixel], for those the caller gave; with a
             // direction per set, 6 rows a set: [range][6 k + ch][pixel] the radiance sums, [range][6 k + 3 + ch][pixel] the derivative sums
             const uint32_t nd = a.dirs_out() < (uint32_t)NC ? a.dirs_out() : (uint32_t)NC;
@@ -1695,6 +1741,21 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
                 if ((uint32_t)(k / TK) < nd) {
                     f[(size_t)(k * 3) * a.Pb] = tk[k][0]; f[(size_t)(k * 3 + 1) * a.Pb] = tk[k][1]; f[(size_t)(k * 3 + 2) * a.Pb] = tk[k][2];
                 }
+        }
+        if constexpr (CROSS) if (gimg_part && have) {
+            // K directions with cross moments: [range][row][pixel] with 6 nd + 3 rows -- 3 nd derivative sums, 3 nd of Q, 3 of S2 --, for the
+            // directions the caller gave
+            const uint32_t nd = a.dirs_out() < (uint32_t)NC ? a.dirs_out() : (uint32_t)NC;
+            double* f = gimg_part + ((size_t)range * (size_t)(nd * 6u + 3u)) * a.Pb + lp;
+            double* fq = f + (size_t)(nd * 3u) * a.Pb;
+#pragma unroll
+            for (int k = 0; k < NC; ++k)
+                if ((uint32_t)k < nd) {
+                    f[(size_t)(k * 3) * a.Pb] = tk[k][0]; f[(size_t)(k * 3 + 1) * a.Pb] = tk[k][1]; f[(size_t)(k * 3 + 2) * a.Pb] = tk[k][2];
+                    fq[(size_t)(k * 3) * a.Pb] = tg.Q[k][0]; fq[(size_t)(k * 3 + 1) * a.Pb] = tg.Q[k][1]; fq[(size_t)(k * 3 + 2) * a.Pb] = tg.Q[k][2];
+                }
+            double* fs = f + (size_t)(nd * 6u) * a.Pb;
+            fs[0] = tg.S2[0]; fs[(size_t)a.Pb] = tg.S2[1]; fs[(size_t)a.Pb * 2] = tg.S2[2];
         }
         if constexpr (DIR && !DIRS) if (gimg_part && have) {
             // forward mode: the pixel's derivative sums leave where a gradient image's do -- same layout, same finishing kernels
@@ -2432,4 +2493,116 @@ k_sets_grad_finish(const double* __restrict__ gpart, int n_blocks, int row_strid
     add_blocks(red, none ? 0 : n_blocks, [&](int b) { return gpart[(size_t)b * row_stride + src]; });
     if (threadIdx.x == 0)
         out[blockIdx.x] = red[0];
+}
+
+// ---- the cross-sample normal equations of a frame in the span of K directions (drt_hip_render_normal_equations_cross) -------------
+// Behind a launch of k_path's cross-moment form: jpart[range][row][pixel] holds, per pixel of the shard and sample range, 3 nd derivative
+// sums (row 3 k + ch), 3 nd moment sums Q_k = sum_s t_{k,s} L_s (row 3 nd + 3 k + ch) and 3 of S2 = sum_s L_s^2 (row 6 nd + ch); fpart the
+// radiance sums.  Per channel (blockIdx.y) and pixel, in fp64, every sum over the ranges in range order, n = spp:
+//     m = sum L / n      T_k = sum t_k / n      r = m - target
+//     bias_k = (Q_k - (sum t_k) m) / ((n - 1) n)        the sample covariance of (t_k, L) over n: what T_k r carries beyond its expectation
+//     noise  = (S2 - (sum L) m) / ((n - 1) n)           the sample variance of L over n: the variance of the pixel's mean
+//     A[k][l] += T_k T_l (l >= k)     b[k] += T_k r - bias_k     bias[k] += bias_k     loss += r r - noise     bias[K] += noise
+// DRT_CROSS_VALUES(NP) running sums per thread, then block_sums; k_cross_eq_finish adds the blocks in a fixed order and mirrors A.  No
+// atomics: the same call gives the same bits.  k_normal_eq's grid rule, a pixel per thread.  The derivative images (float, the layout of
+// drt_hip_render_tangents: T_k formed as k_normal_eq forms it) and the variance image (noise, H x W x 3) leave in the same pass.
+#define DRT_CROSS_VALUES(np) ((np) * ((np) + 1) / 2 + 2 * (np) + 2)
+template <int NP>
+__global__ void __launch_bounds__(DRT_BLOCK)
+k_cross_eq(PathArgs a, const double* __restrict__ jpart, const double* __restrict__ fpart, int n_dirs, const float* __restrict__ target,
+           float* __restrict__ out_tan, float* __restrict__ out_var, double* __restrict__ part)
+{
+    constexpr int NV = DRT_CROSS_VALUES(NP), NT = NP * (NP + 1) / 2;
+    const int ch = (int)blockIdx.y;
+    const size_t Pb = a.Pb, rows = (size_t)n_dirs * 6 + 3, npix = (size_t)a.W * (size_t)a.H;
+    const double n = (double)a.spp, inv = 1.0 / n, inv_pairs = 1.0 / ((n - 1.0) * n);
+    double acc[NV];
+#pragma unroll
+    for (int k = 0; k < NV; ++k)
+        acc[k] = 0.0;
+    for (uint32_t j = blockIdx.x * DRT_BLOCK + threadIdx.x; j < a.Pb; j += gridDim.x * DRT_BLOCK) {
+        double Ts[NP], Qs[NP], S2 = 0.0, Ls = 0.0;
+#pragma unroll
+        for (int p = 0; p < NP; ++p)
+            Ts[p] = Qs[p] = 0.0;
+        for (uint32_t q = 0; q < a.n_ranges; ++q) {
+            const double* fj = jpart + ((size_t)q * rows + (size_t)ch) * Pb + j;
+#pragma unroll
+            for (int p = 0; p < NP; ++p)
+                if (p < n_dirs) {
+                    Ts[p] += fj[(size_t)(p * 3) * Pb];
+                    Qs[p] += fj[((size_t)n_dirs * 3 + (size_t)(p * 3)) * Pb];
+                }
+            S2 += fj[((size_t)n_dirs * 6) * Pb];
+            Ls += fpart[((size_t)q * 3 + (size_t)ch) * Pb + j];
+        }
+        const size_t gp = path_global_pixel(a, a.p0 + j);
+        const double m = Ls * inv, r = m - (double)target[gp * 3 + (size_t)ch];
+        const double noise = (S2 - Ls * m) * inv_pairs;
+        double T[NP], bias[NP];
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+            T[p] = Ts[p] * inv;
+            bias[p] = (Qs[p] - Ts[p] * m) * inv_pairs;
+        }
+        if (out_tan) {
+#pragma unroll
+            for (int p = 0; p < NP; ++p)
+                if (p < n_dirs)
+                    out_tan[((size_t)p * npix + gp) * 3 + (size_t)ch] = (float)T[p];
+        }
+        if (out_var)
+            out_var[gp * 3 + (size_t)ch] = (float)noise;
+        int k = 0;
+#pragma unroll
+        for (int p = 0; p < NP; ++p)
+#pragma unroll
+            for (int q2 = p; q2 < NP; ++q2)
+                acc[k++] += T[p] * T[q2];
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+            acc[NT + p] += T[p] * r - bias[p];
+            acc[NT + NP + p] += bias[p];
+        }
+        acc[NT + 2 * NP] += r * r - noise;
+        acc[NT + 2 * NP + 1] += noise;
+    }
+    block_sums(acc, part, ((size_t)ch * gridDim.x + blockIdx.x) * NV);
+}
+
+// ... its second stage: block (channel, value) adds that value's partials over k_cross_eq's blocks (add_blocks) and writes it where it belongs:
+// A[ch][k][l] and its mirror, b[ch][k], bias[ch][k], loss[ch], bias[ch][K], for the n_out directions of the caller (np_w: k_cross_eq's width)
+__global__ void __launch_bounds__(DRT_BLOCK)
+k_cross_eq_finish(const double* __restrict__ part, int n_blocks, int np_w, int n_out, double* __restrict__ out_A, double* __restrict__ out_b,
+                  double* __restrict__ out_loss, double* __restrict__ out_bias)
+{
+    __shared__ double red[DRT_BLOCK];
+    const int nv = DRT_CROSS_VALUES(np_w);
+    const int ch = (int)blockIdx.x / nv, k = (int)blockIdx.x - ch * nv;
+    add_blocks(red, n_blocks, [&](int b) { return part[((size_t)ch * n_blocks + b) * nv + k]; });
+    if (threadIdx.x != 0)
+        return;
+    const int n_tri = np_w * (np_w + 1) / 2;
+    if (k < n_tri) {
+        int p = 0, first = 0;                                // row p of the upper triangle starts at `first` and holds np_w - p values
+        while (k >= first + (np_w - p)) {
+            first += np_w - p;
+            ++p;
+        }
+        const int q = p + (k - first);
+        if (p < n_out && q < n_out) {
+            out_A[((size_t)ch * n_out + p) * n_out + q] = red[0];
+            out_A[((size_t)ch * n_out + q) * n_out + p] = red[0];
+        }
+    } else if (k < n_tri + np_w) {
+        if (k - n_tri < n_out)
+            out_b[(size_t)ch * n_out + (k - n_tri)] = red[0];
+    } else if (k < n_tri + 2 * np_w) {
+        if (out_bias && k - n_tri - np_w < n_out)
+            out_bias[(size_t)ch * (n_out + 1) + (k - n_tri - np_w)] = red[0];
+    } else if (k == n_tri + 2 * np_w) {
+        if (out_loss)
+            out_loss[ch] = red[0];
+    } else if (out_bias)
+        out_bias[(size_t)ch * (n_out + 1) + n_out] = red[0];
 }

@@ -151,12 +151,13 @@ inline int np_width(int n_params, int general)
 }
 
 // ---- which instantiation of the one-launch path kernels a render runs (shard_plan decides it, path_batch launches it) ----
-enum class PathOp { biased, unbiased, mesh, tangent, jacobian, tangents, param_sets, param_sets_along, param_sets_grad };   // k_path (the gradient image included), k_path_unbiased, k_path_mesh, k_path's forward-mode form,
+enum class PathOp { biased, unbiased, mesh, tangent, jacobian, tangents, param_sets, param_sets_along, param_sets_grad, cross };   // k_path (the gradient image included), k_path_unbiased, k_path_mesh, k_path's forward-mode form,
                                                                     // its Jacobian form (lockstep, parameters in columns: DRT_NC_JACOBIAN),
                                                                     // its K-direction forward form (lockstep, nc = K),
                                                                     // its parameter-set form (lockstep, np = DRT_NP_SETS, nc = K),
                                                                     // ... with a direction per set (lockstep, np = DRT_NP_SETS_ALONG, nc = K)
                                                                     // ... with a summed gradient per set (lockstep, np = DRT_NP_SETS_GRAD, nc = K)
+                                                                    // its K-direction form with cross moments (lockstep, np = DRT_NP_CROSS, nc = K)
 enum class PathProg { cornell, sorted, scene };  // closest-hit program: the reference's kinds compiled in (SigCornell), kinds read at
                                                  // run time (SigNone), or compiled by hiprtc for the scene's own KindSig (drt_jit.h)
 struct PathForm {
@@ -198,7 +199,8 @@ struct Shard {
     int neq_vw = 1;                 // ... pixels per lane (2: 16-byte loads, an even number of pixels)
     int n_dirs = 0;                 // ... > 0: its rows are directions -- k_path's K-direction forward form in place of the Jacobian form
     const ParamSetsRequest* sets = nullptr;   // drt_hip_render_param_sets: the parameter-set form, then k_sets_finish (n_dirs: the caller's sets)
-    int jac_rows() const { return (neq || sets) ? (n_dirs > 0 ? n_dirs : ctx->n_params) * (sets && sets->along ? 6 : 3) : 3; }   // rows a pixel's sums have in `gpix`
+    bool cross() const { return neq && neq->cross; }   // drt_hip_render_normal_equations_cross: 6 rows a direction + 3, k_cross_eq
+    int jac_rows() const { return cross() ? n_dirs * 6 + 3 : (neq || sets) ? (n_dirs > 0 ? n_dirs : ctx->n_params) * (sets && sets->along ? 6 : 3) : 3; }   // rows a pixel's sums have in `gpix`
     bool sets_grad() const { return sets && sets->grad; }   // drt_hip_render_param_sets_grad: gradient tables, no per-pixel sums
     bool pixel_sums() const { return gimg_param >= 0 || fwd_tangent || neq || (sets && !sets->grad); }   // the lanes' per-pixel sums leave the path kernel (gimg_part)
     // the scene in compute type R
@@ -307,7 +309,7 @@ template <typename R>
 unsigned path_dynamic_lds(const PathForm& f, int n_params, unsigned hist_bytes)
 {
     const uint32_t n = (uint32_t)std::min(n_params, DRT_PATH_LDS_PARAMS), K = (uint32_t)f.nc;
-    if (f.op == PathOp::tangents) return dirs_table_words(n, K) * (unsigned)sizeof(R);
+    if (f.op == PathOp::tangents || f.op == PathOp::cross) return dirs_table_words(n, K) * (unsigned)sizeof(R);
     if (f.op == PathOp::param_sets) return sets_table_words(n, K) * (unsigned)sizeof(R);
     if (f.op == PathOp::param_sets_along) return sets_along_table_words(n, K) * (unsigned)sizeof(R);
     if (f.op == PathOp::param_sets_grad) return hist_bytes + sets_grad_table_words(n, K) * (unsigned)sizeof(R);   // (the history words, then the tables: 51 KB in f32, 98 KB in f64 at 136 parameters x 8 sets)
@@ -363,8 +365,8 @@ const void* library_path_kernel(const PathForm& f)
     // one path under K parameter sets, each set with a direction, along K directions -- the op names its NP tag --: lockstep, every program,
     // widths 2, 4 and 8; with a direction per set 2 and 4 (drt_path.h: K = 8 is not kept)
     if (const int tag = f.op == PathOp::param_sets ? DRT_NP_SETS : (f.op == PathOp::param_sets_along ? DRT_NP_SETS_ALONG
-                        : (f.op == PathOp::param_sets_grad ? DRT_NP_SETS_GRAD : (f.op == PathOp::tangents ? DRT_NP_TANGENT : 0))))
-        return f.regen ? nullptr : with_int<DRT_NP_SETS, DRT_NP_SETS_ALONG, DRT_NP_SETS_GRAD, DRT_NP_TANGENT>(tag, [&](auto np) {
+                        : (f.op == PathOp::param_sets_grad ? DRT_NP_SETS_GRAD : (f.op == PathOp::tangents ? DRT_NP_TANGENT : (f.op == PathOp::cross ? DRT_NP_CROSS : 0)))))
+        return f.regen ? nullptr : with_int<DRT_NP_SETS, DRT_NP_SETS_ALONG, DRT_NP_SETS_GRAD, DRT_NP_TANGENT, DRT_NP_CROSS>(tag, [&](auto np) {
             return with_int<2, 4, 8>(f.nc, [&](auto k) {
                 if constexpr (decltype(np)::value == DRT_NP_SETS_ALONG && decltype(k)::value > 4)
                     return (const void*)nullptr;
@@ -469,6 +471,10 @@ void shard_plan(Shard<R>& s)
         f.op = PathOp::tangents;
         f.np = DRT_NP_TANGENT;
         f.nc = s.n_dirs <= 2 ? 2 : (s.n_dirs <= 4 ? 4 : 8);
+        if (s.cross()) {            // ... with the samples' cross moments
+            f.op = PathOp::cross;
+            f.np = DRT_NP_CROSS;
+        }
     }
     if (s.sets && !s.mesh_path) {   // the parameter-set form, at the width the host staged its tables for
         f.op = PathOp::param_sets;
@@ -634,10 +640,10 @@ int shard_buffers(Shard<R>& s)
             if ((rc = ensure(ctx, ctx->gpix, (size_t)s.path_ranges * (size_t)s.jac_rows() * s.Pb * sizeof(double))) != DRT_OK) return rc;
         if (s.neq) {
             // k_normal_eq: a memory-bound grid-stride pass per channel -- up to four blocks per CU and channel keep twelve resident
-            s.neq_vw = (s.Pb & 1u) ? 1 : 2;
+            s.neq_vw = (s.Pb & 1u) || s.cross() ? 1 : 2;   // (k_cross_eq: a pixel per thread)
             const uint64_t items = ((uint64_t)s.Pb + s.neq_vw - 1) / s.neq_vw;
             s.neq_blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((items + DRT_BLOCK - 1) / DRT_BLOCK, (uint64_t)ctx->n_cu * 4));
-            if ((rc = ensure(ctx, ctx->neq_part, (size_t)3 * s.neq_blocks * DRT_NEQ_VALUES(DRT_FAST_PARAMS) * sizeof(double))) != DRT_OK) return rc;
+            if ((rc = ensure(ctx, ctx->neq_part, (size_t)3 * s.neq_blocks * DRT_CROSS_VALUES(DRT_FAST_PARAMS) * sizeof(double))) != DRT_OK) return rc;
         }
         if (s.sets) {
             // k_sets_finish: k_normal_eq's grid rule, a pixel per thread
@@ -800,7 +806,7 @@ int path_batch(Shard<R>& s)
     pa.ct_step_f = (float)(2. * pa.tan_half * pa.inv_H);
     pa.gimg_param = s.gimg_param;
     pa.gen_rows = s.gen_rows; pa.gen_clog2 = s.gen_clog2;
-    if (s.path.op == PathOp::tangents || s.path.op == PathOp::param_sets || s.path.op == PathOp::param_sets_along)
+    if (s.path.op == PathOp::tangents || s.path.op == PathOp::cross || s.path.op == PathOp::param_sets || s.path.op == PathOp::param_sets_along)
         pa.set_dirs_out((uint32_t)s.n_dirs);       // (the K-direction / parameter-set form: the directions / sets whose sums leave the kernel)
     // the general form's vertex history: a word per four vertices and thread, in dynamic shared memory
     // (the parameter-set gradient form shares it: the general form's history, tables and block sums, K R rows of them)
@@ -936,6 +942,19 @@ int path_batch(Shard<R>& s)
         }
         // what the Jacobian, K-direction and parameter-set forms reduce from `gpix`: per block, then over the blocks (timed in the reduction's slot)
         double* part = (double*)ctx->neq_part.p;
+        if (s.cross()) {
+            // the cross-sample normal equations: per-pixel products of the means, less the samples' covariances
+            const NormalEqRequest& q = *s.neq;
+            const int npw = np_width(s.n_dirs, DRT_FAST_PARAMS);
+            DRT_TIMED(s, DRT_K_GRADREDUCE, with_int<4, 8>(npw, [&](auto np) {
+                hipLaunchKernelGGL((k_cross_eq<decltype(np)::value>), dim3(s.neq_blocks, 3), dim3(DRT_BLOCK), 0, ctx->stream, pa, (const double*)gpix,
+                                   (const double*)fpart, s.n_dirs, q.d_target, q.d_jacobian, q.d_variance, part);
+                return 0;
+            }));
+            DRT_TIMED(s, DRT_K_GRADREDUCE,
+                      hipLaunchKernelGGL(k_cross_eq_finish, dim3(3 * DRT_CROSS_VALUES(npw)), dim3(DRT_BLOCK), 0, ctx->stream, (const double*)part,
+                                         (int)s.neq_blocks, npw, s.n_dirs, q.d_A, q.d_b, q.d_loss, q.d_bias));
+        } else
         if (s.neq) {
             // the normal equations: per-pixel products
             const NormalEqRequest& q = *s.neq;
@@ -1314,12 +1333,16 @@ int render_impl(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_p
                           "(bounces_per_launch >= 1, DRT_RENDER_UNFUSED, a DRT_HIP_* setting that forces the queue wavefront, or a scene its "
                           "intersection program does not cover)");
     if (jacobian || directions || param_sets) {
-        const PathOp op = jacobian ? PathOp::jacobian : (directions ? PathOp::tangents : (sets_along ? PathOp::param_sets_along : (sets_grad ? PathOp::param_sets_grad : PathOp::param_sets)));
+        const bool cross = directions && tangent->neq && tangent->neq->cross;
+        const PathOp op = jacobian ? PathOp::jacobian : (cross ? PathOp::cross : directions ? PathOp::tangents : (sets_along ? PathOp::param_sets_along : (sets_grad ? PathOp::param_sets_grad : PathOp::param_sets)));
         if (!s.use_path || s.mesh_path || !s.path_finish || s.path.op != op)
             return fail(ctx, DRT_ERR_UNSUPPORTED,
                         jacobian ? "normal equations: they come from the one-launch path kernel's Jacobian form over the whole shard in one "
                                    "batch, which this render does not take (a DRT_HIP_* setting that forces the queue wavefront or a batch size, "
                                    "more than 2^31 camera samples, or a scene its intersection program does not cover)"
+                        : cross ? "normal equations cross: they come from the one-launch path kernel's K-direction form with cross moments over the "
+                                  "whole shard in one batch, which this render does not take (a DRT_HIP_* setting that forces the queue wavefront or a "
+                                  "batch size, more than 2^31 camera samples, or a scene its intersection program does not cover)"
                         : directions ? "tangents / normal equations along: they come from the one-launch path kernel's K-direction form over the whole "
                                        "shard in one batch, which this render does not take (a DRT_HIP_* setting that forces the queue wavefront or a "
                                        "batch size, more than 2^31 camera samples, or a scene its intersection program does not cover)"

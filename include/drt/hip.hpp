@@ -17,6 +17,7 @@
 //   drt::hip::render_param_sets_along(scene, cam, tracer, spp, {set, ...}, target [, imgs, tangent_imgs, options])   up to 4 sets with a direction each: loss, slope, curvature
 //   drt::hip::render_param_sets_grad(scene, cam, tracer, spp, {set, ...} [, adjoints, options])     up to 8 sets with a summed gradient each, one trace
 //   drt::hip::normal_equations_along(scene, cam, tracer, spp, {direction, ...}, options, target_or_residual) Gauss-Newton in their span
+//   drt::hip::normal_equations_cross(scene, cam, tracer, spp, {direction, ...}, options, target)             ... unbiased from one render
 //   drt::hip::render(scene of Dual<U>, ...)
 //
 // forward mode (drt_hip_render_tangent): the image and its derivative along one direction of parameter space -- given as
@@ -1003,6 +1004,61 @@ inline NormalEquationsAlong<T> normal_equations_along(const Scene<T>& scene, con
     ne.stats = detail::tangents_call("drt::hip::normal_equations_along", flat, describe(cam), tracer.absorb(), tracer.min_bounces(), spp, K, v,
                                      in.data(), target_or_residual.is_residual, rgb, tangent_imgs ? &trgb : nullptr, ne.A.data(), ne.b.data(),
                                      ne.loss.data(), opt);
+    detail::from_buffer(rgb.data(), npix, img);
+    if (tangent_imgs)
+        detail::from_buffer(trgb.data(), npix * K, tangent_imgs);
+    return ne;
+}
+
+// ... with b and the loss unbiased from this ONE render (drt_hip_render_normal_equations_cross): the products of each pixel's means less
+// the sample covariance of its samples over spp -- the mean over ordered pairs of DIFFERENT samples, whose expectation is the product of
+// the expectations.  A is NormalEquationsAlong's (its Cov / spp excess is positive semi-definite: damping).  bias[ch * (K + 1) + k] is what
+// was subtracted from b[ch * K + k], bias[ch * (K + 1) + K] what was subtracted from loss[ch]: the render's own noise floor.  variance
+// (width x height x 3, where asked for) is the variance of each pixel's mean.
+template <typename T>
+struct NormalEquationsCross : NormalEquationsAlong<T> {
+    std::vector<double> bias;                   // 3 x (K + 1)
+    std::vector<float> variance;                // width x height x 3, or empty
+};
+
+template <typename T>
+inline NormalEquationsCross<T> normal_equations_cross(const Scene<T>& scene, const Camera<T>& cam, const Pathtracer<T>& tracer, std::size_t spp,
+                                                      const std::vector<Direction<T>>& directions, const Options& opt, const Vector<T, 3>* target,
+                                                      Vector<T, 3>* img = nullptr, Vector<T, 3>* tangent_imgs = nullptr, bool want_variance = false)
+{
+    const char* who = "drt::hip::normal_equations_cross";
+    if (!target)
+        throw std::runtime_error("drt::hip::normal_equations_cross: the cross-sample normal equations need a target image");
+    if (spp < 2)
+        throw std::runtime_error("drt::hip::normal_equations_cross: spp < 2 (the estimator needs a pair of samples per pixel)");
+    detail::forward_only(who, opt, "forward mode");
+    detail::one_device(who, opt);
+    FlatScene<T> flat = flatten(scene);
+    const std::vector<double> v = detail::directions_of(who, flat, directions);
+    const drt_camera_desc cd = describe(cam);
+    const std::size_t npix = cam.width() * cam.height(), K = directions.size();
+    const std::vector<float> in = detail::to_floats(target, npix);
+    NormalEquationsCross<T> ne;
+    ne.n_dirs = K;
+    ne.A.assign(3 * (K ? K * K : 1), 0.0);
+    ne.b.assign(3 * (K ? K : 1), 0.0);
+    ne.loss.assign(3, 0.0);
+    ne.bias.assign(3 * (K + 1), 0.0);
+    if (want_variance)
+        ne.variance.assign(npix * 3, 0.f);
+    std::vector<float> rgb(npix * 3, 0.f), trgb;
+    if (tangent_imgs)
+        trgb.assign((K ? K : 1) * npix * 3, 0.f);
+    const drt_render_params rp = detail::render_params(tracer.absorb(), tracer.min_bounces(), spp, opt, detail::f64_flag(opt));
+    drt_hip_stats st{};
+    {
+        detail::Session s = detail::Session::on_first_device(opt, flat);
+        s.ctx.check(drt_hip_render_normal_equations_cross(s.ctx.get(), &cd, &rp, (int32_t)K, v.data(), in.data(), rgb.data(), ne.A.data(), ne.b.data(),
+                                                          ne.loss.data(), ne.bias.data(), tangent_imgs ? trgb.data() : nullptr,
+                                                          want_variance ? ne.variance.data() : nullptr, &st),
+                    "drt_hip_render_normal_equations_cross");
+    }
+    ne.stats = detail::to_stats(st);
     detail::from_buffer(rgb.data(), npix, img);
     if (tangent_imgs)
         detail::from_buffer(trgb.data(), npix * K, tangent_imgs);

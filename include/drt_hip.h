@@ -474,6 +474,36 @@ int drt_hip_render_normal_equations_along(drt_hip_ctx* ctx, const drt_camera_des
                                           float* out_rgb /* may be NULL */, double* out_A /* 3 x K x K */, double* out_b /* 3 x K */,
                                           double* out_loss /* 3, may be NULL */, float* out_tangents /* n_dirs x H x W x 3, may be NULL */,
                                           drt_hip_stats* stats);
+/* ... with b and the loss UNBIASED from this one render.  drt_hip_render_normal_equations_along with target_rgb forms b = J^T r from pixel
+ * means that share their samples with J: per pixel b carries Cov(t_k, L) / n and the loss Var(L) / n (n = spp, t_k = J_s v_k and L per
+ * sample), so a fit settles where the NOISY objective has its minimum.  The camera samples of a pixel are independent streams (the RNG
+ * contract above), so the mean over ordered pairs s != s' of the pixel's samples -- a U-statistic, all samples used -- has the product of
+ * the expectations as its expectation, exactly.  With T_k, m the pixel means, r = m - target, cov and var the SAMPLE covariance and variance:
+ *   out_A[ch][k][l]  = sum_x T_k T_l                       (what _along returns: the products of the means.  Its expectation exceeds
+ *                                                           mu mu^T by the positive semi-definite Cov / n: damping, which does not move
+ *                                                           the point where out_b = 0.  Debiasing A would take K (K + 1) / 2 more moment
+ *                                                           rows per channel and is not done)
+ *   out_b[ch][k]     = sum_x (T_k r - cov(t_k, L) / n)     = sum_x 1 / (n (n - 1)) sum_{s != s'} t_{k,s} (L_s' - target)
+ *   out_loss[ch]     = sum_x (r^2 - var(L) / n)            = sum_x 1 / (n (n - 1)) sum_{s != s'} (L_s - target) (L_s' - target)
+ *   out_bias[ch][k]  = sum_x cov(t_k, L) / n  (k < K),  out_bias[ch][K] = sum_x var(L) / n       (3 x (K + 1), may be NULL): what was
+ *                      subtracted -- out_b + out_bias and out_loss + out_bias[.][K] are the plain values of _along; out_bias[.][K] is the
+ *                      render's own noise floor in the loss
+ *   out_variance_rgb[x][ch] = var(L) / n                   (H x W x 3 floats, may be NULL): the variance of the pixel's mean
+ * out_rgb and out_tangents (both may be NULL) are what drt_hip_render_tangents returns, bit for bit in the library's kernels.  The path
+ * kernel is the K-direction form plus 3 K + 3 fp64 moment sums per lane; k_cross_eq reduces in fp64 without atomics: the same call
+ * returns the same bits; the sums are over this call's shard.  1 <= n_dirs <= DRT_HIP_MAX_DIRS_CROSS.  Rules of _along for everything else
+ * (shards, DRT_RENDER_DEVICE_OUT -- every pointer but the directions is then a device pointer --, _F64, _SYNC, _TIMING, one batch,
+ * lockstep under the roulette, 2^31 samples).
+ * DRT_ERR_INVALID: spp < 2 (the estimator needs a pair), NULL target_rgb, out_A, out_b, out_loss or param_tangents, n_dirs outside
+ * 1 ... DRT_HIP_MAX_DIRS_CROSS, a value of the directions or of a host target that is not finite, asynchronous frames in flight.
+ * DRT_ERR_UNSUPPORTED: whatever _along refuses.  The message says "normal equations cross"; the context stays usable. */
+#define DRT_HIP_MAX_DIRS_CROSS 8
+int drt_hip_render_normal_equations_cross(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_params* rp, int32_t n_dirs,
+                                          const double* param_tangents /* n_dirs x n_params x 3 */, const float* target_rgb /* H x W x 3 */,
+                                          float* out_rgb /* may be NULL */, double* out_A /* 3 x K x K */, double* out_b /* 3 x K */,
+                                          double* out_loss /* 3 */, double* out_bias /* 3 x (K + 1), may be NULL */,
+                                          float* out_tangents /* n_dirs x H x W x 3, may be NULL */,
+                                          float* out_variance_rgb /* H x W x 3, may be NULL */, drt_hip_stats* stats);
 /* ONE frame under n_sets parameter vectors in one trace: out_images[k] (H x W x 3 floats) is what drt_hip_update_params(param_sets[k])
  * followed by drt_hip_render returns -- a parameter is a colour or an emission, nothing that decides where a path goes sees its value, so
  * the sets share the ray, the RNG key, the hit and the BxDF sample and each keeps its own throughput and radiance, moved by the forward

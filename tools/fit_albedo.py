@@ -14,7 +14,7 @@ the noisy objective sits ~9 % below the true albedo at 16 spp.  The per-pixel ad
 (the ABI's adjoint_rgb seeds every sample of a pixel alike); the reference's per-sample `loss_func(radiance).backward()` is
 the same thing for a loss that is linear in the radiance.
 
-    python tools/fit_albedo.py [--size 128] [--spp 16] [--steps 60] [--async] [--oracle] [--gauss-newton [--one-render] [--lambda-sets N]]
+    python tools/fit_albedo.py [--size 128] [--spp 16] [--steps 60] [--async] [--oracle] [--gauss-newton [--one-render [--cross]] [--lambda-sets N]]
     python tools/fit_albedo.py --scene cornell_shapes --multi-start N [--oracle]
 
 --async: the same loop through drt_hip_render_async / drt_hip_wait (frame i + 1 needs the parameters of step i, so frames
@@ -41,6 +41,15 @@ objective has its minimum -- ~9 % below the true albedo at 16 spp with one sampl
 Here the same covariance is divided by a J^T J that the pixels' variance inflates, and the Gauss-Newton fixed point is lower still:
 measured on the device at the defaults, red settles at 0.286 (6 steps, the last two 0.2866 and 0.2857), so this form exits with
 status 1 at the defaults; it is for frames with enough samples that the bias is below what the caller needs.
+--one-render --cross: the one-render loop on drt_hip_render_normal_equations_cross (the device only).  b and the loss are then the means
+over ordered pairs of DIFFERENT samples of each pixel -- unbiased from the one render: the covariance and the variance above are
+subtracted, estimated from the same samples --, so the loss can decide again.  One call per step, on a fresh seed: it gives the
+candidate's loss, compared with the current point's (from the call that produced the step: smaller: accept, lambda / 3; else keep,
+lambda x 4), and, where the candidate is accepted, the next step.  --steps + 1 renders.  Measured on the device at the defaults: the
+first step is accepted (red 0.3677, loss 0.590 with a subtracted noise floor of 14.48) and the four candidates after it are rejected,
+so red stays at 0.3677 and this form exits with status 1 too: the two losses that are compared come from different sample sets, and
+what is left of the loss after the subtraction is 1 / 25 of the noise floor.  The values are unbiased (tests/test_gpu_cross.py); a
+loop that compares them across seeds at 16 spp is not yet a fit.
 --oracle runs the same loop on the CPU restatement, J assembled from oracle.render(backward=True, grad_image_param=p).
 --lambda-sets N (N <= 7): after the two normal-equation renders the candidates for lambda x {1, 1/3, 4, 1/9, 16, 1/27, 64}[:N] are
 evaluated in ONE drt_hip_render_param_sets call per seed (one trace for all N: a parameter does not decide where a path goes), the
@@ -208,6 +217,31 @@ def fit_gauss_newton(render, p_index, start, steps, one_render=False, lam=1e-3, 
         hist.append(params[p_index].copy())
         if log:
             log(f"step {k:3d}  loss {loss:.6f}  lambda {lam:.2e}  {verdict}  red = ({params[p_index][0]:.4f}, {params[p_index][1]:.4f}, {params[p_index][2]:.4f})")
+    return params[p_index].copy(), hist
+
+
+def fit_gauss_newton_cross(render, p_index, start, steps, lam=1e-3, log=None):
+    """Levenberg-Marquardt on parameter p_index, per channel, one render_normal_equations_cross call per step (the module's docstring):
+    render.normal_equations_cross(params, seed, V) -> (A [3,1,1], b [3,1], loss [3], bias [3,2]).  -> (fitted rgb, history of rgb per step)"""
+    params = render.params0.copy()
+    params[p_index] = start
+    V = np.zeros((1,) + params.shape)
+    V[0, p_index] = 1.0                              # (a channel of the radiance depends on the same channel of the albedo alone)
+    hist = []
+    A, b, loss3, bias = render.normal_equations_cross(params, 1000, V)
+    for k in range(steps):
+        d = A[:, 0, 0] * (1.0 + lam)
+        cand = params.copy()
+        cand[p_index] = np.clip(params[p_index] + np.where(d > 0, -b[:, 0] / np.where(d > 0, d, 1.0), 0.0), 0.0, 1.0)
+        Ac, bc, lc, biasc = render.normal_equations_cross(cand, 1001 + k, V)
+        if float(lc.sum()) < float(loss3.sum()):
+            params, A, b, loss3, bias, lam, verdict = cand, Ac, bc, lc, biasc, max(lam / 3.0, 1e-9), "accepted"
+        else:
+            lam, verdict = lam * 4.0, "rejected"
+        hist.append(params[p_index].copy())
+        if log:
+            log(f"step {k:3d}  loss {float(loss3.sum()):.6f} (noise floor subtracted: {float(bias[:, 1].sum()):.6f})  lambda {lam:.2e}  {verdict}  "
+                f"red = ({params[p_index][0]:.4f}, {params[p_index][1]:.4f}, {params[p_index][2]:.4f})")
     return params[p_index].copy(), hist
 
 
@@ -448,6 +482,13 @@ class DeviceRender:
         o = self.r.render_normal_equations_along(self.cam, rp, V, residual=residual)
         return o["A"], o["b"], o["image"]
 
+    def normal_equations_cross(self, params, seed, V):
+        self.r.update_params(params)
+        rp = self.pkg.RenderParams(spp=self.spp, min_bounces=self.depth, absorb=1.0, seed=seed)
+        self.calls += 1
+        o = self.r.render_normal_equations_cross(self.cam, rp, V, self.target.astype(np.float32))
+        return o["A"], o["b"], o["loss"], o["bias"]
+
     def param_sets(self, sets, seed):
         """the frame under every row of `sets` [N, P, 3] in one trace: [N, H, W, 3]"""
         rp = self.pkg.RenderParams(spp=self.spp, min_bounces=self.depth, absorb=1.0, seed=seed)
@@ -560,6 +601,8 @@ def main():
     ap.add_argument("--steps", type=int, default=None, help="default: 60 (Adam), %d (--gauss-newton)" % GN_STEPS)
     ap.add_argument("--gauss-newton", dest="gauss_newton", action="store_true")
     ap.add_argument("--one-render", dest="one_render", action="store_true")
+    ap.add_argument("--cross", action="store_true",
+                    help="with --gauss-newton --one-render: b and the loss unbiased from the one render (render_normal_equations_cross)")
     ap.add_argument("--lambda-sets", dest="lambda_sets", type=int, default=0,
                     help="with --gauss-newton: try this many dampings (<= 7) per step in one render_param_sets call per seed")
     ap.add_argument("--line-search", dest="line_search", type=int, default=0,
@@ -576,6 +619,8 @@ def main():
     a = ap.parse_args()
     if a.lambda_sets and (not a.gauss_newton or a.one_render or not 1 <= a.lambda_sets <= len(LAMBDA_FACTORS)):
         ap.error("--lambda-sets N (1 ... 7) goes with --gauss-newton (not --one-render)")
+    if a.cross and (not a.gauss_newton or not a.one_render or a.oracle or a.scene != "cornell" or a.spp < 2):
+        ap.error("--cross goes with --gauss-newton --one-render on the device, --scene cornell, --spp >= 2")
     if a.line_search and (not a.gauss_newton or a.scene == "cornell" or a.oracle or a.lambda_sets or not 1 <= a.line_search <= len(STEP_LENGTHS)):
         ap.error("--line-search N (1 ... 4) goes with --gauss-newton --scene cornell_shapes on the device (not --oracle, not --lambda-sets)")
     if a.multi_start and (a.gauss_newton or a.use_async or a.lambda_sets or a.line_search or not 1 <= a.multi_start <= 8):
@@ -612,13 +657,16 @@ def main():
         a.steps = GN_STEPS if a.gauss_newton else 60
     if a.gauss_newton:
         t0 = time.time()
-        rgb, hist = fit_gauss_newton(render, 0, np.array([0.2, 0.2, 0.2]), a.steps, a.one_render, log=None if a.quiet else print,
-                                     lambda_sets=a.lambda_sets)
+        if a.cross:
+            rgb, hist = fit_gauss_newton_cross(render, 0, np.array([0.2, 0.2, 0.2]), a.steps, log=None if a.quiet else print)
+        else:
+            rgb, hist = fit_gauss_newton(render, 0, np.array([0.2, 0.2, 0.2]), a.steps, a.one_render, log=None if a.quiet else print,
+                                         lambda_sets=a.lambda_sets)
         dt = time.time() - t0
         if a.lambda_sets:
             print(f"--lambda-sets {a.lambda_sets}: {render.traces_of_sets} of the renders below were traces of {a.lambda_sets} candidates each")
         err = np.abs(rgb - np.array([0.5, 0.0, 0.0])).max()
-        n = a.steps if a.one_render else 4 * a.steps
+        n = (a.steps + 1 if a.cross else a.steps) if a.one_render else 4 * a.steps
         print(f"fitted red = ({rgb[0]:.4f}, {rgb[1]:.4f}, {rgb[2]:.4f})  max error {err:.4f}  "
               f"{a.steps} Gauss-Newton steps, {n} renders in {dt:.2f} s")
         return 0 if err <= 1e-2 else 1
