@@ -1,6 +1,8 @@
 // drt_tuning.h -- every environment variable libdrt_hip.so reads, in ONE table: name, default, meaning.  Read once per
 // process (the first context).  None of them changes a result beyond f32 summation order; they size grids and batches, pick
-// between equivalent routes for measurement, or switch debugging output on.  What a caller is meant to choose lives in the ABI
+// between equivalent routes for measurement, or switch debugging output on.  (tests/test_gpu_launch_geometry.py holds this for
+// PATH_SPR, PATH_REGEN, PATH_REGEN_MIN, GEN_ABOVE, GEN_HIST_LDS and GEN_COPIES_LOG2: every entry point in a process per setting, against
+// the fp64 restatement and against the default process.)  What a caller is meant to choose lives in the ABI
 // (drt_render_params, the DRT_RENDER_* flags, drt_hip_set_specialisation), not here.  INTEGRATION.md section 2 lists this
 // table; tests/test_abi.py checks that the two agree.
 #pragma once

@@ -741,7 +741,10 @@ def test_path_kernel_regenerating_lanes(pkg, hip, oracle, scene_name, b, p, max_
     """Roulette-terminated renders (the reference's defaults are -b 1 -p 0.5) take k_path's regenerating form: every
     lane on its own depth, restarting with its next sample when its path ends.  Against the oracle: f64 mode to 1e-9
     (same paths, same segment and capped-path counts), f32 mode within the stated bounds; frame width not a multiple
-    of the wave, sample ranges that do not divide the samples, several batches; forward-only gives the same image."""
+    of the wave, several batches; forward-only gives the same image.  At 77 x 45 the plan gives every wave a range of ONE
+    sample (55 pixel groups against the ~8192 waves a 256-CU device wants: as many ranges as samples), so a lane takes one
+    item and never another pixel's sample: ranges of several samples, short last ranges and lanes that do regenerate are
+    tests/test_gpu_launch_geometry.py (regen_eager, regen_lazy)."""
     import dataclasses
     scene = pkg.scene_by_name(scene_name)
     cam = pkg.cornell_camera(77, 45)
