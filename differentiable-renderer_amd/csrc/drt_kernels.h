@@ -1021,17 +1021,20 @@ k_shade(BatchArgs a, int k, int nb, const DevScene<R>* __restrict__ sc, const R*
 // segments of one batch = rays queued at depths 0..D-1, summed over regions -> 64-bit total
 __global__ void __launch_bounds__(DRT_BLOCK)
 k_sum_counts(const uint32_t* __restrict__ counts, uint32_t n_words, unsigned long long* __restrict__ total,
-             uint32_t row_words, unsigned long long read_rows, unsigned long long written_rows, uint32_t cap_row)
+             uint32_t row_words, unsigned long long read_rows, unsigned long long written_rows, uint32_t cap_row,
+             uint32_t walk_row = 0xFFFFFFFFu)
 {
     // total[0] += all words of rows != cap_row (= segments); total[1] += the rows a shade launch STARTED from (rays
     // read from the queue), total[2] += the rows a launch ended on (survivors written back); row r = bit r of the
-    // masks; total[3] += row cap_row (paths that were still alive when the depth cap cut them: never queued)
-    __shared__ unsigned long long red[4][DRT_BLOCK / DRT_WAVE];
-    unsigned long long v = 0, vr = 0, vw = 0, vc = 0;
+    // masks; total[3] += row cap_row (paths that were still alive when the depth cap cut them: never queued);
+    // total[5] += row walk_row (k_path_mesh in batches: the rays its BVH walk took -- a frame in one batch has k_path_finish add them)
+    __shared__ unsigned long long red[5][DRT_BLOCK / DRT_WAVE];
+    unsigned long long v = 0, vr = 0, vw = 0, vc = 0, vk = 0;
     for (uint32_t i = blockIdx.x * DRT_BLOCK + threadIdx.x; i < n_words; i += gridDim.x * DRT_BLOCK) {
         const unsigned long long c = counts[i];
         const uint32_t row = row_words ? i / row_words : 0u;
         if (row == cap_row) { vc += c; continue; }
+        if (row == walk_row) { vk += c; continue; }
         v += c;
         if (row < 64u && ((read_rows >> row) & 1ull)) vr += c;
         if (row < 64u && ((written_rows >> row) & 1ull)) vw += c;
@@ -1041,20 +1044,22 @@ k_sum_counts(const uint32_t* __restrict__ counts, uint32_t n_words, unsigned lon
         vr += __shfl_down(vr, off);
         vw += __shfl_down(vw, off);
         vc += __shfl_down(vc, off);
+        vk += __shfl_down(vk, off);
     }
     if ((threadIdx.x & (DRT_WAVE - 1)) == 0) {
+        red[4][threadIdx.x / DRT_WAVE] = vk;
         red[0][threadIdx.x / DRT_WAVE] = v;
         red[1][threadIdx.x / DRT_WAVE] = vr;
         red[2][threadIdx.x / DRT_WAVE] = vw;
         red[3][threadIdx.x / DRT_WAVE] = vc;
     }
     __syncthreads();
-    if (threadIdx.x < 4) {
+    if (threadIdx.x < 5) {
         unsigned long long t = 0;
         for (int w = 0; w < DRT_BLOCK / DRT_WAVE; ++w)
             t += red[threadIdx.x][w];
         if (t)
-            atomicAdd(total + threadIdx.x, t);   // integer: order-independent
+            atomicAdd(total + (threadIdx.x < 4 ? threadIdx.x : 5u), t);   // integer: order-independent
     }
 }
 

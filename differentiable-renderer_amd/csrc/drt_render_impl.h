@@ -1018,8 +1018,9 @@ int path_batch(Shard<R>& s)
         s.path_finished = true;
         return DRT_OK;
     }
-    hipLaunchKernelGGL(k_sum_counts, dim3(64), dim3(DRT_BLOCK), 0, ctx->stream, counts, (uint32_t)(2 * n_waves),
-                       s.totals, (uint32_t)n_waves, 0ull, 0ull, 1u);
+    // (k_path_mesh: a third row, the rays its BVH walk took -- the queue route's k_intersect_mesh adds the same figure itself)
+    hipLaunchKernelGGL(k_sum_counts, dim3(64), dim3(DRT_BLOCK), 0, ctx->stream, counts, (uint32_t)((s.mesh_path ? 3 : 2) * n_waves),
+                       s.totals, (uint32_t)n_waves, 0ull, 0ull, 1u, s.mesh_path ? 2u : 0xFFFFFFFFu);
     if (backward) {
         DRT_TIMED(s, DRT_K_GRADREDUCE,
                   hipLaunchKernelGGL(k_gradreduce, dim3(gen ? ctx->n_params * 3 : (s.n_fast > 0 ? s.n_fast * 3 : 1)), dim3(DRT_BLOCK), 0, ctx->stream, gpart,

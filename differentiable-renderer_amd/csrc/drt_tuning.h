@@ -2,7 +2,8 @@
 // process (the first context).  None of them changes a result beyond f32 summation order; they size grids and batches, pick
 // between equivalent routes for measurement, or switch debugging output on.  (tests/test_gpu_launch_geometry.py holds this for
 // PATH_SPR, PATH_REGEN, PATH_REGEN_MIN, GEN_ABOVE, GEN_HIST_LDS and GEN_COPIES_LOG2: every entry point in a process per setting, against
-// the fp64 restatement and against the default process.)  What a caller is meant to choose lives in the ABI
+// the fp64 restatement and against the default process; tests/test_gpu_mesh_geometry.py holds it for the mesh routes' MESH_SHADE_MIN,
+// BVH_DESCEND_MIN, BVH_REFILL, SHADE_LIST_GROUP and MESH_BLOCKS_PER_CU the same way, on both routes.)  What a caller is meant to choose lives in the ABI
 // (drt_render_params, the DRT_RENDER_* flags, drt_hip_set_specialisation), not here.  INTEGRATION.md section 2 lists this
 // table; tests/test_abi.py checks that the two agree.
 #pragma once
