@@ -295,6 +295,11 @@ struct Tangents {
 #define DRT_LOCKSTEP_SPEC_MIN_BLOCKS 6  // with the glossy lobe (config 5), <= 4 parameters: 78-80 registers; config 5's shape (2048 x 2048 x 16, depth 16): five 7.92, six 7.79,
                                         // seven 7.81 (tools/ab_kernel.py)
 #endif
+#ifndef DRT_LEAN_PATH_MIN_BLOCKS
+#define DRT_LEAN_PATH_MIN_BLOCKS 8      // k_path_lean (no roulette in the loop, no emitting scatterer): 51 registers, no scratch, eight blocks' LDS in a CU.
+                                        // Seven (53 registers, 5.13e8 instructions against k_path's 5.36e8 -- and k_path's time) 0.640, eight 0.614, k_path 0.644;
+                                        // through the kind-sorted program 0.830 / 0.795 / 0.904; forward only 0.621 / 0.623 / 0.629 (profiles/r15_path_lean.txt)
+#endif
 #ifndef DRT_REGEN_MIN_BLOCKS
 #define DRT_REGEN_MIN_BLOCKS 5       // blocks per CU the f32 regenerating diffuse k_path is compiled for
 #endif
@@ -1100,7 +1105,10 @@ struct PathVertex {
     bool hit, scattered;       // the ray hit something / something with a BxDF
 };
 
-template <typename R, bool SPEC, int NP, int NC, typename SG, bool FREEZE_BY_ROW = false>
+// FIXED, NO_LIT_BXDF (k_path_lean, below; no other caller names them): what the host knows about the render and the scene as
+// compile-time facts -- no vertex inside the loop sees the roulette and the cap IS the roulette's, so no draw, no capped path; no shape
+// that scatters also emits, so no emission is added here.
+template <typename R, bool SPEC, int NP, int NC, typename SG, bool FREEZE_BY_ROW = false, bool FIXED = false, bool NO_LIT_BXDF = false>
 __device__ inline void path_bounce(const PathArgs& a, const PathSceneLds<R>& lds, const TangentLds<R>& tl, const DevScene<R>* __restrict__ sc,
                                    const R* __restrict__ params, const ProgRecs<SG::n, R>& recs, uint32_t key,
                                    R pk, R inv_pk, uint32_t n_theta, bool next_rr, bool next_cap, bool live, V3<R> g,
@@ -1132,7 +1140,7 @@ __device__ inline void path_bounce(const PathArgs& a, const PathSceneLds<R>& lds
     on_light = emits && !has_bxdf;
     light = eid;
     if (last && !vo) {
-        if (wave_any(emits && has_bxdf)) {
+        if constexpr (!NO_LIT_BXDF) if (wave_any(emits && has_bxdf)) {
             if (emits && has_bxdf) {
                 if (NP != 0 && seed_px)
                     g = mk<R>((R)seed_px[0], (R)seed_px[1], (R)seed_px[2]);
@@ -1141,7 +1149,7 @@ __device__ inline void path_bounce(const PathArgs& a, const PathSceneLds<R>& lds
         }
         alive = false;
         capped = false;
-        if (!a.cap_is_roulette) {                                      // (a user max_depth: had the roulette let the path live?)
+        if constexpr (!FIXED) if (!a.cap_is_roulette) {                // (a user max_depth: had the roulette let the path live?)
             const bool rr_kills = next_rr && draw(n_theta + 2) < a.rr_threshold;
             capped = hit && has_bxdf && !rr_kills;
         }
@@ -1166,7 +1174,7 @@ __device__ inline void path_bounce(const PathArgs& a, const PathSceneLds<R>& lds
         vo->hit = hit;
         vo->scattered = hit && has_bxdf;
     }
-    if (wave_any(emits && has_bxdf)) {
+    if constexpr (!NO_LIT_BXDF) if (wave_any(emits && has_bxdf)) {
         if (emits && has_bxdf) {
             if (NP != 0 && seed_px)
                 g = mk<R>((R)seed_px[0], (R)seed_px[1], (R)seed_px[2]);
@@ -1181,9 +1189,9 @@ __device__ inline void path_bounce(const PathArgs& a, const PathSceneLds<R>& lds
     const R c = dot(nrm, wo);                                         // pathtracer.hpp:103
     const R mk_ = div_r(bs * c, q * pk);                              // T_{k+1} = T_k * colour * m_k (f32: v_rcp, 1 ulp)
     // roulette / cap of the next depth (pathtracer.hpp:128)
-    const bool rr_kills = next_rr && draw(n_theta + 2) < a.rr_threshold;
+    const bool rr_kills = !FIXED && next_rr && draw(n_theta + 2) < a.rr_threshold;
     alive = hit && has_bxdf && !next_cap && !rr_kills;
-    capped = hit && has_bxdf && next_cap && !a.cap_is_roulette && !rr_kills;
+    capped = !FIXED && hit && has_bxdf && next_cap && !a.cap_is_roulette && !rr_kills;
     // the throughput moves on only in lanes whose path goes on (the others stay frozen for the light's turn); with
     // gradients it leaves zero colour channels out and counts them, and counts the bounce for its colour (see Tangents)
     // (REST, the lockstep kernel's colour-column form: a lane that does not go on reads the table's row of ones and zero increments)
@@ -1810,6 +1818,147 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
             if ((int)threadIdx.x < NP * 3)
                 for (int ww = 0; ww < DRT_BLOCK / DRT_WAVE; ++ww)
                     v += red[ww][threadIdx.x];
+            gpart[(size_t)blockIdx.x * (DRT_FAST_PARAMS * 3) + threadIdx.x] = v;
+        }
+    }
+}
+
+// ---- k_path_lean: the lockstep f32 column-form k_path with two more facts compiled in --------------------------------------
+// What the host knows before it launches (shard_plan: PathForm::fixed, ::no_lit_bxdf), as it knows the slots' roles:
+//   FIXED        the render has no roulette inside the loop: absorb == 1 at min_bounces == the depth cap (a.cap_is_roulette &&
+//                a.min_bounces == a.depth_cap: the reference's -b depth -p 1, every configuration of the benchmark).  p_k = 1 / p_k = 1 at
+//                every vertex, no vertex draws for the roulette, no path is "capped", and the draws of vertex k are 2 k + 2, 2 k + 3.
+//   NO_LIT_BXDF  no shape of the scene has both a material and an emitter (the reference's scene; every scene whose lights have no BxDF):
+//                the only emission of a path is the light it ends on.
+// The kernel is k_path<R, false, NP, NCR, SG, false, false> with those constants in place -- x * 1.0f is exact, a term never added is
+// never added: the same operations on the same operands in the same order, every sum keeps its bits -- as an entry point of its own, so
+// that no instantiation of k_path changes its name or its code.  Forms: the gradient columns of <= 4 parameters (NP = 4) and forward
+// only (NP = 0); no gradient image, no Jacobian, no loss seed: those renders keep k_path.
+template <typename R, int NP, int NCR, typename SG>
+__global__ void __launch_bounds__(DRT_BLOCK, (SG::n <= DRT_LEAN_MAX_SHAPES ? DRT_LEAN_PATH_MIN_BLOCKS : DRT_LOCKSTEP_GEN_MIN_BLOCKS))
+k_path_lean(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ params, const float* __restrict__ adjoint,
+            double* __restrict__ gpart, double* __restrict__ fpart, uint32_t* __restrict__ counts,
+            unsigned long long* __restrict__ total, double* __restrict__ gimg_part)
+{
+    static_assert(sizeof(R) == 4 && (NP == 0 || NP == 4), "k_path_lean: f32, four parameters in columns or none");
+    static_assert(!DRT_JACOBIAN_OF(NCR), "k_path_lean has no Jacobian form");
+    (void)gimg_part;                                      // (k_path's argument list: one launch site)
+    if (total && blockIdx.x == 0 && threadIdx.x < 8)
+        total[threadIdx.x] = 0;                           // (the finishing kernel behind this launch adds into them)
+    typedef typename Q4<R>::T R4;
+    typedef typename Q2<R>::T R2;
+    constexpr int NC = DRT_NC_OF(NCR), ROLES = DRT_ROLES_OF(NCR);
+    __shared__ PathSceneLds<R> lds;
+    __shared__ double s_red[DRT_BLOCK / DRT_WAVE][DRT_FAST_PARAMS * 3];
+    __shared__ TangentLds<R> s_tl;
+    stage_path_scene(lds, sc, params);
+    const TangentLds<R>& tl = s_tl;
+    if (NC > 0)
+        stage_tangents(s_tl, lds);
+
+    const uint32_t lane = threadIdx.x & (DRT_WAVE - 1);
+    const uint32_t w = grid_wave();                       // wave of the grid = group + n_groups * range
+    const uint32_t range = w / a.n_groups, group = w - range * a.n_groups;
+    const uint32_t lp = group * DRT_WAVE + lane;          // batch-local pixel of this lane
+    const bool have = range < a.n_ranges && lp < a.Pb;
+    const uint32_t s_begin = range * a.spr;
+    const uint32_t s_end = s_begin + a.spr < a.Sb ? s_begin + a.spr : a.Sb;
+
+    Tangents<R, NP, NC> tg;
+    __shared__ R s_acc[NP > 0 ? NP * 3 : 1][DRT_BLOCK];
+    tg.acc = &s_acc[0][threadIdx.x];
+#pragma unroll
+    for (int p = 0; p < NP; ++p)
+        tg.acc_set(p, mk<R>(R(0), R(0), R(0)));
+    double fx = 0, fy = 0, fz = 0;                        // radiance sum of this lane's pixel over the range
+    uint32_t n_seg = 0;                                   // wave-uniform counter
+
+    uint32_t gpix = 0, px = 0, py = 0;
+    V3<R> g = mk<R>(R(1), R(1), R(1));                    // render.cpp:80: radiance.backward(Vec3(1))
+    if (have) {
+        gpix = path_global_pixel(a, a.p0 + lp);
+        py = gpix / (uint32_t)a.W;
+        px = gpix - py * (uint32_t)a.W;
+        if (NP != 0 && adjoint)
+            g = mk<R>((R)adjoint[(size_t)gpix * 3], (R)adjoint[(size_t)gpix * 3 + 1], (R)adjoint[(size_t)gpix * 3 + 2]);
+    }
+    CameraLane<R> cl;                                     // (see k_path)
+    cl.cs0 = (R)((2. * (double)px * a.inv_W - 1.) * a.aspect * a.tan_half);
+    cl.ct0 = (R)((2. * (double)py * a.inv_H - 1.) * a.tan_half);
+    constexpr bool ARGS_F32 = DRT_CAMERA_ARGS_F32 != 0 && SG::n <= DRT_LEAN_MAX_SHAPES;   // (see path_camera)
+    ProgRecs<SG::n, R> recs;
+    __shared__ typename PickT<(SG::n == 0), ProgLds, NoLds>::T s_prog;
+    recs.lds = reinterpret_cast<const ProgLds*>(&s_prog);
+    if (SG::n > 0)
+        recs.template load<SG>(sc);
+    if constexpr (SG::n == 0) {
+        const DevScene<float>* scf = reinterpret_cast<const DevScene<float>*>(sc);
+        if (threadIdx.x < DRT_PROG_SORTED_MAX) {
+            s_prog.rec[threadIdx.x] = *reinterpret_cast<const float4*>(scf->sorted[threadIdx.x]);
+            s_prog.shape[threadIdx.x] = scf->sorted_shape[threadIdx.x];
+        }
+        if (threadIdx.x < 8)
+            s_prog.kind_begin[threadIdx.x] = scf->kind_begin[threadIdx.x];
+        __syncthreads();
+    }
+
+    if (range < a.n_ranges) {
+        for (uint32_t sl = s_begin; sl < s_end; ++sl) {
+            R4 ra;
+            R2 rb;
+            const uint32_t key = path_camera<R, ARGS_F32>(a, cl, gpix, px, py, sl, ra, rb);
+            bool live = have;                             // (pathtracer.hpp:128 at depth 0: min_bounces = the cap > 0, no roulette there either)
+            V3<R> T = mk<R>(R(1), R(1), R(1)), L = mk<R>(R(0), R(0), R(0));
+            uint32_t end_ids = DRT_ID_NONE;               // emission parameter of the light the path ended on
+            if (NC > 0)
+                tg.new_path();
+            for (int kk = 0; kk < a.depth_cap; ++kk) {
+                const uint32_t n_live = (uint32_t)__popcll(wave_ballot(live));
+                if (n_live == 0)
+                    break;
+                n_seg += n_live;
+                const uint32_t n_theta = 2u * (uint32_t)kk + 2u;       // draw_offset + camera_draw_base below min_bounces
+                const bool next_cap = (kk + 1) >= a.depth_cap;
+                bool alive, capped, on_light;
+                uint32_t light;
+                path_bounce<R, false, NP, NC, SG, (DRT_FREEZE_BY_ROW != 0 && SG::n <= DRT_LEAN_MAX_SHAPES), true, true>(
+                    a, lds, tl, sc, params, recs, key, R(1), R(1), n_theta, false, next_cap, live, g, ra, rb, T, L, tg, alive, capped, on_light, light, nullptr, next_cap);
+                end_ids = on_light ? light : end_ids;     // (its emission: once per sample, below -- see k_path)
+                live = alive;
+            }
+            if (wave_any(end_ids != DRT_ID_NONE)) {
+                if (end_ids != DRT_ID_NONE)
+                    add_emission<R, NP, NC, false, PathSceneLds<R>, ROLES>(lds, tl, params, end_ids, R(1), T, g, L, tg);
+            }
+            fx += (double)L.x; fy += (double)L.y; fz += (double)L.z;
+        }
+        if (fpart && have) {
+            double* f = fpart + ((size_t)range * 3) * a.Pb + lp;       // [range][channel][pixel]: coalesced
+            f[0] = fx; f[(size_t)a.Pb] = fy; f[(size_t)a.Pb * 2] = fz;
+        }
+        if (lane == 0) {
+            counts[w] = n_seg;
+            counts[(size_t)a.n_groups * a.n_ranges + w] = 0;           // (no path is cut short by a cap that is the roulette's)
+        }
+    }
+    if constexpr (NP > 0) {
+        // block reduction in fp64: thread -> wave (shuffles) -> block (LDS), fixed order; K7 adds the blocks
+        const int wv = threadIdx.x / DRT_WAVE;
+#pragma unroll
+        for (int r = 0; r < NP * 3; ++r) {
+            double v = (double)tg.acc[r * DRT_BLOCK];
+#pragma unroll
+            for (int o2 = DRT_WAVE / 2; o2 > 0; o2 >>= 1)
+                v += __shfl_down(v, o2);
+            if (lane == 0)
+                s_red[wv][r] = v;
+        }
+        __syncthreads();
+        if (threadIdx.x < DRT_FAST_PARAMS * 3) {
+            double v = 0;
+            if ((int)threadIdx.x < NP * 3)
+                for (int ww = 0; ww < DRT_BLOCK / DRT_WAVE; ++ww)
+                    v += s_red[ww][threadIdx.x];
             gpart[(size_t)blockIdx.x * (DRT_FAST_PARAMS * 3) + threadIdx.x] = v;
         }
     }

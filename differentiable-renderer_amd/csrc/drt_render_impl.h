@@ -170,7 +170,10 @@ struct PathForm {
     bool loss;                      // DRT_RENDER_LOSS_L2's instantiation: made at run time only
     int roles;                      // the parameter slots' roles, colour mask | emission mask << 8 (drt_path.h: PathRoles); 0: not specialised --
                                     // every form but the lockstep k_path with <= 8 parameters in columns
+    bool fixed, no_lit_bxdf;        // k_path_lean's facts (drt_path.h), set together or not at all: no roulette inside the loop (the cap is the
+                                    // roulette's, at min_bounces) / no shape both scatters and emits -- the lockstep f32 column forms of <= 4 parameters and forward only
     PathProg prog;
+    bool lean() const { return fixed && no_lit_bxdf; }
 };
 
 // ---- one shard's render: what the caller asked for, what the library decided, what both routes share -------------------
@@ -286,7 +289,8 @@ struct Shard {
 };
 
 // "k_path<float, SPEC, NP, NC | roles << 8, KindSig<...>, REGEN[, LOSS]>" / "k_path_unbiased<float, SPEC, NP, KindSig<...>>": the name expression
-// of the form for the scene's own signature, what hiprtc compiles (k_path_mesh has no such form)
+// of the form for the scene's own signature, what hiprtc compiles (k_path_mesh has no such form); "k_path_lean<float, NP, NC | roles << 8, KindSig<...>>"
+// where the form has both of that kernel's facts
 inline std::string path_kernel_name(const drt_hip_ctx* ctx, const PathForm& f)
 {
     const std::string sg = drt_jit::sig_type(ctx->prog_sig, ctx->n_shapes);
@@ -295,6 +299,8 @@ inline std::string path_kernel_name(const drt_hip_ctx* ctx, const PathForm& f)
     char name[400];
     if (f.op == PathOp::unbiased)
         snprintf(name, sizeof name, "k_path_unbiased<%s, %s, %d, %s>", type, sp, f.np, sg.c_str());
+    else if (f.lean())
+        snprintf(name, sizeof name, "k_path_lean<%s, %d, %d, %s>", type, f.np, DRT_NC_ROLES(f.nc, 0, 0) | f.roles << 8, sg.c_str());
     else
         snprintf(name, sizeof name, "k_path<%s, %s, %d, %d, %s, %s%s>", type, sp, f.np,
                  DRT_NC_ROLES(f.nc, 0, 0) | f.roles << 8 | (f.op == PathOp::jacobian ? DRT_NC_JACOBIAN : 0), sg.c_str(), f.regen ? "true" : "false", f.loss ? ", true" : "");
@@ -332,6 +338,19 @@ const void* library_path_kernel(const PathForm& f)
         if (f.np == 0 && f.nc == 0) return k(IntC<0>(), IntC<0>());
         return (const void*)nullptr;
     };
+    if (f.lean()) {
+        // no roulette in the loop, no emitting scatterer (shard_plan: biased, f32, diffuse, lockstep): the headline's gradient form with the
+        // reference's roles and the forward-only form, for the reference's kinds and the kind-sorted program; any other roles through hiprtc
+        if constexpr (sizeof(R) == 4) {
+            if (f.np == 4 && f.nc == 3 && f.roles == DRT_ROLES_CORNELL)
+                return with_bool(f.prog == PathProg::cornell, [](auto cornell) {
+                    return (const void*)k_path_lean<R, 4, DRT_NC_ROLES(3, 0, 0) | DRT_ROLES_CORNELL << 8, std::conditional_t<cornell, SigCornell, SigNone>>; });
+            if (f.np == 0 && f.nc == 0 && f.roles == 0)
+                return with_bool(f.prog == PathProg::cornell, [](auto cornell) {
+                    return (const void*)k_path_lean<R, 0, 0, std::conditional_t<cornell, SigCornell, SigNone>>; });
+        }
+        return nullptr;
+    }
     // SPEC, and the closest-hit program compiled in: the reference's kinds or the kind-sorted program
     const auto spec_sig = [&f](auto k) {
         return with_bool(f.spec, [&](auto spec) { return with_bool(f.prog == PathProg::cornell, [&](auto cornell) {
@@ -495,6 +514,13 @@ void shard_plan(Shard<R>& s)
     if (tuning().path_roles && tangents && !gen && sizeof(R) == 4 && !f.spec && !f.regen && !f.loss && f.op == PathOp::biased && s.gimg_param < 0 && !s.neq &&
         ctx->colour_mask != 0 && ctx->emission_mask != 0)
         f.roles = (int)(ctx->colour_mask | ctx->emission_mask << 8);
+    // ... and, for that form and the forward-only one, what else the host knows (k_path_lean, drt_path.h): the render has no roulette inside
+    // the loop -- shard_args: cap_is_roulette, at min_bounces == the cap --, and no shape of the scene both scatters and emits
+    f.fixed = f.no_lit_bxdf = false;
+    if (sizeof(R) == 4 && !f.spec && !f.regen && !f.loss && f.op == PathOp::biased && !s.pixel_sums() &&
+        ((f.np == 4 && f.roles != 0) || (f.np == 0 && f.nc == 0)) &&
+        rp->absorb >= 1.0 && rp->min_bounces == D && !ctx->emissive_bxdf)
+        f.fixed = f.no_lit_bxdf = true;
     if (s.use_path && s.loss_l2) {
         // The per-sample seed 2 (L_s - target) needs the path's radiance before its gradients.  k_path has it where the path
         // ends on a light -- the only emissive vertex of a path unless some shape carries a BxDF AND an emitter -- in the LOSS
@@ -870,6 +896,10 @@ int path_batch(Shard<R>& s)
             return fail(ctx, DRT_ERR_UNSUPPORTED, ("render: the scene's caller-defined shape kinds did not compile: " + ctx->jit_error).c_str());
     }
     const void* fn = library_path_kernel<R>(form);
+    if (!jit && !fn && form.lean()) {          // (its facts with roles the library does not carry: k_path, as before)
+        form.fixed = form.no_lit_bxdf = false;
+        fn = library_path_kernel<R>(form);
+    }
     if (!jit && !fn && form.roles != 0) {      // (a layout of roles the library does not carry: its kernel for any layout)
         form.roles = 0;
         fn = library_path_kernel<R>(form);
