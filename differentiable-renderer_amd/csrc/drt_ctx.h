@@ -108,6 +108,7 @@ struct drt_hip_ctx {
     bool has_scene = false;
     bool has_specular = false;
     bool emissive_bxdf = false;           // some analytic shape carries a BxDF AND an emitter (several emission terms per path)
+    unsigned long long pure_lights = 0;   // bit s: analytic shape s < 64 has an emitter and no BxDF; 0 where the scene has a mesh or more than 64 shapes (k_path_lean's LIGHTS)
     int max_colour_param = -1;            // largest parameter index that is some material's colour (device numbering)
     unsigned colour_mask = 0, emission_mask = 0;   // bit p: parameter p < 8 is some material's colour / some emitter's emission (PathRoles, drt_path.h)
     bool prog_ok = false;                 // k_path's intersection program covers the scene (drt_path.h)

@@ -104,6 +104,19 @@ __device__ inline HitRec<double> path_closest_hit(const DevScene<double>* __rest
      (unsigned long long)DRT_PK_AY << 18 | (unsigned long long)DRT_PK_AY << 21 | (unsigned long long)DRT_PK_SPHERE << 24)
 #define DRT_NSIG_CORNELL 9
 typedef KindSig<DRT_SIG_CORNELL, 0ull, 0ull, 0ull, DRT_NSIG_CORNELL> SigCornell;
+// ... and its pure lights (an emitter, no BxDF) as a bit set in scene order: the last sphere (k_path_lean's LIGHTS)
+#ifndef DRT_LEAN_LIGHTS
+#define DRT_LEAN_LIGHTS 1               // the host hands k_path_lean the scene's light set (0: never, the last vertex as it was; the per-part A/B of profiles/r17_path_ends.txt)
+#endif
+#define DRT_LIGHTS_CORNELL (DRT_LEAN_LIGHTS != 0 ? 1ull << 8 : 0ull)
+#ifndef DRT_LEAN_PEEL_LAST
+#ifdef DRT_USER_SHAPES
+#define DRT_LEAN_PEEL_LAST 0            // (caller-defined kinds: the compiler contracts the caller's inlined intersect body as its surroundings suggest -- written any other
+                                        //  way than k_path's loop one pixel of tests/test_gpu_param_sets.py differed by 6.6e-9 from k_path's kernel: the loop's text stays)
+#else
+#define DRT_LEAN_PEEL_LAST 1            // k_path_lean's last vertex stands behind the bounce loop (0: a test inside the loop, as it was: profiles/r17_path_ends.txt)
+#endif
+#endif
 
 // (DRT_PATH_LDS_PARAMS, drt_device.h: parameters staged in LDS; more: read from L2)
 
@@ -296,7 +309,7 @@ struct Tangents {
                                         // seven 7.81 (tools/ab_kernel.py)
 #endif
 #ifndef DRT_LEAN_PATH_MIN_BLOCKS
-#define DRT_LEAN_PATH_MIN_BLOCKS 8      // k_path_lean (no roulette in the loop, no emitting scatterer): 51 registers, no scratch, eight blocks' LDS in a CU.
+#define DRT_LEAN_PATH_MIN_BLOCKS 8      // k_path_lean (no roulette in the loop, no emitting scatterer): 54 registers (forward only 50), no scratch, eight blocks' LDS in a CU.
                                         // Seven (53 registers, 5.13e8 instructions against k_path's 5.36e8 -- and k_path's time) 0.640, eight 0.614, k_path 0.644;
                                         // through the kind-sorted program 0.830 / 0.795 / 0.904; forward only 0.621 / 0.623 / 0.629 (profiles/r15_path_lean.txt)
 #endif
@@ -333,6 +346,7 @@ struct Tangents {
 template <bool B, typename X, typename Y> struct PickT { typedef X T; };
 template <typename X, typename Y> struct PickT<false, X, Y> { typedef Y T; };
 struct NoLds { int unused; };
+template <bool B> struct BoolT { static constexpr bool value = B; };   // a compile-time tag for generic lambdas
 // The tables are fp64 in the f32 kernels too (ds_add_f64): a table sums what 64 lanes x their samples add, and ONE heavy sample
 // (the unbiased operator's L' g / pdf; a roulette-boosted path) in an f32 sum costs every later add its low bits -- measured
 // with f32 tables: 3.4e-3 of the largest component on the 12-parameter unbiased fixture, where per-lane f32 sums give 3e-6.
@@ -1108,7 +1122,11 @@ struct PathVertex {
 // FIXED, NO_LIT_BXDF (k_path_lean, below; no other caller names them): what the host knows about the render and the scene as
 // compile-time facts -- no vertex inside the loop sees the roulette and the cap IS the roulette's, so no draw, no capped path; no shape
 // that scatters also emits, so no emission is added here.
-template <typename R, bool SPEC, int NP, int NC, typename SG, bool FREEZE_BY_ROW = false, bool FIXED = false, bool NO_LIT_BXDF = false>
+// LIGHTS (k_path_lean again) != 0: the scene's pure lights (an emitter, no BxDF) as a bit set in scene order -- at the `last` vertex, where
+// only on_light and light leave the bounce, the hit is light_end_sig (drt_prog.h): the closest light and whether anything hides it, no
+// closest hit over all shapes, no read of the hit's record.
+template <typename R, bool SPEC, int NP, int NC, typename SG, bool FREEZE_BY_ROW = false, bool FIXED = false, bool NO_LIT_BXDF = false,
+          unsigned long long LIGHTS = 0ull>
 __device__ inline void path_bounce(const PathArgs& a, const PathSceneLds<R>& lds, const TangentLds<R>& tl, const DevScene<R>* __restrict__ sc,
                                    const R* __restrict__ params, const ProgRecs<SG::n, R>& recs, uint32_t key,
                                    R pk, R inv_pk, uint32_t n_theta, bool next_rr, bool next_cap, bool live, V3<R> g,
@@ -1116,6 +1134,7 @@ __device__ inline void path_bounce(const PathArgs& a, const PathSceneLds<R>& lds
                                    bool& alive, bool& capped, bool& on_light, uint32_t& light, PathVertex<R>* vo = nullptr,
                                    bool last = false, const float* __restrict__ seed_px = nullptr, const uint32_t* ih = nullptr)
 {
+    static_assert(LIGHTS == 0ull || (sizeof(R) == 4 && SG::n > 0 && FIXED && NO_LIT_BXDF), "LIGHTS: k_path_lean's compiled-in program");
     // (ih, the forms whose lanes stand at their own depths: the draw indices' hash rounds h(n) as a table in LDS -- where all
     //  lanes of a wave share the index, the lockstep kernel, the scalar unit computes h(n) and the table would only cost)
     auto draw = [&](uint32_t n) { return ih ? drt_rng_combine(ih[n], key) : rng_draw(a.rng_stream, key, n); };
@@ -1126,6 +1145,15 @@ __device__ inline void path_bounce(const PathArgs& a, const PathSceneLds<R>& lds
     // casts a ray (pathtracer.hpp:128): a factor of exactly 0.  What is left of the bounce is the hit, the light it may have
     // ended on, and the count of paths a user cap (not the roulette) cut short.  Same results bit for bit, ~110 of the
     // bounce's ~280 vector instructions less: 5 % of a depth-8 frame.
+    if constexpr (LIGHTS != 0ull) if (last) {
+        constexpr int l0 = __builtin_ctzll(LIGHTS);                   // (one light: its record's place is a constant)
+        const int il = light_end_sig<SG, LIGHTS>(recs, mk<R>(ra.x, ra.y, ra.z), mk<R>(ra.w, rb.x, rb.y));
+        on_light = live && il >= 0;
+        light = (uint32_t)lds.sc.shapes[(LIGHTS & (LIGHTS - 1ull)) == 0ull || il < 0 ? l0 : il].pad >> 16;
+        alive = false;
+        capped = false;
+        return;
+    }
     const HitRec<R> h = path_closest_hit<SG>(sc, recs, ra, rb);
     const bool hit = live && h.prim >= 0;
     const int prim = h.prim >= 0 ? h.prim : 0;                        // (a miss reads record 0, uses nothing of it)
@@ -1834,7 +1862,12 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
 // never added: the same operations on the same operands in the same order, every sum keeps its bits -- as an entry point of its own, so
 // that no instantiation of k_path changes its name or its code.  Forms: the gradient columns of <= 4 parameters (NP = 4) and forward
 // only (NP = 0); no gradient image, no Jacobian, no loss seed: those renders keep k_path.
-template <typename R, int NP, int NCR, typename SG>
+// The last vertex of a path, where the program is compiled in (SG::n > 0; the kind-sorted program keeps the loop as it was):
+//   LIGHTS  the scene's pure lights as a bit set in scene order (shard_plan: PathForm::lights; 0: not known) -- the last vertex asks only
+//           whether the path ended on one of them (path_bounce: LIGHTS);
+//   and it stands behind the bounce loop, not inside it: with both hits in one loop body the compiler merged their common beginnings and
+//   the plain bounce grew by 7 vector instructions (profiles/r17_path_ends.txt: 2.8 % SLOWER than without LIGHTS).
+template <typename R, int NP, int NCR, typename SG, unsigned long long LIGHTS = 0ull>
 __global__ void __launch_bounds__(DRT_BLOCK, (SG::n <= DRT_LEAN_MAX_SHAPES ? DRT_LEAN_PATH_MIN_BLOCKS : DRT_LOCKSTEP_GEN_MIN_BLOCKS))
 k_path_lean(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ params, const float* __restrict__ adjoint,
             double* __restrict__ gpart, double* __restrict__ fpart, uint32_t* __restrict__ counts,
@@ -1842,6 +1875,7 @@ k_path_lean(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict_
 {
     static_assert(sizeof(R) == 4 && (NP == 0 || NP == 4), "k_path_lean: f32, four parameters in columns or none");
     static_assert(!DRT_JACOBIAN_OF(NCR), "k_path_lean has no Jacobian form");
+    static_assert(LIGHTS == 0ull || SG::n > 0, "k_path_lean: the light set belongs to a compiled-in program");
     (void)gimg_part;                                      // (k_path's argument list: one launch site)
     if (total && blockIdx.x == 0 && threadIdx.x < 8)
         total[threadIdx.x] = 0;                           // (the finishing kernel behind this launch adds into them)
@@ -1912,6 +1946,32 @@ k_path_lean(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict_
             uint32_t end_ids = DRT_ID_NONE;               // emission parameter of the light the path ended on
             if (NC > 0)
                 tg.new_path();
+            if constexpr (SG::n > 0 && DRT_LEAN_PEEL_LAST != 0) {
+                // the last vertex behind the loop: the loop's body is the plain bounce -- no test for the last vertex, no code of it for the
+                // compiler to merge with the bounce's.  `is_last`: known where the vertex stands in the code
+                const auto vertex = [&](int kk, auto is_last) {
+                    const uint32_t n_theta = 2u * (uint32_t)kk + 2u;   // draw_offset + camera_draw_base below min_bounces
+                    constexpr bool next_cap = decltype(is_last)::value;
+                    bool alive, capped, on_light;
+                    uint32_t light;
+                    path_bounce<R, false, NP, NC, SG, (DRT_FREEZE_BY_ROW != 0 && SG::n <= DRT_LEAN_MAX_SHAPES), true, true, LIGHTS>(
+                        a, lds, tl, sc, params, recs, key, R(1), R(1), n_theta, false, next_cap, live, g, ra, rb, T, L, tg, alive, capped, on_light, light, nullptr, next_cap);
+                    end_ids = on_light ? light : end_ids;
+                    live = alive;
+                };
+                for (int kk = 0; kk < a.depth_cap - 1; ++kk) {
+                    const uint32_t n_live = (uint32_t)__popcll(wave_ballot(live));
+                    if (n_live == 0)
+                        break;
+                    n_seg += n_live;
+                    vertex(kk, BoolT<false>());
+                }
+                const uint32_t n_live = (uint32_t)__popcll(wave_ballot(live));
+                if (a.depth_cap > 0 && n_live != 0) {
+                    n_seg += n_live;
+                    vertex(a.depth_cap - 1, BoolT<true>());
+                }
+            } else
             for (int kk = 0; kk < a.depth_cap; ++kk) {
                 const uint32_t n_live = (uint32_t)__popcll(wave_ballot(live));
                 if (n_live == 0)
@@ -1921,7 +1981,7 @@ k_path_lean(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict_
                 const bool next_cap = (kk + 1) >= a.depth_cap;
                 bool alive, capped, on_light;
                 uint32_t light;
-                path_bounce<R, false, NP, NC, SG, (DRT_FREEZE_BY_ROW != 0 && SG::n <= DRT_LEAN_MAX_SHAPES), true, true>(
+                path_bounce<R, false, NP, NC, SG, (DRT_FREEZE_BY_ROW != 0 && SG::n <= DRT_LEAN_MAX_SHAPES), true, true, LIGHTS>(
                     a, lds, tl, sc, params, recs, key, R(1), R(1), n_theta, false, next_cap, live, g, ra, rb, T, L, tg, alive, capped, on_light, light, nullptr, next_cap);
                 end_ids = on_light ? light : end_ids;     // (its emission: once per sample, below -- see k_path)
                 live = alive;

@@ -199,6 +199,63 @@ __device__ inline HitRec<R> closest_hit_sig(const ProgRecs<SG::n, R>& recs, V3<R
     return h;
 }
 
+// ---- the last vertex of a path (k_path_lean, drt_path.h; compiled-in program only) ------------------------------------------
+// Nothing is sampled there, so all the hit is used for is "did the path end on a pure light (an emitter, no BxDF), and on which".
+// LM = the pure lights as a bit set in scene order.  The closest light (t_L, i_L) by the usual accept over the light shapes; every
+// other shape only has to say whether it is a valid hit that wins against it -- t_s > 0 && (t_s < t_L || (t_s == t_L && s < i_L)): the
+// closest hit is the least (t, index) over the valid hits, the accept's order -- which needs no select on t or on the index, and is
+// t_s <= t_L where every light stands behind s in scene order, t_s < t_L where every light stands before it.  A NaN t_s fails t_s > 0,
+// a negative discriminant never hits, as in prog_test.  Returns the light's shape, -1: the path did not end on one.
+// t of shape S of the compiled-in program, by prog_t
+template <typename SG, int S>
+__device__ inline bool prog_t_sig(const ProgRecs<SG::n, float>& recs, V3<float> o, V3<float> d, V3<float> inv_d, float& t)
+{
+    constexpr int kind = SG::kind(S);
+    constexpr int known = (kind == DRT_PK_AX || kind == DRT_PK_AY || kind == DRT_PK_AZ || kind == DRT_PK_PLANE) ? kind : DRT_PK_SPHERE;   // (as closest_hit_sig)
+    static_assert(!(kind >= DRT_PK_USER0 && kind < DRT_PK_USER0 + DRT_MAX_USER_KINDS), "no light set beside caller-defined kinds (shard_plan)");
+    return prog_t<known, float>(recs.r[S], o, d, inv_d, t);
+}
+template <typename SG, unsigned long long LM, int S = 0>
+__device__ inline void light_end_lights(const ProgRecs<SG::n, float>& recs, V3<float> o, V3<float> d, V3<float> inv_d, float& tl, int& il)
+{
+    if constexpr (S < SG::n) {
+        if constexpr ((LM >> S & 1ull) != 0) {
+            float t;
+            if (prog_t_sig<SG, S>(recs, o, d, inv_d, t))
+                prog_accept(t, S, tl, il);
+        }
+        light_end_lights<SG, LM, S + 1>(recs, o, d, inv_d, tl, il);
+    }
+}
+template <typename SG, unsigned long long LM, int S = 0>
+__device__ inline void light_end_others(const ProgRecs<SG::n, float>& recs, V3<float> o, V3<float> d, V3<float> inv_d, float tl, int il, bool& hidden)
+{
+    if constexpr (S < SG::n) {
+        if constexpr ((LM >> S & 1ull) == 0) {
+            constexpr bool lights_before = (LM & ((1ull << S) - 1ull)) != 0, lights_behind = (LM >> S) != 0;
+            float t;
+            if (prog_t_sig<SG, S>(recs, o, d, inv_d, t)) {
+                if (!lights_before) hidden = hidden || (t > 0.f && t <= tl);
+                else if (!lights_behind) hidden = hidden || (t > 0.f && t < tl);
+                else hidden = hidden || (t > 0.f && (t < tl || (t == tl && S < il)));
+            }
+        }
+        light_end_others<SG, LM, S + 1>(recs, o, d, inv_d, tl, il, hidden);
+    }
+}
+template <typename SG, unsigned long long LM>
+__device__ inline int light_end_sig(const ProgRecs<SG::n, float>& recs, V3<float> o, V3<float> d)
+{
+    static_assert(LM != 0 && SG::n > 0 && SG::n <= 64 && (SG::n == 64 || (LM >> (SG::n & 63)) == 0), "light_end_sig: a light set of the program's own shapes");
+    const V3<float> inv_d = mk<float>(prog_rcp(d.x), prog_rcp(d.y), prog_rcp(d.z));
+    float tl = INFINITY;
+    int il = -1;
+    light_end_lights<SG, LM>(recs, o, d, inv_d, tl, il);
+    bool hidden = false;
+    light_end_others<SG, LM>(recs, o, d, inv_d, tl, il, hidden);
+    return hidden ? -1 : il;
+}
+
 template <typename SG>
 __device__ inline HitRec<float> closest_hit_prog(const DevScene<float>* __restrict__ sc, const ProgRecs<SG::n>& recs,
                                                  V3<float> o, V3<float> d)

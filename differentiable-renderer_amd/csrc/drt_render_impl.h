@@ -172,6 +172,8 @@ struct PathForm {
                                     // every form but the lockstep k_path with <= 8 parameters in columns
     bool fixed, no_lit_bxdf;        // k_path_lean's facts (drt_path.h), set together or not at all: no roulette inside the loop (the cap is the
                                     // roulette's, at min_bounces) / no shape both scatters and emits -- the lockstep f32 column forms of <= 4 parameters and forward only
+    unsigned long long lights;      // ... and with them, for a compiled-in program: the scene's pure lights (an emitter, no BxDF) as a bit set in scene
+                                    // order -- k_path_lean's last vertex asks only whether the path ended on one; 0: not known
     PathProg prog;
     bool lean() const { return fixed && no_lit_bxdf; }
 };
@@ -300,7 +302,7 @@ inline std::string path_kernel_name(const drt_hip_ctx* ctx, const PathForm& f)
     if (f.op == PathOp::unbiased)
         snprintf(name, sizeof name, "k_path_unbiased<%s, %s, %d, %s>", type, sp, f.np, sg.c_str());
     else if (f.lean())
-        snprintf(name, sizeof name, "k_path_lean<%s, %d, %d, %s>", type, f.np, DRT_NC_ROLES(f.nc, 0, 0) | f.roles << 8, sg.c_str());
+        snprintf(name, sizeof name, "k_path_lean<%s, %d, %d, %s, 0x%llxull>", type, f.np, DRT_NC_ROLES(f.nc, 0, 0) | f.roles << 8, sg.c_str(), f.lights);
     else
         snprintf(name, sizeof name, "k_path<%s, %s, %d, %d, %s, %s%s>", type, sp, f.np,
                  DRT_NC_ROLES(f.nc, 0, 0) | f.roles << 8 | (f.op == PathOp::jacobian ? DRT_NC_JACOBIAN : 0), sg.c_str(), f.regen ? "true" : "false", f.loss ? ", true" : "");
@@ -341,13 +343,16 @@ const void* library_path_kernel(const PathForm& f)
     if (f.lean()) {
         // no roulette in the loop, no emitting scatterer (shard_plan: biased, f32, diffuse, lockstep): the headline's gradient form with the
         // reference's roles and the forward-only form, for the reference's kinds and the kind-sorted program; any other roles through hiprtc
+        // (its kernels for the reference's kinds know the reference's light: the same kinds with another light set keep the built-in k_path, path_batch)
         if constexpr (sizeof(R) == 4) {
+            if (f.prog == PathProg::cornell && f.lights != DRT_LIGHTS_CORNELL)
+                return nullptr;
             if (f.np == 4 && f.nc == 3 && f.roles == DRT_ROLES_CORNELL)
                 return with_bool(f.prog == PathProg::cornell, [](auto cornell) {
-                    return (const void*)k_path_lean<R, 4, DRT_NC_ROLES(3, 0, 0) | DRT_ROLES_CORNELL << 8, std::conditional_t<cornell, SigCornell, SigNone>>; });
+                    return (const void*)k_path_lean<R, 4, DRT_NC_ROLES(3, 0, 0) | DRT_ROLES_CORNELL << 8, std::conditional_t<cornell, SigCornell, SigNone>, (cornell ? DRT_LIGHTS_CORNELL : 0ull)>; });
             if (f.np == 0 && f.nc == 0 && f.roles == 0)
                 return with_bool(f.prog == PathProg::cornell, [](auto cornell) {
-                    return (const void*)k_path_lean<R, 0, 0, std::conditional_t<cornell, SigCornell, SigNone>>; });
+                    return (const void*)k_path_lean<R, 0, 0, std::conditional_t<cornell, SigCornell, SigNone>, (cornell ? DRT_LIGHTS_CORNELL : 0ull)>; });
         }
         return nullptr;
     }
@@ -516,11 +521,17 @@ void shard_plan(Shard<R>& s)
         f.roles = (int)(ctx->colour_mask | ctx->emission_mask << 8);
     // ... and, for that form and the forward-only one, what else the host knows (k_path_lean, drt_path.h): the render has no roulette inside
     // the loop -- shard_args: cap_is_roulette, at min_bounces == the cap --, and no shape of the scene both scatters and emits
+    // ... and, with both, which shapes are pure lights (upload_scene_one: an emitter, no BxDF), for the kernels whose program is compiled in
     f.fixed = f.no_lit_bxdf = false;
+    f.lights = 0;
     if (sizeof(R) == 4 && !f.spec && !f.regen && !f.loss && f.op == PathOp::biased && !s.pixel_sums() &&
         ((f.np == 4 && f.roles != 0) || (f.np == 0 && f.nc == 0)) &&
-        rp->absorb >= 1.0 && rp->min_bounces == D && !ctx->emissive_bxdf)
+        rp->absorb >= 1.0 && rp->min_bounces == D && !ctx->emissive_bxdf) {
         f.fixed = f.no_lit_bxdf = true;
+        // (not beside caller-defined kinds: the compiler contracts the caller's intersect body as its surroundings suggest, and a second inlined
+        //  copy of it need not give the first one's bits -- drt_path.h: DRT_LEAN_PEEL_LAST)
+        f.lights = DRT_LEAN_LIGHTS != 0 && ctx->user_header.empty() ? ctx->pure_lights : 0ull;
+    }
     if (s.use_path && s.loss_l2) {
         // The per-sample seed 2 (L_s - target) needs the path's radiance before its gradients.  k_path has it where the path
         // ends on a light -- the only emissive vertex of a path unless some shape carries a BxDF AND an emitter -- in the LOSS
@@ -896,8 +907,9 @@ int path_batch(Shard<R>& s)
             return fail(ctx, DRT_ERR_UNSUPPORTED, ("render: the scene's caller-defined shape kinds did not compile: " + ctx->jit_error).c_str());
     }
     const void* fn = library_path_kernel<R>(form);
-    if (!jit && !fn && form.lean()) {          // (its facts with roles the library does not carry: k_path, as before)
+    if (!jit && !fn && form.lean()) {          // (its facts with roles, or for the reference's kinds a light set, the library does not carry: k_path)
         form.fixed = form.no_lit_bxdf = false;
+        form.lights = 0;
         fn = library_path_kernel<R>(form);
     }
     if (!jit && !fn && form.roles != 0) {      // (a layout of roles the library does not carry: its kernel for any layout)

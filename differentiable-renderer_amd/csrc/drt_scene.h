@@ -460,6 +460,11 @@ int upload_scene_one(drt_hip_ctx* ctx, const drt_scene_desc* s)
     for (int i = 0; i < s->n_shapes; ++i)
         if (s->shapes[i].type != DRT_SHAPE_MESH && s->shapes[i].material >= 0 && s->shapes[i].emitter >= 0)
             ctx->emissive_bxdf = true;
+    ctx->pure_lights = 0;
+    if (!ctx->has_mesh && s->n_shapes <= 64)
+        for (int i = 0; i < s->n_shapes; ++i)
+            if (s->shapes[i].material < 0 && s->shapes[i].emitter >= 0)
+                ctx->pure_lights |= 1ull << i;
     ctx->has_specular = false;
     // (mirrors live in the specular instantiation too)
     auto uses = [&](int m) { if (m >= 0 && s->materials[m].type != DRT_BXDF_DIFFUSE) ctx->has_specular = true; };
