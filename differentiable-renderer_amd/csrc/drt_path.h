@@ -117,6 +117,9 @@ typedef KindSig<DRT_SIG_CORNELL, 0ull, 0ull, 0ull, DRT_NSIG_CORNELL> SigCornell;
 #define DRT_LEAN_PEEL_LAST 1            // k_path_lean's last vertex stands behind the bounce loop (0: a test inside the loop, as it was: profiles/r17_path_ends.txt)
 #endif
 #endif
+#ifndef DRT_LEAN_LIVE_MASK
+#define DRT_LEAN_LIVE_MASK 1            // k_path_lean's gradient form carries "the lane's path goes on" round its loop as the wave's mask in a scalar pair (0: as a bool; profiles/r18_bounce_fusions.txt)
+#endif
 
 // (DRT_PATH_LDS_PARAMS, drt_device.h: parameters staged in LDS; more: read from L2)
 
@@ -264,6 +267,66 @@ __device__ inline void stage_tangents(TangentLds<R>& tl, const SL& lds)
     __syncthreads();
 }
 
+// ---- k_path_lean's bounce tables (compiled-in program; profiles/r18_bounce_fusions.txt) -----------------------------------
+// What a bounce reads of the shape it hit and of the colour it scattered on, laid out so that ONE register -- the index shifted
+// -- addresses every read of a record through the instruction's own offset, and the reads are wide:
+//   rec[s]   32 B per shape: (n.xyz | c.xyz, type) -- one ds_read_b128 -- and (the colour row's byte offset, the emission id) -- one
+//            ds_read_b64.  DevShape's own record took a shift, two adds, three reads and the split of `pad`.  rec[NS] is the MISS
+//            record, where the closest hit's index starts (closest_hit_sig: MISS): neither BxDF nor emitter, so "hit" needs no
+//            test and the index no clamp.  Without colour columns (NC == 0) the row offset is the colour id itself.
+//   col[r]   32 B per colour: (colnz.xyz, n_p increment low) -- one ds_read_b128 -- and (zc increment, n_p increment high).  Row 0 is
+//            TangentLds's rest row (1, 1, 1), zeros; colour p stands in row p + 1.  A lane that goes on selects its record's offset,
+//            any other lane 0: no shift, no add.  The same values as TangentLds's colnz / inc, copied, not recomputed.
+#ifndef DRT_LEAN_REC
+#define DRT_LEAN_REC 1                  // 0: the bounce reads DevShape and TangentLds as before (the per-part A/B of profiles/r18_bounce_fusions.txt)
+#endif
+struct alignas(16) LeanRec {
+    float4 a;                  // p[0..2], type (bits)
+    uint2 b;                   // colour row offset (DRT_ID_NONE: no BxDF), emission id
+    uint2 pad;
+};
+struct alignas(16) LeanCol {
+    float4 a;                  // colnz[0..2], inc[0] (bits)
+    uint2 b;                   // inc[2], inc[1]
+    uint2 pad;
+};
+template <int NS, int NC>
+struct alignas(16) LeanLds {
+    LeanRec rec[NS + 1];
+    LeanCol col[NC > 0 ? DRT_FAST_PARAMS + 1 : 1];
+};
+template <typename SG, int NC, bool BY_ROW, bool FIXED, bool NO_LIT_BXDF, bool SPEC, typename R>
+constexpr bool lean_rec()
+{
+#ifdef DRT_USER_SHAPES
+    return false;
+#else
+    return DRT_LEAN_REC != 0 && SG::n > 0 && FIXED && NO_LIT_BXDF && !SPEC && sizeof(R) == 4 && (NC == 0 || BY_ROW);
+#endif
+}
+template <int NS, int NC, typename SL>
+__device__ inline void stage_lean(LeanLds<NS, NC>& ll, const SL& lds, const TangentLds<float>& tl)
+{
+    // (after stage_path_scene's and stage_tangents' barriers: the colour rows are TangentLds's own words)
+    if (threadIdx.x <= NS) {
+        const int s = threadIdx.x;
+        const bool in = s < NS;
+        const DevShape<float>& sh = lds.sc.shapes[in ? s : 0];
+        const uint32_t ids = in ? (uint32_t)sh.pad : 0xFFFFFFFFu;
+        const uint32_t cid = ids & 0xFFFFu, eid = ids >> 16;
+        const uint32_t row = NC > 0 ? ((cid < DRT_FAST_PARAMS ? cid : DRT_FAST_PARAMS - 1u) + 1u) * (uint32_t)sizeof(LeanCol) : cid;
+        ll.rec[s].a = make_float4(sh.p[0], sh.p[1], sh.p[2], __int_as_float(in ? sh.type : -1));   // (the miss record: shape 0's values, of which nothing is used)
+        ll.rec[s].b = make_uint2(cid == DRT_ID_NONE ? DRT_ID_NONE : row, eid);
+    }
+    if (NC > 0 && threadIdx.x >= DRT_WAVE && threadIdx.x < DRT_WAVE + DRT_FAST_PARAMS + 1) {
+        const int r = (int)threadIdx.x - DRT_WAVE;              // row 0: the rest row, row p + 1: colour p
+        const int t = r == 0 ? DRT_TANGENT_REST : r - 1;
+        ll.col[r].a = make_float4(tl.colnz[t][0], tl.colnz[t][1], tl.colnz[t][2], __uint_as_float(tl.inc[t][0]));
+        ll.col[r].b = make_uint2(tl.inc[t][2], tl.inc[t][1]);
+    }
+    __syncthreads();
+}
+
 template <typename R, int NP, int NC>
 struct Tangents {
     uint32_t cnt[NC > 4 ? 2 : 1];   // n_p of the current path, 8 bits per colour parameter
@@ -309,7 +372,7 @@ struct Tangents {
                                         // seven 7.81 (tools/ab_kernel.py)
 #endif
 #ifndef DRT_LEAN_PATH_MIN_BLOCKS
-#define DRT_LEAN_PATH_MIN_BLOCKS 8      // k_path_lean (no roulette in the loop, no emitting scatterer): 54 registers (forward only 50), no scratch, eight blocks' LDS in a CU.
+#define DRT_LEAN_PATH_MIN_BLOCKS 8      // k_path_lean (no roulette in the loop, no emitting scatterer): 55 registers (forward only 49), no scratch, eight blocks' LDS in a CU (19,312 B each).
                                         // Seven (53 registers, 5.13e8 instructions against k_path's 5.36e8 -- and k_path's time) 0.640, eight 0.614, k_path 0.644;
                                         // through the kind-sorted program 0.830 / 0.795 / 0.904; forward only 0.621 / 0.623 / 0.629 (profiles/r15_path_lean.txt)
 #endif
@@ -1132,9 +1195,12 @@ __device__ inline void path_bounce(const PathArgs& a, const PathSceneLds<R>& lds
                                    R pk, R inv_pk, uint32_t n_theta, bool next_rr, bool next_cap, bool live, V3<R> g,
                                    typename Q4<R>::T& ra, typename Q2<R>::T& rb, V3<R>& T, V3<R>& L, Tangents<R, NP, NC>& tg,
                                    bool& alive, bool& capped, bool& on_light, uint32_t& light, PathVertex<R>* vo = nullptr,
-                                   bool last = false, const float* __restrict__ seed_px = nullptr, const uint32_t* ih = nullptr)
+                                   bool last = false, const float* __restrict__ seed_px = nullptr, const uint32_t* ih = nullptr,
+                                   const LeanLds<SG::n, NC>* ll = nullptr, uint64_t* live_mask = nullptr)
 {
     static_assert(LIGHTS == 0ull || (sizeof(R) == 4 && SG::n > 0 && FIXED && NO_LIT_BXDF), "LIGHTS: k_path_lean's compiled-in program");
+    // LEAN_REC (k_path_lean's facts beside a compiled-in program): the hit's record and the colour's row come from `ll` (LeanLds)
+    constexpr bool LEAN_REC = lean_rec<SG, NC, FREEZE_BY_ROW, FIXED, NO_LIT_BXDF, SPEC, R>();
     // (ih, the forms whose lanes stand at their own depths: the draw indices' hash rounds h(n) as a table in LDS -- where all
     //  lanes of a wave share the index, the lockstep kernel, the scalar unit computes h(n) and the table would only cost)
     auto draw = [&](uint32_t n) { return ih ? drt_rng_combine(ih[n], key) : rng_draw(a.rng_stream, key, n); };
@@ -1154,15 +1220,31 @@ __device__ inline void path_bounce(const PathArgs& a, const PathSceneLds<R>& lds
         capped = false;
         return;
     }
-    const HitRec<R> h = path_closest_hit<SG>(sc, recs, ra, rb);
-    const bool hit = live && h.prim >= 0;
-    const int prim = h.prim >= 0 ? h.prim : 0;                        // (a miss reads record 0, uses nothing of it)
+    HitRec<R> h;
+    if constexpr (LEAN_REC)                                           // (a miss: the index of LeanLds's miss record)
+        h = closest_hit_sig<SG, R, SG::n>(recs, mk<R>(ra.x, ra.y, ra.z), mk<R>(ra.w, rb.x, rb.y));
+    else
+        h = path_closest_hit<SG>(sc, recs, ra, rb);
+    // (LEAN_REC: a miss reads the miss record -- no BxDF, no emitter -- and every use of `hit` below asks for one of the two)
+    const bool hit = LEAN_REC ? live : live && h.prim >= 0;
+    const int prim = LEAN_REC ? h.prim : (h.prim >= 0 ? h.prim : 0);  // (a miss reads record 0, uses nothing of it)
     const V3<R> o = mk<R>(ra.x, ra.y, ra.z);
     const V3<R> d = mk<R>(ra.w, rb.x, rb.y);
     const V3<R> P = o + d * h.t;                                      // pathtracer.hpp:83
-    const DevShape<R>& sh = lds.sc.shapes[prim];
-    const uint32_t ids = (uint32_t)sh.pad;                            // colour | emission << 16 parameter ids
-    const uint32_t cid = ids & 0xFFFFu, eid = ids >> 16;
+    const DevShape<R>& sh = lds.sc.shapes[LEAN_REC ? 0 : prim];
+    uint32_t ids = 0, cid, eid, crow = 0;                             // colour | emission << 16 parameter ids
+    float4 lean_a = make_float4(0.f, 0.f, 0.f, 0.f);
+    if constexpr (LEAN_REC) {
+        const LeanRec& lr = ll->rec[prim];
+        lean_a = lr.a;
+        const uint2 b = lr.b;
+        crow = cid = b.x;                                             // (with colour columns: the colour row's offset, not the id)
+        eid = b.y;
+    } else {
+        ids = (uint32_t)sh.pad;
+        cid = ids & 0xFFFFu;
+        eid = ids >> 16;
+    }
     const bool has_bxdf = cid != DRT_ID_NONE, emits = hit && eid != DRT_ID_NONE;
     // emission, pathtracer.hpp:113-114: a shape with BxDF AND emitter (rare) adds it here, a pure light is the caller's
     on_light = emits && !has_bxdf;
@@ -1183,11 +1265,11 @@ __device__ inline void path_bounce(const PathArgs& a, const PathSceneLds<R>& lds
         }
         return;
     }
-    const V3<R> ctr = mk<R>(sh.p[0], sh.p[1], sh.p[2]);
+    const V3<R> ctr = LEAN_REC ? mk<R>((R)lean_a.x, (R)lean_a.y, (R)lean_a.z) : mk<R>(sh.p[0], sh.p[1], sh.p[2]);
     // (f32: (P - c) / r with 1 / r from a table would save the rsq and the select -- and moves sphere normals by a few ulp,
     //  which flips one grazing path of the 64 x 48 x 8 smoke frame: measured, not kept; the literal form stays)
     const V3<R> nsph = normalize(P - ctr);                            // shape.hpp:105-106
-    const bool is_plane = sh.type == DRT_SHAPE_PLANE;                 // shape.hpp:58-59: the normal as stored
+    const bool is_plane = (LEAN_REC ? __float_as_int(lean_a.w) : sh.type) == DRT_SHAPE_PLANE;   // shape.hpp:58-59: the normal as stored
     V3<R> nrm = mk<R>(is_plane ? ctr.x : nsph.x, is_plane ? ctr.y : nsph.y, is_plane ? ctr.z : nsph.z);
 #ifdef DRT_USER_SHAPES
     if (sh.type >= DRT_SHAPE_USER) {                                  // a caller-defined kind: its own normal(point) (shape.hpp:22)
@@ -1220,6 +1302,10 @@ __device__ inline void path_bounce(const PathArgs& a, const PathSceneLds<R>& lds
     const bool rr_kills = !FIXED && next_rr && draw(n_theta + 2) < a.rr_threshold;
     alive = hit && has_bxdf && !next_cap && !rr_kills;
     capped = !FIXED && hit && has_bxdf && next_cap && !a.cap_is_roulette && !rr_kills;
+    // (live_mask, LEAN_REC: the wave's mask of `live`, of which the caller made `live` -- the mask of `alive` is then that AND the
+    //  mask of a compare, on the scalar unit; a ballot of `alive` itself goes through a 0 / 1 vector register)
+    if constexpr (LEAN_REC) if (live_mask)
+        *live_mask &= wave_ballot(has_bxdf && !next_cap);
     // the throughput moves on only in lanes whose path goes on (the others stay frozen for the light's turn); with
     // gradients it leaves zero colour channels out and counts them, and counts the bounce for its colour (see Tangents)
     // (REST, the lockstep kernel's colour-column form: a lane that does not go on reads the table's row of ones and zero increments)
@@ -1259,6 +1345,19 @@ __device__ inline void path_bounce(const PathArgs& a, const PathSceneLds<R>& lds
             tg.zc[k] += pid_unpack(rec[3]);
         }
         tg.h.template push<true>(live, alive ? cid : 0xFFu);
+    } else if constexpr (LEAN_REC && REST) {
+        // the colour's row of LeanLds by its offset (row 0: the rest row, for a lane that does not go on): one address, two reads
+        const LeanCol& lc = *reinterpret_cast<const LeanCol*>(reinterpret_cast<const char*>(ll->col) + (alive ? crow : 0u));
+        const float4 c4 = lc.a;
+        const V3<R> cm = mk<R>((R)c4.x, (R)c4.y, (R)c4.z) * (alive ? mk_ : R(1));
+        tg.cnt[0] += __float_as_uint(c4.w);
+        if constexpr (NC > 4) {
+            const uint2 b = lc.b;
+            tg.cnt[NC > 4 ? 1 : 0] += b.y;
+            tg.zc += b.x;
+        } else
+            tg.zc += lc.b.x;
+        T = T * cm;
     } else {
         const int cidx = DIR ? (alive ? (int)cid : DRT_PATH_LDS_PARAMS) : (REST ? (alive ? (int)cid : DRT_TANGENT_REST) : (has_bxdf ? (int)cid : 0));
         V3<R> col;
@@ -1887,8 +1986,15 @@ k_path_lean(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict_
     __shared__ TangentLds<R> s_tl;
     stage_path_scene(lds, sc, params);
     const TangentLds<R>& tl = s_tl;
+    // the bounce's own tables (LeanLds): the hit shape's record and the colour's row, one address each
+    constexpr bool BY_ROW = DRT_FREEZE_BY_ROW != 0 && SG::n <= DRT_LEAN_MAX_SHAPES;
+    constexpr bool LEAN_REC = lean_rec<SG, NC, BY_ROW, true, true, false, R>();
+    __shared__ typename PickT<LEAN_REC, LeanLds<SG::n, NC>, NoLds>::T s_lean;
+    const LeanLds<SG::n, NC>* ll = reinterpret_cast<const LeanLds<SG::n, NC>*>(&s_lean);
     if (NC > 0)
         stage_tangents(s_tl, lds);
+    if constexpr (LEAN_REC)
+        stage_lean(s_lean, lds, s_tl);
 
     const uint32_t lane = threadIdx.x & (DRT_WAVE - 1);
     const uint32_t w = grid_wave();                       // wave of the grid = group + n_groups * range
@@ -1949,24 +2055,34 @@ k_path_lean(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict_
             if constexpr (SG::n > 0 && DRT_LEAN_PEEL_LAST != 0) {
                 // the last vertex behind the loop: the loop's body is the plain bounce -- no test for the last vertex, no code of it for the
                 // compiler to merge with the bounce's.  `is_last`: known where the vertex stands in the code
+                // LIVE_MASK: "this lane's path goes on" crosses the loop's back edge as the wave's mask in a scalar pair -- the bounce moves it on
+                // by a scalar AND (path_bounce: live_mask) and a lane reads its bit back; carried as a bool it came round as 0 / 1 in a vector
+                // register, v_cndmask + v_cmp at the top of every vertex.  The gradient form only: the forward-only kernel, two instructions
+                // shorter per vertex with it all the same, ran 1.7 % SLOWER than without (profiles/r18_bounce_fusions.txt)
+                constexpr bool LIVE_MASK = DRT_LEAN_LIVE_MASK != 0 && LEAN_REC && NP > 0;
+                uint64_t lm = LIVE_MASK ? wave_ballot(live) : 0ull;
                 const auto vertex = [&](int kk, auto is_last) {
                     const uint32_t n_theta = 2u * (uint32_t)kk + 2u;   // draw_offset + camera_draw_base below min_bounces
                     constexpr bool next_cap = decltype(is_last)::value;
                     bool alive, capped, on_light;
                     uint32_t light;
-                    path_bounce<R, false, NP, NC, SG, (DRT_FREEZE_BY_ROW != 0 && SG::n <= DRT_LEAN_MAX_SHAPES), true, true, LIGHTS>(
-                        a, lds, tl, sc, params, recs, key, R(1), R(1), n_theta, false, next_cap, live, g, ra, rb, T, L, tg, alive, capped, on_light, light, nullptr, next_cap);
+                    if constexpr (LIVE_MASK)
+                        live = __builtin_amdgcn_inverse_ballot_w64(lm);
+                    path_bounce<R, false, NP, NC, SG, BY_ROW, true, true, LIGHTS>(
+                        a, lds, tl, sc, params, recs, key, R(1), R(1), n_theta, false, next_cap, live, g, ra, rb, T, L, tg, alive, capped, on_light, light, nullptr, next_cap,
+                        nullptr, nullptr, ll, LIVE_MASK ? &lm : nullptr);
                     end_ids = on_light ? light : end_ids;
                     live = alive;
                 };
+                const auto n_alive = [&]() { return (uint32_t)__popcll(LIVE_MASK ? lm : wave_ballot(live)); };
                 for (int kk = 0; kk < a.depth_cap - 1; ++kk) {
-                    const uint32_t n_live = (uint32_t)__popcll(wave_ballot(live));
+                    const uint32_t n_live = n_alive();
                     if (n_live == 0)
                         break;
                     n_seg += n_live;
                     vertex(kk, BoolT<false>());
                 }
-                const uint32_t n_live = (uint32_t)__popcll(wave_ballot(live));
+                const uint32_t n_live = n_alive();
                 if (a.depth_cap > 0 && n_live != 0) {
                     n_seg += n_live;
                     vertex(a.depth_cap - 1, BoolT<true>());
@@ -1981,8 +2097,9 @@ k_path_lean(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict_
                 const bool next_cap = (kk + 1) >= a.depth_cap;
                 bool alive, capped, on_light;
                 uint32_t light;
-                path_bounce<R, false, NP, NC, SG, (DRT_FREEZE_BY_ROW != 0 && SG::n <= DRT_LEAN_MAX_SHAPES), true, true, LIGHTS>(
-                    a, lds, tl, sc, params, recs, key, R(1), R(1), n_theta, false, next_cap, live, g, ra, rb, T, L, tg, alive, capped, on_light, light, nullptr, next_cap);
+                path_bounce<R, false, NP, NC, SG, BY_ROW, true, true, LIGHTS>(
+                    a, lds, tl, sc, params, recs, key, R(1), R(1), n_theta, false, next_cap, live, g, ra, rb, T, L, tg, alive, capped, on_light, light, nullptr, next_cap,
+                    nullptr, nullptr, ll);
                 end_ids = on_light ? light : end_ids;     // (its emission: once per sample, below -- see k_path)
                 live = alive;
             }

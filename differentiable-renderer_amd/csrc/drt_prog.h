@@ -168,12 +168,13 @@ struct ProgRecs {
 };
 
 // the compiled-in form, f32 or f64: SG::n records in scalar registers, kinds from SG
-template <typename SG, typename R>
+// (MISS: the index a ray that hits nothing comes back with -- k_path_lean's bounce hands in the place of its table's miss record)
+template <typename SG, typename R, int MISS = -1>
 __device__ inline HitRec<R> closest_hit_sig(const ProgRecs<SG::n, R>& recs, V3<R> o, V3<R> d)
 {
     const V3<R> inv_d = mk<R>(prog_rcp(d.x), prog_rcp(d.y), prog_rcp(d.z));
     R tmin = (R)INFINITY;
-    int prim = -1;
+    int prim = MISS;
 #pragma unroll
     for (int s = 0; s < SG::n; ++s) {
         const int kind = SG::kind(s);

@@ -2,6 +2,7 @@
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/microbench_imul.hip -o gpurun_out/microbench_imul
 // Every kernel runs N dependent-chain-free rounds of ONE instruction kind on 8 independent accumulators per lane, 5 waves per
 // SIMD resident: time per wave-instruction = what the instruction occupies the SIMD's issue port for.
+// `microbench_imul mix` runs only the bounce of k_path_lean as a mixed stream of the three issue classes, plain against packed (k_mix).
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -115,6 +116,82 @@ __global__ void __launch_bounds__(256) k_ops(uint32_t* out, uint32_t c, int roun
         out[0] = s;
 }
 
+// The bounce of k_path_lean as a MIXED stream (profiles/r18_bounce_fusions.txt): per round the 238 vector instructions of one iteration of
+// its loop by issue class (tools/isa_cycles.py) -- 153 full rate (v_fma_f32 / v_mul_f32), 72 half rate (v_cndmask / v_cmp), 13
+// transcendental (v_rcp / v_sqrt / v_rsq) -- interleaved over 8 independent accumulators, 8 waves per SIMD as the kernel runs.
+// MODE 0: plain.  MODE 1: the 30 full-rate instructions of the two sphere tests and the two axis-plane pairs that could share an instruction
+// as 15 v_pk_fma_f32 on register pairs.  MODE 2: the same 15 with the constant operand in a scalar pair and the first operand's low half
+// broadcast to both results (op_sel_hi), the form a packed shape test would take.
+template <int MODE>
+__global__ void __launch_bounds__(256, 2) k_mix(uint32_t* out, uint32_t c, int rounds)
+{
+    uint32_t a[8];
+    uint64_t q[4];
+    const uint64_t cc = ((uint64_t)c << 32) | c;
+    const uint64_t cs = __builtin_amdgcn_readfirstlane(c) * 0x100000001ull;
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+        a[i] = threadIdx.x * 2654435761u + i * 40503u + c;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        q[i] = (uint64_t)(threadIdx.x * 2654435761u + i * 40503u + c) * 0x100000001ull;
+    for (int r = 0; r < rounds; ++r) {
+        int k = 0, kq = 0;
+#pragma unroll
+        for (int g = 0; g < 13; ++g) {
+            if (g % 3 == 0) asm volatile("v_rcp_f32 %0, %0" : "+v"(a[k++ & 7]));
+            else if (g % 3 == 1) asm volatile("v_sqrt_f32 %0, %0" : "+v"(a[k++ & 7]));
+            else asm volatile("v_rsq_f32 %0, %0" : "+v"(a[k++ & 7]));
+            // full rate: 11 per group and one more in the first ten = 153; MODE > 0: two of them are one packed instruction in every group,
+            // four in the first two = 15 packed for 30 plain
+            const int full = 11 + (g < 10 ? 1 : 0), packed = MODE > 0 ? (g < 2 ? 2 : 1) : 0;
+#pragma unroll
+            for (int i = 0; i < full - 2 * packed; ++i) {
+                if (i & 1) asm volatile("v_mul_f32 %0, %0, %1" : "+v"(a[k++ & 7]) : "v"(c));
+                else asm volatile("v_fma_f32 %0, %0, %1, %0" : "+v"(a[k++ & 7]) : "v"(c));
+            }
+#pragma unroll
+            for (int i = 0; i < packed; ++i) {
+                if (MODE == 1) asm volatile("v_pk_fma_f32 %0, %0, %1, %0" : "+v"(q[kq++ & 3]) : "v"(cc));
+                else asm volatile("v_pk_fma_f32 %0, %0, %1, %0 op_sel_hi:[0,1,1]" : "+v"(q[kq++ & 3]) : "s"(cs));
+            }
+            // half rate: 5 per group and one more in the first seven = 72
+#pragma unroll
+            for (int i = 0; i < 5 + (g < 7 ? 1 : 0); ++i) {
+                if (i & 1) asm volatile("v_cmp_lt_f32 vcc, %0, %1" :: "v"(a[k & 7]), "v"(c) : "vcc");
+                else asm volatile("v_cndmask_b32 %0, %0, %1, vcc" : "+v"(a[k++ & 7]) : "v"(c) : "vcc");
+            }
+        }
+    }
+    uint64_t s = 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+        s ^= a[i];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        s ^= q[i];
+    if (s == 0x12345678u)
+        out[0] = (uint32_t)s;
+}
+
+template <int MODE>
+double run_mix(const char* name, uint32_t* out)
+{
+    const int rounds = 2048, grid = 256 * 8;     // 8 blocks of 4 waves per CU: 8 waves per SIMD
+    const int per_round = MODE > 0 ? 223 : 238;
+    hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
+    hipLaunchKernelGGL(k_mix<MODE>, dim3(grid), dim3(256), 0, 0, out, 0x3f7feb35u, rounds);
+    CK(hipDeviceSynchronize());
+    CK(hipEventRecord(e0));
+    for (int i = 0; i < 5; ++i)
+        hipLaunchKernelGGL(k_mix<MODE>, dim3(grid), dim3(256), 0, 0, out, 0x3f7feb35u, rounds);
+    CK(hipEventRecord(e1)); CK(hipEventSynchronize(e1));
+    float ms; CK(hipEventElapsedTime(&ms, e0, e1)); ms /= 5;
+    const double wave_instr = (double)grid * 4 * rounds * per_round;
+    printf("%-44s %8.3f ms  %8.1f G wave-instr/s  (%d instructions per round)\n", name, ms, wave_instr / ms * 1e-6, per_round);
+    return ms;
+}
+
 template <int OP>
 void run_pk(const char* name, uint32_t* out)
 {
@@ -147,9 +224,19 @@ void run(const char* name, uint32_t* out, int per_step)
     printf("%-26s %8.3f ms  %8.1f G wave-instr/s  (%.2f of 1228.8)\n", name, ms, wave_instr / ms * 1e-6, wave_instr / ms * 1e-6 / 1228.8);
 }
 
-int main()
+int main(int argc, char** argv)
 {
     uint32_t* out; CK(hipMalloc(&out, 64));
+    // `microbench_imul mix`: only the bounce's mixed stream, plain against packed, three times over (the order alternates)
+    if (argc > 1 && argv[1][0] == 'm') {
+        for (int rep = 0; rep < 3; ++rep) {
+            const double p = run_mix<0>("bounce mix, plain", out);
+            const double v = run_mix<1>("bounce mix, 30 fma as 15 v_pk_fma (vgpr)", out);
+            const double w = run_mix<2>("bounce mix, 30 fma as 15 v_pk_fma (sgpr, sel)", out);
+            printf("  packed / plain time: %.4f (vgpr pair)  %.4f (sgpr pair, op_sel)   -- 0.9370 if a packed instruction cost what a plain one does, 1.0 if two\n", v / p, w / p);
+        }
+        return 0;
+    }
     run<OP_ADD>("v_add_u32", out, 1);
     run<OP_FMA>("v_fma_f32", out, 1);
     run<OP_MUL_LO>("v_mul_lo_u32", out, 1);
