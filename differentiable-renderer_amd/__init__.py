@@ -48,6 +48,7 @@ MAX_DIRS_CROSS = 8           # DRT_HIP_MAX_DIRS_CROSS: ... per render_normal_equ
 MAX_PARAM_SETS = 8           # DRT_HIP_MAX_PARAM_SETS: parameter sets per render_param_sets call
 MAX_SETS_ALONG = 4           # DRT_HIP_MAX_SETS_ALONG: parameter sets with a direction each per render_param_sets_along call
 MAX_SETS_GRAD = 8            # DRT_HIP_MAX_SETS_GRAD: parameter sets with a summed gradient each per render_param_sets_grad call
+MAX_SETS_CROSS = 8           # DRT_HIP_MAX_SETS_CROSS: parameter sets with an unbiased loss each per render_param_sets_cross call
 ABI_VERSION = 8
 UNIQUE_ID_BYTES = 128
 
@@ -724,14 +725,15 @@ class DrtHipError(RuntimeError):
     pass
 
 
-def check_param_sets(sets, n_params: int, tangents=None, grad: bool = False):
+def check_param_sets(sets, n_params: int, tangents=None, grad: bool = False, cross: bool = False):
     """K parameter sets as drt_hip_render_param_sets takes them: float64 [K, n_params, 3], 1 <= K <= MAX_PARAM_SETS, finite values -- or,
     with `tangents`, the sets and their K directions as drt_hip_render_param_sets_along takes them: the same shape each,
     1 <= K <= MAX_SETS_ALONG -> (sets, directions) -- or, with `grad`, the sets as drt_hip_render_param_sets_grad takes them:
-    1 <= K <= MAX_SETS_GRAD.  Raises ValueError otherwise (what the library would refuse, said before the call)."""
+    1 <= K <= MAX_SETS_GRAD -- or, with `cross`, as drt_hip_render_param_sets_cross takes them: 1 <= K <= MAX_SETS_CROSS.  Raises ValueError otherwise (what the library would refuse, said before the call)."""
     along = tangents is not None
     who, cap, cap_name = ("param sets along", MAX_SETS_ALONG, "MAX_SETS_ALONG") if along else \
-                         (("param sets grad", MAX_SETS_GRAD, "MAX_SETS_GRAD") if grad else ("param sets", MAX_PARAM_SETS, "MAX_PARAM_SETS"))
+                         (("param sets grad", MAX_SETS_GRAD, "MAX_SETS_GRAD") if grad else
+                          (("param sets cross", MAX_SETS_CROSS, "MAX_SETS_CROSS") if cross else ("param sets", MAX_PARAM_SETS, "MAX_PARAM_SETS")))
     v = np.ascontiguousarray(sets, dtype=np.float64)
     if v.ndim != 3 or v.shape[1:] != (n_params, 3):
         raise ValueError(f"{who}: expected {'sets of ' if along else ''}shape [n_sets, {n_params}, 3], got {list(v.shape)}")
@@ -759,7 +761,7 @@ _ABI_SYMBOLS = ["drt_hip_abi_version", "drt_hip_device_count", "drt_hip_create",
                 "drt_hip_upload_scene", "drt_hip_update_params", "drt_hip_set_specialisation", "drt_hip_render", "drt_hip_render_async", "drt_hip_wait",
                 "drt_hip_render_gradient_image", "drt_hip_render_tangent", "drt_hip_render_tangent_double", "drt_hip_render_normal_equations", "drt_hip_render_tangents",
                 "drt_hip_render_normal_equations_along", "drt_hip_render_normal_equations_cross", "drt_hip_render_param_sets", "drt_hip_render_param_sets_double",
-                "drt_hip_render_param_sets_along", "drt_hip_render_param_sets_along_double", "drt_hip_render_param_sets_grad", "drt_hip_pin_host", "drt_hip_unpin_host", "drt_hip_stream",
+                "drt_hip_render_param_sets_along", "drt_hip_render_param_sets_along_double", "drt_hip_render_param_sets_grad", "drt_hip_render_param_sets_cross", "drt_hip_pin_host", "drt_hip_unpin_host", "drt_hip_stream",
                 "drt_hip_synchronize", "drt_hip_last_error", "drt_hip_kernel_name"]
 
 
@@ -816,6 +818,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.drt_hip_render_param_sets_along_double.argtypes = lib.drt_hip_render_param_sets_along.argtypes
     lib.drt_hip_render_param_sets_grad.argtypes = [C.c_void_p, C.POINTER(CameraDesc), C.POINTER(RenderParamsDesc), C.c_int32, C.c_void_p,
                                                    C.c_void_p, C.c_void_p, C.POINTER(HipStats)]
+    lib.drt_hip_render_param_sets_cross.argtypes = [C.c_void_p, C.POINTER(CameraDesc), C.POINTER(RenderParamsDesc), C.c_int32, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(HipStats)]
     lib.drt_hip_pin_host.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
     lib.drt_hip_unpin_host.argtypes = [C.c_void_p, C.c_void_p]
     lib.drt_hip_stream.argtypes = [C.c_void_p]
@@ -1231,11 +1235,11 @@ class HipRenderer:
             raise ValueError(f"{who}: expected a target of shape {[cam.height, cam.width, 3]}, got {list(target.shape)}")
         return target, target.ctypes.data_as(C.c_void_p)
 
-    def _begin_sets(self, cam: Camera, rp: RenderParams, flags: int, sets, *tangents, grad: bool = False):
-        """what the six parameter-set calls start with -> (the checked sets -- with `tangents`: (sets, directions) --, then what _begin gives)"""
+    def _begin_sets(self, cam: Camera, rp: RenderParams, flags: int, sets, *tangents, grad: bool = False, cross: bool = False):
+        """what the eight parameter-set calls start with -> (the checked sets -- with `tangents`: (sets, directions) --, then what _begin gives)"""
         assert self.scene is not None
         n = self.scene.n_params
-        return (check_param_sets_along(sets, *tangents, n) if tangents else check_param_sets(sets, n, grad=grad),) + self._begin(cam, rp, flags)
+        return (check_param_sets_along(sets, *tangents, n) if tangents else check_param_sets(sets, n, grad=grad, cross=cross),) + self._begin(cam, rp, flags)
 
     def render_param_sets(self, cam: Camera, rp: RenderParams, sets: np.ndarray, target: Optional[np.ndarray] = None, f64: bool = False,
                           images: bool = True, timing: bool = False, double: bool = False) -> dict:
@@ -1343,6 +1347,44 @@ class HipRenderer:
                                                      C.c_void_p(adjoints_ptr or None), C.c_void_p(out_grads_ptr or None),
                                                      C.byref(stats) if want_stats else None)
         self._check(rc, "drt_hip_render_param_sets_grad")
+        return stats.as_dict() if want_stats else {}
+
+    def render_param_sets_cross(self, cam: Camera, rp: RenderParams, sets: np.ndarray, target: np.ndarray, f64: bool = False,
+                                images: bool = False, variance: bool = False, timing: bool = False) -> dict:
+        """drt_hip_render_param_sets_cross: the frame under the K <= MAX_SETS_CROSS parameter vectors `sets` ([K, n_params, 3]) in ONE trace,
+        each set's loss against `target` (float32 [H,W,3]) UNBIASED; the context's own parameters stay what they are.  spp >= 2.
+        -> {"loss" [K,3] float64 = sum over this shard's pixels of (mean_k - target)^2 - var^(L_k) / spp,
+            "bias" [K,3] float64 = sum of var^(L_k) / spp, what was subtracted (loss + bias is render_param_sets' loss),
+            "images" [K,H,W,3] float32 (render_param_sets' images) or None, "variance" [K,H,W,3] float32 = var^(L_k) / spp or None, "stats"}"""
+        if target is None:
+            raise ValueError("param sets cross: NULL target_rgb")
+        if rp.spp < 2:
+            raise ValueError("param sets cross: spp < 2 (a product of two different samples of a pixel needs two)")
+        v, cd, d, stats = self._begin_sets(cam, rp, self._host_flags(rp, f64, timing), sets, cross=True)
+        K = v.shape[0]
+        target, t_ptr = self._target_arg(target, cam, "param sets cross")
+        imgs = np.zeros((K, cam.height, cam.width, 3), dtype=np.float32) if images else None
+        var = np.zeros((K, cam.height, cam.width, 3), dtype=np.float32) if variance else None
+        loss = np.zeros((K, 3), dtype=np.float64)
+        bias = np.zeros((K, 3), dtype=np.float64)
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+        rc = self.lib.drt_hip_render_param_sets_cross(self.ctx, C.byref(cd), C.byref(d), K, ptr(v), t_ptr, ptr(imgs), ptr(loss), ptr(bias),
+                                                      ptr(var), C.byref(stats))
+        self._check(rc, "drt_hip_render_param_sets_cross")
+        return {"loss": loss, "bias": bias, "images": imgs, "variance": var, "stats": stats.as_dict()}
+
+    def render_param_sets_cross_device(self, cam: Camera, rp: RenderParams, sets: np.ndarray, target_ptr: int, out_loss_ptr: int,
+                                       out_bias_ptr: int = 0, out_images_ptr: int = 0, out_variance_ptr: int = 0, f64: bool = False,
+                                       timing: bool = False, sync: bool = False, want_stats: Optional[bool] = None) -> dict:
+        """drt_hip_render_param_sets_cross on device pointers (images and variance float32 [K,H,W,3], target float32 [H,W,3], loss and bias
+        float64 [K,3]), enqueued on the context's stream; the sets are host memory."""
+        want_stats = timing if want_stats is None else want_stats
+        v, cd, d, stats = self._begin_sets(cam, rp, self._device_flags(rp, f64, timing, sync), sets, cross=True)
+        rc = self.lib.drt_hip_render_param_sets_cross(self.ctx, C.byref(cd), C.byref(d), v.shape[0], v.ctypes.data_as(C.c_void_p),
+                                                      C.c_void_p(target_ptr or None), C.c_void_p(out_images_ptr or None),
+                                                      C.c_void_p(out_loss_ptr or None), C.c_void_p(out_bias_ptr or None),
+                                                      C.c_void_p(out_variance_ptr or None), C.byref(stats) if want_stats else None)
+        self._check(rc, "drt_hip_render_param_sets_cross")
         return stats.as_dict() if want_stats else {}
 
     def render_device(self, cam: Camera, rp: RenderParams, out_rgb_ptr: int, out_grad_ptr: int,

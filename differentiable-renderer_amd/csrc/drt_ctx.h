@@ -46,6 +46,10 @@ struct ParamSetsRequest {
     bool grad = false;
     const float* d_adjoints = nullptr;    // n_sets x H x W x 3: set k's seed image, or none (every seed (1, 1, 1))
     double* d_grads = nullptr;            // n_sets x the caller's parameters x 3
+    // drt_hip_render_param_sets_cross: every set's second moments too -- k_path_sets_cross, then k_sets_cross_finish; d_loss is the unbiased loss
+    bool cross = false;
+    double* d_bias = nullptr;             // n_sets x 3: what was subtracted from the loss, or none
+    float* d_variance = nullptr;          // n_sets x H x W x 3: the variance of the pixel's mean under set k, or none
 };
 // A render on one of the path kernel's special forms, as render_common / render_launch / render_impl are told about it: which form, and what
 // that form reads.  render_impl decodes it, in one place

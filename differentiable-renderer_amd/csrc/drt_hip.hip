@@ -671,6 +671,7 @@ struct SetsForm {
     int most;
     const char *outside, *null_input, *no_output, *needs_target;
     bool grad = false;          // drt_hip_render_param_sets_grad: reverse mode -- a seed image per set in, a summed gradient per set out, no images
+    bool cross = false;         // drt_hip_render_param_sets_cross: every set's second moments too -- the unbiased loss, what was subtracted, the variance image
 };
 static const SetsForm plain_sets = {false,
                                     {"param sets", "render the shards on plain contexts", "a forward render", DRT_PATH_LDS_PARAMS,
@@ -688,6 +689,11 @@ static const SetsForm sets_grad = {false,
                                     "more parameters than the path kernels stage (136)"},
                                    DRT_HIP_MAX_SETS_GRAD, "n_sets outside 1 ... DRT_HIP_MAX_SETS_GRAD = 8", "NULL param_sets or out_param_grads",
                                    "", "", true};
+static const SetsForm sets_cross = {false,
+                                    {"param sets cross", "render the shards on plain contexts", "a forward render", DRT_PATH_LDS_PARAMS,
+                                     "more parameters than the path kernels stage (136)"},
+                                    DRT_HIP_MAX_SETS_CROSS, "n_sets outside 1 ... DRT_HIP_MAX_SETS_CROSS = 8", "NULL param_sets",
+                                    "NULL out_loss", "NULL target_rgb", false, true};
 
 // this shard's rows of n_sets images, from `from` bytes into ctx->neq_jac to the caller's buffer: a copy per band (the render has waited
 // for its stream)
@@ -706,13 +712,14 @@ static int fetch_set_images(drt_hip_ctx* ctx, const drt_camera_desc* cam, int n_
     return DRT_OK;
 }
 
-// the one call behind the five entry points.  The plain form has no param_tangents, out_tangents, out_dloss and out_curv; the form with
+// the one call behind the six entry points.  The plain form has no param_tangents, out_tangents, out_dloss and out_curv; the form with
 // directions has no out_rgb; the gradient form has adjoints_rgb and out_param_grads and nothing else.  `wide`: the images are double (host
-// buffers only)
+// buffers only).  The form with second moments has target_rgb and out_loss always, out_bias and out_variance, and no out_rgb
 static int render_sets_common(drt_hip_ctx* ctx, const SetsForm& form, const drt_camera_desc* cam, const drt_render_params* rp, int32_t n_sets,
                               const double* param_sets, const double* param_tangents, const float* target_rgb, void* out_images, void* out_tangents,
                               bool wide, double* out_loss, double* out_dloss, double* out_curv, float* out_rgb, drt_hip_stats* stats,
-                              const float* adjoints_rgb = nullptr, double* out_param_grads = nullptr)
+                              const float* adjoints_rgb = nullptr, double* out_param_grads = nullptr, double* out_bias = nullptr,
+                              float* out_variance = nullptr)
 {
     if (!ctx)
         return DRT_ERR_INVALID;
@@ -727,8 +734,12 @@ static int render_sets_common(drt_hip_ctx* ctx, const SetsForm& form, const drt_
         return refuse(ctx, me, DRT_ERR_INVALID, form.null_input);
     if (!form.grad && !out_images && !out_tangents && !out_loss && !out_dloss && !out_curv)
         return refuse(ctx, me, DRT_ERR_INVALID, form.no_output);
-    if ((out_loss || out_dloss) && !target_rgb)
+    if ((out_loss || out_dloss || form.cross) && !target_rgb)
         return refuse(ctx, me, DRT_ERR_INVALID, form.needs_target);
+    if (form.cross && !out_loss)
+        return refuse(ctx, me, DRT_ERR_INVALID, form.no_output);
+    if (form.cross && rp->spp < 2)
+        return refuse(ctx, me, DRT_ERR_INVALID, "spp < 2 (a product of two different samples of a pixel needs two)");
     if (!form.grad && (rp->flags & DRT_RENDER_BACKWARD))
         return refuse(ctx, me, DRT_ERR_INVALID, "a forward render: no DRT_RENDER_BACKWARD");
     for (size_t i = 0; i < (size_t)n_sets * (size_t)ctx->n_user_params * 3; ++i) {
@@ -771,6 +782,7 @@ static int render_sets_common(drt_hip_ctx* ctx, const SetsForm& form, const drt_
     q.width = K;
     q.along = form.along;
     q.grad = form.grad;
+    q.cross = form.cross;
     const size_t el = wide ? sizeof(double) : sizeof(float), n_img = (size_t)n_sets * npix * 3 * el, ns3 = (size_t)n_sets * 3;
     const size_t n_grads = (size_t)n_sets * (size_t)ctx->n_user_params * 3;
     if (form.grad) {
@@ -797,31 +809,35 @@ static int render_sets_common(drt_hip_ctx* ctx, const SetsForm& form, const drt_
         q.d_loss = out_loss;
         q.d_dloss = out_dloss;
         q.d_curv = out_curv;
+        q.d_bias = out_bias;
+        q.d_variance = out_variance;
     } else {
         if (target_rgb) {
             if ((rc = ensure(ctx, ctx->neq_in, npix * 3 * sizeof(float))) != DRT_OK) return rc;
             HIPCHK(ctx, hipMemcpyAsync(ctx->neq_in.p, target_rgb, npix * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
             q.d_target = (const float*)ctx->neq_in.p;
         }
-        if (out_images || out_tangents) {
-            // (the images, then the derivative images)
-            if ((rc = ensure(ctx, ctx->neq_jac, (form.along ? 2 : 1) * n_img)) != DRT_OK) return rc;
+        if (out_images || out_tangents || out_variance) {
+            // (the images, then the derivative images / the variance images)
+            if ((rc = ensure(ctx, ctx->neq_jac, (form.along || form.cross ? 2 : 1) * n_img)) != DRT_OK) return rc;
             uint8_t* base = (uint8_t*)ctx->neq_jac.p;
             if (out_images && wide) q.d_images64 = (double*)base;
             if (out_images && !wide) q.d_images = (float*)base;
             if (out_tangents && wide) q.d_tangents64 = (double*)(base + n_img);
             if (out_tangents && !wide) q.d_tangents = (float*)(base + n_img);
+            if (out_variance) q.d_variance = (float*)(base + n_img);
         }
         if (out_loss || out_dloss || out_curv) {
-            if ((rc = ensure(ctx, ctx->neq_out, (size_t)(form.along ? DRT_SETS_ALONG_VALUES : DRT_SETS_VALUES) * sizeof(double))) != DRT_OK) return rc;
+            if ((rc = ensure(ctx, ctx->neq_out, (size_t)(form.along ? DRT_SETS_ALONG_VALUES : 2 * DRT_SETS_VALUES) * sizeof(double))) != DRT_OK) return rc;
             double* sums = (double*)ctx->neq_out.p;
             if (out_loss) q.d_loss = sums;
+            if (out_bias) q.d_bias = sums + ns3;
             if (out_dloss) q.d_dloss = sums + ns3;
             if (out_curv) q.d_curv = sums + 2 * ns3;
         }
     }
     // (a shard without rows launches nothing: its sums are zero)
-    for (double* sum : {q.d_loss, q.d_dloss, q.d_curv})
+    for (double* sum : {q.d_loss, q.d_dloss, q.d_curv, q.d_bias})
         if (sum) HIPCHK(ctx, hipMemsetAsync(sum, 0, ns3 * sizeof(double), ctx->stream));
     TangentRequest req;
     req.kind = TangentRequest::Kind::param_sets;
@@ -841,6 +857,8 @@ static int render_sets_common(drt_hip_ctx* ctx, const SetsForm& form, const drt_
     if (out_curv) HIPCHK(ctx, hipMemcpy(out_curv, q.d_curv, ns3 * sizeof(double), hipMemcpyDeviceToHost));
     if (out_images && (rc = fetch_set_images(ctx, cam, n_sets, out_images, 0, el)) != DRT_OK) return rc;
     if (out_tangents && (rc = fetch_set_images(ctx, cam, n_sets, out_tangents, n_img, el)) != DRT_OK) return rc;
+    if (out_bias) HIPCHK(ctx, hipMemcpy(out_bias, q.d_bias, ns3 * sizeof(double), hipMemcpyDeviceToHost));
+    if (out_variance && (rc = fetch_set_images(ctx, cam, n_sets, out_variance, n_img, el)) != DRT_OK) return rc;
     return DRT_OK;
 }
 
@@ -883,6 +901,14 @@ int drt_hip_render_param_sets_grad(drt_hip_ctx* ctx, const drt_camera_desc* cam,
 {
     return render_sets_common(ctx, sets_grad, cam, rp, n_sets, param_sets, nullptr, nullptr, nullptr, nullptr, false, nullptr, nullptr, nullptr, nullptr,
                               stats, adjoints_rgb, out_param_grads);
+}
+
+int drt_hip_render_param_sets_cross(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_params* rp, int32_t n_sets,
+                                    const double* param_sets, const float* target_rgb, float* out_images, double* out_loss, double* out_bias,
+                                    float* out_variance, drt_hip_stats* stats)
+{
+    return render_sets_common(ctx, sets_cross, cam, rp, n_sets, param_sets, nullptr, target_rgb, out_images, nullptr, false, out_loss, nullptr, nullptr,
+                              nullptr, stats, nullptr, nullptr, out_bias, out_variance);
 }
 
 // ---- asynchronous host-buffer renders ---------------------------------------------------------------

@@ -1950,6 +1950,159 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
     }
 }
 
+// ---- k_path_sets_cross: one path under K parameter sets, with every set's second moments (drt_hip_render_param_sets_cross) ------------
+// The lockstep half of k_path for NP = DRT_NP_SETS, as an entry point of its own -- so that no instantiation of k_path changes its name
+// or its code --: the same staging (stage_path_scene, path_tables_begin / stage_sets), the same camera, path_bounce and add_emission on
+// the same operands in the same order, so set k's radiance sums keep the bits drt_hip_render_param_sets gives.  Beside them, per lane and
+// after each sample, from the sample's own tg.L[k]:
+//     S2_k[ch] += L_k[ch]^2          in fp64 (exact products for f32 operands)
+// the raw moment an unbiased square of a pixel's residual needs (a U-statistic over the pixel's n samples): the mean over s != s' of
+// (L_{k,s} - target)(L_{k,s'} - target) = r_k^2 - var(L_k) / n with the sample variance (S2_k - n m_k^2) / (n - 1).  Raw moments add across
+// sample ranges.  At the end of its range a lane writes gpix[range][row][pixel] with 6 nd rows: 3 nd radiance sums (row 3 k + ch), then
+// 3 nd of S2 (row 3 nd + 3 k + ch), nd = PathArgs::dirs_out(), the caller's sets; k_sets_cross_finish (below) forms the corrections per
+// pixel.  Nothing goes to `fpart` (this call has no plain image) or `gpart`.
+// blocks per CU (= waves per SIMD) of the f32 forms: the most that stay free of scratch (the compiler's report: DESIGN.md 9b)
+#ifndef DRT_SETS_CROSS2_MIN_BLOCKS
+#define DRT_SETS_CROSS2_MIN_BLOCKS 6      // (diffuse; the glossy forms keep 32-48 bytes of scratch at six: five)
+#endif
+#ifndef DRT_SETS_CROSS4_MIN_BLOCKS
+#define DRT_SETS_CROSS4_MIN_BLOCKS 3      // (24-28 bytes of scratch at four)
+#endif
+#ifndef DRT_SETS_CROSS8_MIN_BLOCKS
+#define DRT_SETS_CROSS8_MIN_BLOCKS 2
+#endif
+template <size_t RB, bool SPEC, int K>
+constexpr int sets_cross_min_blocks()
+{
+    return RB == 4 ? (K <= 2 ? (SPEC ? 5 : DRT_SETS_CROSS2_MIN_BLOCKS) : (K <= 4 ? DRT_SETS_CROSS4_MIN_BLOCKS : DRT_SETS_CROSS8_MIN_BLOCKS))
+                   : (K <= 2 ? 2 : 1);
+}
+template <typename R, bool SPEC, int K, typename SG>
+__global__ void __launch_bounds__(DRT_BLOCK, (sets_cross_min_blocks<sizeof(R), SPEC, K>()))
+k_path_sets_cross(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ params, const float* __restrict__ adjoint,
+                  double* __restrict__ gpart, double* __restrict__ fpart, uint32_t* __restrict__ counts,
+                  unsigned long long* __restrict__ total, double* __restrict__ gimg_part)
+{
+    static_assert(K == 2 || K == 4 || K == 8, "k_path_sets_cross: 2, 4 or 8 sets");
+    (void)adjoint; (void)gpart; (void)fpart;              // (k_path's argument list: one launch site)
+    if (total && blockIdx.x == 0 && threadIdx.x < 8)
+        total[threadIdx.x] = 0;                           // (the finishing kernel behind this launch adds into them)
+    typedef typename Q4<R>::T R4;
+    typedef typename Q2<R>::T R2;
+    __shared__ PathSceneLds<R> lds;
+    __shared__ TangentLds<R> s_tl;                        // (never staged: path_bounce's argument, unread in this form)
+    stage_path_scene(lds, sc, params);
+    const TangentLds<R>& tl = s_tl;
+
+    const uint32_t lane = threadIdx.x & (DRT_WAVE - 1);
+    const uint32_t w = grid_wave();                       // wave of the grid = group + n_groups * range
+    const uint32_t range = w / a.n_groups, group = w - range * a.n_groups;
+    const uint32_t lp = group * DRT_WAVE + lane;          // batch-local pixel of this lane
+    const bool have = range < a.n_ranges && lp < a.Pb;
+    const uint32_t s_begin = range * a.spr;
+    const uint32_t s_end = s_begin + a.spr < a.Sb ? s_begin + a.spr : a.Sb;
+
+    Tangents<R, DRT_NP_SETS, K> tg;
+    path_tables_begin(tg, lds, params);
+    double tk[K][3], s2[K][3];                            // per set: the radiance sums and the sums of squares of this lane's pixel over the range
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        tk[k][0] = tk[k][1] = tk[k][2] = 0.0;
+        s2[k][0] = s2[k][1] = s2[k][2] = 0.0;
+    }
+    uint32_t n_seg = 0, n_capped = 0;                     // wave-uniform counters
+
+    uint32_t gpix = 0, px = 0, py = 0;
+    const V3<R> g = mk<R>(R(1), R(1), R(1));
+    if (have) {
+        gpix = path_global_pixel(a, a.p0 + lp);
+        py = gpix / (uint32_t)a.W;
+        px = gpix - py * (uint32_t)a.W;
+    }
+    CameraLane<R> cl;                                     // (k_path: the pixel's corner in double once per lane)
+    cl.cs0 = (R)((2. * (double)px * a.inv_W - 1.) * a.aspect * a.tan_half);
+    cl.ct0 = (R)((2. * (double)py * a.inv_H - 1.) * a.tan_half);
+    constexpr bool ARGS_F32 = sizeof(R) == 4 && DRT_CAMERA_ARGS_F32 != 0 && SG::n <= DRT_LEAN_MAX_SHAPES;   // (see path_camera)
+    const R pk_rr = ARGS_F32 ? (R)a.p_rr_f : (R)a.p_rr, inv_p_rr = ARGS_F32 ? (R)a.inv_p_rr_f : (R)a.inv_p_rr;
+    ProgRecs<SG::n, R> recs;
+    __shared__ typename PickT<(SG::n == 0), ProgLds, NoLds>::T s_prog;
+    recs.lds = reinterpret_cast<const ProgLds*>(&s_prog);
+    if (SG::n > 0)
+        recs.template load<SG>(sc);
+    if constexpr (sizeof(R) == 4 && SG::n == 0) {
+        const DevScene<float>* scf = reinterpret_cast<const DevScene<float>*>(sc);
+        if (threadIdx.x < DRT_PROG_SORTED_MAX) {
+            s_prog.rec[threadIdx.x] = *reinterpret_cast<const float4*>(scf->sorted[threadIdx.x]);
+            s_prog.shape[threadIdx.x] = scf->sorted_shape[threadIdx.x];
+        }
+        if (threadIdx.x < 8)
+            s_prog.kind_begin[threadIdx.x] = scf->kind_begin[threadIdx.x];
+        __syncthreads();
+    }
+
+    if (range >= a.n_ranges)
+        return;
+    for (uint32_t sl = s_begin; sl < s_end; ++sl) {
+        R4 ra;
+        R2 rb;
+        const uint32_t key = path_camera<R, ARGS_F32>(a, cl, gpix, px, py, sl, ra, rb);
+        // pathtracer.hpp:128 at depth 0
+        bool live = have && a.depth_cap > 0 && !(a.min_bounces <= 0 && rng_draw(a.rng_stream, key, 2) < a.rr_threshold);
+        V3<R> T = mk<R>(R(1), R(1), R(1)), L = mk<R>(R(0), R(0), R(0));
+        uint32_t end_ids = DRT_ID_NONE;                   // emission parameter of the light the path ended on
+        R end_inv_pk = R(1);
+        tg.new_path();
+        for (int kk = 0; kk < a.depth_cap; ++kk) {
+            const uint32_t n_live = (uint32_t)__popcll(wave_ballot(live));
+            if (n_live == 0)
+                break;
+            n_seg += n_live;
+            const R pk = kk >= a.min_bounces ? pk_rr : R(1);                  // pathtracer.hpp:130
+            const R inv_pk = kk >= a.min_bounces ? inv_p_rr : R(1);
+            const uint32_t n_theta = draw_offset(kk, 0, a.min_bounces) + camera_draw_base(a.min_bounces);
+            const bool next_rr = (kk + 1) >= a.min_bounces;
+            const bool next_cap = (kk + 1) >= a.depth_cap;
+            bool alive, capped, on_light;
+            uint32_t light;
+            path_bounce<R, SPEC, DRT_NP_SETS, K, SG, (DRT_FREEZE_BY_ROW != 0 && sizeof(R) == 4 && !SPEC && SG::n <= DRT_LEAN_MAX_SHAPES)>(a, lds, tl, sc, params, recs, key, pk, inv_pk, n_theta, next_rr, next_cap, live, g,
+                                                    ra, rb, T, L, tg, alive, capped, on_light, light, nullptr, next_cap);
+            // (k_path: a light without a BxDF ends the path; its emission is added once per sample, behind the loop)
+            end_ids = on_light ? light : end_ids;
+            end_inv_pk = on_light ? inv_pk : end_inv_pk;
+            if (next_cap && !a.cap_is_roulette)
+                n_capped += (uint32_t)__popcll(wave_ballot(capped));
+            live = alive;
+        }
+        if (wave_any(end_ids != DRT_ID_NONE)) {
+            if (end_ids != DRT_ID_NONE)
+                add_emission<R, DRT_NP_SETS, K, false, PathSceneLds<R>, 0>(lds, tl, params, end_ids, end_inv_pk, T, g, L, tg);
+        }
+        // the sample's sums and squares, from its own values
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const double lx = (double)tg.L[k].x, ly = (double)tg.L[k].y, lz = (double)tg.L[k].z;
+            tk[k][0] += lx; tk[k][1] += ly; tk[k][2] += lz;
+            s2[k][0] += lx * lx; s2[k][1] += ly * ly; s2[k][2] += lz * lz;
+        }
+    }
+    if (gimg_part && have) {
+        // [range][row][pixel] with 6 nd rows -- 3 nd radiance sums, 3 nd of S2 --, for the sets the caller gave
+        const uint32_t nd = a.dirs_out() < (uint32_t)K ? a.dirs_out() : (uint32_t)K;
+        double* f = gimg_part + ((size_t)range * (size_t)(nd * 6u)) * a.Pb + lp;
+        double* fs = f + (size_t)(nd * 3u) * a.Pb;
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+            if ((uint32_t)k < nd) {
+                f[(size_t)(k * 3) * a.Pb] = tk[k][0]; f[(size_t)(k * 3 + 1) * a.Pb] = tk[k][1]; f[(size_t)(k * 3 + 2) * a.Pb] = tk[k][2];
+                fs[(size_t)(k * 3) * a.Pb] = s2[k][0]; fs[(size_t)(k * 3 + 1) * a.Pb] = s2[k][1]; fs[(size_t)(k * 3 + 2) * a.Pb] = s2[k][2];
+            }
+    }
+    if (lane == 0) {
+        counts[w] = n_seg;
+        counts[(size_t)a.n_groups * a.n_ranges + w] = n_capped;
+    }
+}
+
 // ---- k_path_lean: the lockstep f32 column-form k_path with two more facts compiled in --------------------------------------
 // What the host knows before it launches (shard_plan: PathForm::fixed, ::no_lit_bxdf), as it knows the slots' roles:
 //   FIXED        the render has no roulette inside the loop: absorb == 1 at min_bounces == the depth cap (a.cap_is_roulette &&
@@ -2731,6 +2884,62 @@ k_sets_loss_finish(const double* __restrict__ part, int n_blocks, int n_values, 
     add_blocks(red, n_blocks, [&](int b) { return part[(size_t)b * DRT_SETS_VALUES + v]; });
     if (threadIdx.x == 0 && v < n_values)
         out_loss[v] = red[0];
+}
+
+// ---- the images and the unbiased losses of a frame under K parameter sets (drt_hip_render_param_sets_cross) ------------------------
+// Behind a launch of k_path_sets_cross: spart[range][row][pixel] holds, per pixel of the shard and sample range, set k's radiance sums
+// (row 3 k + ch) and the sums of its samples' squares S2 (row 3 n_sets + 3 k + ch).  Per pixel, set and channel, in fp64, both sums over
+// the ranges in range order, n = spp:
+//     m = sum L / n      r = m - target      noise = (S2 - (sum L) m) / ((n - 1) n)      the sample variance of L over n (k_cross_eq's form)
+//     loss[k][ch] += r r - noise      bias[k][ch] += noise
+// the set's image (float, the layout of n_sets images: k_sets_finish's mean) and its variance image (noise, the same layout) where the
+// caller wants them.  2 DRT_SETS_VALUES running sums per thread -- value 3 k + ch the loss, DRT_SETS_VALUES + 3 k + ch the bias --, then
+// block_sums; k_sets_cross_sums adds the blocks in a fixed order.  No atomics: the same call gives the same bits.  k_sets_finish's
+// structure and grid rule.
+__global__ void __launch_bounds__(DRT_BLOCK)
+k_sets_cross_finish(PathArgs a, const double* __restrict__ spart, int n_sets, const float* __restrict__ target, float* __restrict__ out_img,
+                    float* __restrict__ out_var, double* __restrict__ part)
+{
+    const size_t Pb = a.Pb, half = (size_t)n_sets * 3, rows = half * 2, npix = (size_t)a.W * (size_t)a.H;
+    const double n = (double)a.spp, inv = 1.0 / n, inv_pairs = 1.0 / ((n - 1.0) * n);
+    double acc[2 * DRT_SETS_VALUES];
+#pragma unroll
+    for (int v = 0; v < 2 * DRT_SETS_VALUES; ++v)
+        acc[v] = 0.0;
+    for (uint32_t j = blockIdx.x * DRT_BLOCK + threadIdx.x; j < a.Pb; j += gridDim.x * DRT_BLOCK) {
+        const size_t gp = path_global_pixel(a, a.p0 + j);
+        const double tg[3] = {(double)target[gp * 3], (double)target[gp * 3 + 1], (double)target[gp * 3 + 2]};
+#pragma unroll
+        for (int v = 0; v < DRT_SETS_VALUES; ++v)
+            if (v < (int)half) {
+                double sum = 0.0, sq = 0.0;
+                for (uint32_t q = 0; q < a.n_ranges; ++q) {
+                    sum += spart[((size_t)q * rows + (size_t)v) * Pb + j];
+                    sq += spart[((size_t)q * rows + half + (size_t)v) * Pb + j];
+                }
+                const double mean = sum * inv, r = mean - tg[v % 3];
+                const double noise = (sq - sum * mean) * inv_pairs;
+                const size_t at = ((size_t)(v / 3) * npix + gp) * 3 + (size_t)(v % 3);
+                if (out_img) out_img[at] = (float)mean;
+                if (out_var) out_var[at] = (float)noise;
+                acc[v] += r * r - noise;
+                acc[DRT_SETS_VALUES + v] += noise;
+            }
+    }
+    block_sums(acc, part, (size_t)blockIdx.x * (2 * DRT_SETS_VALUES));
+}
+
+// ... its second stage: block v adds value v's partials over k_sets_cross_finish's blocks -- a strided sum per thread, then an LDS tree,
+// both in a fixed order -- into out_loss[set][channel] or out_bias[set][channel] (where the caller gave it)
+__global__ void __launch_bounds__(DRT_BLOCK)
+k_sets_cross_sums(const double* __restrict__ part, int n_blocks, int n_values, double* __restrict__ out_loss, double* __restrict__ out_bias)
+{
+    __shared__ double red[DRT_BLOCK];
+    const int v = (int)blockIdx.x % DRT_SETS_VALUES;
+    double* out = (int)blockIdx.x < DRT_SETS_VALUES ? out_loss : out_bias;
+    add_blocks(red, n_blocks, [&](int b) { return part[(size_t)b * (2 * DRT_SETS_VALUES) + blockIdx.x]; });
+    if (threadIdx.x == 0 && v < n_values && out)
+        out[v] = red[0];
 }
 
 // ---- the images, losses, slopes and curvatures of a frame under K parameter sets with a direction each (drt_hip_render_param_sets_along) ----

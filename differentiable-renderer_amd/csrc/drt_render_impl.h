@@ -151,13 +151,14 @@ inline int np_width(int n_params, int general)
 }
 
 // ---- which instantiation of the one-launch path kernels a render runs (shard_plan decides it, path_batch launches it) ----
-enum class PathOp { biased, unbiased, mesh, tangent, jacobian, tangents, param_sets, param_sets_along, param_sets_grad, cross };   // k_path (the gradient image included), k_path_unbiased, k_path_mesh, k_path's forward-mode form,
+enum class PathOp { biased, unbiased, mesh, tangent, jacobian, tangents, param_sets, param_sets_along, param_sets_grad, cross, param_sets_cross };   // k_path (the gradient image included), k_path_unbiased, k_path_mesh, k_path's forward-mode form,
                                                                     // its Jacobian form (lockstep, parameters in columns: DRT_NC_JACOBIAN),
                                                                     // its K-direction forward form (lockstep, nc = K),
                                                                     // its parameter-set form (lockstep, np = DRT_NP_SETS, nc = K),
                                                                     // ... with a direction per set (lockstep, np = DRT_NP_SETS_ALONG, nc = K)
                                                                     // ... with a summed gradient per set (lockstep, np = DRT_NP_SETS_GRAD, nc = K)
                                                                     // its K-direction form with cross moments (lockstep, np = DRT_NP_CROSS, nc = K)
+                                                                    // k_path_sets_cross: the parameter-set form with every set's second moments (np = DRT_NP_SETS, nc = K)
 enum class PathProg { cornell, sorted, scene };  // closest-hit program: the reference's kinds compiled in (SigCornell), kinds read at
                                                  // run time (SigNone), or compiled by hiprtc for the scene's own KindSig (drt_jit.h)
 struct PathForm {
@@ -205,7 +206,7 @@ struct Shard {
     int n_dirs = 0;                 // ... > 0: its rows are directions -- k_path's K-direction forward form in place of the Jacobian form
     const ParamSetsRequest* sets = nullptr;   // drt_hip_render_param_sets: the parameter-set form, then k_sets_finish (n_dirs: the caller's sets)
     bool cross() const { return neq && neq->cross; }   // drt_hip_render_normal_equations_cross: 6 rows a direction + 3, k_cross_eq
-    int jac_rows() const { return cross() ? n_dirs * 6 + 3 : (neq || sets) ? (n_dirs > 0 ? n_dirs : ctx->n_params) * (sets && sets->along ? 6 : 3) : 3; }   // rows a pixel's sums have in `gpix`
+    int jac_rows() const { return cross() ? n_dirs * 6 + 3 : (neq || sets) ? (n_dirs > 0 ? n_dirs : ctx->n_params) * (sets && (sets->along || sets->cross) ? 6 : 3) : 3; }   // rows a pixel's sums have in `gpix`
     bool sets_grad() const { return sets && sets->grad; }   // drt_hip_render_param_sets_grad: gradient tables, no per-pixel sums
     bool pixel_sums() const { return gimg_param >= 0 || fwd_tangent || neq || (sets && !sets->grad); }   // the lanes' per-pixel sums leave the path kernel (gimg_part)
     // the scene in compute type R
@@ -292,7 +293,7 @@ struct Shard {
 
 // "k_path<float, SPEC, NP, NC | roles << 8, KindSig<...>, REGEN[, LOSS]>" / "k_path_unbiased<float, SPEC, NP, KindSig<...>>": the name expression
 // of the form for the scene's own signature, what hiprtc compiles (k_path_mesh has no such form); "k_path_lean<float, NP, NC | roles << 8, KindSig<...>>"
-// where the form has both of that kernel's facts
+// where the form has both of that kernel's facts; "k_path_sets_cross<float, SPEC, K, KindSig<...>>" for the parameter sets with second moments
 inline std::string path_kernel_name(const drt_hip_ctx* ctx, const PathForm& f)
 {
     const std::string sg = drt_jit::sig_type(ctx->prog_sig, ctx->n_shapes);
@@ -301,6 +302,8 @@ inline std::string path_kernel_name(const drt_hip_ctx* ctx, const PathForm& f)
     char name[400];
     if (f.op == PathOp::unbiased)
         snprintf(name, sizeof name, "k_path_unbiased<%s, %s, %d, %s>", type, sp, f.np, sg.c_str());
+    else if (f.op == PathOp::param_sets_cross)
+        snprintf(name, sizeof name, "k_path_sets_cross<%s, %s, %d, %s>", type, sp, f.nc, sg.c_str());
     else if (f.lean())
         snprintf(name, sizeof name, "k_path_lean<%s, %d, %d, %s, 0x%llxull>", type, f.np, DRT_NC_ROLES(f.nc, 0, 0) | f.roles << 8, sg.c_str(), f.lights);
     else
@@ -318,7 +321,7 @@ unsigned path_dynamic_lds(const PathForm& f, int n_params, unsigned hist_bytes)
 {
     const uint32_t n = (uint32_t)std::min(n_params, DRT_PATH_LDS_PARAMS), K = (uint32_t)f.nc;
     if (f.op == PathOp::tangents || f.op == PathOp::cross) return dirs_table_words(n, K) * (unsigned)sizeof(R);
-    if (f.op == PathOp::param_sets) return sets_table_words(n, K) * (unsigned)sizeof(R);
+    if (f.op == PathOp::param_sets || f.op == PathOp::param_sets_cross) return sets_table_words(n, K) * (unsigned)sizeof(R);
     if (f.op == PathOp::param_sets_along) return sets_along_table_words(n, K) * (unsigned)sizeof(R);
     if (f.op == PathOp::param_sets_grad) return hist_bytes + sets_grad_table_words(n, K) * (unsigned)sizeof(R);   // (the history words, then the tables: 51 KB in f32, 98 KB in f64 at 136 parameters x 8 sets)
     return f.op == PathOp::unbiased ? 0u : hist_bytes;
@@ -397,6 +400,10 @@ const void* library_path_kernel(const PathForm& f)
                 else
                     return spec_sig([](auto spec, auto sg) { return (const void*)k_path<R, decltype(spec)::value, decltype(np)::value, decltype(k)::value, decltype(sg), false>; });
             });
+        });
+    if (f.op == PathOp::param_sets_cross)   // K parameter sets with their second moments: a kernel of its own, lockstep, every program, widths 2, 4 and 8
+        return f.regen ? nullptr : with_int<2, 4, 8>(f.nc, [&](auto k) {
+            return spec_sig([](auto spec, auto sg) { return (const void*)k_path_sets_cross<R, decltype(spec)::value, decltype(k)::value, decltype(sg)>; });
         });
     if (f.op == PathOp::tangent)   // forward mode: both forms, every program
         return spec_sig([&f](auto spec, auto sg) {
@@ -512,6 +519,8 @@ void shard_plan(Shard<R>& s)
             f.op = PathOp::param_sets_grad;
             f.np = DRT_NP_SETS_GRAD;
         }
+        if (s.sets->cross)          // (the same tag: the form's own kernel, k_path_sets_cross)
+            f.op = PathOp::param_sets_cross;
     }
     f.loss = s.loss_l2;
     // the slots' roles as the scene's records give them: for the form the headline runs -- diffuse, f32, lockstep, parameters in columns
@@ -685,7 +694,7 @@ int shard_buffers(Shard<R>& s)
         if (s.sets) {
             // k_sets_finish: k_normal_eq's grid rule, a pixel per thread
             s.neq_blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(((uint64_t)s.Pb + DRT_BLOCK - 1) / DRT_BLOCK, (uint64_t)ctx->n_cu * 4));
-            if ((rc = ensure(ctx, ctx->neq_part, (size_t)s.neq_blocks * (s.sets->along ? DRT_SETS_ALONG_VALUES : DRT_SETS_VALUES) * sizeof(double))) != DRT_OK) return rc;
+            if ((rc = ensure(ctx, ctx->neq_part, (size_t)s.neq_blocks * (s.sets->cross ? 2 * DRT_SETS_VALUES : (s.sets->along ? DRT_SETS_ALONG_VALUES : DRT_SETS_VALUES)) * sizeof(double))) != DRT_OK) return rc;
         }
         if (s.mesh_path) {   // the traversal stack's entries beyond the ones in LDS, per thread of the grid (one area per k_path stream)
             const size_t threads = ((s.path_waves + DRT_BLOCK / DRT_WAVE - 1) / (DRT_BLOCK / DRT_WAVE)) * DRT_BLOCK;
@@ -843,7 +852,7 @@ int path_batch(Shard<R>& s)
     pa.ct_step_f = (float)(2. * pa.tan_half * pa.inv_H);
     pa.gimg_param = s.gimg_param;
     pa.gen_rows = s.gen_rows; pa.gen_clog2 = s.gen_clog2;
-    if (s.path.op == PathOp::tangents || s.path.op == PathOp::cross || s.path.op == PathOp::param_sets || s.path.op == PathOp::param_sets_along)
+    if (s.path.op == PathOp::tangents || s.path.op == PathOp::cross || s.path.op == PathOp::param_sets || s.path.op == PathOp::param_sets_along || s.path.op == PathOp::param_sets_cross)
         pa.set_dirs_out((uint32_t)s.n_dirs);       // (the K-direction / parameter-set form: the directions / sets whose sums leave the kernel)
     // the general form's vertex history: a word per four vertices and thread, in dynamic shared memory
     // (the parameter-set gradient form shares it: the general form's history, tables and block sums, K R rows of them)
@@ -1035,6 +1044,15 @@ int path_batch(Shard<R>& s)
             const ParamSetsRequest& q = *s.sets;
             const bool sums = q.d_loss || q.d_dloss || q.d_curv;
             double* spart = sums ? part : (double*)nullptr;
+            if (q.cross) {
+                // (the unbiased losses: the entry point has asked for a target and out_loss)
+                DRT_TIMED(s, DRT_K_GRADREDUCE,
+                          hipLaunchKernelGGL(k_sets_cross_finish, dim3(s.neq_blocks), dim3(DRT_BLOCK), 0, ctx->stream, pa, (const double*)gpix, s.n_dirs, q.d_target,
+                                             q.d_images, q.d_variance, part));
+                DRT_TIMED(s, DRT_K_GRADREDUCE,
+                          hipLaunchKernelGGL(k_sets_cross_sums, dim3(2 * DRT_SETS_VALUES), dim3(DRT_BLOCK), 0, ctx->stream, (const double*)part, (int)s.neq_blocks,
+                                             s.n_dirs * 3, q.d_loss, q.d_bias));
+            } else
             if (q.along) {
                 DRT_TIMED(s, DRT_K_GRADREDUCE,
                           hipLaunchKernelGGL(k_sets_along_finish, dim3(s.neq_blocks), dim3(DRT_BLOCK), 0, ctx->stream, pa, (const double*)gpix, s.n_dirs, q.d_target,
@@ -1358,7 +1376,8 @@ int render_impl(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_p
     using Kind = TangentRequest::Kind;
     const bool forward = tangent && tangent->kind == Kind::forward, jacobian = tangent && tangent->kind == Kind::jacobian,
                directions = tangent && tangent->kind == Kind::directions, param_sets = tangent && tangent->kind == Kind::param_sets,
-               sets_along = param_sets && tangent->sets->along, sets_grad = param_sets && tangent->sets->grad;
+               sets_along = param_sets && tangent->sets->along, sets_grad = param_sets && tangent->sets->grad,
+               sets_cross = param_sets && tangent->sets->cross;
     s.fwd_tangent = forward;
     s.keep_sums = forward && tangent->keep_sums;
     s.neq = jacobian || directions ? tangent->neq : nullptr;
@@ -1377,7 +1396,7 @@ int render_impl(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_p
                           "intersection program does not cover)");
     if (jacobian || directions || param_sets) {
         const bool cross = directions && tangent->neq && tangent->neq->cross;
-        const PathOp op = jacobian ? PathOp::jacobian : (cross ? PathOp::cross : directions ? PathOp::tangents : (sets_along ? PathOp::param_sets_along : (sets_grad ? PathOp::param_sets_grad : PathOp::param_sets)));
+        const PathOp op = jacobian ? PathOp::jacobian : (cross ? PathOp::cross : directions ? PathOp::tangents : (sets_along ? PathOp::param_sets_along : (sets_grad ? PathOp::param_sets_grad : (sets_cross ? PathOp::param_sets_cross : PathOp::param_sets))));
         if (!s.use_path || s.mesh_path || !s.path_finish || s.path.op != op)
             return fail(ctx, DRT_ERR_UNSUPPORTED,
                         jacobian ? "normal equations: they come from the one-launch path kernel's Jacobian form over the whole shard in one "
@@ -1395,6 +1414,9 @@ int render_impl(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_p
                         : sets_grad ? "param sets grad: they come from the one-launch path kernel's parameter-set gradient form over the whole "
                                       "shard in one batch, which this render does not take (a DRT_HIP_* setting that forces the queue wavefront or a "
                                       "batch size, paths that end at depth 0, or a scene its intersection program does not cover)"
+                        : sets_cross ? "param sets cross: they come from the one-launch path kernel's parameter-set form with second moments over the whole "
+                                       "shard in one batch, which this render does not take (a DRT_HIP_* setting that forces the queue wavefront or a "
+                                       "batch size, paths that end at depth 0, or a scene its intersection program does not cover)"
                                      : "param sets: they come from the one-launch path kernel's parameter-set form over the whole shard in one batch, "
                                        "which this render does not take (a DRT_HIP_* setting that forces the queue wavefront or a batch size, paths "
                                        "that end at depth 0, or a scene its intersection program does not cover)");

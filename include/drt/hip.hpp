@@ -1131,6 +1131,47 @@ inline Stats render_param_sets(const Scene<T>& scene, const Camera<T>& cam, cons
                              });
 }
 
+// ---- ... each set's loss unbiased (drt_hip_render_param_sets_cross) -------------------------------------------------------------
+// The loss of the frame under each of up to DRT_HIP_MAX_SETS_CROSS parameter sets, from one trace, without the share the samples' noise
+// adds to a squared residual: with m_k the pixel's mean over its n = spp samples, r_k = m_k - target and var^ their sample variance, per
+// set and channel (index k * 3 + ch)
+//     losses = sum (r_k^2 - var^(L_k) / n)      biases = sum var^(L_k) / n      (losses + biases: render_param_sets' losses)
+// imgs (nullptr: none): render_param_sets' images; variance_imgs (nullptr: none): [k * width * height + pixel] var^(L_k) / n.  spp < 2 and
+// a missing target throw before a device is asked for.  The scene's own values are not changed.
+template <typename T>
+struct SetsCross {
+    std::vector<double> losses, biases;
+    Stats stats;
+};
+
+template <typename T>
+inline SetsCross<T> render_param_sets_cross(const Scene<T>& scene, const Camera<T>& cam, const Pathtracer<T>& tracer, std::size_t spp,
+                                            const std::vector<ParamSet<T>>& sets, const Vector<T, 3>* target, Vector<T, 3>* imgs = nullptr,
+                                            Vector<T, 3>* variance_imgs = nullptr, const Options& opt = Options())
+{
+    const char* who = "drt::hip::render_param_sets_cross";
+    detail::forward_only(who, opt, "a forward render");
+    detail::one_device(who, opt);
+    if (spp < 2)
+        throw std::runtime_error(std::string(who) + ": spp < 2 (a product of two different samples of a pixel needs two)");
+    if (!target)
+        throw std::runtime_error(std::string(who) + ": the unbiased losses need a target");
+    FlatScene<T> flat = flatten(scene);
+    const std::size_t K = sets.size();
+    const std::vector<double> values =
+        detail::rows_of(who, flat, sets, flat.params.data(), false, [](const auto& t) { return std::make_pair(&t.first, &t.second); });
+    SetsCross<T> r;
+    r.losses.assign(K * 3, 0.0);
+    r.biases.assign(K * 3, 0.0);
+    r.stats = detail::sets_call("drt_hip_render_param_sets_cross", flat, cam, tracer, spp, K, target, imgs, variance_imgs, opt,
+                                [&](drt_hip_ctx* ctx, const drt_camera_desc* cd, const drt_render_params* rp, const float* tgt, float* out, float* vout,
+                                    drt_hip_stats* st) {
+                                    return drt_hip_render_param_sets_cross(ctx, cd, rp, (int32_t)K, values.data(), tgt, out, K ? r.losses.data() : nullptr,
+                                                                           K ? r.biases.data() : nullptr, vout, st);
+                                });
+    return r;
+}
+
 // ---- ... each set with a direction of its own (drt_hip_render_param_sets_along) ----------------------------------------------
 // A parameter set with its direction: (handle, value, direction) triples over the scene's current values; handles not listed keep the
 // value they have in the scene and get direction 0

@@ -590,6 +590,32 @@ int drt_hip_render_param_sets_grad(drt_hip_ctx* ctx, const drt_camera_desc* cam,
                                    const double* param_sets /* n_sets x n_params x 3 */,
                                    const float* adjoints_rgb /* n_sets x H x W x 3, may be NULL */,
                                    double* out_param_grads /* n_sets x n_params x 3 */, drt_hip_stats* stats);
+/* ... each set's loss UNBIASED, from the one trace: what an accept / reject, a gain ratio, a line search or a population compares.
+ * drt_hip_render_param_sets' loss sum_x (mean_k - target)^2 carries sum_x Var(L_k) / n (n = spp), which depends on the set -- a brighter
+ * candidate is noisier --, so the plain losses of two candidates differ by the difference of their noise as well.  Per set k, over the pixels
+ * of this shard, with m_k the pixel's mean, r_k = m_k - target and var^ the sample variance of the pixel's n samples under set k:
+ *   out_loss[k][ch]         sum_x (r_k^2 - var^(L_k) / n) = sum_x 1 / (n (n - 1)) sum_{s != s'} (L_{k,s} - t)(L_{k,s'} - t): its expectation is
+ *                           the loss of the converged images (it may be negative)
+ *   out_bias[k][ch]         sum_x var^(L_k) / n, what was subtracted: out_loss + out_bias is drt_hip_render_param_sets' loss
+ *   out_variance[k][x][ch]  var^(L_k) / n, the variance of the pixel's mean under set k
+ *   out_images[k]           drt_hip_render_param_sets' image k, bit for bit
+ * The path kernel is a form of its own (k_path_sets_cross): drt_hip_render_param_sets' operations on the path, plus per lane and set the fp64
+ * sums of the samples' squares (exact products of f32 values; raw moments add across sample ranges); k_sets_cross_finish forms the
+ * corrections per pixel in fp64 and adds them in a fixed order without atomics: the same call returns the same bits.  1 <= n_sets <=
+ * DRT_HIP_MAX_SETS_CROSS; the kernel is instantiated for 2, 4 and 8 sets and a call's count is padded up with copies of the context's own
+ * parameters, which are never written out: a set's results depend neither on its companions nor on its position nor on n_sets, bit for bit.
+ * The context's own parameters are not changed.  There is no out_rgb and no _double twin.  Everything else -- shards,
+ * DRT_RENDER_DEVICE_OUT (target_rgb and the outputs are then device pointers; param_sets is host memory always), _F64, _SYNC, _TIMING, one
+ * batch per shard, lockstep under the roulette, the 2^31-sample limit, the slot the reduction is timed in -- as drt_hip_render_param_sets.
+ * DRT_ERR_INVALID: spp < 2, NULL target_rgb, out_loss or param_sets, n_sets outside 1 ... DRT_HIP_MAX_SETS_CROSS, a set or a target value
+ * that is not finite (host buffers), asynchronous frames in flight, DRT_RENDER_BACKWARD, bad camera or render parameters.
+ * DRT_ERR_UNSUPPORTED: what drt_hip_render_param_sets refuses.  The message of either says "param sets cross"; the context stays usable. */
+#define DRT_HIP_MAX_SETS_CROSS 8
+int drt_hip_render_param_sets_cross(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_params* rp, int32_t n_sets,
+                                    const double* param_sets /* n_sets x n_params x 3 */, const float* target_rgb /* H x W x 3 */,
+                                    float* out_images /* n_sets x H x W x 3, may be NULL */, double* out_loss /* n_sets x 3 */,
+                                    double* out_bias /* n_sets x 3, may be NULL */, float* out_variance /* n_sets x H x W x 3, may be NULL */,
+                                    drt_hip_stats* stats);
 /* stream the context launches on (a hipStream_t), for event timing / interop */
 void* drt_hip_stream(drt_hip_ctx* ctx);
 int drt_hip_synchronize(drt_hip_ctx* ctx);

@@ -14,7 +14,7 @@ the noisy objective sits ~9 % below the true albedo at 16 spp.  The per-pixel ad
 (the ABI's adjoint_rgb seeds every sample of a pixel alike); the reference's per-sample `loss_func(radiance).backward()` is
 the same thing for a loss that is linear in the radiance.
 
-    python tools/fit_albedo.py [--size 128] [--spp 16] [--steps 60] [--async] [--oracle] [--gauss-newton [--one-render [--cross]] [--lambda-sets N]]
+    python tools/fit_albedo.py [--size 128] [--spp 16] [--steps 60] [--async] [--oracle] [--gauss-newton [--one-render [--cross [--lambda-sets N]]] [--lambda-sets N]]
     python tools/fit_albedo.py --scene cornell_shapes --multi-start N [--oracle]
 
 --async: the same loop through drt_hip_render_async / drt_hip_wait (frame i + 1 needs the parameters of step i, so frames
@@ -50,6 +50,13 @@ first step is accepted (red 0.3677, loss 0.590 with a subtracted noise floor of 
 so red stays at 0.3677 and this form exits with status 1 too: the two losses that are compared come from different sample sets, and
 what is left of the loss after the subtraction is 1 / 25 of the noise floor.  The values are unbiased (tests/test_gpu_cross.py); a
 loop that compares them across seeds at 16 spp is not yet a fit.
+--one-render --cross --lambda-sets N (N <= 7): the comparison on COMMON paths.  Per step one drt_hip_render_normal_equations_cross call at
+the current point (seed A: the step for each of N dampings), then ONE drt_hip_render_param_sets_cross call on a fresh seed B that prices
+[current, candidate_1 ... candidate_N] on the same paths, each loss unbiased: the best candidate is accepted iff its loss~ is below the
+current point's on that trace (lambda becomes the winner's / 3; else the largest tried x 4).  Two traces per step.  Measured on the device at the defaults with N = 3: four steps accepted (red 0.3678, 0.4421, 0.4800, 0.4878), the
+fifth rejected (loss~ 0.903306 at the current point against 0.903329 for the best candidate on the same trace): fitted red (0.4878, 0.0118,
+0.0139) in 10 renders, 0.0139 from the truth -- status 1 against this tool's bound of 1e-2, beside 0.3677, 0.2866 and the two-seed loop's
+0.4960 in 20 renders.
 --oracle runs the same loop on the CPU restatement, J assembled from oracle.render(backward=True, grad_image_param=p).
 --lambda-sets N (N <= 7): after the two normal-equation renders the candidates for lambda x {1, 1/3, 4, 1/9, 16, 1/27, 64}[:N] are
 evaluated in ONE drt_hip_render_param_sets call per seed (one trace for all N: a parameter does not decide where a path goes), the
@@ -243,6 +250,42 @@ def fit_gauss_newton_cross(render, p_index, start, steps, lam=1e-3, log=None):
             log(f"step {k:3d}  loss {float(loss3.sum()):.6f} (noise floor subtracted: {float(bias[:, 1].sum()):.6f})  lambda {lam:.2e}  {verdict}  "
                 f"red = ({params[p_index][0]:.4f}, {params[p_index][1]:.4f}, {params[p_index][2]:.4f})")
     return params[p_index].copy(), hist
+
+
+def fit_gauss_newton_cross_sets(render, p_index, start, steps, n_sets, lam=1e-3, log=None):
+    """Levenberg-Marquardt on parameter p_index, per channel, TWO traces per step (the module's docstring): one
+    render.normal_equations_cross(params, seed A, V) at the current point, then the candidates of n_sets dampings and the current point
+    itself priced on ONE fresh trace, render.param_sets_cross([current, cand_1 ... cand_N], seed B) -> (loss~ [N + 1, 3], bias [N + 1, 3]):
+    common paths, each loss unbiased.  The best candidate is accepted iff its loss~ is below the current point's on that same trace.
+    -> (fitted rgb, history of rgb per step, per step {"losses": loss~ summed over the channels [N + 1], "best": index, "accepted"})"""
+    params = render.params0.copy()
+    params[p_index] = start
+    V = np.zeros((1,) + params.shape)
+    V[0, p_index] = 1.0                              # (a channel of the radiance depends on the same channel of the albedo alone)
+    hist, trace = [], []
+    for k in range(steps):
+        A, b, _, _ = render.normal_equations_cross(params, 1000 + 2 * k, V)
+        lams = [lam * f for f in LAMBDA_FACTORS[:n_sets]]
+        cands = []
+        for l in lams:
+            d = A[:, 0, 0] * (1.0 + l)
+            c = params.copy()
+            c[p_index] = np.clip(params[p_index] + np.where(d > 0, -b[:, 0] / np.where(d > 0, d, 1.0), 0.0), 0.0, 1.0)
+            cands.append(c)
+        loss3, bias3 = render.param_sets_cross(np.stack([params] + cands), 1001 + 2 * k)
+        losses = loss3.sum(1)
+        i = 1 + int(np.argmin(losses[1:]))
+        accepted = bool(losses[i] < losses[0])
+        trace.append({"losses": losses.copy(), "best": i, "accepted": accepted})
+        if accepted:
+            params, lam, verdict = cands[i - 1], max(lams[i - 1] / 3.0, 1e-9), "accepted"
+        else:
+            lam, verdict = max(lams) * 4.0, "rejected"
+        hist.append(params[p_index].copy())
+        if log:
+            log(f"step {k:3d}  loss~ {losses[0]:.6f} -> best of {n_sets} {losses[i]:.6f} (noise floors subtracted: {bias3[0].sum():.6f}, {bias3[i].sum():.6f})  "
+                f"lambda {lam:.2e}  {verdict}  red = ({params[p_index][0]:.4f}, {params[p_index][1]:.4f}, {params[p_index][2]:.4f})")
+    return params[p_index].copy(), hist, trace
 
 
 def used_params(scene):
@@ -496,6 +539,14 @@ class DeviceRender:
         self.traces_of_sets += 1
         return self.r.render_param_sets(self.cam, rp, sets)["images"]
 
+    def param_sets_cross(self, sets, seed):
+        """the unbiased loss of every row of `sets` [N, P, 3] against the target, and what was subtracted, in one trace: two of [N, 3]"""
+        rp = self.pkg.RenderParams(spp=self.spp, min_bounces=self.depth, absorb=1.0, seed=seed)
+        self.calls += 1
+        self.traces_of_sets += 1
+        o = self.r.render_param_sets_cross(self.cam, rp, sets, self.target.astype(np.float32))
+        return o["loss"], o["bias"]
+
     def sets_along(self, sets, dirs, seed):
         """the frame and its derivative along dirs[k] under every row of `sets` [N, P, 3] in one trace: two of [N, H, W, 3]"""
         rp = self.pkg.RenderParams(spp=self.spp, min_bounces=self.depth, absorb=1.0, seed=seed)
@@ -617,8 +668,8 @@ def main():
     ap.add_argument("--scene", default="cornell", help="cornell: the red albedo (the loops above); cornell_shapes: every parameter, with --gauss-newton")
     ap.add_argument("--subspace", choices=("tint",), default=None, help="with --scene cornell_shapes: one tint over the albedos instead of every parameter")
     a = ap.parse_args()
-    if a.lambda_sets and (not a.gauss_newton or a.one_render or not 1 <= a.lambda_sets <= len(LAMBDA_FACTORS)):
-        ap.error("--lambda-sets N (1 ... 7) goes with --gauss-newton (not --one-render)")
+    if a.lambda_sets and (not a.gauss_newton or (a.one_render and not a.cross) or not 1 <= a.lambda_sets <= len(LAMBDA_FACTORS)):
+        ap.error("--lambda-sets N (1 ... 7) goes with --gauss-newton (not --one-render, unless with --cross)")
     if a.cross and (not a.gauss_newton or not a.one_render or a.oracle or a.scene != "cornell" or a.spp < 2):
         ap.error("--cross goes with --gauss-newton --one-render on the device, --scene cornell, --spp >= 2")
     if a.line_search and (not a.gauss_newton or a.scene == "cornell" or a.oracle or a.lambda_sets or not 1 <= a.line_search <= len(STEP_LENGTHS)):
@@ -657,7 +708,9 @@ def main():
         a.steps = GN_STEPS if a.gauss_newton else 60
     if a.gauss_newton:
         t0 = time.time()
-        if a.cross:
+        if a.cross and a.lambda_sets:
+            rgb, hist, _ = fit_gauss_newton_cross_sets(render, 0, np.array([0.2, 0.2, 0.2]), a.steps, a.lambda_sets, log=None if a.quiet else print)
+        elif a.cross:
             rgb, hist = fit_gauss_newton_cross(render, 0, np.array([0.2, 0.2, 0.2]), a.steps, log=None if a.quiet else print)
         else:
             rgb, hist = fit_gauss_newton(render, 0, np.array([0.2, 0.2, 0.2]), a.steps, a.one_render, log=None if a.quiet else print,
@@ -666,7 +719,7 @@ def main():
         if a.lambda_sets:
             print(f"--lambda-sets {a.lambda_sets}: {render.traces_of_sets} of the renders below were traces of {a.lambda_sets} candidates each")
         err = np.abs(rgb - np.array([0.5, 0.0, 0.0])).max()
-        n = (a.steps + 1 if a.cross else a.steps) if a.one_render else 4 * a.steps
+        n = (2 * a.steps if a.lambda_sets else (a.steps + 1 if a.cross else a.steps)) if a.one_render else 4 * a.steps
         print(f"fitted red = ({rgb[0]:.4f}, {rgb[1]:.4f}, {rgb[2]:.4f})  max error {err:.4f}  "
               f"{a.steps} Gauss-Newton steps, {n} renders in {dt:.2f} s")
         return 0 if err <= 1e-2 else 1
