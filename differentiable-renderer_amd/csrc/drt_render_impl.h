@@ -605,13 +605,9 @@ void shard_plan(Shard<R>& s)
     if (s.Sb < 1) s.Sb = 1;
     s.N = (size_t)s.Pb * s.Sb;
     // queue regions: one wave each; enough of them to fill 256 CUs several times over
-    s.region_shift = 8;          // 256 slots: 4 chunks per wave (sweep in profiles/: 64..4096)
-    if (tuning().region_size > 0)
-        for (s.region_shift = 6; s.region_shift < 20 && (1l << s.region_shift) < (long)tuning().region_size; ++s.region_shift) { }
-    while (s.region_shift > 6 && (s.N >> s.region_shift) < (size_t)ctx->n_cu * 32)
-        --s.region_shift;
+    s.region_shift = queue_region_shift(s.N, ctx->n_cu, tuning().region_size);
     s.region_size = 1u << s.region_shift;
-    s.max_regions = (uint32_t)((s.N + s.region_size - 1) / s.region_size);
+    s.max_regions = queue_regions(s.N, s.region_shift);
     // k_path geometry: wave <-> (64 pixels, spr samples); enough waves for ~5-6 rounds of what the chip holds (the tail stays
     // short) in ranges of equal length (sweep on config 3, ms per launch: 16 samples per range 0.827, 13: 0.818, 10: 0.793,
     // 8: 0.812, 7: 0.795, 4: 0.811); regenerating lanes balance themselves over their sample range: longer ranges, fewer waves

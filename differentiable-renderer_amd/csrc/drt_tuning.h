@@ -3,7 +3,9 @@
 // between equivalent routes for measurement, or switch debugging output on.  (tests/test_gpu_launch_geometry.py holds this for
 // PATH_SPR, PATH_REGEN, PATH_REGEN_MIN, GEN_ABOVE, GEN_HIST_LDS and GEN_COPIES_LOG2: every entry point in a process per setting, against
 // the fp64 restatement and against the default process; tests/test_gpu_mesh_geometry.py holds it for the mesh routes' MESH_SHADE_MIN,
-// BVH_DESCEND_MIN, BVH_REFILL, SHADE_LIST_GROUP and MESH_BLOCKS_PER_CU the same way, on both routes.)  What a caller is meant to choose lives in the ABI
+// BVH_DESCEND_MIN, BVH_REFILL, SHADE_LIST_GROUP and MESH_BLOCKS_PER_CU the same way, on both routes; tests/test_gpu_queue_geometry.py holds
+// it for the queue wavefront's REGION_SIZE, with BATCH_PATHS and TAIL_BOUNCES: regions of 2, 4 and 16 chunks at frames of 315 and 1771
+// paths, every call of the queue route in a process per setting.)  What a caller is meant to choose lives in the ABI
 // (drt_render_params, the DRT_RENDER_* flags, drt_hip_set_specialisation), not here.  INTEGRATION.md section 2 lists this
 // table; tests/test_abi.py checks that the two agree.
 #pragma once
@@ -12,6 +14,28 @@
 #include <cstring>
 
 namespace {
+
+// The queue wavefront's region: 1 << shift slots of every queue, one wave's share (drt_kernels.h); the wave takes them in chunks of 64.
+// setting <= 0: 256 slots, halved down to 64 while the batch's N paths make fewer than 32 regions per CU (a 256-CU device keeps 256
+// from 2^21 paths on).  setting > 0 (DRT_HIP_REGION_SIZE): the smallest power of two in [64, 2^20] that holds it, taken as given --
+// never halved, so that frames of a few hundred paths can be rendered in regions of several chunks (tests/test_gpu_queue_geometry.py;
+// tests/cpp/queue_regions_kat.cpp holds the answers).  The plan's buffers are sized from the result: ceil(N / size) regions.
+inline unsigned queue_region_shift(unsigned long long N, int n_cu, long long setting)
+{
+    unsigned shift = 8;          // 256 slots: 4 chunks per wave (sweep in profiles/: 64..4096)
+    if (setting > 0) {
+        for (shift = 6; shift < 20 && (1ll << shift) < setting; ++shift) { }
+        return shift;
+    }
+    while (shift > 6 && (N >> shift) < (unsigned long long)n_cu * 32)
+        --shift;
+    return shift;
+}
+
+inline unsigned queue_regions(unsigned long long N, unsigned shift)
+{
+    return (unsigned)((N + (1ull << shift) - 1) >> shift);
+}
 
 struct Tuning {
     // ---- k_path
@@ -29,7 +53,7 @@ struct Tuning {
     int gen_copies_log2 = -1;      // DRT_HIP_GEN_COPIES_LOG2  log2 of the copies a wave keeps of every row of its gradient table (general form); -1 = as many as fit, at most 16
     // ---- the queue wavefront
     long long batch_paths = 0;     // DRT_HIP_BATCH_PATHS      paths per batch; 0 = drt_render_params.batch_paths, else sized by the device's memory
-    int region_size = 0;           // DRT_HIP_REGION_SIZE      slots per queue region (a wave's share of a queue); 0 = 256
+    int region_size = 0;           // DRT_HIP_REGION_SIZE      slots per queue region (a wave's share of a queue), rounded up to a power of two in [64, 2^20] and taken as given; 0 = 256, halved down to 64 while a batch makes fewer than 32 regions per CU
     int shade_bounces = 0;         // DRT_HIP_SHADE_BOUNCES    overrides drt_render_params.bounces_per_launch
     // ---- triangle meshes
     int mesh_blocks_per_cu = 0;    // DRT_HIP_MESH_BLOCKS_PER_CU   blocks of the BVH walk's persistent grid per CU; 0 = what the occupancy query says (5)

@@ -276,6 +276,19 @@ def plain_counts(c, E, call, f64):
     assert c.stat(call, f64, "segments") == E["segments"] and c.stat(call, f64, "capped_paths") == E["capped"], (call, c.where)
 
 
+def flat_materials(scene):
+    """the material of every entry of the flattened scene, in which the restatement's vertices name what they hit (oracle/drt_oracle.c,
+    raycast: every triangle of a mesh counts as a shape): the face's own material where the mesh has one per face, else the shape's"""
+    out, mesh = [], sys.modules[type(scene).__module__].SHAPE_MESH
+    for t, m, _, p in scene.shapes:
+        if t != mesh:
+            out.append(m)
+            continue
+        _, indices, face_material = scene.meshes[int(p[0])]
+        out.extend([m] * len(indices) if face_material is None else [int(f) for f in face_material])
+    return out
+
+
 def lobe_conditioning(oracle, x):
     """The f32 conditioning of the reference's specular lobe, per pixel [H,W]: the largest c^2 / (1 - c^2) over the specular bounces of the
     pixel's paths, c = normal . half vector, from the restatement's vertices.  The lobe's factor s = sqrt(1 - c^2) (bxdf.hpp:104-107) loses
@@ -284,7 +297,7 @@ def lobe_conditioning(oracle, x):
     first half vector lies 5e-3 rad off the sphere's normal, c^2 / (1 - c^2) = 40969 -- every f32 geometry, `default` included, gives
     that pixel 0.54 % above the restatement, in the image and in every derivative image alike."""
     scene, cam, rp = x.scene, x.cam, x.rp
-    specular = [i for i, (_, m, _, _) in enumerate(scene.shapes) if m >= 0 and scene.materials[m][0] == 1]
+    specular = [i for i, m in enumerate(flat_materials(scene)) if m >= 0 and scene.materials[m][0] == 1]
     v = oracle.render(scene, cam, rp, dump_paths=cam.width * cam.height * rp.spp)["vertices"]
     v = v[np.lexsort((v[:, 1], v[:, 0]))]
     a, b = v[:-1], v[1:]                                  # a vertex and the next one of the same path: directions in and out

@@ -58,6 +58,19 @@ def test_bvh_builder_and_node_encoding_known_answers(tmp_path):
     assert out.strip().endswith("ok"), out
 
 
+def test_queue_region_size_known_answers(tmp_path):
+    """csrc/drt_tuning.h, queue_region_shift: without DRT_HIP_REGION_SIZE exactly what shard_plan chose before (64 slots for every batch
+    under 2^20 paths on 256 CUs, 256 from 2^21 on); a set size is taken as given, so that a frame of 315 paths has two regions of 256
+    slots -- what tests/test_gpu_queue_geometry.py renders with."""
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(tmp_path / "queue_regions_kat")
+    subprocess.run(["g++", "-O1", "-std=c++17", "-Wall", os.path.join(root, "tests", "cpp", "queue_regions_kat.cpp"), "-o", exe],
+                   check=True)
+    out = subprocess.run([exe], check=True, capture_output=True, text=True).stdout
+    assert out.strip().endswith("ok"), out
+
+
 def test_integer_reduced_sincos_known_answers(tmp_path):
     """csrc/drt_sincos.h (the f32 sin/cos of phi = 2 pi u that every BxDF sample uses on the device) compiled for
     the host: a sweep of the 31-bit draw range against libm in double, max abs error < 2e-7, exact at 0 and 1/2."""
