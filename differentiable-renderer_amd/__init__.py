@@ -49,6 +49,7 @@ MAX_PARAM_SETS = 8           # DRT_HIP_MAX_PARAM_SETS: parameter sets per render
 MAX_SETS_ALONG = 4           # DRT_HIP_MAX_SETS_ALONG: parameter sets with a direction each per render_param_sets_along call
 MAX_SETS_GRAD = 8            # DRT_HIP_MAX_SETS_GRAD: parameter sets with a summed gradient each per render_param_sets_grad call
 MAX_SETS_CROSS = 8           # DRT_HIP_MAX_SETS_CROSS: parameter sets with an unbiased loss each per render_param_sets_cross call
+MAX_LOSS_VALUES = 4          # DRT_MAX_LOSS_VALUES: the constants q[0..3] of a per-sample loss (set_sample_loss)
 ABI_VERSION = 8
 UNIQUE_ID_BYTES = 128
 
@@ -81,6 +82,10 @@ class ShapeKindDesc(C.Structure):
 
 class BxdfKindDesc(C.Structure):
     _fields_ = [("name", C.c_char_p), ("sample_src", C.c_char_p)]
+
+
+class SampleLossDesc(C.Structure):
+    _fields_ = [("name", C.c_char_p), ("loss_src", C.c_char_p), ("values", C.c_double * 4)]
 
 
 class SceneDesc(C.Structure):
@@ -761,7 +766,8 @@ _ABI_SYMBOLS = ["drt_hip_abi_version", "drt_hip_device_count", "drt_hip_create",
                 "drt_hip_upload_scene", "drt_hip_update_params", "drt_hip_set_specialisation", "drt_hip_render", "drt_hip_render_async", "drt_hip_wait",
                 "drt_hip_render_gradient_image", "drt_hip_render_tangent", "drt_hip_render_tangent_double", "drt_hip_render_normal_equations", "drt_hip_render_tangents",
                 "drt_hip_render_normal_equations_along", "drt_hip_render_normal_equations_cross", "drt_hip_render_param_sets", "drt_hip_render_param_sets_double",
-                "drt_hip_render_param_sets_along", "drt_hip_render_param_sets_along_double", "drt_hip_render_param_sets_grad", "drt_hip_render_param_sets_cross", "drt_hip_pin_host", "drt_hip_unpin_host", "drt_hip_stream",
+                "drt_hip_render_param_sets_along", "drt_hip_render_param_sets_along_double", "drt_hip_render_param_sets_grad", "drt_hip_render_param_sets_cross",
+                "drt_hip_set_sample_loss", "drt_hip_render_sample_loss", "drt_hip_pin_host", "drt_hip_unpin_host", "drt_hip_stream",
                 "drt_hip_synchronize", "drt_hip_last_error", "drt_hip_kernel_name"]
 
 
@@ -820,6 +826,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
                                                    C.c_void_p, C.c_void_p, C.POINTER(HipStats)]
     lib.drt_hip_render_param_sets_cross.argtypes = [C.c_void_p, C.POINTER(CameraDesc), C.POINTER(RenderParamsDesc), C.c_int32, C.c_void_p,
                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(HipStats)]
+    lib.drt_hip_set_sample_loss.argtypes = [C.c_void_p, C.POINTER(SampleLossDesc)]
+    lib.drt_hip_render_sample_loss.argtypes = [C.c_void_p, C.POINTER(CameraDesc), C.POINTER(RenderParamsDesc), C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.POINTER(HipStats)]
     lib.drt_hip_pin_host.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
     lib.drt_hip_unpin_host.argtypes = [C.c_void_p, C.c_void_p]
     lib.drt_hip_stream.argtypes = [C.c_void_p]
@@ -954,6 +963,49 @@ class HipRenderer:
                                      C.byref(stats) if (want_stats or timing) else None)
         self._check(rc, "drt_hip_render")
         return img, grads, (stats.as_dict() if (want_stats or timing) else {})
+
+    def set_sample_loss(self, name: Optional[str] = None, src: Optional[str] = None, values: Sequence[float] = ()):
+        """The per-sample loss render_sample_loss back-propagates (drt_hip_set_sample_loss): `src` is the body of
+            template <typename R> void sample_loss(const R* q, V3<R> L, V3<R> t, R& value, V3<R>& grad)
+        -- L one camera sample's radiance, t its target pixel, value = loss_func(L), grad = d value / d L --, `values` its constants q[0..3]
+        (data: the same source with other values compiles nothing).  src=None (or name=None): the squared error."""
+        if src is None or name is None:
+            self._check(self.lib.drt_hip_set_sample_loss(self.ctx, None), "drt_hip_set_sample_loss")
+            return
+        q = [float(v) for v in values]
+        assert len(q) <= MAX_LOSS_VALUES, len(q)
+        desc = SampleLossDesc(name.encode(), src.encode(), (C.c_double * 4)(*(q + [0.0] * (MAX_LOSS_VALUES - len(q)))))
+        self._check(self.lib.drt_hip_set_sample_loss(self.ctx, C.byref(desc)), "drt_hip_set_sample_loss")
+
+    def render_sample_loss(self, cam: Camera, rp: RenderParams, target: np.ndarray, f64: bool = False, timing: bool = False,
+                           want_image: bool = True, want_grads: bool = True, want_loss: bool = True):
+        """One render under the context's per-sample loss (drt_hip_render_sample_loss): every camera sample is back-propagated through
+        loss_func(its radiance); backward is implied.  -> (image float32 [H,W,3] or None, grads float64 [P,3] or None, loss -- the sum of
+        the samples' values over this shard, a float, or None --, stats dict)."""
+        assert self.scene is not None
+        cd, d, stats = self._begin(cam, rp, self._host_flags(rp, f64, timing))
+        _keep, t_ptr = self._image_arg(target, cam)
+        img = np.zeros((cam.height, cam.width, 3), dtype=np.float32) if want_image else None
+        grads = np.zeros((self.scene.n_params, 3), dtype=np.float64) if want_grads else None
+        loss = C.c_double(0.0)
+        rc = self.lib.drt_hip_render_sample_loss(self.ctx, C.byref(cd), C.byref(d), t_ptr,
+                                                 img.ctypes.data_as(C.c_void_p) if want_image else None,
+                                                 grads.ctypes.data_as(C.c_void_p) if want_grads else None,
+                                                 C.cast(C.byref(loss), C.c_void_p) if want_loss else None, C.byref(stats))
+        self._check(rc, "drt_hip_render_sample_loss")
+        return img, grads, (loss.value if want_loss else None), stats.as_dict()
+
+    def render_sample_loss_device(self, cam: Camera, rp: RenderParams, target_ptr: int, out_rgb_ptr: int = 0, out_grad_ptr: int = 0,
+                                  out_loss_ptr: int = 0, f64: bool = False, timing: bool = False, sync: bool = False, want_stats: bool = True):
+        """render_sample_loss on device pointers (DRT_RENDER_DEVICE_OUT), enqueued on the context's stream: target float32 [H,W,3], image
+        float32 [H,W,3], gradients float64 [P,3], loss one float64 -- each output may be 0.  -> stats dict."""
+        assert self.scene is not None
+        cd, d, stats = self._begin(cam, rp, self._device_flags(rp, f64, timing, sync))
+        rc = self.lib.drt_hip_render_sample_loss(self.ctx, C.byref(cd), C.byref(d), C.c_void_p(target_ptr), C.c_void_p(out_rgb_ptr or None),
+                                                 C.c_void_p(out_grad_ptr or None), C.c_void_p(out_loss_ptr or None),
+                                                 C.byref(stats) if want_stats else None)
+        self._check(rc, "drt_hip_render_sample_loss")
+        return stats.as_dict() if want_stats else {}
 
     def render_async(self, cam: Camera, rp: RenderParams, backward: bool = False, adjoint: Optional[np.ndarray] = None,
                      f64: bool = False, unbiased: bool = False, img_out: Optional[np.ndarray] = None,

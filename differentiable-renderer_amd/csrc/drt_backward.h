@@ -328,10 +328,15 @@ __device__ inline V3<R> backward_path(const BatchArgs& a, const SceneLds<R>& lds
 // the seed a path is back-propagated with: (1, 1, 1) (render.cpp:80), the caller's per-pixel adjoint, or -- DRT_RENDER_LOSS_L2,
 // `radiance` given -- the derivative of the per-sample squared error against the target image, 2 (L_path - target_pixel)
 // (README.md:93-98: loss = loss_func(radiance); loss.backward())
-template <typename R>
+// (SEEDED, the caller's own per-sample loss: `radiance` holds the seed already -- k_sample_seed, drt_loss.h, wrote it in place)
+template <typename R, bool SEEDED = false>
 __device__ inline V3<R> path_seed(const BatchArgs& a, const float* __restrict__ adjoint, uint32_t i,
                                   const typename Q4<R>::T* __restrict__ radiance = nullptr)
 {
+    if constexpr (SEEDED) {
+        const typename Q4<R>::T g = radiance[i];
+        return mk<R>(g.x, g.y, g.z);
+    }
     if (!adjoint)
         return mk<R>(R(1), R(1), R(1));                       // render.cpp:80
     const uint32_t gp = global_pixel(a, a.p0 + i % a.Pb);
@@ -393,6 +398,53 @@ k_backward(BatchArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict_
         if (K > 0 || GradAcc<R, NP>::kWave)
             L0 = backward_path<R, SMALL>(a, lds, params, tape, N, i, K, path_seed<R>(a, adjoint, i, radiance_in), inv_p_rr, ga, acc, grad, first);
         if (lacc && valid) {
+            R4 o;
+            o.x = L0.x; o.y = L0.y; o.z = L0.z; o.w = R(0);
+            lacc[i] = o;
+        }
+    }
+
+    flush_grad_block<R, NP>(ga, acc, red, gpart, n_rows, row_stride);
+}
+
+// k_backward behind k_sample_seed (drt_hip_render_sample_loss): `lacc` holds every path's seed and gets its radiance back, as the plain
+// backward render's does.  A kernel of its own, so that k_backward keeps its instruction stream; the same walk, the same accumulators,
+// the same launch bounds.
+template <typename R, int NP>
+__global__ void __launch_bounds__(DRT_BLOCK, (sizeof(R) == 4 && NP == 4) ? DRT_BACKWARD_MIN_BLOCKS : ((sizeof(R) == 4 && NP == 0) ? DRT_BACKWARD_GEN_MIN_BLOCKS : 1))
+k_backward_seeded(BatchArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ params,
+                  const TapeRec<R>* __restrict__ tape, const uint32_t* __restrict__ nv,
+                  double* __restrict__ gpart, double* __restrict__ grad, typename Q4<R>::T* lacc, int n_rows, int row_stride)
+{
+    typedef typename Q4<R>::T R4;
+    constexpr bool SMALL = NP > 0;
+    __shared__ SceneLds<R> lds;
+    __shared__ double acc_d[NP > 0 ? 1 : DRT_LDS_PARAMS * 3];
+    R (*acc)[DRT_BLOCK] = reinterpret_cast<R(*)[DRT_BLOCK]>(acc_d);
+    __shared__ double red[DRT_BLOCK / DRT_WAVE][DRT_FAST_PARAMS * 3];
+    GradAcc<R, NP> ga;
+    ga.init(acc);
+    stage_scene(lds, sc, params);
+
+    const size_t N = a.n_paths;
+    const R inv_p_rr = (R)(1.0 / (1.0 - a.absorb));
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t base = blockIdx.x * blockDim.x; base < a.n_paths; base += stride) {
+        const bool valid = base + threadIdx.x < a.n_paths;
+        const uint32_t i = valid ? base + threadIdx.x : a.n_paths - 1;
+        const int K = valid ? (int)nv[i] : 0;
+        constexpr int CH = GradAcc<R, NP>::kWave ? DRT_TAPE_CHUNK_WAVE : DRT_TAPE_CHUNK;
+        TapeRec<R> first[CH];
+#pragma unroll
+        for (int j = 0; j < CH; ++j)
+            if (j < a.depth_cap)
+                first[j] = tape[(size_t)j * N + i];
+        V3<R> L0 = mk<R>(R(0), R(0), R(0));
+        // (a lane beyond the batch walks no vertices and reads no seed: the word it would read is the last path's, which that path's own lane overwrites)
+        const V3<R> seed = valid ? path_seed<R, true>(a, nullptr, i, lacc) : L0;
+        if (K > 0 || GradAcc<R, NP>::kWave)
+            L0 = backward_path<R, SMALL>(a, lds, params, tape, N, i, K, seed, inv_p_rr, ga, acc, grad, first);
+        if (valid) {
             R4 o;
             o.x = L0.x; o.y = L0.y; o.z = L0.z; o.w = R(0);
             lacc[i] = o;

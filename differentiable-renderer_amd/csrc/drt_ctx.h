@@ -126,6 +126,12 @@ struct drt_hip_ctx {
     std::vector<hipModule_t> jit_modules;
     std::string user_header;              // the scene's caller-defined shape kinds as the header hiprtc compiles them from (drt_prog.h); empty: none
     std::string jit_error;                // why the last specialisation failed (the kind-sorted program renders instead)
+    // the caller's per-sample loss (drt_hip_set_sample_loss; drt_loss.h): its generated header -- the default, the squared error, has one
+    // too --, its values, and what a drt_hip_render_sample_loss call in progress tells the shard's render
+    std::string loss_header, loss_name;   // (the name: for messages, sanitised)
+    double loss_values[DRT_MAX_LOSS_VALUES] = {0, 0, 0, 0};
+    bool sample_loss_render = false;      // set around render_common by drt_hip_render_sample_loss: render_impl copies it into its Shard, where the plan and the routes read it
+    DevBuf loss_part, loss_out;           // the value's partial sums, per batch and block (tape route) or wave (k_path); the shard's sum (one double)
     double jit_ms = 0;                    // compile + load time spent by this context
     int n_params = 0, n_shapes = 0;   // n_params: as the device sees them (user parameters + internal constants)
     int n_user_params = 0;            // what the caller uploaded and gets gradients for

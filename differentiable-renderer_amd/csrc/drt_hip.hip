@@ -10,12 +10,14 @@
 //   drt_kernels.h      K1-K5 of the queue wavefront + what all kernels share (RNG, camera, analytic closest hit, BxDF sampler)
 //   drt_walk.h         K2 on triangles: the BVH walk
 //   drt_backward.h     K6 / K7: the tape's reverse sweep, gradient accumulators, the fixed-order reduction
+//   drt_loss.h         the caller's per-sample loss on the tape route: seeds in place, the loss's value
 //   drt_chain.h        the unbiased operator's adjoint rounds on the queue wavefront
 //   drt_path.h         k_path / k_path_unbiased: the whole path in one launch (analytic scenes)
 //   drt_path_mesh.h    k_path_mesh: the same with the BVH walk inside (small frames of mesh scenes)
 #include "drt_kernels.h"
 #include "drt_walk.h"
 #include "drt_backward.h"
+#include "drt_loss.h"
 #include "drt_chain.h"
 #include "drt_path.h"
 #include "drt_path_mesh.h"
@@ -133,7 +135,7 @@ void drt_hip_destroy(drt_hip_ctx* ctx)
     DevBuf* bufs[] = {&ctx->hist_ovf[0], &ctx->hist_ovf[1], &ctx->mesh_ovf[0], &ctx->mesh_ovf[1], &ctx->fpart2, &ctx->gpart2, &ctx->counts2, &ctx->fpart, &ctx->gpix, &ctx->cand[0], &ctx->cand[1], &ctx->cand_a[0], &ctx->cand_a[1], &ctx->cand_b[0], &ctx->cand_b[1], &ctx->cand_count[0], &ctx->cand_count[1], &ctx->ray_a[0], &ctx->ray_a[1], &ctx->ray_a[2], &ctx->ray_b[0], &ctx->ray_b[1], &ctx->ray_b[2], &ctx->ray_id[0], &ctx->ray_id[1], &ctx->ray_id[2], &ctx->hit, &ctx->hit2, &ctx->hit3, &ctx->lacc, &ctx->gpath, &ctx->gfilm, &ctx->gimg_out, &ctx->tape, &ctx->nv,
                       &ctx->ch_cva, &ctx->ch_cvb, &ctx->ch_cvh, &ctx->ch_nxa, &ctx->ch_nxb, &ctx->ch_nxh, &ctx->ch_g,
                       &ctx->ch_w, &ctx->ch_ids, &ctx->ch_ndraw, &ctx->ch_dbase, &ctx->counts, &ctx->film, &ctx->gpart, &ctx->adjoint, &ctx->tangent,
-                      &ctx->neq_part, &ctx->neq_out, &ctx->neq_in, &ctx->neq_jac, &ctx->neq_rgb};
+                      &ctx->neq_part, &ctx->neq_out, &ctx->neq_in, &ctx->neq_jac, &ctx->neq_rgb, &ctx->loss_part, &ctx->loss_out};
     for (DevBuf* b : bufs)
         release(*b);
     for (int i = 0; i < DRT_HIP_FRAMES_IN_FLIGHT; ++i) {
@@ -909,6 +911,108 @@ int drt_hip_render_param_sets_cross(drt_hip_ctx* ctx, const drt_camera_desc* cam
 {
     return render_sets_common(ctx, sets_cross, cam, rp, n_sets, param_sets, nullptr, target_rgb, out_images, nullptr, false, out_loss, nullptr, nullptr,
                               nullptr, stats, nullptr, nullptr, out_bias, out_variance);
+}
+
+// ---- the per-sample loss from the caller's own source (drt_loss.h) ---------------------------------------------------
+// "drt_sample_loss.h" as hiprtc sees it: the one function, the caller's text its body -- and nothing else of the caller's: the header, and
+// with it the compile cache's key, is the source alone.  The loss's name is for messages, reduced to letters, digits and [ _.-].
+static std::string sample_loss_header(const char* src)
+{
+    return std::string("template <typename R>\n"
+                       "__device__ inline void sample_loss(const R* q, V3<R> L, V3<R> t, R& value, V3<R>& grad)\n"
+                       "{\n") + src + "\n}\n";
+}
+static std::string sample_loss_name(const char* name)
+{
+    std::string clean;
+    for (const char* c = name ? name : ""; *c && clean.size() < 64; ++c)
+        clean += (isalnum((unsigned char)*c) || *c == '_' || *c == '.' || *c == '-' || *c == ' ') ? *c : '_';
+    return clean;
+}
+// the squared error, DRT_RENDER_LOSS_L2's seed 2 (L - t) with its value
+static const char* const sample_loss_l2_src = "    const V3<R> d = L - t;\n    value = dot(d, d);\n    grad = mk<R>(R(2) * d.x, R(2) * d.y, R(2) * d.z);";
+
+int drt_hip_set_sample_loss(drt_hip_ctx* ctx, const drt_sample_loss_desc* loss)
+{
+    if (!ctx)
+        return DRT_ERR_INVALID;
+    if (!ctx->members.empty())
+        return fail(ctx, DRT_ERR_UNSUPPORTED, "set_sample_loss: no sample loss on a group context");
+    if (loss && !loss->loss_src)
+        return fail(ctx, DRT_ERR_INVALID, "set_sample_loss: a sample loss needs its source (loss_src)");
+    for (int k = 0; loss && k < DRT_MAX_LOSS_VALUES; ++k)
+        if (!std::isfinite(loss->values[k]))
+            return fail(ctx, DRT_ERR_INVALID, "set_sample_loss: the sample loss holds a value that is not finite");
+    ctx->loss_header = loss ? sample_loss_header(loss->loss_src) : std::string();
+    ctx->loss_name = loss ? sample_loss_name(loss->name) : std::string();
+    for (int k = 0; k < DRT_MAX_LOSS_VALUES; ++k)
+        ctx->loss_values[k] = loss ? loss->values[k] : 0.0;
+    return DRT_OK;
+}
+
+int drt_hip_render_sample_loss(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_params* rp, const float* target_rgb,
+                               float* out_rgb, double* out_param_grad, double* out_loss, drt_hip_stats* stats)
+{
+    if (!ctx)
+        return DRT_ERR_INVALID;
+    if (!ctx->members.empty())
+        return fail(ctx, DRT_ERR_UNSUPPORTED, "sample loss: not on a group context (render the shards on plain contexts and add their gradients and losses)");
+    if (!ctx->has_scene)
+        return fail(ctx, DRT_ERR_NO_SCENE, "render before upload_scene");
+    if (!cam || !rp || cam->width <= 0 || cam->height <= 0)
+        return fail(ctx, DRT_ERR_INVALID, "sample loss: bad camera or render parameters");
+    if (!target_rgb)
+        return fail(ctx, DRT_ERR_INVALID, "sample loss: NULL target_rgb");
+    if (!out_rgb && !out_param_grad && !out_loss)
+        return fail(ctx, DRT_ERR_INVALID, "sample loss: nothing to return (out_rgb, out_param_grad and out_loss are all NULL)");
+    if (rp->flags & (DRT_RENDER_UNBIASED | DRT_RENDER_ALLREDUCE | DRT_RENDER_ALLREDUCE_ASYNC))
+        return fail(ctx, DRT_ERR_INVALID, "sample loss: not with DRT_RENDER_UNBIASED or _ALLREDUCE* (the biased operator, one context; the shards' gradients and losses add)");
+    for (int i = 0; i < DRT_HIP_FRAMES_IN_FLIGHT; ++i)
+        if (ctx->in_flight[i])
+            return fail(ctx, DRT_ERR_INVALID, "sample loss: asynchronous frames are in flight -- drt_hip_wait for them first");
+    const bool dev_out = (rp->flags & DRT_RENDER_DEVICE_OUT) != 0;
+    if (!dev_out) {
+        const size_t n = (size_t)cam->width * (size_t)cam->height * 3;
+        for (size_t i = 0; i < n; ++i)
+            if (!std::isfinite(target_rgb[i]))
+                return fail(ctx, DRT_ERR_INVALID, "sample loss: the target image holds a value that is not finite");
+    }
+    if (ctx->jit_mode <= 0)
+        return fail(ctx, DRT_ERR_UNSUPPORTED, "sample loss: the loss is compiled at run time and this context may not compile (drt_hip_set_specialisation / DRT_HIP_JIT)");
+    if (ctx->loss_header.empty()) {     // (the default: its header is made once)
+        ctx->loss_header = sample_loss_header(sample_loss_l2_src);
+        ctx->loss_name = "squared error";
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    // the shard's loss (a shard without rows: zero), and behind it a place for the gradients nobody asked for
+    const size_t grad_bytes = (size_t)(ctx->n_user_params > 0 ? ctx->n_user_params : 1) * 3 * sizeof(double);
+    int rc;
+    if ((rc = ensure(ctx, ctx->loss_out, sizeof(double) + grad_bytes)) != DRT_OK) return rc;
+    HIPCHK(ctx, hipMemsetAsync(ctx->loss_out.p, 0, sizeof(double), ctx->stream));
+    std::vector<double> grad_sink;
+    double* grad_out = out_param_grad;
+    if (!grad_out) {
+        if (dev_out)
+            grad_out = (double*)ctx->loss_out.p + 1;
+        else {
+            grad_sink.resize(grad_bytes / sizeof(double));
+            grad_out = grad_sink.data();
+        }
+    }
+    drt_render_params r = *rp;
+    r.flags |= DRT_RENDER_BACKWARD | DRT_RENDER_LOSS_L2;      // (the target travels as DRT_RENDER_LOSS_L2's does; the seed is the context's loss's)
+    ctx->sample_loss_render = true;
+    rc = render_common(ctx, cam, &r, target_rgb, out_rgb, grad_out, stats, -1, nullptr);
+    ctx->sample_loss_render = false;
+    if (rc != DRT_OK)
+        return rc;
+    if (out_loss) {
+        if (dev_out)
+            HIPCHK(ctx, hipMemcpyAsync(out_loss, ctx->loss_out.p, sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+        else
+            HIPCHK(ctx, hipMemcpy(out_loss, ctx->loss_out.p, sizeof(double), hipMemcpyDeviceToHost));     // (the render has waited for the stream)
+    }
+    return DRT_OK;
 }
 
 // ---- asynchronous host-buffer renders ---------------------------------------------------------------

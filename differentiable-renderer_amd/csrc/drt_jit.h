@@ -38,8 +38,9 @@ struct Code {
 
 // the hiprtc work itself (no lock held; ~0.3-0.7 s of one host core)
 // (user_header: the scene's caller-defined shape kinds as "drt_user_shapes.h" -- drt_prog.h includes it under DRT_USER_SHAPES --,
-//  empty: none)
-inline void build(const std::string& arch, const std::string& name_expr, const std::string& user_header, Code& c)
+//  empty: none.  loss_header: the caller's per-sample loss as "drt_sample_loss.h" -- drt_loss.h includes it under DRT_SAMPLE_LOSS --, empty:
+//  none; k_sample_seed, which needs nothing of the path kernels, is compiled from drt_loss.h alone)
+inline void build(const std::string& arch, const std::string& name_expr, const std::string& user_header, Code& c, const std::string& loss_header = std::string())
 {
     const auto t0 = std::chrono::steady_clock::now();
     hiprtcProgram prog = nullptr;
@@ -49,8 +50,13 @@ inline void build(const std::string& arch, const std::string& name_expr, const s
         srcs.push_back(user_header.c_str());
         names.push_back("drt_user_shapes.h");
     }
-    hiprtcResult r = hiprtcCreateProgram(&prog, user_header.empty() ? "#include \"drt_path.h\"\n" : "#define DRT_USER_SHAPES 1\n#include \"drt_path.h\"\n",
-                                         "drt_jit.hip", (int)srcs.size(), srcs.data(), names.data());
+    if (!loss_header.empty()) {
+        srcs.push_back(loss_header.c_str());
+        names.push_back("drt_sample_loss.h");
+    }
+    const std::string root = std::string(user_header.empty() ? "" : "#define DRT_USER_SHAPES 1\n") + (loss_header.empty() ? "" : "#define DRT_SAMPLE_LOSS 1\n") +
+                             (name_expr.compare(0, 13, "k_sample_seed") == 0 ? "#include \"drt_loss.h\"\n" : "#include \"drt_path.h\"\n");
+    hiprtcResult r = hiprtcCreateProgram(&prog, root.c_str(), "drt_jit.hip", (int)srcs.size(), srcs.data(), names.data());
     if (r != HIPRTC_SUCCESS) {
         c.log = std::string("hiprtcCreateProgram: ") + hiprtcGetErrorString(r);
         return;
@@ -90,10 +96,11 @@ inline void build(const std::string& arch, const std::string& name_expr, const s
 // build() behind a catch-all: nothing may leave a compile as an exception -- it would leave the cache entry "in progress" for
 // ever (every later compile() of that key waits on the condition variable) and cross the C ABI.  A failed allocation is a
 // failed compile.
-inline void build_guarded(const std::string& arch, const std::string& name_expr, const std::string& user_header, Code& c) noexcept
+inline void build_guarded(const std::string& arch, const std::string& name_expr, const std::string& user_header, Code& c,
+                          const std::string& loss_header = std::string()) noexcept
 {
     try {
-        build(arch, name_expr, user_header, c);
+        build(arch, name_expr, user_header, c, loss_header);
     } catch (...) {
         c.ok = false;
         try {
@@ -147,23 +154,30 @@ inline State& state() { static State s; return s; }
 // compile the instantiation `name_expr` of a kernel template of drt_path.h for `arch` and WAIT for it (thread-safe: the
 // members of a group context launch from threads of their own; a compile already running in the background is joined)
 // (the cache key carries the caller-defined kinds' source: two scenes with the same signature and other shape code are two kernels)
-inline std::string cache_key(const std::string& arch, const std::string& name_expr, const std::string& user_header)
+// (... and the per-sample loss's source -- never its values, which are a kernel argument)
+inline std::string cache_key(const std::string& arch, const std::string& name_expr, const std::string& user_header,
+                             const std::string& loss_header = std::string())
 {
     std::string key = arch + "|" + name_expr;
-    if (!user_header.empty()) {
+    const auto fold = [&key](const char* tag, const std::string& text) {
+        if (text.empty())
+            return;
         unsigned long long h = 1469598103934665603ull;        // FNV-1a
-        for (unsigned char ch : user_header) { h ^= ch; h *= 1099511628211ull; }
+        for (unsigned char ch : text) { h ^= ch; h *= 1099511628211ull; }
         char buf[40];
-        snprintf(buf, sizeof buf, "|user:%016llx:%zu", h, user_header.size());
+        snprintf(buf, sizeof buf, "|%s:%016llx:%zu", tag, h, text.size());
         key += buf;
-    }
+    };
+    fold("user", user_header);
+    fold("loss", loss_header);
     return key;
 }
 
-inline EntryPtr compile(const std::string& arch, const std::string& name_expr, const std::string& user_header = std::string())
+inline EntryPtr compile(const std::string& arch, const std::string& name_expr, const std::string& user_header = std::string(),
+                        const std::string& loss_header = std::string())
 {
     State& st = state();
-    const std::string key = cache_key(arch, name_expr, user_header);
+    const std::string key = cache_key(arch, name_expr, user_header, loss_header);
     std::unique_lock<std::mutex> lock(st.m);
     auto it = st.cache.find(key);
     if (it != st.cache.end()) {
@@ -176,7 +190,7 @@ inline EntryPtr compile(const std::string& arch, const std::string& name_expr, c
     st.cache[key] = e;
     st.order.push_back(key);
     lock.unlock();
-    build_guarded(arch, name_expr, user_header, e->code);
+    build_guarded(arch, name_expr, user_header, e->code, loss_header);
     lock.lock();
     e->done = true;
     st.cv.notify_all();

@@ -35,6 +35,11 @@
 #pragma once
 
 #include "drt_kernels.h"
+#ifdef DRT_SAMPLE_LOSS
+// the caller's per-sample loss (drt_hip_render_sample_loss): sample_loss<R> and its values; in this build only, the LOSS instantiation's two
+// seeds call it, and k_path takes the values and a place for its waves' sums of the samples' values behind its arguments
+#include "drt_loss.h"
+#endif
 
 #define DRT_DRAW_TABLE (3 * DRT_MAX_DEPTH + 8)     // camera 2 (+1), then per vertex theta, phi and the next depth's roulette
 
@@ -1054,7 +1059,11 @@ struct PathRoles {
 // in the same order: the sums keep their bits.
 template <typename R, int NP, int NC, bool LOSS = false, typename SL = PathSceneLds<R>, int ROLES = 0>
 __device__ inline void add_emission(const SL& lds, const TangentLds<R>& tl, const R* __restrict__ params, uint32_t eid, R inv_pk,
-                                    V3<R> T, V3<R> g, V3<R>& L, Tangents<R, NP, NC>& tg)
+                                    V3<R> T, V3<R> g, V3<R>& L, Tangents<R, NP, NC>& tg
+#ifdef DRT_SAMPLE_LOSS
+                                    , const R* loss_q = nullptr
+#endif
+                                    )
 {
     if constexpr (NP == DRT_NP_SETS) {
         // K parameter sets: the forward-only form's L = L + T (e inv_pk), once per set on the set's own emission, T and L
@@ -1110,8 +1119,17 @@ __device__ inline void add_emission(const SL& lds, const TangentLds<R>& tl, cons
         } else
         if constexpr (NP == DRT_NP_ANY) {
             // any number of parameters: the light's own row, then every vertex of the path's history adds to its colour's row
+#ifdef DRT_SAMPLE_LOSS
+            if (LOSS) {
+                R value_;
+                V3<R> seed_ = mk<R>(R(0), R(0), R(0));
+                sample_loss<R>(loss_q, L, g, value_, seed_);
+                g = seed_;
+            }
+#else
             if (LOSS)
                 g = mk<R>(R(2) * (L.x - g.x), R(2) * (L.y - g.y), R(2) * (L.z - g.z));
+#endif
             const V3<R> gE = g * E;
             const uint32_t ebits = pid_unpack(tg.gl->invc[eid < DRT_PATH_LDS_PARAMS ? eid : 0][3]);
             if ((ebits & 0xFFFFu) != DRT_SLOT_NONE && eid < DRT_PATH_LDS_PARAMS)
@@ -1127,8 +1145,17 @@ __device__ inline void add_emission(const SL& lds, const TangentLds<R>& tl, cons
         if constexpr (NP > 0) {
             if (NC > 0)
                 asm volatile("" ::: "memory");    // (keeps the reads of `tl` below where they are: see there)
+#ifdef DRT_SAMPLE_LOSS
+            if (LOSS) {
+                R value_;
+                V3<R> seed_ = mk<R>(R(0), R(0), R(0));
+                sample_loss<R>(loss_q, L, g, value_, seed_);
+                g = seed_;
+            }
+#else
             if (LOSS)
                 g = mk<R>(R(2) * (L.x - g.x), R(2) * (L.y - g.y), R(2) * (L.z - g.z));
+#endif
             const V3<R> gE = g * E, gT = g * Tr * inv_pk;
 #pragma unroll
             for (int p = 0; p < NP; ++p) {
@@ -1531,13 +1558,24 @@ template <typename R, bool SPEC, int NP, int NCR, typename SG, bool REGEN = fals
 __global__ void __launch_bounds__(DRT_BLOCK, (path_min_blocks<sizeof(R), SPEC, NP, SG::n, REGEN, NCR>()))
 k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ params, const float* __restrict__ adjoint,
        double* __restrict__ gpart, double* __restrict__ fpart, uint32_t* __restrict__ counts,
-       unsigned long long* __restrict__ total, double* __restrict__ gimg_part)
+       unsigned long long* __restrict__ total, double* __restrict__ gimg_part
+#ifdef DRT_SAMPLE_LOSS
+       , LossValues loss_lv, double* __restrict__ loss_part     // loss_part[wave of the grid]: the sum of the values of the wave's samples
+#endif
+       )
 {
     if (total && blockIdx.x == 0 && threadIdx.x < 8)
         total[threadIdx.x] = 0;                           // (the finishing kernel behind this launch adds into them)
     typedef typename Q4<R>::T R4;
     typedef typename Q2<R>::T R2;
     constexpr int NC = DRT_NC_OF(NCR), ROLES = DRT_ROLES_OF(NCR);
+#ifdef DRT_SAMPLE_LOSS
+    R loss_q[DRT_MAX_LOSS_VALUES];
+#pragma unroll
+    for (int k = 0; k < DRT_MAX_LOSS_VALUES; ++k)
+        loss_q[k] = (R)loss_lv.q[k];
+    double loss_sum = 0.0;                                // this lane's sum of value_s over the samples it finished
+#endif
     constexpr bool JAC = DRT_JACOBIAN_OF(NCR) && NP > 0 && !REGEN;   // the Jacobian form: every row of the lane's column leaves per pixel
     __shared__ PathSceneLds<R> lds;
     __shared__ double s_red[REGEN ? 1 : DRT_BLOCK / DRT_WAVE][DRT_FAST_PARAMS * 3];   // (REGEN: the block's gradient partials reuse the pixel sums' table)
@@ -1691,8 +1729,21 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
         }
         if (wave_any(end_ids != DRT_ID_NONE)) {
             if (end_ids != DRT_ID_NONE)
-                add_emission<R, NP, NC, LOSS, PathSceneLds<R>, ROLES>(lds, tl, params, end_ids, end_inv_pk, T, g, L, tg);
+                add_emission<R, NP, NC, LOSS, PathSceneLds<R>, ROLES>(lds, tl, params, end_ids, end_inv_pk, T, g, L, tg
+#ifdef DRT_SAMPLE_LOSS
+                                                                      , loss_q
+#endif
+                                                                      );
         }
+#ifdef DRT_SAMPLE_LOSS
+        if (LOSS && have) {
+            // L is final: no shape of the scenes this form takes both scatters and emits.  A path that reached no light counts with L = 0.
+            R value_ = R(0);
+            V3<R> seed_ = mk<R>(R(0), R(0), R(0));
+            sample_loss<R>(loss_q, L, g, value_, seed_);
+            loss_sum += (double)value_;
+        }
+#endif
         if constexpr (ALONG) {
 #pragma unroll
             for (int k = 0; k < NC; ++k) {
@@ -1825,8 +1876,21 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
                     if (on_light) {
                         if (seed_px)
                             gp3 = mk<R>((R)seed_px[0], (R)seed_px[1], (R)seed_px[2]);
-                        add_emission<R, NP, NC, LOSS>(lds, tl, params, light, inv_pk, T, gp3, L, tg);
+                        add_emission<R, NP, NC, LOSS>(lds, tl, params, light, inv_pk, T, gp3, L, tg
+#ifdef DRT_SAMPLE_LOSS
+                                                      , loss_q
+#endif
+                                                      );
                     }
+#ifdef DRT_SAMPLE_LOSS
+                    if (LOSS && seed_px) {
+                        // the lane's path ends here, L is final (L = 0 where it reached no light): its value, against its pixel's target
+                        R value_ = R(0);
+                        V3<R> seed_ = mk<R>(R(0), R(0), R(0));
+                        sample_loss<R>(loss_q, L, mk<R>((R)seed_px[0], (R)seed_px[1], (R)seed_px[2]), value_, seed_);
+                        loss_sum += (double)value_;
+                    }
+#endif
                     if (L.x != R(0) || L.y != R(0) || L.z != R(0)) {
                         atomicAdd(&s_film[0][pix], (double)L.x);
                         atomicAdd(&s_film[REGEN ? 1 : 0][pix], (double)L.y);
@@ -1918,6 +1982,16 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
             counts[w] = n_seg;
             counts[(size_t)a.n_groups * a.n_ranges + w] = n_capped;
         }
+#ifdef DRT_SAMPLE_LOSS
+        if (LOSS && loss_part) {
+            // the wave's sum, lanes added in a fixed order (every lane of the wave is here: `range` is the wave's)
+            double v = loss_sum;
+            for (int o2 = DRT_WAVE / 2; o2 > 0; o2 >>= 1)
+                v += __shfl_down(v, o2);
+            if (lane == 0)
+                loss_part[w] = v;
+        }
+#endif
     }
     if constexpr (GEN || SGRAD)
         gen_finish(s_gen, a, gpart);

@@ -76,14 +76,18 @@ int queue_length(drt_hip_ctx* ctx, const uint32_t* counts_row, uint32_t n_region
 // on this context's device (drt_jit.h).  nullptr: it could not be made (ctx->jit_error says why; the caller renders with
 // the kind-sorted program, same results).  wait = false: also nullptr while the compiler is still at it on its own thread --
 // nothing is recorded then, the next frame asks again.
-hipFunction_t jit_function(drt_hip_ctx* ctx, const std::string& name_expr, bool wait = true)
+// (loss_header, the caller's per-sample loss: the LOSS instantiation with sample_loss in its seeds -- another kernel under the same name
+//  expression, kept by the source's hash; always waited for)
+hipFunction_t jit_function(drt_hip_ctx* ctx, const std::string& name_expr, bool wait = true, const std::string& loss_header = std::string())
 {
-    auto it = ctx->jit_fn.find(name_expr);
+    const std::string fn_key = loss_header.empty() ? name_expr : drt_jit::cache_key(std::string(), name_expr, std::string(), loss_header);
+    auto it = ctx->jit_fn.find(fn_key);
     if (it != ctx->jit_fn.end())
         return it->second;
     const auto t0 = std::chrono::steady_clock::now();
     hipFunction_t fn = nullptr;
-    const drt_jit::EntryPtr pe = wait ? drt_jit::compile(ctx->arch, name_expr, ctx->user_header) : drt_jit::poll(ctx->arch, name_expr, ctx->user_header);
+    const drt_jit::EntryPtr pe = (wait || !loss_header.empty()) ? drt_jit::compile(ctx->arch, name_expr, ctx->user_header, loss_header)
+                                                                : drt_jit::poll(ctx->arch, name_expr, ctx->user_header);
     if (!pe)
         return nullptr;
     const drt_jit::Code& c = pe->code;
@@ -104,9 +108,44 @@ hipFunction_t jit_function(drt_hip_ctx* ctx, const std::string& name_expr, bool 
     }
     if (!fn && tuning().jit_verbose)
         fprintf(stderr, "[drt_hip] specialisation failed: %s\n", ctx->jit_error.c_str());
-    ctx->jit_fn[name_expr] = fn;
+    if (fn || loss_header.empty())      // (a loss that did not compile is not remembered here: the process-wide cache keeps its log)
+        ctx->jit_fn[fn_key] = fn;
     // (what the kernel cost: the compile, on whichever thread it ran, and this context's load)
     ctx->jit_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() + (wait ? 0. : c.ms);
+    return fn;
+}
+// k_sample_seed<R> (drt_loss.h) for the context's per-sample loss, compiled -- and waited for -- by hiprtc, loaded on this context's device.
+// By the loss's SOURCE: the same source with other values is the same kernel.  nullptr: it did not compile (ctx->jit_error holds the
+// compiler's log); a failure is not remembered here, the process-wide cache keeps the log.
+hipFunction_t loss_seed_function(drt_hip_ctx* ctx, bool f64)
+{
+    const std::string name_expr = f64 ? "k_sample_seed<double>" : "k_sample_seed<float>";
+    const std::string key = drt_jit::cache_key(std::string(), name_expr, std::string(), ctx->loss_header);
+    auto it = ctx->jit_fn.find(key);
+    if (it != ctx->jit_fn.end())
+        return it->second;
+    const auto t0 = std::chrono::steady_clock::now();
+    const drt_jit::EntryPtr pe = drt_jit::compile(ctx->arch, name_expr, std::string(), ctx->loss_header);
+    const drt_jit::Code& c = pe->code;
+    hipFunction_t fn = nullptr;
+    if (!c.ok) {
+        ctx->jit_error = c.log;
+    } else {
+        hipModule_t mod = nullptr;
+        hipError_t e = hipModuleLoadData(&mod, c.bin.data());
+        if (e == hipSuccess) {
+            ctx->jit_modules.push_back(mod);
+            e = hipModuleGetFunction(&fn, mod, c.lowered.c_str());
+        }
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            fn = nullptr;
+            ctx->jit_error = std::string("loading ") + name_expr + ": " + hipGetErrorString(e);
+        }
+    }
+    if (fn)
+        ctx->jit_fn[key] = fn;
+    ctx->jit_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return fn;
 }
 // A compile costs ~0.5 s of host time and buys ~25 % of the kind-sorted program's time: it pays once the scene has rendered
@@ -219,6 +258,9 @@ struct Shard {
     bool unbiased;                  // the reference's unbiased integration operator (integrate.hpp:39-52)
     bool loss_l2;                   // DRT_RENDER_LOSS_L2: every sample seeded with 2 (L_s - target_pixel), d_adjoint is the target
     hipFunction_t loss_kernel = nullptr;   // ... on k_path: the LOSS instantiation, made at run time only (drt_jit.h)
+    bool sample_loss = false;       // drt_hip_render_sample_loss: loss_l2's plumbing, the seed and the value from the context's loss (drt_loss.h)
+    hipFunction_t loss_seed_fn = nullptr;  // ... on the tape route: k_sample_seed<R>
+    uint32_t loss_parts = 0;        // ... partial sums of the loss's value the batches have written into ctx->loss_part so far
     bool can_fuse;                  // K2 folded into K3: analytic scenes, unless DRT_RENDER_UNFUSED asks for the textbook pipeline
     bool use_path;                  // the whole path in one launch (k_path)
     PathForm path;                  // ... its instantiation
@@ -541,6 +583,17 @@ void shard_plan(Shard<R>& s)
         //  copy of it need not give the first one's bits -- drt_path.h: DRT_LEAN_PEEL_LAST)
         f.lights = DRT_LEAN_LIGHTS != 0 && ctx->user_header.empty() ? ctx->pure_lights : 0ull;
     }
+    if (s.use_path && s.sample_loss) {
+        // The caller's own per-sample loss takes LOSS_L2's plan: the LOSS instantiation, in the build whose seeds call sample_loss and whose
+        // lanes sum its value -- in f64 wherever in f32, always waited for -- where no shape both scatters and emits and every path has a
+        // vertex (a path the roulette ends before its first one never reaches the lanes' end-of-path code); else the tape route --
+        // k_radiance, k_sample_seed, k_backward_seeded.  A loss that does not compile is reported from there.
+        s.use_path = false;
+        if (!ctx->emissive_bxdf && rp->min_bounces > 0) {
+            s.loss_kernel = jit_function(ctx, path_kernel_name(ctx, f), true, ctx->loss_header);
+            s.use_path = s.loss_kernel != nullptr;
+        }
+    } else
     if (s.use_path && s.loss_l2) {
         // The per-sample seed 2 (L_s - target) needs the path's radiance before its gradients.  k_path has it where the path
         // ends on a light -- the only emissive vertex of a path unless some shape carries a BxDF AND an emitter -- in the LOSS
@@ -631,7 +684,7 @@ void shard_plan(Shard<R>& s)
     const int tail_bounces = tail_bounces_now();
     s.tail_nb = s.shade_tail && (tail_bounces > 1 || (tail_bounces == 0 && s.unbiased)) ? 2 : 1;
     s.tail_ring = s.tail_nb > 1 ? 3 : 2;
-    s.overlap_ok = ctx->overlap_next && s.use_path && !s.timing && !s.pixel_sums() && !s.sets && ctx->path_stream[0] && ctx->ev_copied[0];
+    s.overlap_ok = ctx->overlap_next && s.use_path && !s.timing && !s.pixel_sums() && !s.sets && !s.sample_loss && ctx->path_stream[0] && ctx->ev_copied[0];
     const bool odd = s.overlap_ok && (ctx->slot & 1);
     s.fpart_buf = odd ? &ctx->fpart2 : &ctx->fpart;
     s.gpart_buf = odd ? &ctx->gpart2 : &ctx->gpart;
@@ -953,7 +1006,11 @@ int path_batch(Shard<R>& s)
     if (sets_grad)
         pa.gimg_row = (uint32_t)s.n_dirs;      // (no gradient image in this form: the word carries the caller's set count)
     // the arguments of each operator: k_path_unbiased has no gradient image, k_path_mesh the BVH and its traversal stacks too
-    void* args_path[] = {&pa, &d_scene, &d_params, &d_adjoint, &gpart, &fpart, &counts, &ptotal, &gpix};
+    // (the caller's per-sample loss: its values and the place of this batch's per-wave sums, behind the kernel's own arguments)
+    LossValues loss_lv;
+    memcpy(loss_lv.q, ctx->loss_values, sizeof loss_lv.q);
+    double* loss_part = s.sample_loss ? (double*)ctx->loss_part.p + s.loss_parts : (double*)nullptr;
+    void* args_path[] = {&pa, &d_scene, &d_params, &d_adjoint, &gpart, &fpart, &counts, &ptotal, &gpix, &loss_lv, &loss_part};
     void* args_unb[] = {&pa, &d_scene, &d_params, &d_adjoint, &gpart, &fpart, &counts, &ptotal};
     void* args_mesh[] = {&pa, &d_scene, &d_params, &d_adjoint, &s.bvh, &ovf, &ovf_stride, &gpart, &fpart, &counts, &ptotal, &gpix};
     void** args = form.op == PathOp::unbiased ? args_unb : (form.op == PathOp::mesh ? args_mesh : args_path);
@@ -968,6 +1025,8 @@ int path_batch(Shard<R>& s)
         HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_path[lane2], 0));
     }
     st->launches[DRT_K_PATH]++;
+    if (s.sample_loss)
+        s.loss_parts += (uint32_t)n_waves;
     st->path_bytes += (s.film ? (uint64_t)pa.n_ranges * a.Pb * 3 * sizeof(double) : 0) +
                       (backward ? (uint64_t)gpath * (uint64_t)g_stride * sizeof(double) : 0) + (s.mesh_path ? 3 : 2) * n_waves * sizeof(uint32_t);
     if (s.path_finish) {
@@ -1326,6 +1385,35 @@ int queue_batch(Shard<R>& s)
         hipLaunchKernelGGL(k_film<R>, dim3(grid_for(ctx, a.Pb)), dim3(DRT_BLOCK), 0, ctx->stream, a, (const R4*)ctx->gpath.p, s.gfilm);
     } else if (s.unbiased && D > 0) {
         if ((rc = adjoint_rounds<R>(s)) != DRT_OK) return rc;
+    } else if (s.backward && s.sample_loss) {
+        // the caller's per-sample loss: the radiance walk, the seeds in place of the radiances (+ the batch's partial sums of the loss's
+        // value, behind the earlier batches'), then the gradient walk, which puts the radiances back for k_film
+        if (D > 0)
+            DRT_TIMED(s, DRT_K_BACKWARD,
+                      hipLaunchKernelGGL(k_radiance<R>, dim3(gp), dim3(DRT_BLOCK), 0, ctx->stream, a, s.d_scene, s.d_params, s.tape, s.nv, s.lacc));
+        else
+            HIPCHK(ctx, hipMemsetAsync(s.lacc, 0, (size_t)a.n_paths * sizeof(R4), ctx->stream));
+        {
+            BatchArgs ba = a;
+            LossValues lv;
+            memcpy(lv.q, ctx->loss_values, sizeof lv.q);
+            const float* target = s.d_adjoint;
+            R4* lacc = s.lacc;
+            double* part = (double*)ctx->loss_part.p + s.loss_parts;
+            void* args[] = {&ba, &lv, &target, &lacc, &part};
+            DRT_TIMED(s, DRT_K_BACKWARD, HIPCHK(ctx, hipModuleLaunchKernel(s.loss_seed_fn, (unsigned)gp, 1, 1, DRT_BLOCK, 1, 1, 0, ctx->stream, args, nullptr)));
+            s.loss_parts += (uint32_t)gp;
+        }
+        if (D > 0) {
+            DRT_TIMED(s, DRT_K_BACKWARD, with_int<4, 8, 0>(np_width(ctx->n_params, 0), [&](auto np) {
+                hipLaunchKernelGGL((k_backward_seeded<R, np>), dim3(gp), dim3(DRT_BLOCK), 0, ctx->stream, a, s.d_scene, s.d_params, s.tape, s.nv,
+                                   s.gpart, s.grad, s.lacc, s.g_rows, s.g_stride);
+            }));
+            DRT_TIMED(s, DRT_K_GRADREDUCE,
+                      hipLaunchKernelGGL(k_gradreduce, dim3(s.g_rows > 0 ? s.g_rows : 1), dim3(DRT_BLOCK), 0, ctx->stream, s.gpart, gp,
+                                         s.g_rows, s.grad, s.g_stride));
+            st->units[DRT_K_GRADREDUCE] += (uint64_t)gp;
+        }
     } else if (s.backward && D > 0) {
         // DRT_RENDER_LOSS_L2: the seed of a path is 2 (L_path - target): the radiance walk first, then the gradient walk
         if (s.loss_l2)
@@ -1383,6 +1471,7 @@ int render_impl(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_p
         s.d_adjoint = tangent->sets->d_adjoints;
     s.d_params = forward || directions || param_sets ? (const R*)tangent->d_params
                                                      : (sizeof(R) == 4 ? (const R*)ctx->d_params_f : (const R*)ctx->d_params_d);
+    s.sample_loss = ctx->sample_loss_render;
     shard_plan(s);
     if (forward && s.D > 0 && (!s.use_path || s.mesh_path))
         return fail(ctx, DRT_ERR_UNSUPPORTED, s.mesh_path || ctx->has_mesh
@@ -1438,6 +1527,20 @@ int render_impl(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_p
             HIPCHK(ctx, hipMemcpyAsync(ctx->adjoint.p, ctx->adj_src_host, ctx->adj_bytes, hipMemcpyHostToDevice, ctx->stream));
     }
     if ((rc = shard_buffers(s)) != DRT_OK) return rc;
+    if (s.sample_loss) {
+        // the tape route: k_sample_seed for the loss's source, waited for, before anything of the frame is enqueued.  A partial sum of the
+        // loss's value per batch and block of k_sample_seed's grid, or per batch and wave of k_path's
+        if (!s.use_path) {
+            s.loss_seed_fn = loss_seed_function(ctx, sizeof(R) == 8);
+            if (!s.loss_seed_fn)
+                return fail(ctx, DRT_ERR_UNSUPPORTED, ("sample loss '" + ctx->loss_name + "': the loss's source did not compile: " + ctx->jit_error).c_str());
+        }
+        const uint64_t n_batches = (uint64_t)((n_local_pixels + s.Pb - 1) / s.Pb) * (uint64_t)(((uint32_t)s.spp + s.Sb - 1) / s.Sb);
+        const uint64_t per_batch = s.use_path ? (uint64_t)s.path_waves : (uint64_t)grid_for(ctx, s.N);
+        if (n_batches * per_batch > 0x7FFFFFFFull)
+            return fail(ctx, DRT_ERR_INVALID, "sample loss: too many batches (batch_paths)");
+        if ((rc = ensure(ctx, ctx->loss_part, (size_t)(n_batches * per_batch) * sizeof(double))) != DRT_OK) return rc;
+    }
     *n_count_words = s.cw;
     if (!s.path_finish) {
         HIPCHK(ctx, hipMemsetAsync(s.totals, 0, DRT_TOTAL_WORDS * sizeof(unsigned long long), ctx->stream));
@@ -1474,6 +1577,9 @@ int render_impl(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_p
             }
         }
     }
+    if (s.sample_loss)   // (timed in the reduction's slot)
+        DRT_TIMED(s, DRT_K_GRADREDUCE,
+                  hipLaunchKernelGGL(k_loss_finish, dim3(1), dim3(DRT_BLOCK), 0, ctx->stream, (const double*)ctx->loss_part.p, s.loss_parts, (double*)ctx->loss_out.p));
     st->batches = batch;
     st->paths = s.total_paths;
     if (film && d_out_rgb && !s.path_finished)

@@ -1269,6 +1269,63 @@ inline SetsGrad<T> render_param_sets_grad(const Scene<T>& scene, const Camera<T>
     return r;
 }
 
+// ---- the per-sample loss from the caller's own source (drt_hip_set_sample_loss / drt_hip_render_sample_loss) ------------------------
+// The reference's loop -- radiance = tracer.trace(...); loss = loss_func(radiance); loss.backward() (README.md:93-98) -- with loss_func the
+// caller's: `src` is the body of
+//     template <typename R> void sample_loss(const R* q, V3<R> L, V3<R> t, R& value, V3<R>& grad)
+// (L one camera sample's radiance, t its pixel of `target`, value = loss_func(L), grad = d value / d L; helpers: csrc/drt_device.h),
+// `values` its constants q[0 .. DRT_MAX_LOSS_VALUES) -- data: the same source with other values compiles nothing.  An empty `src`: the
+// squared error.
+struct SampleLoss {
+    std::string name, src;
+    std::vector<double> values;
+};
+struct SampleLossResult {
+    Stats stats;
+    double loss = 0.0;              // the sum of the samples' values over the frame
+};
+// One render under `loss`: backward is implied, the gradients are ADDED to the handles' .grad() as render does with Options::backward, `img`
+// (may be nullptr) gets the plain mean image.  One device.  Options::backward is the call's own and is ignored; unbiased and sample_loss_l2
+// make no sense here and throw, like more values than the ABI takes and a missing target, before a device is asked for.
+template <typename T>
+inline SampleLossResult render_sample_loss(const Scene<T>& scene, const Camera<T>& cam, const Pathtracer<T>& tracer, std::size_t spp,
+                                           const Vector<T, 3>* target, Vector<T, 3>* img, const SampleLoss& loss, const Options& opt = Options())
+{
+    const char* who = "drt::hip::render_sample_loss";
+    if (opt.unbiased || opt.sample_loss_l2)
+        throw std::runtime_error(std::string(who) + ": the sample loss is the call's own -- no unbiased operator, no sample_loss_l2 beside it");
+    detail::one_device(who, opt);
+    if (!target)
+        throw std::runtime_error(std::string(who) + ": a sample loss needs a target image");
+    if (loss.values.size() > (std::size_t)DRT_MAX_LOSS_VALUES)
+        throw std::runtime_error(std::string(who) + ": a sample loss takes at most DRT_MAX_LOSS_VALUES (4) values");
+    FlatScene<T> flat = flatten(scene);
+    const drt_camera_desc cd = describe(cam);
+    const std::size_t npix = cam.width() * cam.height();
+    const std::vector<float> tgt = detail::to_floats(target, npix);
+    const drt_render_params rp = detail::render_params(tracer.absorb(), tracer.min_bounces(), spp, opt, detail::f64_flag(opt));
+    drt_sample_loss_desc desc{};
+    desc.name = loss.name.c_str();
+    desc.loss_src = loss.src.c_str();
+    for (std::size_t k = 0; k < loss.values.size(); ++k)
+        desc.values[k] = loss.values[k];
+    std::vector<double> grads(flat.requires_grad.size() * 3, 0.0);
+    std::vector<float> frame(img ? npix * 3 : 0, 0.f);
+    drt_hip_stats st{};
+    SampleLossResult r;
+    {
+        detail::Session s = detail::Session::on_first_device(opt, flat);
+        s.ctx.check(drt_hip_set_sample_loss(s.ctx.get(), loss.src.empty() ? nullptr : &desc), "drt_hip_set_sample_loss");
+        const int rc = drt_hip_render_sample_loss(s.ctx.get(), &cd, &rp, tgt.data(), img ? frame.data() : nullptr, grads.data(), &r.loss, &st);
+        (void)drt_hip_set_sample_loss(s.ctx.get(), nullptr);   // (a pooled context goes back with the default loss)
+        s.ctx.check(rc, "drt_hip_render_sample_loss");
+    }
+    detail::from_buffer(frame.data(), npix, img);
+    detail::accumulate_grads(flat.handles, flat.requires_grad, grads.data());
+    r.stats = detail::to_stats(st);
+    return r;
+}
+
 // A Scene<Dual<U>> for the device: the real parts as the scene, the dual parts of its PARAMETERS as the direction (n_params x 3).
 // A nonzero dual part anywhere the device does not differentiate -- a plane's normal, a sphere's centre, a mesh's vertices --
 // throws and names the field: a seed is never dropped silently.  (Offsets, radii, exponents and the tracer's absorb are plain

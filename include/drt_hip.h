@@ -616,6 +616,48 @@ int drt_hip_render_param_sets_cross(drt_hip_ctx* ctx, const drt_camera_desc* cam
                                     float* out_images /* n_sets x H x W x 3, may be NULL */, double* out_loss /* n_sets x 3 */,
                                     double* out_bias /* n_sets x 3, may be NULL */, float* out_variance /* n_sets x H x W x 3, may be NULL */,
                                     drt_hip_stats* stats);
+/* ---- the per-sample loss from the caller's own source, with the loss's value.  The reference's loop is
+ *     auto radiance = tracer.trace(scene, orig, dir);  auto loss = loss_func(radiance);  loss.backward();       (README.md:93-98)
+ * with loss_func the caller's code; DRT_RENDER_LOSS_L2 is the one loss_func the library carries, and returns no value.  Here the loss is the
+ * BODY of
+ *     template <typename R> void sample_loss(const R* q, V3<R> L, V3<R> t, R& value, V3<R>& grad) { <loss_src> }
+ * L = the radiance of ONE camera sample, t = its pixel of the target image, value = loss_func(L), grad = d value / d L; R is float, or double
+ * under DRT_RENDER_F64.  Helpers: those of csrc/drt_device.h (mk, dot, sqrt_r, div_r, abs_r, max_r, ...), as for caller-defined shapes.  q[0 ..
+ * DRT_MAX_LOSS_VALUES) are the caller's constants (a Huber delta, an epsilon): DATA -- they reach the kernel as an argument, the compile
+ * cache goes by the source alone, and setting the same source with other values compiles nothing.  NULL: the squared error, value =
+ * |L - t|^2, grad = 2 (L - t).  The source is compiled by hiprtc at the first render that uses it (~0.3-0.5 s, waited for, cached per
+ * process).  `name` appears in messages only, reduced to letters, digits and [ _.-]; it never reaches the generated header.
+ * drt_hip_render with DRT_RENDER_LOSS_L2 ignores the context's loss.
+ * DRT_ERR_INVALID: NULL loss_src, a value that is not finite.  DRT_ERR_UNSUPPORTED: a group context. */
+#define DRT_MAX_LOSS_VALUES 4
+typedef struct drt_sample_loss_desc {
+    const char* name;                       /* for messages */
+    const char* loss_src;                   /* the body of sample_loss */
+    double values[DRT_MAX_LOSS_VALUES];     /* q[0..3] */
+} drt_sample_loss_desc;
+int drt_hip_set_sample_loss(drt_hip_ctx* ctx, const drt_sample_loss_desc* loss /* NULL: squared error */);
+/* One render under the context's per-sample loss; backward is implied.
+ *   out_param_grad[p][c] = sum over this shard's samples of grad_s[c] dL_s[c] / dtheta[p][c] -- with the default loss what
+ *                          drt_hip_render(DRT_RENDER_BACKWARD | DRT_RENDER_LOSS_L2, adjoint_rgb = target_rgb) returns
+ *   out_loss             = sum over this shard's samples of value_s; a path that reaches no light counts with L = 0
+ *   out_rgb              the plain mean image
+ * requires_grad, DRT_RENDER_F64, _TIMING, _SYNC, _DEVICE_OUT (target_rgb and the three outputs are then device pointers), shards and
+ * batch_paths as in drt_hip_render; the shards' and batches' gradients and losses add.  The route is DRT_RENDER_LOSS_L2's plan, in f64 wherever
+ * in f32: ONE k_path launch -- its LOSS instantiation compiled with the loss, whose two seeds call sample_loss and whose lanes add the
+ * samples' values into fp64 sums of their own, one partial per wave -- in analytic scenes where no shape both scatters and emits (lockstep
+ * and regenerating forms, columns and the general form); else the tape route (meshes, an emitting scatterer, bounces_per_launch >= 1,
+ * min_bounces == 0): k_radiance writes every path's radiance, k_sample_seed -- the kernel compiled from the loss -- turns it into the path's
+ * seed in place and adds its value into fp64 partials per block, k_backward_seeded walks the gradients.  k_loss_finish adds the partials in
+ * a fixed order.  No atomics on the loss: two identical calls return identical bits.  It never falls back to another loss.
+ * DRT_ERR_INVALID (the message says "sample loss"): NULL target_rgb; neither out_param_grad nor out_loss nor out_rgb; a target value that is
+ * not finite (host buffers only: with DRT_RENDER_DEVICE_OUT the target is device memory the library does not read on the host, and a value
+ * that is not finite there comes back as a loss and gradients that are not finite); asynchronous frames in flight; DRT_RENDER_UNBIASED; DRT_RENDER_ALLREDUCE*.  DRT_ERR_UNSUPPORTED ("sample
+ * loss"): a group context; a context that may not compile (drt_hip_set_specialisation(DRT_SPECIALISE_NEVER / _GENERIC)); a body hiprtc
+ * rejects -- drt_hip_last_error holds the compiler's log.  The context stays usable after each. */
+int drt_hip_render_sample_loss(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_params* rp,
+                               const float* target_rgb /* H x W x 3 */, float* out_rgb /* may be NULL */,
+                               double* out_param_grad /* n_params x 3, may be NULL */,
+                               double* out_loss /* 1 double, may be NULL */, drt_hip_stats* stats);
 /* stream the context launches on (a hipStream_t), for event timing / interop */
 void* drt_hip_stream(drt_hip_ctx* ctx);
 int drt_hip_synchronize(drt_hip_ctx* ctx);
