@@ -1540,6 +1540,99 @@ constexpr int path_min_blocks()
     return (RB == 8 && NP <= 4 && !REGEN && !SPEC) ? DRT_F64_MIN_BLOCKS : 1;
 }
 
+// ---- what the entry points share: k_path, k_path_sets_cross, k_path_lean, k_path_unbiased (below) and k_path_mesh (drt_path_mesh.h) ----
+// Prologue and epilogue of a launch whose wave is (pixel group, sample range), written once.  None of these functions knows its caller.
+// The kernels keep their own __shared__ declarations, in their own order -- the order of the LDS symbols is part of a kernel's code -- and
+// hand them in by reference.
+
+// the finishing kernel behind a path launch adds into total[0..7]: the launch's first block zeroes them
+__device__ inline void zero_totals(unsigned long long* __restrict__ total)
+{
+    if (total && blockIdx.x == 0 && threadIdx.x < 8)
+        total[threadIdx.x] = 0;
+}
+
+// where a lane stands in the launch: its wave's pixel group and sample range
+struct PathLane {
+    uint32_t lane, w;          // lane of the wave; wave of the grid = group + n_groups * range
+    uint32_t range, lp;        // the wave's sample range; batch-local pixel of this lane
+    bool have;                 // the range and the pixel exist
+    uint32_t s_begin, s_end;   // the range's samples
+};
+__device__ inline PathLane path_lane(const PathArgs& a)
+{
+    PathLane pl;
+    pl.lane = threadIdx.x & (DRT_WAVE - 1);
+    pl.w = grid_wave();
+    pl.range = pl.w / a.n_groups;
+    const uint32_t group = pl.w - pl.range * a.n_groups;
+    pl.lp = group * DRT_WAVE + pl.lane;
+    pl.have = pl.range < a.n_ranges && pl.lp < a.Pb;
+    pl.s_begin = pl.range * a.spr;
+    pl.s_end = pl.s_begin + a.spr < a.Sb ? pl.s_begin + a.spr : a.Sb;
+    return pl;
+}
+// f32: the pixel's corner in double ONCE per lane; a sample then only adds its jitter (camera.hpp:53-58 in the form
+// cs = cs0 + u1 (2 aspect tan / W)): the sample's position inside the pixel is exact to ~2e-5 of a pixel and the
+// direction to 1 ulp of f32 -- the resolution the ray has anyway once it is stored in f32
+template <typename R>
+__device__ inline CameraLane<R> camera_lane(const PathArgs& a, uint32_t px, uint32_t py)
+{
+    CameraLane<R> cl;
+    cl.cs0 = (R)((2. * (double)px * a.inv_W - 1.) * a.aspect * a.tan_half);
+    cl.ct0 = (R)((2. * (double)py * a.inv_H - 1.) * a.tan_half);
+    return cl;
+}
+
+// Does the kernel take the camera's and the roulette's constants as the floats among its arguments (see path_camera)?  The lockstep f32
+// kernels of few compiled-in shapes; not the kernels whose lanes stand at their own depths (REGEN; k_path_mesh), whose scalar registers are taken.
+template <typename R, typename SG, bool REGEN = false>
+constexpr bool path_args_f32()
+{
+    return sizeof(R) == 4 && !REGEN && DRT_CAMERA_ARGS_F32 != 0 && SG::n <= DRT_LEAN_MAX_SHAPES;
+}
+// three rows of a [range][row][pixel] array of Pb pixels a row, from the lane's place in the first of them: coalesced over the wave
+template <typename T>
+__device__ inline void store_rows3(double* f, uint32_t Pb, T x, T y, T z)
+{
+    f[0] = (double)x; f[(size_t)Pb] = (double)y; f[(size_t)Pb * 2] = (double)z;
+}
+// the wave's segments and the paths a user cap cut short, for the finishing kernel: counts[row][wave of the grid]
+__device__ inline void store_counts(const PathArgs& a, const PathLane& pl, uint32_t* __restrict__ counts, uint32_t n_seg, uint32_t n_capped)
+{
+    if (pl.lane == 0) {
+        counts[pl.w] = n_seg;
+        counts[(size_t)a.n_groups * a.n_ranges + pl.w] = n_capped;
+    }
+}
+
+// Block reduction of the gradient columns in fp64: thread -> wave (shuffles) -> block (LDS: `red`, the kernel's own), fixed order; thread r
+// writes row r of the block's sums to its row of gpart (rows >= 3 NP: 0) and the finishing kernel adds the blocks.  The columns are the ones
+// the lanes keep in LDS (Tangents::acc: row r of this thread at acc[r * DRT_BLOCK]).  (Always inline: at eight parameters the compiler
+// otherwise leaves it a call, with a stack pointer, in k_path_mesh.)
+template <int NP, typename R>
+__device__ __forceinline__ void block_grad_sums(const R* acc, double (*red)[DRT_FAST_PARAMS * 3], double* gpart, uint32_t lane)
+{
+    const int wv = threadIdx.x / DRT_WAVE;
+#pragma unroll
+    for (int r = 0; r < NP * 3; ++r) {
+        double v = (double)acc[r * DRT_BLOCK];
+#pragma unroll
+        for (int o2 = DRT_WAVE / 2; o2 > 0; o2 >>= 1)
+            v += __shfl_down(v, o2);
+        if (lane == 0)
+            red[wv][r] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < DRT_FAST_PARAMS * 3) {
+        double v = 0;
+        if ((int)threadIdx.x < NP * 3)
+            for (int ww = 0; ww < DRT_BLOCK / DRT_WAVE; ++ww)
+                v += red[ww][threadIdx.x];
+        gpart[(size_t)blockIdx.x * (DRT_FAST_PARAMS * 3) + threadIdx.x] = v;
+    }
+}
+
 // ---- the kernel -----------------------------------------------------------------------------------
 // The bounce loop is written WITHOUT per-lane branches: every lane of the wave executes every bounce of the sample --
 // a lane whose path has ended keeps tracing a stale ray whose results are never used (`live` guards every
@@ -1564,8 +1657,7 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
 #endif
        )
 {
-    if (total && blockIdx.x == 0 && threadIdx.x < 8)
-        total[threadIdx.x] = 0;                           // (the finishing kernel behind this launch adds into them)
+    zero_totals(total);
     typedef typename Q4<R>::T R4;
     typedef typename Q2<R>::T R2;
     constexpr int NC = DRT_NC_OF(NCR), ROLES = DRT_ROLES_OF(NCR);
@@ -1602,13 +1694,7 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
     if (NC > 0 && !GEN && !DIR && !SETS && !ALONG && !SGRAD)
         stage_tangents(s_tl, lds);
 
-    const uint32_t lane = threadIdx.x & (DRT_WAVE - 1);
-    const uint32_t w = grid_wave();                       // wave of the grid = group + n_groups * range
-    const uint32_t range = w / a.n_groups, group = w - range * a.n_groups;
-    const uint32_t lp = group * DRT_WAVE + lane;          // batch-local pixel of this lane
-    const bool have = range < a.n_ranges && lp < a.Pb;
-    const uint32_t s_begin = range * a.spr;
-    const uint32_t s_end = s_begin + a.spr < a.Sb ? s_begin + a.spr : a.Sb;
+    const PathLane pl = path_lane(a);
 
     Tangents<R, NP, NC> tg;
     __shared__ R s_acc[NP > 0 ? NP * 3 : 1][DRT_BLOCK];
@@ -1649,8 +1735,8 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
 
     uint32_t gpix = 0, px = 0, py = 0;
     V3<R> g = mk<R>(R(1), R(1), R(1));                    // render.cpp:80: radiance.backward(Vec3(1))
-    if (have) {
-        gpix = path_global_pixel(a, a.p0 + lp);
+    if (pl.have) {
+        gpix = path_global_pixel(a, a.p0 + pl.lp);
         py = gpix / (uint32_t)a.W;
         px = gpix - py * (uint32_t)a.W;
         if (NP != 0 && adjoint)
@@ -1665,13 +1751,8 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
                 }
         }
     }
-    // f32: the pixel's corner in double ONCE per lane; a sample then only adds its jitter (camera.hpp:53-58 in the form
-    // cs = cs0 + u1 (2 aspect tan / W)): the sample's position inside the pixel is exact to ~2e-5 of a pixel and the
-    // direction to 1 ulp of f32 -- the resolution the ray has anyway once it is stored in f32
-    CameraLane<R> cl;
-    cl.cs0 = (R)((2. * (double)px * a.inv_W - 1.) * a.aspect * a.tan_half);
-    cl.ct0 = (R)((2. * (double)py * a.inv_H - 1.) * a.tan_half);
-    constexpr bool ARGS_F32 = sizeof(R) == 4 && !REGEN && DRT_CAMERA_ARGS_F32 != 0 && SG::n <= DRT_LEAN_MAX_SHAPES;   // (see path_camera)
+    const CameraLane<R> cl = camera_lane<R>(a, px, py);
+    constexpr bool ARGS_F32 = path_args_f32<R, SG, REGEN>();
     const R pk_rr = ARGS_F32 ? (R)a.p_rr_f : (R)a.p_rr, inv_p_rr = ARGS_F32 ? (R)a.inv_p_rr_f : (R)a.inv_p_rr;
     ProgRecs<SG::n, R> recs;
     // (the kind-sorted program's 1.3 KB only where it runs: with the kinds compiled in they are what stands between the
@@ -1691,13 +1772,13 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
         __syncthreads();
     }
 
-    if (range < a.n_ranges && !REGEN) {
-    for (uint32_t sl = s_begin; sl < s_end; ++sl) {
+    if (pl.range < a.n_ranges && !REGEN) {
+    for (uint32_t sl = pl.s_begin; sl < pl.s_end; ++sl) {
         R4 ra;
         R2 rb;
         const uint32_t key = path_camera<R, ARGS_F32>(a, cl, gpix, px, py, sl, ra, rb);
         // pathtracer.hpp:128 at depth 0
-        bool live = have && a.depth_cap > 0 && !(a.min_bounces <= 0 && rng_draw(a.rng_stream, key, 2) < a.rr_threshold);
+        bool live = pl.have && a.depth_cap > 0 && !(a.min_bounces <= 0 && rng_draw(a.rng_stream, key, 2) < a.rr_threshold);
         V3<R> T = mk<R>(R(1), R(1), R(1)), L = mk<R>(R(0), R(0), R(0));
         uint32_t end_ids = DRT_ID_NONE;                   // emission parameter of the light the path ended on
         R end_inv_pk = R(1);
@@ -1736,7 +1817,7 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
                                                                       );
         }
 #ifdef DRT_SAMPLE_LOSS
-        if (LOSS && have) {
+        if (LOSS && pl.have) {
             // L is final: no shape of the scenes this form takes both scatters and emits.  A path that reached no light counts with L = 0.
             R value_ = R(0);
             V3<R> seed_ = mk<R>(R(0), R(0), R(0));
@@ -1800,13 +1881,13 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
             s_ih[REGEN ? n : 0] = drt_rng_index_hash(a.rng_stream, n);
         s_pcs[threadIdx.x] = cl.cs0;
         s_pct[threadIdx.x] = cl.ct0;
-        s_pgpix[threadIdx.x] = have ? gpix : 0xFFFFFFFFu;       // (no such pixel: its samples are skipped)
+        s_pgpix[threadIdx.x] = pl.have ? gpix : 0xFFFFFFFFu;       // (no such pixel: its samples are skipped)
         s_film[0][threadIdx.x] = 0.0; s_film[REGEN ? 1 : 0][threadIdx.x] = 0.0; s_film[REGEN ? 2 : 0][threadIdx.x] = 0.0;
         __syncthreads();
     }
-    if (range < a.n_ranges && REGEN) {
+    if (pl.range < a.n_ranges && REGEN) {
         const uint32_t wbase = threadIdx.x & ~(uint32_t)(DRT_WAVE - 1);      // this wave's first slot in the pixel tables
-        const uint32_t n_items = DRT_WAVE * (s_end - s_begin);
+        const uint32_t n_items = DRT_WAVE * (pl.s_end - pl.s_begin);
         uint32_t n_next = 0;                              // wave-uniform: the next camera sample of the wave to hand out
         uint32_t key = 0, pix = wbase, pgpix = 0;         // RNG key, pixel slot and pixel of the lane's current path
         int kk = 0;                                       // depth of the lane's current path
@@ -1834,7 +1915,7 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
                         CameraLane<R> pc;
                         pc.cs0 = s_pcs[pix];
                         pc.ct0 = s_pct[pix];
-                        key = path_camera<R>(a, pc, gp, s_begin + (n >> 6), ra, rb);
+                        key = path_camera<R>(a, pc, gp, pl.s_begin + (n >> 6), ra, rb);
                         kk = 0;
                         live = a.depth_cap > 0 && !(a.min_bounces <= 0 && rng_draw(a.rng_stream, key, 2) < a.rr_threshold);
                         T = mk<R>(R(1), R(1), R(1));
@@ -1920,32 +2001,32 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
     if constexpr (SETS) {                                 // the plain image's sums: the last set (the context's own parameters)
         fx = tk[NC - 1][0]; fy = tk[NC - 1][1]; fz = tk[NC - 1][2];
     }
-    if (range < a.n_ranges) {
-        if (fpart && have) {
-            double* f = fpart + ((size_t)range * 3) * a.Pb + lp;       // [range][channel][pixel]: coalesced
+    if (pl.range < a.n_ranges) {
+        if (fpart && pl.have) {
+            double* f = fpart + ((size_t)pl.range * 3) * a.Pb + pl.lp;       // [range][channel][pixel]: coalesced
             f[0] = fx; f[(size_t)a.Pb] = fy; f[(size_t)a.Pb * 2] = fz;
         }
-        if constexpr (GEN && NC == 1) if (gimg_part && have) {
+        if constexpr (GEN && NC == 1) if (gimg_part && pl.have) {
             // gradient image, general form: the lane's own adds to the row of the image's parameter
-            double* f = gimg_part + ((size_t)range * 3) * a.Pb + lp;
+            double* f = gimg_part + ((size_t)pl.range * 3) * a.Pb + pl.lp;
             f[0] = (double)tg.gsum.x; f[(size_t)a.Pb] = (double)tg.gsum.y; f[(size_t)a.Pb * 2] = (double)tg.gsum.z;
         }
-        if constexpr ((DIRS && !CROSS) || SETS || ALONG) if (gimg_part && have) {
+        if constexpr ((DIRS && !CROSS) || SETS || ALONG) if (gimg_part && pl.have) {
             // K directions / K sets: the pixel's sums in the Jacobian form's layout, [range][3 k + ch][pixel], for those the caller gave; with a
             // direction per set, 6 rows a set: [range][6 k + ch][pixel] the radiance sums, [range][6 k + 3 + ch][pixel] the derivative sums
             const uint32_t nd = a.dirs_out() < (uint32_t)NC ? a.dirs_out() : (uint32_t)NC;
-            double* f = gimg_part + ((size_t)range * (size_t)(nd * (3u * TK))) * a.Pb + lp;
+            double* f = gimg_part + ((size_t)pl.range * (size_t)(nd * (3u * TK))) * a.Pb + pl.lp;
 #pragma unroll
             for (int k = 0; k < TK * NC; ++k)
                 if ((uint32_t)(k / TK) < nd) {
                     f[(size_t)(k * 3) * a.Pb] = tk[k][0]; f[(size_t)(k * 3 + 1) * a.Pb] = tk[k][1]; f[(size_t)(k * 3 + 2) * a.Pb] = tk[k][2];
                 }
         }
-        if constexpr (CROSS) if (gimg_part && have) {
+        if constexpr (CROSS) if (gimg_part && pl.have) {
             // K directions with cross moments: [range][row][pixel] with 6 nd + 3 rows -- 3 nd derivative sums, 3 nd of Q, 3 of S2 --, for the
             // directions the caller gave
             const uint32_t nd = a.dirs_out() < (uint32_t)NC ? a.dirs_out() : (uint32_t)NC;
-            double* f = gimg_part + ((size_t)range * (size_t)(nd * 6u + 3u)) * a.Pb + lp;
+            double* f = gimg_part + ((size_t)pl.range * (size_t)(nd * 6u + 3u)) * a.Pb + pl.lp;
             double* fq = f + (size_t)(nd * 3u) * a.Pb;
 #pragma unroll
             for (int k = 0; k < NC; ++k)
@@ -1956,40 +2037,37 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
             double* fs = f + (size_t)(nd * 6u) * a.Pb;
             fs[0] = tg.S2[0]; fs[(size_t)a.Pb] = tg.S2[1]; fs[(size_t)a.Pb * 2] = tg.S2[2];
         }
-        if constexpr (DIR && !DIRS) if (gimg_part && have) {
+        if constexpr (DIR && !DIRS) if (gimg_part && pl.have) {
             // forward mode: the pixel's derivative sums leave where a gradient image's do -- same layout, same finishing kernels
-            double* f = gimg_part + ((size_t)range * 3) * a.Pb + lp;
+            double* f = gimg_part + ((size_t)pl.range * 3) * a.Pb + pl.lp;
             f[0] = tx; f[(size_t)a.Pb] = ty; f[(size_t)a.Pb * 2] = tz;
         }
-        if constexpr (JAC) if (gimg_part && have) {
+        if constexpr (JAC) if (gimg_part && pl.have) {
             // the Jacobian: all rows of the lane's column -- the pixel's gradient sums of every parameter over the samples of this range,
             // [range][row][pixel] with the scene's own 3 x n_params rows (k_normal_eq reads them back, coalesced like the radiance partials)
             const int rows = (lds.sc.n_params < NP ? lds.sc.n_params : NP) * 3;
-            double* f = gimg_part + ((size_t)range * (size_t)rows) * a.Pb + lp;
+            double* f = gimg_part + ((size_t)pl.range * (size_t)rows) * a.Pb + pl.lp;
 #pragma unroll
             for (int r = 0; r < NP * 3; ++r)
                 if (r < rows)
                     f[(size_t)r * a.Pb] = (double)tg.acc[r * DRT_BLOCK];
         }
-        if constexpr (NP > 0 && !JAC) if (gimg_part && have) {
+        if constexpr (NP > 0 && !JAC) if (gimg_part && pl.have) {
             // gradient image (README.md:142-145): a lane IS a pixel, its gradient sum of one parameter over the samples of
             // this range is that pixel's share -- same layout as the radiance partials, same finishing kernels
             const V3<R> v = tg.acc_get(a.gimg_param > 0 && a.gimg_param < NP ? a.gimg_param : 0);
-            double* f = gimg_part + ((size_t)range * 3) * a.Pb + lp;
+            double* f = gimg_part + ((size_t)pl.range * 3) * a.Pb + pl.lp;
             f[0] = (double)v.x; f[(size_t)a.Pb] = (double)v.y; f[(size_t)a.Pb * 2] = (double)v.z;
         }
-        if (lane == 0) {
-            counts[w] = n_seg;
-            counts[(size_t)a.n_groups * a.n_ranges + w] = n_capped;
-        }
+        store_counts(a, pl, counts, n_seg, n_capped);
 #ifdef DRT_SAMPLE_LOSS
         if (LOSS && loss_part) {
             // the wave's sum, lanes added in a fixed order (every lane of the wave is here: `range` is the wave's)
             double v = loss_sum;
             for (int o2 = DRT_WAVE / 2; o2 > 0; o2 >>= 1)
                 v += __shfl_down(v, o2);
-            if (lane == 0)
-                loss_part[w] = v;
+            if (pl.lane == 0)
+                loss_part[pl.w] = v;
         }
 #endif
     }
@@ -1997,20 +2075,19 @@ k_path(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict__ par
         gen_finish(s_gen, a, gpart);
     else
     if constexpr (NP > 0 && !JAC) {
-        // block reduction in fp64: thread -> wave (shuffles) -> block (LDS), fixed order; K7 adds the blocks
-        const int wv = threadIdx.x / DRT_WAVE;
         double (*red)[DRT_FAST_PARAMS * 3] = s_red;
         if (REGEN) {
             __syncthreads();                               // (every thread has read its pixel's sums out of s_film)
             red = reinterpret_cast<double (*)[DRT_FAST_PARAMS * 3]>(&s_film[0][0]);
         }
+        const int wv = threadIdx.x / DRT_WAVE;
 #pragma unroll
         for (int r = 0; r < NP * 3; ++r) {
             double v = (double)tg.acc[r * DRT_BLOCK];
 #pragma unroll
             for (int o2 = DRT_WAVE / 2; o2 > 0; o2 >>= 1)
                 v += __shfl_down(v, o2);
-            if (lane == 0)
+            if (pl.lane == 0)
                 red[wv][r] = v;
         }
         __syncthreads();
@@ -2058,9 +2135,8 @@ k_path_sets_cross(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __res
                   unsigned long long* __restrict__ total, double* __restrict__ gimg_part)
 {
     static_assert(K == 2 || K == 4 || K == 8, "k_path_sets_cross: 2, 4 or 8 sets");
-    (void)adjoint; (void)gpart; (void)fpart;              // (k_path's argument list: one launch site)
-    if (total && blockIdx.x == 0 && threadIdx.x < 8)
-        total[threadIdx.x] = 0;                           // (the finishing kernel behind this launch adds into them)
+    (void)adjoint; (void)gpart; (void)fpart;              // (the path kernels share one argument list and one launch site)
+    zero_totals(total);
     typedef typename Q4<R>::T R4;
     typedef typename Q2<R>::T R2;
     __shared__ PathSceneLds<R> lds;
@@ -2068,13 +2144,7 @@ k_path_sets_cross(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __res
     stage_path_scene(lds, sc, params);
     const TangentLds<R>& tl = s_tl;
 
-    const uint32_t lane = threadIdx.x & (DRT_WAVE - 1);
-    const uint32_t w = grid_wave();                       // wave of the grid = group + n_groups * range
-    const uint32_t range = w / a.n_groups, group = w - range * a.n_groups;
-    const uint32_t lp = group * DRT_WAVE + lane;          // batch-local pixel of this lane
-    const bool have = range < a.n_ranges && lp < a.Pb;
-    const uint32_t s_begin = range * a.spr;
-    const uint32_t s_end = s_begin + a.spr < a.Sb ? s_begin + a.spr : a.Sb;
+    const PathLane pl = path_lane(a);
 
     Tangents<R, DRT_NP_SETS, K> tg;
     path_tables_begin(tg, lds, params);
@@ -2087,16 +2157,14 @@ k_path_sets_cross(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __res
     uint32_t n_seg = 0, n_capped = 0;                     // wave-uniform counters
 
     uint32_t gpix = 0, px = 0, py = 0;
-    const V3<R> g = mk<R>(R(1), R(1), R(1));
-    if (have) {
-        gpix = path_global_pixel(a, a.p0 + lp);
+    const V3<R> g = mk<R>(R(1), R(1), R(1));                    // render.cpp:80: radiance.backward(Vec3(1))
+    if (pl.have) {
+        gpix = path_global_pixel(a, a.p0 + pl.lp);
         py = gpix / (uint32_t)a.W;
         px = gpix - py * (uint32_t)a.W;
     }
-    CameraLane<R> cl;                                     // (k_path: the pixel's corner in double once per lane)
-    cl.cs0 = (R)((2. * (double)px * a.inv_W - 1.) * a.aspect * a.tan_half);
-    cl.ct0 = (R)((2. * (double)py * a.inv_H - 1.) * a.tan_half);
-    constexpr bool ARGS_F32 = sizeof(R) == 4 && DRT_CAMERA_ARGS_F32 != 0 && SG::n <= DRT_LEAN_MAX_SHAPES;   // (see path_camera)
+    const CameraLane<R> cl = camera_lane<R>(a, px, py);
+    constexpr bool ARGS_F32 = path_args_f32<R, SG>();
     const R pk_rr = ARGS_F32 ? (R)a.p_rr_f : (R)a.p_rr, inv_p_rr = ARGS_F32 ? (R)a.inv_p_rr_f : (R)a.inv_p_rr;
     ProgRecs<SG::n, R> recs;
     __shared__ typename PickT<(SG::n == 0), ProgLds, NoLds>::T s_prog;
@@ -2114,14 +2182,14 @@ k_path_sets_cross(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __res
         __syncthreads();
     }
 
-    if (range >= a.n_ranges)
+    if (pl.range >= a.n_ranges)
         return;
-    for (uint32_t sl = s_begin; sl < s_end; ++sl) {
+    for (uint32_t sl = pl.s_begin; sl < pl.s_end; ++sl) {
         R4 ra;
         R2 rb;
         const uint32_t key = path_camera<R, ARGS_F32>(a, cl, gpix, px, py, sl, ra, rb);
         // pathtracer.hpp:128 at depth 0
-        bool live = have && a.depth_cap > 0 && !(a.min_bounces <= 0 && rng_draw(a.rng_stream, key, 2) < a.rr_threshold);
+        bool live = pl.have && a.depth_cap > 0 && !(a.min_bounces <= 0 && rng_draw(a.rng_stream, key, 2) < a.rr_threshold);
         V3<R> T = mk<R>(R(1), R(1), R(1)), L = mk<R>(R(0), R(0), R(0));
         uint32_t end_ids = DRT_ID_NONE;                   // emission parameter of the light the path ended on
         R end_inv_pk = R(1);
@@ -2140,7 +2208,7 @@ k_path_sets_cross(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __res
             uint32_t light;
             path_bounce<R, SPEC, DRT_NP_SETS, K, SG, (DRT_FREEZE_BY_ROW != 0 && sizeof(R) == 4 && !SPEC && SG::n <= DRT_LEAN_MAX_SHAPES)>(a, lds, tl, sc, params, recs, key, pk, inv_pk, n_theta, next_rr, next_cap, live, g,
                                                     ra, rb, T, L, tg, alive, capped, on_light, light, nullptr, next_cap);
-            // (k_path: a light without a BxDF ends the path; its emission is added once per sample, behind the loop)
+            // (a light without a BxDF ends the path; its emission is added once per sample, behind the loop)
             end_ids = on_light ? light : end_ids;
             end_inv_pk = on_light ? inv_pk : end_inv_pk;
             if (next_cap && !a.cap_is_roulette)
@@ -2159,22 +2227,19 @@ k_path_sets_cross(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __res
             s2[k][0] += lx * lx; s2[k][1] += ly * ly; s2[k][2] += lz * lz;
         }
     }
-    if (gimg_part && have) {
+    if (gimg_part && pl.have) {
         // [range][row][pixel] with 6 nd rows -- 3 nd radiance sums, 3 nd of S2 --, for the sets the caller gave
         const uint32_t nd = a.dirs_out() < (uint32_t)K ? a.dirs_out() : (uint32_t)K;
-        double* f = gimg_part + ((size_t)range * (size_t)(nd * 6u)) * a.Pb + lp;
+        double* f = gimg_part + ((size_t)pl.range * (size_t)(nd * 6u)) * a.Pb + pl.lp;
         double* fs = f + (size_t)(nd * 3u) * a.Pb;
 #pragma unroll
         for (int k = 0; k < K; ++k)
             if ((uint32_t)k < nd) {
-                f[(size_t)(k * 3) * a.Pb] = tk[k][0]; f[(size_t)(k * 3 + 1) * a.Pb] = tk[k][1]; f[(size_t)(k * 3 + 2) * a.Pb] = tk[k][2];
-                fs[(size_t)(k * 3) * a.Pb] = s2[k][0]; fs[(size_t)(k * 3 + 1) * a.Pb] = s2[k][1]; fs[(size_t)(k * 3 + 2) * a.Pb] = s2[k][2];
+                store_rows3(f + (size_t)(k * 3) * a.Pb, a.Pb, tk[k][0], tk[k][1], tk[k][2]);
+                store_rows3(fs + (size_t)(k * 3) * a.Pb, a.Pb, s2[k][0], s2[k][1], s2[k][2]);
             }
     }
-    if (lane == 0) {
-        counts[w] = n_seg;
-        counts[(size_t)a.n_groups * a.n_ranges + w] = n_capped;
-    }
+    store_counts(a, pl, counts, n_seg, n_capped);
 }
 
 // ---- k_path_lean: the lockstep f32 column-form k_path with two more facts compiled in --------------------------------------
@@ -2202,9 +2267,8 @@ k_path_lean(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict_
     static_assert(sizeof(R) == 4 && (NP == 0 || NP == 4), "k_path_lean: f32, four parameters in columns or none");
     static_assert(!DRT_JACOBIAN_OF(NCR), "k_path_lean has no Jacobian form");
     static_assert(LIGHTS == 0ull || SG::n > 0, "k_path_lean: the light set belongs to a compiled-in program");
-    (void)gimg_part;                                      // (k_path's argument list: one launch site)
-    if (total && blockIdx.x == 0 && threadIdx.x < 8)
-        total[threadIdx.x] = 0;                           // (the finishing kernel behind this launch adds into them)
+    (void)gimg_part;                                      // (the path kernels share one argument list and one launch site)
+    zero_totals(total);
     typedef typename Q4<R>::T R4;
     typedef typename Q2<R>::T R2;
     constexpr int NC = DRT_NC_OF(NCR), ROLES = DRT_ROLES_OF(NCR);
@@ -2223,13 +2287,7 @@ k_path_lean(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict_
     if constexpr (LEAN_REC)
         stage_lean(s_lean, lds, s_tl);
 
-    const uint32_t lane = threadIdx.x & (DRT_WAVE - 1);
-    const uint32_t w = grid_wave();                       // wave of the grid = group + n_groups * range
-    const uint32_t range = w / a.n_groups, group = w - range * a.n_groups;
-    const uint32_t lp = group * DRT_WAVE + lane;          // batch-local pixel of this lane
-    const bool have = range < a.n_ranges && lp < a.Pb;
-    const uint32_t s_begin = range * a.spr;
-    const uint32_t s_end = s_begin + a.spr < a.Sb ? s_begin + a.spr : a.Sb;
+    const PathLane pl = path_lane(a);
 
     Tangents<R, NP, NC> tg;
     __shared__ R s_acc[NP > 0 ? NP * 3 : 1][DRT_BLOCK];
@@ -2242,17 +2300,15 @@ k_path_lean(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict_
 
     uint32_t gpix = 0, px = 0, py = 0;
     V3<R> g = mk<R>(R(1), R(1), R(1));                    // render.cpp:80: radiance.backward(Vec3(1))
-    if (have) {
-        gpix = path_global_pixel(a, a.p0 + lp);
+    if (pl.have) {
+        gpix = path_global_pixel(a, a.p0 + pl.lp);
         py = gpix / (uint32_t)a.W;
         px = gpix - py * (uint32_t)a.W;
         if (NP != 0 && adjoint)
             g = mk<R>((R)adjoint[(size_t)gpix * 3], (R)adjoint[(size_t)gpix * 3 + 1], (R)adjoint[(size_t)gpix * 3 + 2]);
     }
-    CameraLane<R> cl;                                     // (see k_path)
-    cl.cs0 = (R)((2. * (double)px * a.inv_W - 1.) * a.aspect * a.tan_half);
-    cl.ct0 = (R)((2. * (double)py * a.inv_H - 1.) * a.tan_half);
-    constexpr bool ARGS_F32 = DRT_CAMERA_ARGS_F32 != 0 && SG::n <= DRT_LEAN_MAX_SHAPES;   // (see path_camera)
+    const CameraLane<R> cl = camera_lane<R>(a, px, py);
+    constexpr bool ARGS_F32 = path_args_f32<R, SG>();
     ProgRecs<SG::n, R> recs;
     __shared__ typename PickT<(SG::n == 0), ProgLds, NoLds>::T s_prog;
     recs.lds = reinterpret_cast<const ProgLds*>(&s_prog);
@@ -2269,12 +2325,12 @@ k_path_lean(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict_
         __syncthreads();
     }
 
-    if (range < a.n_ranges) {
-        for (uint32_t sl = s_begin; sl < s_end; ++sl) {
+    if (pl.range < a.n_ranges) {
+        for (uint32_t sl = pl.s_begin; sl < pl.s_end; ++sl) {
             R4 ra;
             R2 rb;
             const uint32_t key = path_camera<R, ARGS_F32>(a, cl, gpix, px, py, sl, ra, rb);
-            bool live = have;                             // (pathtracer.hpp:128 at depth 0: min_bounces = the cap > 0, no roulette there either)
+            bool live = pl.have;                             // (pathtracer.hpp:128 at depth 0: min_bounces = the cap > 0, no roulette there either)
             V3<R> T = mk<R>(R(1), R(1), R(1)), L = mk<R>(R(0), R(0), R(0));
             uint32_t end_ids = DRT_ID_NONE;               // emission parameter of the light the path ended on
             if (NC > 0)
@@ -2327,7 +2383,7 @@ k_path_lean(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict_
                 path_bounce<R, false, NP, NC, SG, BY_ROW, true, true, LIGHTS>(
                     a, lds, tl, sc, params, recs, key, R(1), R(1), n_theta, false, next_cap, live, g, ra, rb, T, L, tg, alive, capped, on_light, light, nullptr, next_cap,
                     nullptr, nullptr, ll);
-                end_ids = on_light ? light : end_ids;     // (its emission: once per sample, below -- see k_path)
+                end_ids = on_light ? light : end_ids;     // (its emission: once per sample, below)
                 live = alive;
             }
             if (wave_any(end_ids != DRT_ID_NONE)) {
@@ -2336,36 +2392,13 @@ k_path_lean(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict_
             }
             fx += (double)L.x; fy += (double)L.y; fz += (double)L.z;
         }
-        if (fpart && have) {
-            double* f = fpart + ((size_t)range * 3) * a.Pb + lp;       // [range][channel][pixel]: coalesced
-            f[0] = fx; f[(size_t)a.Pb] = fy; f[(size_t)a.Pb * 2] = fz;
+        if (fpart && pl.have) {
+            store_rows3(fpart + ((size_t)pl.range * 3) * a.Pb + pl.lp, a.Pb, fx, fy, fz);
         }
-        if (lane == 0) {
-            counts[w] = n_seg;
-            counts[(size_t)a.n_groups * a.n_ranges + w] = 0;           // (no path is cut short by a cap that is the roulette's)
-        }
+        store_counts(a, pl, counts, n_seg, 0u);                        // (no path is cut short by a cap that is the roulette's)
     }
-    if constexpr (NP > 0) {
-        // block reduction in fp64: thread -> wave (shuffles) -> block (LDS), fixed order; K7 adds the blocks
-        const int wv = threadIdx.x / DRT_WAVE;
-#pragma unroll
-        for (int r = 0; r < NP * 3; ++r) {
-            double v = (double)tg.acc[r * DRT_BLOCK];
-#pragma unroll
-            for (int o2 = DRT_WAVE / 2; o2 > 0; o2 >>= 1)
-                v += __shfl_down(v, o2);
-            if (lane == 0)
-                s_red[wv][r] = v;
-        }
-        __syncthreads();
-        if (threadIdx.x < DRT_FAST_PARAMS * 3) {
-            double v = 0;
-            if ((int)threadIdx.x < NP * 3)
-                for (int ww = 0; ww < DRT_BLOCK / DRT_WAVE; ++ww)
-                    v += s_red[ww][threadIdx.x];
-            gpart[(size_t)blockIdx.x * (DRT_FAST_PARAMS * 3) + threadIdx.x] = v;
-        }
-    }
+    if constexpr (NP > 0)
+        block_grad_sums<NP>(tg.acc, s_red, gpart, pl.lane);
 }
 
 // ---- the unbiased integration operator (integrate.hpp:11-24, 39-52; README.md:104-136) in one launch ------------------
@@ -2435,8 +2468,7 @@ k_path_unbiased(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restr
                 double* __restrict__ gpart, double* __restrict__ fpart, uint32_t* __restrict__ counts,
                 unsigned long long* __restrict__ total)
 {
-    if (total && blockIdx.x == 0 && threadIdx.x < 8)
-        total[threadIdx.x] = 0;
+    zero_totals(total);
     typedef typename Q4<R>::T R4;
     typedef typename Q2<R>::T R2;
     __shared__ PathSceneLds<R> lds;
@@ -2453,13 +2485,7 @@ k_path_unbiased(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restr
     if constexpr (GEN)
         gen_begin(s_gen, lds, sc, a, (uint32_t*)nullptr, (uint32_t*)nullptr, gt);
 
-    const uint32_t lane = threadIdx.x & (DRT_WAVE - 1);
-    const uint32_t w = grid_wave();
-    const uint32_t range = w / a.n_groups, group = w - range * a.n_groups;
-    const uint32_t lp = group * DRT_WAVE + lane;
-    const bool have = range < a.n_ranges && lp < a.Pb;
-    const uint32_t s_begin = range * a.spr;
-    const uint32_t s_end = s_begin + a.spr < a.Sb ? s_begin + a.spr : a.Sb;
+    const PathLane pl = path_lane(a);
 
     V3<R> acc[NP > 0 ? NP : 1];
 #pragma unroll
@@ -2468,18 +2494,16 @@ k_path_unbiased(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restr
     double fx = 0, fy = 0, fz = 0;
     uint32_t n_seg = 0, n_capped = 0;
     uint32_t gpix = 0, px = 0, py = 0;
-    V3<R> g0 = mk<R>(R(1), R(1), R(1));                   // render.cpp:80: radiance.backward(Vec3(1))
-    if (have) {
-        gpix = path_global_pixel(a, a.p0 + lp);
+    V3<R> g0 = mk<R>(R(1), R(1), R(1));                    // render.cpp:80: radiance.backward(Vec3(1))
+    if (pl.have) {
+        gpix = path_global_pixel(a, a.p0 + pl.lp);
         py = gpix / (uint32_t)a.W;
         px = gpix - py * (uint32_t)a.W;
         if (adjoint)
             g0 = mk<R>((R)adjoint[(size_t)gpix * 3], (R)adjoint[(size_t)gpix * 3 + 1], (R)adjoint[(size_t)gpix * 3 + 2]);
     }
-    CameraLane<R> cl;
-    cl.cs0 = (R)((2. * (double)px * a.inv_W - 1.) * a.aspect * a.tan_half);
-    cl.ct0 = (R)((2. * (double)py * a.inv_H - 1.) * a.tan_half);
-    constexpr bool ARGS_F32 = sizeof(R) == 4 && DRT_CAMERA_ARGS_F32 != 0 && SG::n <= DRT_LEAN_MAX_SHAPES;   // (see path_camera)
+    const CameraLane<R> cl = camera_lane<R>(a, px, py);
+    constexpr bool ARGS_F32 = path_args_f32<R, SG>();
     const R pk_rr = ARGS_F32 ? (R)a.p_rr_f : (R)a.p_rr, inv_p_rr = ARGS_F32 ? (R)a.inv_p_rr_f : (R)a.inv_p_rr;
     ProgRecs<SG::n, R> recs;
     __shared__ ProgLds s_prog;
@@ -2499,13 +2523,13 @@ k_path_unbiased(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restr
     // is the roulette of depth d drawn at all?  (not behind a user cap: the reference tests the cap first)
     auto rr_drawn = [&](int d) { return d >= a.min_bounces && (d < a.depth_cap || a.cap_draws != 0); };
 
-    if (range < a.n_ranges) {
-        for (uint32_t sl = s_begin; sl < s_end; ++sl) {
+    if (pl.range < a.n_ranges) {
+        for (uint32_t sl = pl.s_begin; sl < pl.s_end; ++sl) {
             R4 ra;
             R2 rb;
             const uint32_t key = path_camera<R, ARGS_F32>(a, cl, gpix, px, py, sl, ra, rb);
             uint32_t nd = 2;                                  // the camera's two draws
-            bool live = have && a.depth_cap > 0;
+            bool live = pl.have && a.depth_cap > 0;
             if (rr_drawn(0)) {                                // pathtracer.hpp:128 at depth 0
                 live = live && !(rng_draw(a.rng_stream, key, nd) < a.rr_threshold);
                 ++nd;
@@ -2516,7 +2540,7 @@ k_path_unbiased(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restr
             unbiased_walk<R, SPEC, SG>(a, lds, tl, sc, params, recs, key, pk_rr, inv_p_rr, live, ra, rb, 0, nd, n_seg, n_capped, L0,
                                               cur, in_chain);
             fx += (double)L0.x; fy += (double)L0.y; fz += (double)L0.z;
-            in_chain = in_chain && have;
+            in_chain = in_chain && pl.have;
             int cdepth = 0;
             V3<R> g = g0;
             while (wave_any(in_chain)) {
@@ -2596,19 +2620,15 @@ k_path_unbiased(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restr
                 }
             }
         }
-        if (fpart && have) {
-            double* f = fpart + ((size_t)range * 3) * a.Pb + lp;
-            f[0] = fx; f[(size_t)a.Pb] = fy; f[(size_t)a.Pb * 2] = fz;
+        if (fpart && pl.have) {
+            store_rows3(fpart + ((size_t)pl.range * 3) * a.Pb + pl.lp, a.Pb, fx, fy, fz);
         }
-        if (lane == 0) {
-            counts[w] = n_seg;
-            counts[(size_t)a.n_groups * a.n_ranges + w] = n_capped;
-        }
+        store_counts(a, pl, counts, n_seg, n_capped);
     }
     if constexpr (GEN)
         gen_finish(s_gen, a, gpart);
     else
-    {   // block reduction in fp64 (as in k_path)
+    {   // block_grad_sums' two stages, written out: the columns come from the lane's registers
         const int wv = threadIdx.x / DRT_WAVE;
 #pragma unroll
         for (int r = 0; r < NP * 3; ++r) {
@@ -2617,7 +2637,7 @@ k_path_unbiased(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restr
 #pragma unroll
             for (int o2 = DRT_WAVE / 2; o2 > 0; o2 >>= 1)
                 v += __shfl_down(v, o2);
-            if (lane == 0)
+            if (pl.lane == 0)
                 s_red[wv][r] = v;
         }
         __syncthreads();

@@ -38,8 +38,7 @@ k_path_mesh(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict_
             double* __restrict__ gpart, double* __restrict__ fpart, uint32_t* __restrict__ counts,
             unsigned long long* __restrict__ total, double* __restrict__ gimg_part)
 {
-    if (total && blockIdx.x == 0 && threadIdx.x < 8)
-        total[threadIdx.x] = 0;                           // (the finishing kernel behind this launch adds into them)
+    zero_totals(total);
     typedef typename Q4<R>::T R4;
     typedef typename Q2<R>::T R2;
     __shared__ PathSceneLds<R> lds;
@@ -65,13 +64,7 @@ k_path_mesh(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict_
     recs.lds = &s_prog;
 
     const uint32_t tid = threadIdx.x, gtid = blockIdx.x * DRT_BLOCK + threadIdx.x;
-    const uint32_t lane = threadIdx.x & (DRT_WAVE - 1);
-    const uint32_t w = grid_wave();                       // wave of the grid = group + n_groups * range
-    const uint32_t range = w / a.n_groups, group = w - range * a.n_groups;
-    const uint32_t lp = group * DRT_WAVE + lane;          // batch-local pixel of this lane
-    const bool have = range < a.n_ranges && lp < a.Pb;
-    const uint32_t s_begin = range * a.spr;
-    const uint32_t s_end = s_begin + a.spr < a.Sb ? s_begin + a.spr : a.Sb;
+    const PathLane pl = path_lane(a);
 
     Tangents<R, NP, NC> tg;
     tg.acc = &s_acc[0][threadIdx.x];
@@ -87,24 +80,22 @@ k_path_mesh(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict_
 
     uint32_t gpix = 0, px = 0, py = 0;
     V3<R> g = mk<R>(R(1), R(1), R(1));                    // render.cpp:80: radiance.backward(Vec3(1))
-    if (have) {
-        gpix = path_global_pixel(a, a.p0 + lp);
+    if (pl.have) {
+        gpix = path_global_pixel(a, a.p0 + pl.lp);
         py = gpix / (uint32_t)a.W;
         px = gpix - py * (uint32_t)a.W;
         if (NP != 0 && adjoint)
             g = mk<R>((R)adjoint[(size_t)gpix * 3], (R)adjoint[(size_t)gpix * 3 + 1], (R)adjoint[(size_t)gpix * 3 + 2]);
     }
-    CameraLane<R> cl;                                     // (see k_path)
-    cl.cs0 = (R)((2. * (double)px * a.inv_W - 1.) * a.aspect * a.tan_half);
-    cl.ct0 = (R)((2. * (double)py * a.inv_H - 1.) * a.tan_half);
-    const R pk_rr = (R)a.p_rr, inv_p_rr = (R)a.inv_p_rr;
+    const CameraLane<R> cl = camera_lane<R>(a, px, py);
+    const R pk_rr = (R)a.p_rr, inv_p_rr = (R)a.inv_p_rr;   // (lanes at their own depths, scalar registers all taken: the doubles, see path_args_f32)
     const int n_shapes = lds.sc.n_shapes;
     const int first_rr = a.min_bounces > 1 ? a.min_bounces : 1;
     const V3<R> blo = mk<R>(bvh.lo[0], bvh.lo[1], bvh.lo[2]), bhi = mk<R>(bvh.hi[0], bvh.hi[1], bvh.hi[2]);
 
     // ---- the lane's path
-    uint32_t st = (have && s_begin < s_end) ? DRT_MS_NEW : DRT_MS_DONE;
-    uint32_t sl = s_begin, key = 0;                       // the lane's next sample; RNG key of its current path
+    uint32_t st = (pl.have && pl.s_begin < pl.s_end) ? DRT_MS_NEW : DRT_MS_DONE;
+    uint32_t sl = pl.s_begin, key = 0;                       // the lane's next sample; RNG key of its current path
     int kk = 0;                                           // depth of the vertex the current ray leads to
     V3<R> o = mk<R>(R(0), R(0), R(0)), d = o, inv_d = o;
     V3<R> T = mk<R>(R(1), R(1), R(1));
@@ -132,7 +123,7 @@ k_path_mesh(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict_
         }                                                                                     \
     } while (0)
 
-    if (range < a.n_ranges)
+    if (pl.range < a.n_ranges)
     for (;;) {
         const uint64_t m_ready = wave_ballot(st == DRT_MS_HIT || st == DRT_MS_NEW);
         const uint64_t m_walk = wave_ballot(st == DRT_MS_WALK);
@@ -212,7 +203,7 @@ k_path_mesh(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict_
                 ++kk;
                 fresh = alive;
                 if (!alive)
-                    st = sl < s_end ? DRT_MS_NEW : DRT_MS_DONE;
+                    st = sl < pl.s_end ? DRT_MS_NEW : DRT_MS_DONE;
             }
             if (!a.cap_is_roulette)
                 n_capped += (uint32_t)__popcll(wave_ballot(capped));
@@ -237,7 +228,7 @@ k_path_mesh(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict_
                         // pathtracer.hpp:128 at depth 0
                         fresh = a.depth_cap > 0 && !(a.min_bounces <= 0 && rng_draw(a.rng_stream, key, 2) < a.rr_threshold);
                         if (!fresh)
-                            st = sl < s_end ? DRT_MS_NEW : DRT_MS_DONE;
+                            st = sl < pl.s_end ? DRT_MS_NEW : DRT_MS_DONE;
                     }
                 }
             }
@@ -307,45 +298,23 @@ k_path_mesh(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict_
 #undef DRT_MESH_POP
 #undef DRT_MESH_PUSH
 
-    if (range < a.n_ranges) {
-        if (fpart && have) {
-            double* f = fpart + ((size_t)range * 3) * a.Pb + lp;       // [range][channel][pixel]: coalesced
-            f[0] = fx; f[(size_t)a.Pb] = fy; f[(size_t)a.Pb * 2] = fz;
-        }
-        if constexpr (NP > 0) if (gimg_part && have) {                 // gradient image (README.md:142-145): see k_path
+    if (pl.range < a.n_ranges) {
+        if (fpart && pl.have)
+            store_rows3(fpart + ((size_t)pl.range * 3) * a.Pb + pl.lp, a.Pb, fx, fy, fz);
+        if constexpr (NP > 0) if (gimg_part && pl.have) {              // gradient image (README.md:142-145), as k_path's column forms write it
             const V3<R> v = tg.acc_get(a.gimg_param > 0 && a.gimg_param < NP ? a.gimg_param : 0);
-            double* f = gimg_part + ((size_t)range * 3) * a.Pb + lp;
-            f[0] = (double)v.x; f[(size_t)a.Pb] = (double)v.y; f[(size_t)a.Pb * 2] = (double)v.z;
+            store_rows3(gimg_part + ((size_t)pl.range * 3) * a.Pb + pl.lp, a.Pb, v.x, v.y, v.z);
         }
-        if (lane == 0) {
+        if (pl.lane == 0) {                                            // (store_counts' two rows and a third: the rays the BVH walk took)
             const size_t nw = (size_t)a.n_groups * a.n_ranges;
-            counts[w] = n_seg;
-            counts[nw + w] = n_capped;
-            counts[2 * nw + w] = n_walked;
+            counts[pl.w] = n_seg;
+            counts[nw + pl.w] = n_capped;
+            counts[2 * nw + pl.w] = n_walked;
         }
     }
     if constexpr (GEN)
         gen_finish(s_gen, a, gpart);
     else
-    if (NP > 0) {
-        // block reduction in fp64: thread -> wave (shuffles) -> block (LDS), fixed order; the finishing launch adds the blocks
-        const int wv = threadIdx.x / DRT_WAVE;
-#pragma unroll
-        for (int r = 0; r < NP * 3; ++r) {
-            double v = (double)tg.acc[r * DRT_BLOCK];
-#pragma unroll
-            for (int o2 = DRT_WAVE / 2; o2 > 0; o2 >>= 1)
-                v += __shfl_down(v, o2);
-            if (lane == 0)
-                s_red[wv][r] = v;
-        }
-        __syncthreads();
-        if (threadIdx.x < DRT_FAST_PARAMS * 3) {
-            double v = 0;
-            if ((int)threadIdx.x < NP * 3)
-                for (int ww = 0; ww < DRT_BLOCK / DRT_WAVE; ++ww)
-                    v += s_red[ww][threadIdx.x];
-            gpart[(size_t)blockIdx.x * (DRT_FAST_PARAMS * 3) + threadIdx.x] = v;
-        }
-    }
+    if (NP > 0)
+        block_grad_sums<NP>(tg.acc, s_red, gpart, pl.lane);
 }

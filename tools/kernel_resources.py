@@ -3,7 +3,10 @@
 VGPRs, SGPRs, scratch, LDS, occupancy (-Rpass-analysis=kernel-resource-usage), plus -- for the
 kernels named on the command line -- an instruction-class histogram of their ISA.
 
-  python tools/kernel_resources.py [--keep DIR] [--against DIR] [substring of a demangled kernel name ...]
+  python tools/kernel_resources.py [--keep DIR] [--against DIR] [--root FILE] [substring of a demangled kernel name ...]
+
+--root FILE: compile FILE in place of csrc/drt_hip.hip, with csrc/ on the include path -- a few lines of explicit instantiations, with
+DRT_USER_SHAPES or DRT_SAMPLE_LOSS defined and their headers (drt_user_shapes.h, drt_sample_loss.h) beside it, say: the forms of the path kernels that only hiprtc compiles.
 
 --against DIR (the --keep directory of another build, usually the parent commit's): after the report, one line per kernel saying whether
 its resource figures and its instruction stream are the `same` as in that build or which `differs`, then a count of each.  The stream is
@@ -115,21 +118,19 @@ def compare(asm, parent_asm):
 
 def main():
     args = sys.argv[1:]
-    keep = against = None
-    while args and args[0] in ("--keep", "--against"):
+    opt = {"--keep": None, "--against": None, "--root": None}
+    while args and args[0] in opt:
         if len(args) < 2:
-            sys.exit(f"{args[0]} needs a directory")
-        if args[0] == "--keep":
-            keep = args[1]
-        else:
-            against = args[1]
+            sys.exit(f"{args[0]} needs a {'file' if args[0] == '--root' else 'directory'}")
+        opt[args[0]] = args[1]
         args = args[2:]
+    keep, against, root = opt["--keep"], opt["--against"], opt["--root"]
     d = keep or tempfile.mkdtemp(prefix="drt_isa_")
     os.makedirs(d, exist_ok=True)
     asm = os.path.join(d, "drt.s")
     subprocess.run([sys.executable, os.path.join(os.path.dirname(SRC), "embed_sources.py")], check=True)   # (drt_jit_sources.inc, which drt_hip.hip includes)
     cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-fno-slp-vectorize", "-std=c++17", "-fPIC", "-I" + os.path.join(ROOT, "include"),
-           "--cuda-device-only", "-S", "-o", asm, SRC, "-Rpass-analysis=kernel-resource-usage"] + \
+           "-I" + os.path.dirname(SRC)] + (["-I" + os.path.dirname(os.path.abspath(root))] if root else []) + ["--cuda-device-only", "-S", "-o", asm, root or SRC, "-Rpass-analysis=kernel-resource-usage"] + \
           [a for a in os.environ.get("DRT_EXTRA_FLAGS", "").split() if a]
     res = subprocess.run(cmd, capture_output=True, text=True)
     if res.returncode != 0:
