@@ -2,13 +2,18 @@
 per-wave gradient tables in LDS (csrc/drt_path.h, DRT_NP_ANY) -- against fixtures from the unmodified reference
 (oracle/gen_golden.py p1-p6), against the fp64 restatement run live, and against the queue wavefront (tape + K6) on the same
 frames.  The reference differentiates with respect to any number of Vector<T,3,true> (vector.hpp:185-191).
-Tolerances: f64 mode 1e-9 of the largest gradient component with identical segment counts; f32 1e-4 (north star)."""
+Tolerances: f64 mode 1e-9 of the largest gradient component with identical segment counts; f32 the stated bounds of
+tests/test_gpu_parity.py (GRAD_TOL on the Cornell family, GRAD_TOL_HEAVY in the random rooms, PIXEL_TOL, flip-aware) on every frame
+that the reference-only rule of tests/f32_flips.py calls stable; the frames it calls chaotic keep their f64 pin, the route-against-
+route comparison and the loose f32 terms they had (each such row names the stand-in result that put it there)."""
 import dataclasses
 
 import numpy as np
 import pytest
 
+import f32_flips as ff
 from conftest import MANY_PARAM_GOLDENS, MANY_PARAM_UNBIASED_GOLDENS, case_inputs, load_golden
+from test_gpu_parity import GRAD_TOL_HEAVY
 
 pytestmark = pytest.mark.gpu
 
@@ -18,7 +23,7 @@ def rel(got, want):
 
 
 @pytest.mark.parametrize("name", MANY_PARAM_GOLDENS + MANY_PARAM_UNBIASED_GOLDENS)
-def test_general_form_takes_the_one_launch_route_and_matches_the_reference(pkg, hip, name):
+def test_general_form_takes_the_one_launch_route_and_matches_the_reference(pkg, hip, oracle, name):
     g = load_golden(name)
     case = g["case"]
     scene, cam, rp, adjoint = case_inputs(pkg, case)
@@ -35,8 +40,21 @@ def test_general_form_takes_the_one_launch_route_and_matches_the_reference(pkg, 
             np.testing.assert_allclose(img, g["image"].astype(np.float32), rtol=2e-7, atol=1e-12)
         else:
             g32, seg32 = grads, st["segments"]
-            if seg32 == int(g["segments"]):       # (no path took another surface under f32 rounding)
-                assert rel(grads, g["grads"]) <= 1e-4
+            if any(f[0] == "golden:" + name for f in ff.FIXTURE_STRICT):
+                # p1, p2, p4, p6 (stable under the stand-in: at most one pixel moves, p2's by 6 % of its own value): the stated
+                # bounds against the fixture, flip-aware; the share of a set-aside pixel from the restatement's gradient images
+                n_standin = ff.standin_count(oracle, scene, cam, rp, adjoint)
+                rec = ff.flip_aware(hip, scene, cam, rp, adjoint, g["image"].astype(np.float64), g["grads"], int(g["segments"]),
+                                    ff.reference(oracle, scene, cam, rp, adjoint)[1], ff.pixel_cap(cam, rp, n_standin),
+                                    ff.row(ff.FIXTURE_STRICT, name)[6])
+                ff.report(name, rec)
+            else:
+                # p3 (params20 at depth 12): the stand-in moves 6, 3 and 2 pixels, one by 0.34 % of its own value -- no f32 bound
+                # can hold; p5 (unbiased): the stand-in moves NO pixel and the gradient by 6e-3, a flip in a fresh suffix path
+                # that no image shows.  Both: pinned in f64 above and route against route below
+                assert any(f[0] == "golden:" + name for f in ff.FIXTURE_CHAOTIC + ff.UNBIASED_CHAOTIC)
+                if seg32 == int(g["segments"]):       # (no path took another surface under f32 rounding)
+                    assert rel(grads, g["grads"]) <= 1e-4
         # parameters that do not require a gradient report exactly zero (vector.hpp:228-234)
         if "requires_grad" in case:
             for p, wants in enumerate(case["requires_grad"]):
@@ -54,6 +72,26 @@ def test_general_form_takes_the_one_launch_route_and_matches_the_reference(pkg, 
     assert rel(g32, q32) <= 2e-5
 
 
+def test_general_form_unbiased_in_f32_on_a_frame_without_a_flip(pkg, hip, oracle):
+    """The unbiased operator's general form in f32 against the restatement, unconditionally: p5's room, size and tracer at the
+    first seed after p5's at which the stand-in moves no pixel and the gradient by less than 1e-5 (seed 29: 0 pixels, 1.9e-6;
+    tests/test_f32_flip_check.py re-checks it).  No gradient image exists under this operator, so nothing is set aside."""
+    scene, cam, rp, adjoint = ff.frame_inputs(pkg, ff.P5_LIKE)
+    assert scene.n_params > 8
+    want = oracle.render(scene, cam, rp, backward=True, unbiased=True)
+    hip.upload_scene(scene)
+    _, grads, st = hip.render(cam, rp, backward=True, f64=True, unbiased=True)
+    assert st["kernels"]["path"]["launches"] == 1 and st["kernels"]["shade"]["launches"] == 0
+    assert st["segments"] == want["stats"]["segments"]
+    assert rel(grads, want["grads"]) < 1e-9
+    _, g32, st32 = hip.render(cam, rp, backward=True, unbiased=True)
+    assert st32["kernels"]["path"]["launches"] == 1 and st32["kernels"]["shade"]["launches"] == 0
+    print(f"f32 unbiased params12 seed {rp.seed}: segments {st32['segments'] - want['stats']['segments']:+d}, "
+          f"gradient {rel(g32, want['grads']):.2e}")
+    assert abs(st32["segments"] - want["stats"]["segments"]) <= 64
+    assert rel(g32, want["grads"]) <= GRAD_TOL_HEAVY
+
+
 @pytest.mark.parametrize("scene_name,kw", [("cornell_shapes", dict(min_bounces=8, absorb=1.0)),
                                             ("cornell_shapes", dict(min_bounces=1, absorb=0.5)),
                                             ("cornell_shapes", dict(min_bounces=3, absorb=0.2, max_depth=23)),
@@ -61,7 +99,9 @@ def test_general_form_takes_the_one_launch_route_and_matches_the_reference(pkg, 
                                             ("params64", dict(min_bounces=5, absorb=1.0)),
                                             ("params100", dict(min_bounces=2, absorb=0.3)),
                                             ("params126", dict(min_bounces=3, absorb=1.0)),
-                                            ("params40", dict(min_bounces=0, absorb=0.2))])     # (paths of up to ~45 vertices; the library ends a path at 64)
+                                            ("params40", dict(min_bounces=0, absorb=0.2))]      # (paths of up to ~45 vertices; the library ends a path at 64)
+                         # ... and every room in each form on frames the rule of tests/f32_flips.py accepts: lockstep, regenerating, capped
+                         + [(room, kw) for kw in (ff.LOCKSTEP, ff.REGENERATING, ff.CAPPED) for room in ff.ROOMS])
 def test_general_form_against_the_restatement_live(pkg, hip, oracle, scene_name, kw):
     """depths 5 ... 64 (history words in LDS: depth_cap / 4 per thread), 10 ... 100 parameters (16 ... 2 copies of a row per
     wave), lockstep and regenerating forms, an adjoint image, some parameters without gradients."""
@@ -71,6 +111,8 @@ def test_general_form_against_the_restatement_live(pkg, hip, oracle, scene_name,
     cam = pkg.cornell_camera(40, 32)
     rp = pkg.RenderParams(spp=6, seed=31, **kw)
     adjoint = rs.uniform(-1, 2, (32, 40, 3)).astype(np.float32)
+    frame = ff.row(ff.LIVE_STRICT + ff.LIVE_CHAOTIC, scene_name, kw)        # (the same inputs, as the CPU tests judge them)
+    assert ff.frame_inputs(pkg, frame)[0].requires_grad == scene.requires_grad and np.array_equal(ff.frame_inputs(pkg, frame)[3], adjoint)
     want = oracle.render(scene, cam, rp, backward=True, adjoint=adjoint)
     hip.upload_scene(scene)
     img, grads, st = hip.render(cam, rp, backward=True, adjoint=adjoint, f64=True)
@@ -79,17 +121,26 @@ def test_general_form_against_the_restatement_live(pkg, hip, oracle, scene_name,
     assert rel(grads, want["grads"]) < 1e-9
     np.testing.assert_allclose(img, want["image"].astype(np.float32), rtol=2e-7, atol=1e-12)
     i32, g32, st32 = hip.render(cam, rp, backward=True, adjoint=adjoint)
-    # f32: the same code in another compute type.  Rooms of up to 56 small spheres: a grazing ray may take another surface under
-    # f32 rounding (the segment count then differs) and such a path's whole weight moves -- the stated f32 bound holds for frames
-    # without one; with one, all but a few pixels still agree and the gradient stays within a path's share of it
-    bad = np.abs(i32.astype(np.float64) - want["image"]).max(-1) > 2e-4 * np.abs(want["image"]).max()
-    assert abs(st32["segments"] - want["stats"]["segments"]) <= 64
-    if not bad.any():      # (every pixel within the f32 pixel bound: no path went elsewhere -- a fixed-depth path that does keeps its length)
-        assert rel(g32, want["grads"]) <= 2e-4             # (random rooms: the heavy-tailed bound of test_gpu_parity.py)
+    if frame in ff.LIVE_STRICT:
+        # stable under the stand-in (at most one pixel moves, residual <= 3.5e-6): the stated bounds, flip-aware
+        rec = ff.flip_aware(hip, scene, cam, rp, adjoint, want["image"], want["grads"], want["stats"]["segments"],
+                            ff.reference(oracle, scene, cam, rp, adjoint)[1],
+                            ff.pixel_cap(cam, rp, ff.standin_count(oracle, scene, cam, rp, adjoint)), frame[6])
+        ff.report(f"{scene_name} {kw}", rec)
     else:
-        # (measured: 15 of 1280 pixels in the 100-parameter room, 38 dim lights among 56 spheres of radius 0.15-0.45, at 6 spp)
-        assert bad.mean() <= 2e-2
-        assert rel(g32, want["grads"]) <= 5e-2
+        # params24 d16 (the stand-in moves 7-10 pixels, one by 0.11 % of its own value), params100 rr (21-24 pixels, 0.22 %),
+        # params40 rr (8, 2, 8 pixels, 0.39 %): chaotic -- perfect arithmetic on inputs rounded to f32 fails the flip-aware check here
+        # f32: the same code in another compute type.  Rooms of up to 56 small spheres: a grazing ray may take another surface under
+        # f32 rounding (the segment count then differs) and such a path's whole weight moves -- the stated f32 bound holds for frames
+        # without one; with one, all but a few pixels still agree and the gradient stays within a path's share of it
+        bad = np.abs(i32.astype(np.float64) - want["image"]).max(-1) > 2e-4 * np.abs(want["image"]).max()
+        assert abs(st32["segments"] - want["stats"]["segments"]) <= 64
+        if not bad.any():      # (every pixel within the f32 pixel bound: no path went elsewhere -- a fixed-depth path that does keeps its length)
+            assert rel(g32, want["grads"]) <= 2e-4             # (random rooms: the heavy-tailed bound of test_gpu_parity.py)
+        else:
+            # (measured: 15 of 1280 pixels in the 100-parameter room, 38 dim lights among 56 spheres of radius 0.15-0.45, at 6 spp)
+            assert bad.mean() <= 2e-2
+            assert rel(g32, want["grads"]) <= 5e-2
     for p, wants in enumerate(scene.requires_grad):
         if not wants:
             assert not grads[p].any() and not g32[p].any()
@@ -140,7 +191,8 @@ def test_general_form_per_sample_loss_and_shards(pkg, hip, oracle):
 
 
 @pytest.mark.parametrize("scene_name,kw", [("cornell_shapes", dict(min_bounces=6, absorb=1.0)), ("params24", dict(min_bounces=2, absorb=0.3)),
-                                            ("params40", dict(min_bounces=18, absorb=1.0))])
+                                            ("params40", dict(min_bounces=18, absorb=1.0)),
+                                            ("params24", ff.REGENERATING), ("params40", ff.LOCKSTEP)])       # (two rooms on stable frames)
 def test_gradient_image_in_the_general_form(pkg, hip, oracle, scene_name, kw):
     """The per-pixel gradient of ONE parameter (README.md:142-145) of a scene with more than 8: the lanes' own adds to that
     parameter's row, beside the wave's table (k_path<..., DRT_NP_ANY, 1, ...>: lockstep, a lane is a pixel) -- one launch, against
@@ -149,6 +201,8 @@ def test_gradient_image_in_the_general_form(pkg, hip, oracle, scene_name, kw):
     cam = pkg.cornell_camera(40, 28)
     rp = pkg.RenderParams(spp=5, seed=17, **kw)
     adjoint = np.random.RandomState(4).uniform(-1, 2, (28, 40, 3)).astype(np.float32)
+    frame = ff.row(ff.GRADIENT_IMAGE_STRICT + ff.GRADIENT_IMAGE_CHAOTIC, scene_name, kw)
+    cap = ff.pixel_cap(cam, rp, ff.standin_count(oracle, scene, cam, rp, adjoint))
     hip.upload_scene(scene)
     for p in (scene.n_params - 1, scene.n_params // 2, 1):
         want = oracle.render(scene, cam, rp, backward=True, adjoint=adjoint, grad_image_param=p)
@@ -157,11 +211,18 @@ def test_gradient_image_in_the_general_form(pkg, hip, oracle, scene_name, kw):
         scale = float(np.abs(want["grad_image"]).max())
         assert np.abs(gimg.astype(np.float64) - want["grad_image"]).max() <= 1e-6 * scale
         np.testing.assert_allclose(img, want["image"].astype(np.float32), rtol=2e-7, atol=1e-12)
-        _, g32, _ = hip.render_gradient_image(cam, rp, p, adjoint=adjoint)
-        # f32: the same code in another compute type; in crowded rooms at depth 18 a few paths take another surface (up to 2.4 % of
-        # the pixels beyond 2e-4 of the largest value, measured) -- the image as a whole stays within a per cent
-        d32 = np.abs(g32.astype(np.float64) - want["grad_image"])
-        assert d32.sum() <= 2e-2 * np.abs(want["grad_image"]).sum() and (d32.max(-1) > 2e-4 * scale).mean() <= 5e-2
+        i32, g32, _ = hip.render_gradient_image(cam, rp, p, adjoint=adjoint)
+        if frame in ff.GRADIENT_IMAGE_STRICT:
+            # stable under the stand-in (no pixel moves): per pixel, flip-aware, as tests/test_gpu_tangent.py checks the tangent image
+            n, worst = ff.check_gradient_image(i32, g32, want["image"], want["grad_image"], cap)
+            print(f"f32 gradient image {scene_name} {kw} p={p}: {n} set aside, worst pixel {worst:.2e}")
+        else:
+            # params24 (2, 0.3): the stand-in moves two pixels, one by 0.07 % of its own value; params40 d18: 18-22 pixels --
+            # chaotic frames
+            # f32: the same code in another compute type; in crowded rooms at depth 18 a few paths take another surface (up to 2.4 % of
+            # the pixels beyond 2e-4 of the largest value, measured) -- the image as a whole stays within a per cent
+            d32 = np.abs(g32.astype(np.float64) - want["grad_image"])
+            assert d32.sum() <= 2e-2 * np.abs(want["grad_image"]).sum() and (d32.max(-1) > 2e-4 * scale).mean() <= 5e-2
         _, gq, stq = hip.render_gradient_image(cam, dataclasses.replace(rp, bounces_per_launch=1), p, adjoint=adjoint, f64=True)
         assert stq["kernels"]["path"]["launches"] == 0
         assert np.abs(gq.astype(np.float64) - gimg.astype(np.float64)).max() <= 1e-6 * scale

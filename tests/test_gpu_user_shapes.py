@@ -3,13 +3,17 @@ lobe, fixtures b1-b3 from the harness's CosLobeBxDF plugin of the unmodified ref
 interface (shape.hpp:11-35) becomes -- its intersect / normal bodies as HIP source, compiled by hiprtc into the scene's own path
 kernel.  The two kinds here, a disc and an axis-aligned box, are shapes the library has NO code for; the fixtures come from the
 same two classes compiled as plugins against the UNMODIFIED reference headers (oracle/ref_harness.cpp: Disc, AABox; fixtures s1-s3).
-Tolerances: f64 mode 1e-9 of the largest gradient component with identical segment counts; f32 1e-4 (north star)."""
+Tolerances: f64 mode 1e-9 of the largest gradient component with identical segment counts; f32 the stated bounds of
+tests/test_gpu_parity.py (GRAD_TOL, PIXEL_TOL, flip-aware) -- every frame here is stable under the reference-only rule of
+tests/f32_flips.py (no pixel moves under its stand-in, gradients by <= 2.1e-6)."""
 import dataclasses
 
 import numpy as np
 import pytest
 
+import f32_flips as ff
 from conftest import USER_SHAPE_GOLDENS, USER_SHAPE_UNBIASED_GOLDENS, case_inputs, load_golden
+from test_gpu_parity import GRAD_TOL
 
 pytestmark = pytest.mark.gpu
 
@@ -19,7 +23,7 @@ def rel(got, want):
 
 
 @pytest.mark.parametrize("name", USER_SHAPE_GOLDENS + USER_SHAPE_UNBIASED_GOLDENS)
-def test_caller_defined_shapes_match_the_reference_plugins(pkg, hip, name):
+def test_caller_defined_shapes_match_the_reference_plugins(pkg, hip, oracle, name):
     g = load_golden(name)
     case = g["case"]
     scene, cam, rp, adjoint = case_inputs(pkg, case)
@@ -33,16 +37,33 @@ def test_caller_defined_shapes_match_the_reference_plugins(pkg, hip, name):
     assert rel(grads, g["grads"]) < 1e-9
     np.testing.assert_allclose(img, g["image"].astype(np.float32), rtol=2e-7, atol=1e-12)
     i32, g32, st32 = hip.render(cam, rp, backward=True, adjoint=adjoint, unbiased=unbiased)
-    bad = np.abs(i32.astype(np.float64) - g["image"]).max(-1) > 2e-4 * np.abs(g["image"]).max()
     assert abs(st32["segments"] - int(g["segments"])) <= 64
-    if not bad.any():
-        assert rel(g32, g["grads"]) <= 1e-4
-    else:                                                  # (a path that took another surface under f32 rounding)
-        assert bad.sum() <= 2 and rel(g32, g["grads"]) <= 2e-2
+    if unbiased:
+        # s3, b3: no gradient image under this operator, so no set-aside -- unconditionally (the stand-in of tests/f32_flips.py
+        # moves no pixel of these frames and their gradients by <= 1.2e-6)
+        assert ff.row(ff.UNBIASED_STRICT, name)[6] == GRAD_TOL
+        print(f"f32 {name}: segments {st32['segments'] - int(g['segments']):+d}, gradient {rel(g32, g['grads']):.2e}")
+        assert rel(g32, g["grads"]) <= GRAD_TOL
+    else:
+        # s1, s2, b1, b2: the stated bounds against the fixture, flip-aware (the share of a set-aside pixel from the restatement)
+        rec = ff.flip_aware(hip, scene, cam, rp, adjoint, g["image"].astype(np.float64), g["grads"], int(g["segments"]),
+                            ff.reference(oracle, scene, cam, rp, adjoint)[1],
+                            ff.pixel_cap(cam, rp, ff.standin_count(oracle, scene, cam, rp, adjoint)), ff.row(ff.USER_FIXTURE_STRICT, name)[6])
+        ff.report(name, rec)
     # forward only
     f32, _, fst = hip.render(cam, rp, backward=False)
     assert fst["kernels"]["path"]["launches"] == 1
     np.testing.assert_allclose(f32, i32, rtol=2e-6, atol=1e-9)     # (two kernels, compiled apart: the last bit may differ)
+
+
+def f32_leg(hip, oracle, scene_name, scene, cam, rp, adj, want, kw):
+    """f32 on a live frame of the caller-defined kinds: the stated bounds against the restatement, flip-aware"""
+    frame = ff.row(ff.USER_LIVE_STRICT, scene_name, kw)
+    assert (cam.width, cam.height, rp.spp, rp.seed) == (frame[1][0], frame[1][1], frame[3], frame[4])
+    rec = ff.flip_aware(hip, scene, cam, rp, adj, want["image"], want["grads"], want["stats"]["segments"],
+                        ff.reference(oracle, scene, cam, rp, adj)[1],
+                        ff.pixel_cap(cam, rp, ff.standin_count(oracle, scene, cam, rp, adj)), frame[6])
+    ff.report(f"{scene_name} {kw}", rec)
 
 
 def test_caller_defined_shapes_every_form_of_the_path_kernel(pkg, hip, oracle):
@@ -59,6 +80,7 @@ def test_caller_defined_shapes_every_form_of_the_path_kernel(pkg, hip, oracle):
         assert st["kernels"]["path"]["launches"] == 1 and st["segments"] == want["stats"]["segments"]
         assert rel(grads, want["grads"]) < 1e-9
         np.testing.assert_allclose(img, want["image"].astype(np.float32), rtol=2e-7, atol=1e-12)
+        f32_leg(hip, oracle, "cornell_disc_box", scene, cam, rp, adj, want, kw)
     rp = pkg.RenderParams(spp=6, seed=42, min_bounces=4, absorb=1.0)
     # the per-pixel gradient image of the disc's albedo (README.md:142-145)
     p = scene.param_names.index("disc_albedo")
@@ -92,8 +114,7 @@ def test_caller_defined_bxdf_every_form_of_the_path_kernel(pkg, hip, oracle):
         assert st["kernels"]["path"]["launches"] == 1 and st["segments"] == want["stats"]["segments"]
         assert rel(grads, want["grads"]) < 1e-9
         np.testing.assert_allclose(img, want["image"].astype(np.float32), rtol=2e-7, atol=1e-12)
-        _, g32, _ = hip.render(cam, rp, backward=True, adjoint=adj)
-        assert rel(g32, want["grads"]) <= 2e-2           # (f32: the stated bound holds on the fixtures; here only "the same code in f32")
+        f32_leg(hip, oracle, "cornell_coslobe_disc", scene, cam, rp, adj, want, kw)
     rp = pkg.RenderParams(spp=5, seed=62, min_bounces=4, absorb=1.0)
     p = scene.param_names.index("lobe_albedo")
     want = oracle.render(scene, cam, rp, backward=True, grad_image_param=p)
