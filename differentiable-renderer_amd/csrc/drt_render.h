@@ -40,12 +40,13 @@ static int render_launch(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt
     if (!cam || !rp || cam->width <= 0 || cam->height <= 0 || rp->spp <= 0 || rp->min_bounces < 0 ||
         !(rp->absorb >= 0.0 && rp->absorb <= 1.0))
         return fail(ctx, DRT_ERR_INVALID, "render: bad camera or render parameters");
+    // the path index (pixel * spp + sample) of every camera sample of the FRAME fits 32 bits: the kernels keep its low word
+    // as the path's RNG key and share the high word's hash round (drt_hip.h: path_hi = 0).  Asked first, so that a frame of too
+    // many samples hears so whatever its shape (65536 x 65536 x 2), and without the three-factor product, which can pass 2^64
+    if ((uint64_t)cam->width * (uint64_t)cam->height > (1ull << 32) / (uint64_t)rp->spp)
+        return fail(ctx, DRT_ERR_INVALID, "render: more than 2^32 camera samples in one frame (width x height x spp)");
     if ((uint64_t)cam->width * (uint64_t)cam->height >= 0xFFFFFFFFull)
         return fail(ctx, DRT_ERR_INVALID, "render: image too large");
-    // the path index (pixel * spp + sample) of every camera sample of the FRAME fits 32 bits: the kernels keep its low word
-    // as the path's RNG key and share the high word's hash round (drt_hip.h: path_hi = 0)
-    if ((uint64_t)cam->width * (uint64_t)cam->height * (uint64_t)rp->spp > (1ull << 32))
-        return fail(ctx, DRT_ERR_INVALID, "render: more than 2^32 camera samples in one frame (width x height x spp)");
     if (rp->max_depth > DRT_MAX_DEPTH)
         return fail(ctx, DRT_ERR_INVALID, "render: max_depth above DRT_MAX_DEPTH (64)");
     if (rp->absorb >= 1.0 && rp->max_depth <= 0 && rp->min_bounces > DRT_MAX_DEPTH)

@@ -78,9 +78,12 @@ def lib() -> C.CDLL:
 
 def render(scene, cam, rp, backward: bool = False, adjoint: Optional[np.ndarray] = None,
            rng_mode: int = RNG_KEYED, faithful: bool = False, dump_paths: int = 0,
-           grad_image_param: int = -1, unbiased: bool = False, zero_dir_miss: bool = False, loss_l2: bool = False):
+           grad_image_param: int = -1, unbiased: bool = False, zero_dir_miss: bool = False, loss_l2: bool = False,
+           max_vertices: int = 0):
     """-> dict(image f64 [H,W,3], grads f64 [P,3] | None, stats dict, vertices f64 [n,16] | None,
-    grad_image f64 [H,W,3] | None)"""
+    grad_image f64 [H,W,3] | None)
+    dump_paths: the vertices of the paths with an index below it are logged, into room for max_vertices of them (default: 64 per
+    such path; a shard far up a large frame logs few of the paths below its last index and says how many)."""
     sd, keep = scene.to_desc()
     cd = cam.to_desc()
     rd = rp.to_desc()
@@ -95,7 +98,7 @@ def render(scene, cam, rp, backward: bool = False, adjoint: Optional[np.ndarray]
     nv = C.c_uint64(0)
     max_v = 0
     if dump_paths > 0:
-        max_v = dump_paths * 64
+        max_v = max_vertices if max_vertices > 0 else dump_paths * 64
         vtx = np.zeros((max_v, VERTEX_DOUBLES), dtype=np.float64)
     gimg = None
     if grad_image_param >= 0:

@@ -289,16 +289,17 @@ def flat_materials(scene):
     return out
 
 
-def lobe_conditioning(oracle, x):
+def lobe_conditioning(oracle, x, max_vertices=0):
     """The f32 conditioning of the reference's specular lobe, per pixel [H,W]: the largest c^2 / (1 - c^2) over the specular bounces of the
     pixel's paths, c = normal . half vector, from the restatement's vertices.  The lobe's factor s = sqrt(1 - c^2) (bxdf.hpp:104-107) loses
     what 1 - c^2 cancels: a rounding of 2^-24 in c^2 is a relative 2^-24 c^2 / (1 - c^2) in s^2, and c (two normalisations and a dot
     product) carries a few roundings itself.  First seen on cornell_specular, depth 5, 23 x 11, seed 9: pixel (4, 11) is ONE path whose
     first half vector lies 5e-3 rad off the sphere's normal, c^2 / (1 - c^2) = 40969 -- every f32 geometry, `default` included, gives
-    that pixel 0.54 % above the restatement, in the image and in every derivative image alike."""
+    that pixel 0.54 % above the restatement, in the image and in every derivative image alike.
+    max_vertices: room for the vertex log where the render is a shard of a large frame (tests/index_range.py); default 64 per path."""
     scene, cam, rp = x.scene, x.cam, x.rp
     specular = [i for i, m in enumerate(flat_materials(scene)) if m >= 0 and scene.materials[m][0] == 1]
-    v = oracle.render(scene, cam, rp, dump_paths=cam.width * cam.height * rp.spp)["vertices"]
+    v = oracle.render(scene, cam, rp, dump_paths=cam.width * cam.height * rp.spp, max_vertices=max_vertices)["vertices"]
     v = v[np.lexsort((v[:, 1], v[:, 0]))]
     a, b = v[:-1], v[1:]                                  # a vertex and the next one of the same path: directions in and out
     on = (a[:, 0] == b[:, 0]) & (b[:, 1] == a[:, 1] + 1) & np.isin(a[:, 8].astype(int), specular)

@@ -107,6 +107,9 @@ def test_no_two_paths_of_config_3_share_draws(oracle):
     rs = np.random.RandomState(0)
     for seed, path, n in zip(rs.randint(0, 2**31, 64), rs.randint(0, 2**40, 64, dtype=np.int64), rs.randint(0, 300, 64)):
         assert int(_u31(int(seed), np.array([path], np.uint64), int(n))[0]) == oracle.rng_u31(int(seed), int(path), int(n))
+    for path in (2**31 - 1, 2**31, 2**32 - 1, 2**32):      # the sign bit of the 32-bit key, its last value and the first index past it
+        for seed, n in ((1, 0), (2**31 + 5, 7), (2**32 - 1, 299)):
+            assert int(_u31(seed, np.array([path], np.uint64), n)[0]) == oracle.rng_u31(seed, path, n)
     paths = np.arange(512 * 512 * 64, dtype=np.uint64)
     draws = [_u31(1, paths, n).astype(np.uint64) for n in range(7)]
     for d in draws[:2]:                       # at one draw index the paths get pairwise different 32-bit words (a bijection):
