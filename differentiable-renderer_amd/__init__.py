@@ -49,6 +49,7 @@ MAX_PARAM_SETS = 8           # DRT_HIP_MAX_PARAM_SETS: parameter sets per render
 MAX_SETS_ALONG = 4           # DRT_HIP_MAX_SETS_ALONG: parameter sets with a direction each per render_param_sets_along call
 MAX_SETS_GRAD = 8            # DRT_HIP_MAX_SETS_GRAD: parameter sets with a summed gradient each per render_param_sets_grad call
 MAX_SETS_CROSS = 8           # DRT_HIP_MAX_SETS_CROSS: parameter sets with an unbiased loss each per render_param_sets_cross call
+MAX_VIEWS = 64               # DRT_HIP_MAX_VIEWS: cameras per render_views call
 MAX_LOSS_VALUES = 4          # DRT_MAX_LOSS_VALUES: the constants q[0..3] of a per-sample loss (set_sample_loss)
 ABI_VERSION = 8
 UNIQUE_ID_BYTES = 128
@@ -767,7 +768,7 @@ _ABI_SYMBOLS = ["drt_hip_abi_version", "drt_hip_device_count", "drt_hip_create",
                 "drt_hip_render_gradient_image", "drt_hip_render_tangent", "drt_hip_render_tangent_double", "drt_hip_render_normal_equations", "drt_hip_render_tangents",
                 "drt_hip_render_normal_equations_along", "drt_hip_render_normal_equations_cross", "drt_hip_render_param_sets", "drt_hip_render_param_sets_double",
                 "drt_hip_render_param_sets_along", "drt_hip_render_param_sets_along_double", "drt_hip_render_param_sets_grad", "drt_hip_render_param_sets_cross",
-                "drt_hip_set_sample_loss", "drt_hip_render_sample_loss", "drt_hip_pin_host", "drt_hip_unpin_host", "drt_hip_stream",
+                "drt_hip_render_views", "drt_hip_set_sample_loss", "drt_hip_render_sample_loss", "drt_hip_pin_host", "drt_hip_unpin_host", "drt_hip_stream",
                 "drt_hip_synchronize", "drt_hip_last_error", "drt_hip_kernel_name"]
 
 
@@ -826,6 +827,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
                                                    C.c_void_p, C.c_void_p, C.POINTER(HipStats)]
     lib.drt_hip_render_param_sets_cross.argtypes = [C.c_void_p, C.POINTER(CameraDesc), C.POINTER(RenderParamsDesc), C.c_int32, C.c_void_p,
                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(HipStats)]
+    lib.drt_hip_render_views.argtypes = [C.c_void_p, C.POINTER(CameraDesc), C.c_int32, C.POINTER(RenderParamsDesc), C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(HipStats)]
     lib.drt_hip_set_sample_loss.argtypes = [C.c_void_p, C.POINTER(SampleLossDesc)]
     lib.drt_hip_render_sample_loss.argtypes = [C.c_void_p, C.POINTER(CameraDesc), C.POINTER(RenderParamsDesc), C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_void_p, C.POINTER(HipStats)]
@@ -1437,6 +1440,59 @@ class HipRenderer:
                                                       C.c_void_p(out_loss_ptr or None), C.c_void_p(out_bias_ptr or None),
                                                       C.c_void_p(out_variance_ptr or None), C.byref(stats) if want_stats else None)
         self._check(rc, "drt_hip_render_param_sets_cross")
+        return stats.as_dict() if want_stats else {}
+
+    def _begin_views(self, cams: Sequence[Camera], rp: RenderParams, flags: int, seeds):
+        """the cameras, the render parameters with `flags`, the seeds and a statistics record, as drt_hip_render_views takes them"""
+        assert self.scene is not None
+        cams = list(cams)
+        if not 1 <= len(cams) <= MAX_VIEWS:
+            raise ValueError(f"views: n_views = {len(cams)} outside 1 ... MAX_VIEWS = {MAX_VIEWS}")
+        if any((c.width, c.height) != (cams[0].width, cams[0].height) for c in cams):
+            raise ValueError("views: the cameras differ in width or height (all views share one size)")
+        cds = (CameraDesc * len(cams))(*[c.to_desc() for c in cams])
+        d = rp.to_desc()
+        d.flags = flags
+        sd = None
+        if seeds is not None:
+            sd = np.ascontiguousarray(seeds, dtype=np.uint32)
+            if sd.shape != (len(cams),):
+                raise ValueError(f"views: expected {len(cams)} seeds, got shape {list(sd.shape)}")
+        return cams, cds, d, sd, HipStats()
+
+    def render_views(self, cams: Sequence[Camera], rp: RenderParams, backward: bool = False, adjoints: Optional[np.ndarray] = None,
+                     seeds=None, f64: bool = False, timing: bool = False):
+        """drt_hip_render_views: the scene from the n <= MAX_VIEWS = 64 cameras `cams` (one size) in ONE trace, view v seeded with
+        `seeds[v]` (None: rp.seed for every view) and, with `backward`, back-propagated from `adjoints[v]` (float32 [n,H,W,3]; None: all ones).
+        -> (images float32 [n,H,W,3], grad_sum float64 [P,3] or None, view_grads float64 [n,P,3] or None, stats dict): view v's image and
+        gradient are what render(cams[v], rp with seed seeds[v], backward, adjoint=adjoints[v]) gives, grad_sum the gradients added in view order."""
+        cams, cds, d, sd, stats = self._begin_views(cams, rp, self._host_flags(rp, f64, timing) | (RENDER_BACKWARD if backward else 0), seeds)
+        n, H, W, P = len(cams), cams[0].height, cams[0].width, self.scene.n_params
+        a_ptr = None
+        if adjoints is not None:
+            adjoints = np.ascontiguousarray(adjoints, dtype=np.float32)
+            if adjoints.shape != (n, H, W, 3):
+                raise ValueError(f"views: expected adjoints of shape {[n, H, W, 3]}, got {list(adjoints.shape)}")
+            a_ptr = adjoints.ctypes.data_as(C.c_void_p)
+        imgs = np.zeros((n, H, W, 3), dtype=np.float32)
+        gsum = np.zeros((max(P, 1), 3), dtype=np.float64) if backward else None
+        vg = np.zeros((n, max(P, 1), 3), dtype=np.float64) if backward else None
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+        rc = self.lib.drt_hip_render_views(self.ctx, cds, n, C.byref(d), ptr(sd), a_ptr, ptr(imgs), ptr(gsum), ptr(vg), C.byref(stats))
+        self._check(rc, "drt_hip_render_views")
+        return imgs, (gsum[:P] if backward else None), (vg[:, :P] if backward else None), stats.as_dict()
+
+    def render_views_device(self, cams: Sequence[Camera], rp: RenderParams, out_images_ptr: int = 0, out_grad_ptr: int = 0,
+                            out_view_grads_ptr: int = 0, adjoints_ptr: int = 0, seeds=None, backward: bool = False, f64: bool = False,
+                            timing: bool = False, sync: bool = False, want_stats: Optional[bool] = None) -> dict:
+        """drt_hip_render_views on device pointers (images and adjoints float32 [n,H,W,3], the summed gradient float64 [P,3], the views'
+        gradients float64 [n,P,3]), enqueued on the context's stream; the cameras and the seeds are host memory."""
+        want_stats = timing if want_stats is None else want_stats
+        cams, cds, d, sd, stats = self._begin_views(cams, rp, self._device_flags(rp, f64, timing, sync) | (RENDER_BACKWARD if backward else 0), seeds)
+        rc = self.lib.drt_hip_render_views(self.ctx, cds, len(cams), C.byref(d), sd.ctypes.data_as(C.c_void_p) if sd is not None else None,
+                                           C.c_void_p(adjoints_ptr or None), C.c_void_p(out_images_ptr or None), C.c_void_p(out_grad_ptr or None),
+                                           C.c_void_p(out_view_grads_ptr or None), C.byref(stats) if want_stats else None)
+        self._check(rc, "drt_hip_render_views")
         return stats.as_dict() if want_stats else {}
 
     def render_device(self, cam: Camera, rp: RenderParams, out_rgb_ptr: int, out_grad_ptr: int,

@@ -51,6 +51,17 @@ struct ParamSetsRequest {
     double* d_bias = nullptr;             // n_sets x 3: what was subtracted from the loss, or none
     float* d_variance = nullptr;          // n_sets x H x W x 3: the variance of the pixel's mean under set k, or none
 };
+// ... and one scene from several cameras (drt_hip_render_views): k_path_views over the single frame's grid once per view, then k_views_finish.
+// All pointers are the device's; the first camera is the one the pipeline is told about
+struct ViewsRequest {
+    int n_views = 0;
+    bool backward = false;                // gradients wanted: the kernel's gradient form, as drt_hip_render's plan picks it for one frame
+    const void* d_table = nullptr;        // n_views PathView records (drt_path.h): camera constants, seed, stream
+    const float* d_adjoints = nullptr;    // n_views x H x W x 3: view v's seed image, or none (every seed (1, 1, 1))
+    float* d_images = nullptr;            // n_views x H x W x 3, or none
+    double* d_view_grads = nullptr;       // n_views x the caller's parameters x 3, or none
+    double* d_grad = nullptr;             // the caller's parameters x 3: the views' gradients added in view order, or none
+};
 // A render on one of the path kernel's special forms, as render_common / render_launch / render_impl are told about it: which form, and what
 // that form reads.  render_impl decodes it, in one place
 struct TangentRequest {
@@ -60,6 +71,7 @@ struct TangentRequest {
         directions,                       // ... in the span of K directions (drt_hip_render_tangents / _normal_equations_along): d_params, neq, n_dirs
         param_sets,                       // one frame under K parameter sets (drt_hip_render_param_sets; with sets->along each has a direction:
                                           // drt_hip_render_param_sets_along): d_params, sets
+        views,                            // one scene from several cameras (drt_hip_render_views): views
     } kind = Kind::forward;
     const void* d_params = nullptr;       // the path kernel's `params`, in the render's compute type: [the scene's parameters | row_1 | ... | row_K],
                                           // the rows padded up to an instantiated width K (stage_rows, drt_hip.hip)
@@ -67,6 +79,7 @@ struct TangentRequest {
     const NormalEqRequest* neq = nullptr;
     int n_dirs = 0;                       // the rows k_normal_eq reduces are these directions instead of the parameters
     const ParamSetsRequest* sets = nullptr;
+    const ViewsRequest* views = nullptr;
 };
 
 // One render call between its phases: launch (everything enqueued, gradients in ctx->grad[ctx->slot]) -> reduce (the

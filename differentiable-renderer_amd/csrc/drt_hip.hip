@@ -913,6 +913,139 @@ int drt_hip_render_param_sets_cross(drt_hip_ctx* ctx, const drt_camera_desc* cam
                               nullptr, stats, nullptr, nullptr, out_bias, out_variance);
 }
 
+} // extern "C"
+
+// ---- one scene from several cameras in one trace (k_path_views, drt_path.h) ----------------------------------------------------------
+// The call's pinned block: stage_rows' two pinned copies and their events, used the same way (this call has no rows behind the kernel's
+// `params`, so the buffers are free for it).  [the views' table | `extra` bytes of the caller's]: the table goes to ctx->tangent.p in stream
+// order; -> the block (the extra bytes start 16-byte aligned behind the table: views_extra_offset)
+static size_t views_extra_offset(int n_views) { return ((size_t)n_views * sizeof(PathView) + 15) & ~(size_t)15; }
+static int stage_views(drt_hip_ctx* ctx, const drt_camera_desc* cams, int n_views, const drt_render_params* rp, const uint32_t* seeds, size_t extra,
+                       uint8_t** block)
+{
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const int hb = (int)(ctx->tangent_calls++ & 1);
+    const size_t bytes = (size_t)n_views * sizeof(PathView), need = (views_extra_offset(n_views) + extra + sizeof(double) - 1) / sizeof(double);
+    if (!ctx->ev_tangent[hb])
+        HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_tangent[hb], hipEventDisableTiming));
+    else
+        HIPCHK(ctx, hipEventSynchronize(ctx->ev_tangent[hb]));
+    if (ctx->h_tangent_cap[hb] < need) {
+        if (ctx->h_tangent[hb])
+            (void)hipHostFree(ctx->h_tangent[hb]);
+        ctx->h_tangent[hb] = nullptr;
+        ctx->h_tangent_cap[hb] = 0;
+        HIPCHK(ctx, hipHostMalloc((void**)&ctx->h_tangent[hb], need * sizeof(double)));
+        ctx->h_tangent_cap[hb] = need;
+    }
+    PathView* tab = reinterpret_cast<PathView*>(ctx->h_tangent[hb]);
+    for (int v = 0; v < n_views; ++v)
+        fill_path_view(tab[v], cams[v], seeds ? seeds[v] : rp->seed);
+    int rc;
+    if ((rc = ensure(ctx, ctx->tangent, bytes)) != DRT_OK) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(ctx->tangent.p, tab, bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipEventRecord(ctx->ev_tangent[hb], ctx->stream));
+    *block = reinterpret_cast<uint8_t*>(ctx->h_tangent[hb]);
+    return DRT_OK;
+}
+
+extern "C" {
+
+int drt_hip_render_views(drt_hip_ctx* ctx, const drt_camera_desc* cams, int32_t n_views, const drt_render_params* rp, const uint32_t* seeds,
+                         const float* adjoints_rgb, float* out_images, double* out_param_grad, double* out_view_grads, drt_hip_stats* stats)
+{
+    if (!ctx)
+        return DRT_ERR_INVALID;
+    static const PathFormCaller me = {"views", "render the shards on plain contexts", "the biased operator", DRT_PATH_LDS_PARAMS,
+                                      "more parameters than the path kernels stage (136)"};
+    int rc;
+    if ((rc = refuse_before(ctx, cams, rp, me)) != DRT_OK) return rc;
+    if (n_views < 1 || n_views > DRT_HIP_MAX_VIEWS)
+        return refuse(ctx, me, DRT_ERR_INVALID, "n_views outside 1 ... DRT_HIP_MAX_VIEWS = 64");
+    for (int v = 1; v < n_views; ++v)
+        if (cams[v].width != cams[0].width || cams[v].height != cams[0].height)
+            return refuse(ctx, me, DRT_ERR_INVALID, "the cameras differ in width or height (all views share one size)");
+    if (!out_images && !out_param_grad && !out_view_grads)
+        return refuse(ctx, me, DRT_ERR_INVALID, "no output requested (out_images, out_param_grad and out_view_grads are all NULL)");
+    const bool backward = (out_param_grad || out_view_grads);
+    if (backward && !(rp->flags & DRT_RENDER_BACKWARD))
+        return refuse(ctx, me, DRT_ERR_INVALID, "out_param_grad and out_view_grads need DRT_RENDER_BACKWARD");
+    const bool dev = (rp->flags & DRT_RENDER_DEVICE_OUT) != 0;
+    const size_t npix = (size_t)cams[0].width * (size_t)cams[0].height;
+    if (!dev && adjoints_rgb)
+        for (size_t i = 0; i < (size_t)n_views * npix * 3; ++i)
+            if (!std::isfinite(adjoints_rgb[i]))
+                return refuse(ctx, me, DRT_ERR_INVALID, "an adjoint image holds a value that is not finite");
+    if ((rc = refuse_after(ctx, cams, rp, me)) != DRT_OK) return rc;
+    if ((uint64_t)n_views * npix * (uint64_t)(rp->spp > 0 ? rp->spp : 1) > 0x7FFFFFFFull)
+        return refuse(ctx, me, DRT_ERR_UNSUPPORTED, "more than 2^31 camera samples over all views (they render in one launch)");
+    // Host buffers: everything crosses in the call's pinned block, [table | gradients (the views', then their sum) | images | adjoint images] --
+    // the finishing kernel stores images and sums straight into it (no device copy, no copy launch behind it, as a synchronous drt_hip_render
+    // does), and the path kernel reads its seeds from it where they are small (one 12-byte load per lane: render_impl's rule), from a copy in
+    // device memory else.  Device pointers: the table alone
+    const size_t n_img = (size_t)n_views * npix * 3 * sizeof(float), ng = (size_t)ctx->n_user_params * 3;
+    const bool host_adj = !dev && backward && adjoints_rgb;
+    const size_t grad_bytes = (((size_t)(n_views + 1) * ng + 1) * sizeof(double) + 15) & ~(size_t)15, img_bytes = (n_img + 15) & ~(size_t)15;
+    const size_t off_grad = views_extra_offset(n_views), off_img = off_grad + (backward ? grad_bytes : 0), off_adj = off_img + (out_images ? img_bytes : 0);
+    uint8_t* block = nullptr;
+    if ((rc = stage_views(ctx, cams, n_views, rp, seeds, dev ? 0 : off_adj + (host_adj ? n_img : 0) - off_grad, &block)) != DRT_OK) return rc;
+    ViewsRequest q;
+    q.n_views = n_views;
+    q.backward = backward;
+    q.d_table = ctx->tangent.p;
+    if (dev) {
+        q.d_adjoints = backward ? adjoints_rgb : nullptr;
+        q.d_images = out_images;
+        q.d_view_grads = out_view_grads;
+        q.d_grad = out_param_grad;
+        // (a shard without rows launches nothing: its sums are zero)
+        if (rp->n_shards > 1) {
+            if (q.d_view_grads && ng) HIPCHK(ctx, hipMemsetAsync(q.d_view_grads, 0, (size_t)n_views * ng * sizeof(double), ctx->stream));
+            if (q.d_grad && ng) HIPCHK(ctx, hipMemsetAsync(q.d_grad, 0, ng * sizeof(double), ctx->stream));
+        }
+    } else {
+        if (host_adj) {
+            memcpy(block + off_adj, adjoints_rgb, n_img);
+            q.d_adjoints = (const float*)(block + off_adj);
+            if (n_img > ((size_t)1 << 20)) {
+                if ((rc = ensure(ctx, ctx->neq_in, n_img)) != DRT_OK) return rc;
+                HIPCHK(ctx, hipMemcpyAsync(ctx->neq_in.p, block + off_adj, n_img, hipMemcpyHostToDevice, ctx->stream));
+                q.d_adjoints = (const float*)ctx->neq_in.p;
+            }
+        }
+        if (out_images)
+            q.d_images = (float*)(block + off_img);
+        if (backward) {
+            q.d_view_grads = (double*)(block + off_grad);
+            q.d_grad = q.d_view_grads + (size_t)n_views * ng;
+            memset(q.d_view_grads, 0, (size_t)(n_views + 1) * ng * sizeof(double));      // (a shard without rows launches nothing: its sums are zero)
+        }
+    }
+    TangentRequest req;
+    req.kind = TangentRequest::Kind::views;
+    req.views = &q;
+    // (the pipeline below is told a forward render of the first camera: this form's seeds, images and sums go their own way)
+    drt_render_params r = *rp;
+    r.flags &= ~(uint32_t)DRT_RENDER_BACKWARD;
+    if ((rc = render_common(ctx, &cams[0], &r, nullptr, nullptr, nullptr, stats, -1, nullptr, &req)) != DRT_OK)
+        return rc;
+    if (dev)
+        return DRT_OK;
+    // host buffers: the render has waited for its stream; the sums, and the images' rows of this shard
+    if (out_view_grads && ng) memcpy(out_view_grads, q.d_view_grads, (size_t)n_views * ng * sizeof(double));
+    if (out_param_grad && ng) memcpy(out_param_grad, q.d_grad, ng * sizeof(double));
+    if (out_images) {
+        const RenderJob& j = ctx->job;
+        const size_t row = (size_t)cams[0].width * 3 * sizeof(float), img = (size_t)cams[0].height * row;
+        for (size_t v = 0; v < (size_t)n_views; ++v)
+            for_each_band(cams[0].height, j.band, j.n_shards, j.shard, [&](int y0, int y1) {
+                const size_t at = v * img + (size_t)y0 * row;
+                memcpy((uint8_t*)out_images + at, block + off_img + at, (size_t)(y1 - y0) * row);
+            });
+    }
+    return DRT_OK;
+}
+
 // ---- the per-sample loss from the caller's own source (drt_loss.h) ---------------------------------------------------
 // "drt_sample_loss.h" as hiprtc sees it: the one function, the caller's text its body -- and nothing else of the caller's: the header, and
 // with it the compile cache's key, is the source alone.  The loss's name is for messages, reduced to letters, digits and [ _.-].

@@ -1572,6 +1572,21 @@ __device__ inline PathLane path_lane(const PathArgs& a)
     pl.s_end = pl.s_begin + a.spr < a.Sb ? pl.s_begin + a.spr : a.Sb;
     return pl;
 }
+// ... in a launch that holds several frames (k_path_views): `w` is the wave's place in its own frame's grid.  (A function of its own: with
+// the wave as a defaulted argument of path_lane, 62 instantiations of the kernels above scheduled their prologues differently.)
+__device__ inline PathLane path_lane_in_frame(const PathArgs& a, uint32_t w)
+{
+    PathLane pl;
+    pl.lane = threadIdx.x & (DRT_WAVE - 1);
+    pl.w = w;
+    pl.range = pl.w / a.n_groups;
+    const uint32_t group = pl.w - pl.range * a.n_groups;
+    pl.lp = group * DRT_WAVE + pl.lane;
+    pl.have = pl.range < a.n_ranges && pl.lp < a.Pb;
+    pl.s_begin = pl.range * a.spr;
+    pl.s_end = pl.s_begin + a.spr < a.Sb ? pl.s_begin + a.spr : a.Sb;
+    return pl;
+}
 // f32: the pixel's corner in double ONCE per lane; a sample then only adds its jitter (camera.hpp:53-58 in the form
 // cs = cs0 + u1 (2 aspect tan / W)): the sample's position inside the pixel is exact to ~2e-5 of a pixel and the
 // direction to 1 ulp of f32 -- the resolution the ray has anyway once it is stored in f32
@@ -2401,6 +2416,175 @@ k_path_lean(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict_
         block_grad_sums<NP>(tg.acc, s_red, gpart, pl.lane);
 }
 
+// ---- k_path_views: one scene from several cameras in one launch (drt_hip_render_views) ------------------------------------------------
+// The lockstep half of k_path for the forward-only form, the gradient columns and the general form, as an entry point of its own -- so that
+// no instantiation of k_path changes its name or its code.  The grid is the single-frame grid once per view: `view_blocks` blocks a view,
+// each view's waves exactly the waves drt_hip_render launches for that frame alone (the same spr, n_ranges and n_groups in `a0`), every view
+// starting on a block boundary, so a block's gradient sums add the same four waves.  A block derives its view from its index and takes the
+// view's camera constants, seed and stream from views[view] -- a wave-uniform address: scalar loads into scalar registers, where the
+// kernel's arguments would have been -- into its own copy of the arguments; everything downstream (camera_lane, path_camera, path_bounce,
+// add_emission) then runs as in k_path, on the same operands in the same order: view v's sums keep the bits of the single call.
+// The partial sums gain the view as their outermost dimension: fpart[view][range][row][pixel], counts[view][row][wave of the view],
+// gpart[block of the grid][row] (a view's blocks are consecutive), the general form's global history columns over the threads of the whole
+// grid (a0.hist_stride); the adjoint images stand one behind the other.  k_views_finish (below) reduces them.
+// (a closest-hit program type under a name of the shell's own: the same members, other instantiations of what takes it)
+template <typename SG> struct ViewsSig : SG {};
+struct PathView {
+    double eye[3], fwd[3], right[3], up[3];
+    double tan_half, aspect;
+    float eye_f[3], fwd_f[3], right_f[3], up_f[3], cs_step_f, ct_step_f;   // cast on the host as path_batch casts PathArgs' own
+    uint32_t seed, rng_stream;
+};
+// blocks per CU (= waves per SIMD): the budget of the lockstep k_path instantiation the form mirrors (path_min_blocks) -- but for the diffuse f64
+// gradient forms, columns of four and general: at DRT_F64_MIN_BLOCKS the compiler reports 20-28 bytes of scratch per lane for the shell, as
+// it does for those k_path instantiations themselves; with a block fewer the shell has none
+template <size_t RB, bool SPEC, int NP, int NSG, int NCR>
+constexpr int views_min_blocks()
+{
+    return (RB == 8 && !SPEC && NP != 0 && NP <= 4) ? DRT_F64_MIN_BLOCKS - 1 : path_min_blocks<RB, SPEC, NP, NSG, false, NCR>();
+}
+template <typename R, bool SPEC, int NP, int NCR, typename SG>
+__global__ void __launch_bounds__(DRT_BLOCK, (views_min_blocks<sizeof(R), SPEC, NP, SG::n, NCR>()))
+k_path_views(PathArgs a0, const PathView* __restrict__ views, uint32_t view_blocks, const DevScene<R>* __restrict__ sc, const R* __restrict__ params,
+             const float* __restrict__ adjoint, double* __restrict__ gpart, double* __restrict__ fpart, uint32_t* __restrict__ counts,
+             unsigned long long* __restrict__ total)
+{
+    static_assert(NP == 0 || NP == 4 || NP == 8 || NP == DRT_NP_ANY, "k_path_views: forward only, the gradient columns or the general form");
+    static_assert(!DRT_JACOBIAN_OF(NCR) && DRT_ROLES_OF(NCR) == 0, "k_path_views has no Jacobian form and no roles");
+    zero_totals(total);
+    typedef typename Q4<R>::T R4;
+    typedef typename Q2<R>::T R2;
+    constexpr int NC = DRT_NC_OF(NCR);
+    constexpr bool GEN = NP == DRT_NP_ANY;
+    static_assert(!GEN || NC == 0, "k_path_views: the general form without a gradient image");
+    // the block's view and its place among the view's blocks; the arguments as the single call's kernel would have had them
+    const uint32_t view = __builtin_amdgcn_readfirstlane(blockIdx.x / view_blocks);
+    const uint32_t view_block = blockIdx.x - view * view_blocks;
+    PathArgs a = a0;
+    {
+        const PathView& v = views[view];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            a.eye[i] = v.eye[i]; a.fwd[i] = v.fwd[i]; a.right[i] = v.right[i]; a.up[i] = v.up[i];
+            a.eye_f[i] = v.eye_f[i]; a.fwd_f[i] = v.fwd_f[i]; a.right_f[i] = v.right_f[i]; a.up_f[i] = v.up_f[i];
+        }
+        a.tan_half = v.tan_half; a.aspect = v.aspect;
+        a.cs_step_f = v.cs_step_f; a.ct_step_f = v.ct_step_f;
+        a.seed = v.seed; a.rng_stream = v.rng_stream;
+    }
+    const size_t view_waves = (size_t)a.n_groups * a.n_ranges;
+    if (adjoint)
+        adjoint += (size_t)view * (size_t)a.W * (size_t)a.H * 3;
+    if (fpart)
+        fpart += (size_t)view * ((size_t)a.n_ranges * 3 * a.Pb);
+    counts += (size_t)view * (2 * view_waves);
+
+    __shared__ PathSceneLds<R> lds;
+    __shared__ double s_red[DRT_BLOCK / DRT_WAVE][DRT_FAST_PARAMS * 3];
+    __shared__ TangentLds<R> s_tl;
+    __shared__ typename PickT<GEN, GenBlock<R>, NoLds>::T s_gen;
+    extern __shared__ uint32_t s_hist[];                  // GEN: [a.hist_lds][DRT_BLOCK] history words
+    if constexpr (GEN)
+        gen_zero(s_gen);
+    stage_path_scene(lds, sc, params);
+    const TangentLds<R>& tl = s_tl;
+    if (NC > 0 && !GEN)
+        stage_tangents(s_tl, lds);
+
+    const PathLane pl = path_lane_in_frame(a, __builtin_amdgcn_readfirstlane(view_block * (DRT_BLOCK / DRT_WAVE) + threadIdx.x / DRT_WAVE));
+
+    Tangents<R, NP, NC> tg;
+    __shared__ R s_acc[NP > 0 ? NP * 3 : 1][DRT_BLOCK];
+    tg.acc = &s_acc[0][threadIdx.x];
+    if constexpr (GEN)
+        gen_begin(s_gen, lds, sc, a, s_hist, reinterpret_cast<uint32_t*>(a.hist_ovf), tg);
+    else {
+#pragma unroll
+        for (int p = 0; p < NP; ++p)
+            tg.acc_set(p, mk<R>(R(0), R(0), R(0)));
+    }
+    double fx = 0, fy = 0, fz = 0;                        // radiance sum of this lane's pixel over the range
+    uint32_t n_seg = 0, n_capped = 0;                     // wave-uniform counters
+
+    uint32_t gpix = 0, px = 0, py = 0;                    // (the pixel within the view: the RNG key is the single call's)
+    V3<R> g = mk<R>(R(1), R(1), R(1));                    // render.cpp:80: radiance.backward(Vec3(1))
+    if (pl.have) {
+        gpix = path_global_pixel(a, a.p0 + pl.lp);
+        py = gpix / (uint32_t)a.W;
+        px = gpix - py * (uint32_t)a.W;
+        if (NP != 0 && adjoint)
+            g = mk<R>((R)adjoint[(size_t)gpix * 3], (R)adjoint[(size_t)gpix * 3 + 1], (R)adjoint[(size_t)gpix * 3 + 2]);
+    }
+    const CameraLane<R> cl = camera_lane<R>(a, px, py);
+    constexpr bool ARGS_F32 = path_args_f32<R, SG>();
+    const R pk_rr = ARGS_F32 ? (R)a.p_rr_f : (R)a.p_rr, inv_p_rr = ARGS_F32 ? (R)a.inv_p_rr_f : (R)a.inv_p_rr;
+    ProgRecs<SG::n, R> recs;
+    __shared__ typename PickT<(SG::n == 0), ProgLds, NoLds>::T s_prog;
+    recs.lds = reinterpret_cast<const ProgLds*>(&s_prog);
+    if (SG::n > 0)
+        recs.template load<SG>(sc);
+    if constexpr (sizeof(R) == 4 && SG::n == 0) {
+        const DevScene<float>* scf = reinterpret_cast<const DevScene<float>*>(sc);
+        if (threadIdx.x < DRT_PROG_SORTED_MAX) {
+            s_prog.rec[threadIdx.x] = *reinterpret_cast<const float4*>(scf->sorted[threadIdx.x]);
+            s_prog.shape[threadIdx.x] = scf->sorted_shape[threadIdx.x];
+        }
+        if (threadIdx.x < 8)
+            s_prog.kind_begin[threadIdx.x] = scf->kind_begin[threadIdx.x];
+        __syncthreads();
+    }
+
+    if (pl.range < a.n_ranges) {
+        for (uint32_t sl = pl.s_begin; sl < pl.s_end; ++sl) {
+            R4 ra;
+            R2 rb;
+            const uint32_t key = path_camera<R, ARGS_F32>(a, cl, gpix, px, py, sl, ra, rb);
+            // pathtracer.hpp:128 at depth 0
+            bool live = pl.have && a.depth_cap > 0 && !(a.min_bounces <= 0 && rng_draw(a.rng_stream, key, 2) < a.rr_threshold);
+            V3<R> T = mk<R>(R(1), R(1), R(1)), L = mk<R>(R(0), R(0), R(0));
+            uint32_t end_ids = DRT_ID_NONE;               // emission parameter of the light the path ended on
+            R end_inv_pk = R(1);
+            if (NC > 0 || GEN)
+                tg.new_path();
+            for (int kk = 0; kk < a.depth_cap; ++kk) {
+                const uint32_t n_live = (uint32_t)__popcll(wave_ballot(live));
+                if (n_live == 0)
+                    break;
+                n_seg += n_live;
+                const R pk = kk >= a.min_bounces ? pk_rr : R(1);                  // pathtracer.hpp:130
+                const R inv_pk = kk >= a.min_bounces ? inv_p_rr : R(1);
+                const uint32_t n_theta = draw_offset(kk, 0, a.min_bounces) + camera_draw_base(a.min_bounces);
+                const bool next_rr = (kk + 1) >= a.min_bounces;
+                const bool next_cap = (kk + 1) >= a.depth_cap;
+                bool alive, capped, on_light;
+                uint32_t light;
+                // (the program's type under the shell's own name -- ViewsSig --: the bounce is then the shell's own instantiation.  Shared with
+                //  k_path's, the forward-only f32 k_path's bounce had a second caller, which moved that kernel's inlining, a register and its stream)
+                path_bounce<R, SPEC, NP, NC, ViewsSig<SG>, (DRT_FREEZE_BY_ROW != 0 && sizeof(R) == 4 && !SPEC && SG::n <= DRT_LEAN_MAX_SHAPES)>(a, lds, tl, sc, params, recs, key, pk, inv_pk, n_theta, next_rr, next_cap, live, g,
+                                                        ra, rb, T, L, tg, alive, capped, on_light, light, nullptr, next_cap);
+                // (a light without a BxDF ends the path; its emission is added once per sample, behind the loop)
+                end_ids = on_light ? light : end_ids;
+                end_inv_pk = on_light ? inv_pk : end_inv_pk;
+                if (next_cap && !a.cap_is_roulette)
+                    n_capped += (uint32_t)__popcll(wave_ballot(capped));
+                live = alive;
+            }
+            if (wave_any(end_ids != DRT_ID_NONE)) {
+                if (end_ids != DRT_ID_NONE)
+                    add_emission<R, NP, NC, false, PathSceneLds<R>, 0>(lds, tl, params, end_ids, end_inv_pk, T, g, L, tg);
+            }
+            fx += (double)L.x; fy += (double)L.y; fz += (double)L.z;
+        }
+        if (fpart && pl.have)
+            store_rows3(fpart + ((size_t)pl.range * 3) * a.Pb + pl.lp, a.Pb, fx, fy, fz);
+        store_counts(a, pl, counts, n_seg, n_capped);
+    }
+    if constexpr (GEN)
+        gen_finish(s_gen, a, gpart);
+    else if constexpr (NP > 0)
+        block_grad_sums<NP>(tg.acc, s_red, gpart, pl.lane);
+}
+
 // ---- the unbiased integration operator (integrate.hpp:11-24, 39-52; README.md:104-136) in one launch ------------------
 // The reference's IntegrateBackward does not reuse the forward samples: where a gradient arrives at a vertex it draws a
 // FRESH direction, evaluates forward(sample) -- a whole new suffix path -- back-propagates grad / pdf through
@@ -3122,6 +3306,91 @@ k_sets_grad_finish(const double* __restrict__ gpart, int n_blocks, int row_strid
     add_blocks(red, none ? 0 : n_blocks, [&](int b) { return gpart[(size_t)b * row_stride + src]; });
     if (threadIdx.x == 0)
         out[blockIdx.x] = red[0];
+}
+
+// ---- everything behind a k_path_views launch, in ONE launch (drt_hip_render_views) ----------------------------------------------------
+// k_path_finish over the views' partial sums, view v's with the sums and the order the single call's finishing launch has over that frame's:
+//   blocks [0, n_views film_blocks):          out[v][pixel] = float(sum over the sample ranges, in range order, / spp), film_blocks a view
+//   blocks [.., + grad_words):                word p of every view's gradient -- the sum over the VIEW's blocks of gpart[block][p], a strided sum
+//                                             per thread, then an LDS tree, as k_path_finish adds a frame's -- to view_grads[v][p], and their
+//                                             sum in view order, in fp64, to grad_sum[p].  A parameter that requires no gradient (slot_map:
+//                                             DevScene::grad_slot) gets zero; general: gpart's rows are table rows, slot_map maps to them
+//   the rest:                                 total[0] += segments, total[3] += capped paths over all views (integers; k_path_views zeroed them)
+// No atomics on a float: the same call gives the same bits.
+__global__ void __launch_bounds__(DRT_BLOCK)
+k_views_finish(PathArgs a, uint32_t n_views, const double* __restrict__ fpart, float* __restrict__ out, uint32_t film_blocks,
+               const double* __restrict__ gpart, int view_blocks, int n_rows, int row_stride, int general, const unsigned short* __restrict__ slot_map,
+               double* __restrict__ view_grads, double* __restrict__ grad_sum, uint32_t grad_words,
+               const uint32_t* __restrict__ counts, uint32_t view_waves, unsigned long long* __restrict__ total)
+{
+    __shared__ double red[DRT_BLOCK];
+    const uint32_t all_film = n_views * film_blocks;
+    if (blockIdx.x < all_film) {
+        const uint32_t v = blockIdx.x / film_blocks, fb = blockIdx.x - v * film_blocks;
+        const double* fv = fpart + (size_t)v * ((size_t)a.n_ranges * 3 * a.Pb);
+        float* ov = out + (size_t)v * (size_t)a.W * (size_t)a.H * 3;
+        const uint32_t stride = film_blocks * DRT_BLOCK;
+        const double inv = 1.0 / (double)a.spp;
+        for (uint32_t j = fb * DRT_BLOCK + threadIdx.x; j < a.Pb; j += stride) {
+            double r = 0, g = 0, b = 0;
+            for (uint32_t q = 0; q < a.n_ranges; ++q) {
+                const double* f = fv + ((size_t)q * 3) * a.Pb + j;
+                r += f[0]; g += f[(size_t)a.Pb]; b += f[(size_t)a.Pb * 2];
+            }
+            const uint32_t gp = path_global_pixel(a, a.p0 + j);
+            drt_f3 px;
+            px.x = (float)(r * inv); px.y = (float)(g * inv); px.z = (float)(b * inv);
+            *reinterpret_cast<drt_f3_u*>(ov + (size_t)gp * 3) = px;
+        }
+        return;
+    }
+    if (blockIdx.x < all_film + grad_words) {
+        const int p = (int)(blockIdx.x - all_film);
+        const int slot = slot_map[p / 3];
+        const int src = slot == (int)DRT_SLOT_NONE ? n_rows : (general ? slot * 3 + p % 3 : p);
+        double sum = 0;
+        for (uint32_t v = 0; v < n_views; ++v) {
+            double x = 0;
+            if (src < n_rows)
+                for (int b = threadIdx.x; b < view_blocks; b += DRT_BLOCK)
+                    x += gpart[((size_t)v * view_blocks + b) * row_stride + src];
+            red[threadIdx.x] = x;
+            __syncthreads();
+            for (int off = DRT_BLOCK / 2; off > 0; off >>= 1) {
+                if ((int)threadIdx.x < off)
+                    red[threadIdx.x] += red[threadIdx.x + off];
+                __syncthreads();
+            }
+            if (threadIdx.x == 0) {
+                if (view_grads)
+                    view_grads[(size_t)v * grad_words + p] = red[0];
+                sum = v == 0 ? red[0] : sum + red[0];
+            }
+            __syncthreads();
+        }
+        if (threadIdx.x == 0 && grad_sum)
+            grad_sum[p] = sum;
+        return;
+    }
+    {
+        const uint32_t first = all_film + grad_words, nb = gridDim.x - first, me = blockIdx.x - first;
+        const uint64_t n = (uint64_t)n_views * view_waves;
+        unsigned long long seg = 0, cap = 0;
+        for (uint64_t i = (uint64_t)me * DRT_BLOCK + threadIdx.x; i < n; i += (uint64_t)nb * DRT_BLOCK) {
+            const uint64_t v = i / view_waves, w = i - v * view_waves;
+            const uint32_t* cv = counts + v * 2 * view_waves;
+            seg += cv[w];
+            cap += cv[(size_t)view_waves + w];
+        }
+        for (int off = DRT_WAVE / 2; off > 0; off >>= 1) {
+            seg += __shfl_down(seg, off);
+            cap += __shfl_down(cap, off);
+        }
+        if ((threadIdx.x & (DRT_WAVE - 1)) == 0) {
+            if (seg) atomicAdd(total, seg);
+            if (cap) atomicAdd(total + 3, cap);
+        }
+    }
 }
 
 // ---- the cross-sample normal equations of a frame in the span of K directions (drt_hip_render_normal_equations_cross) -------------

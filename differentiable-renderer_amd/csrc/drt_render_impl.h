@@ -215,6 +215,7 @@ struct PathForm {
     unsigned long long lights;      // ... and with them, for a compiled-in program: the scene's pure lights (an emitter, no BxDF) as a bit set in scene
                                     // order -- k_path_lean's last vertex asks only whether the path ended on one; 0: not known
     PathProg prog;
+    bool views;                     // k_path_views: the biased lockstep forms -- forward only, columns, general -- over several frames (drt_hip_render_views)
     bool lean() const { return fixed && no_lit_bxdf; }
 };
 
@@ -247,6 +248,9 @@ struct Shard {
     bool cross() const { return neq && neq->cross; }   // drt_hip_render_normal_equations_cross: 6 rows a direction + 3, k_cross_eq
     int jac_rows() const { return cross() ? n_dirs * 6 + 3 : (neq || sets) ? (n_dirs > 0 ? n_dirs : ctx->n_params) * (sets && (sets->along || sets->cross) ? 6 : 3) : 3; }   // rows a pixel's sums have in `gpix`
     bool sets_grad() const { return sets && sets->grad; }   // drt_hip_render_param_sets_grad: gradient tables, no per-pixel sums
+    const ViewsRequest* views = nullptr;      // drt_hip_render_views: k_path_views, then k_views_finish
+    size_t n_views() const { return views ? (size_t)views->n_views : 1; }   // frames in the one path launch: the partial sums' outermost dimension
+    bool views_grad() const { return views && views->backward; }
     bool pixel_sums() const { return gimg_param >= 0 || fwd_tangent || neq || (sets && !sets->grad); }   // the lanes' per-pixel sums leave the path kernel (gimg_part)
     // the scene in compute type R
     const DevScene<R>* d_scene;
@@ -346,6 +350,8 @@ inline std::string path_kernel_name(const drt_hip_ctx* ctx, const PathForm& f)
         snprintf(name, sizeof name, "k_path_unbiased<%s, %s, %d, %s>", type, sp, f.np, sg.c_str());
     else if (f.op == PathOp::param_sets_cross)
         snprintf(name, sizeof name, "k_path_sets_cross<%s, %s, %d, %s>", type, sp, f.nc, sg.c_str());
+    else if (f.views)
+        snprintf(name, sizeof name, "k_path_views<%s, %s, %d, %d, %s>", type, sp, f.np, DRT_NC_ROLES(f.nc, 0, 0), sg.c_str());
     else if (f.lean())
         snprintf(name, sizeof name, "k_path_lean<%s, %d, %d, %s, 0x%llxull>", type, f.np, DRT_NC_ROLES(f.nc, 0, 0) | f.roles << 8, sg.c_str(), f.lights);
     else
@@ -385,6 +391,15 @@ const void* library_path_kernel(const PathForm& f)
         if (f.np == 0 && f.nc == 0) return k(IntC<0>(), IntC<0>());
         return (const void*)nullptr;
     };
+    if (f.views) {
+        // several frames in one launch: the lockstep biased forms -- forward only, the columns, the general form --, every program
+        if (f.op != PathOp::biased || f.regen || f.roles != 0 || f.nc == 1)
+            return nullptr;
+        return columns([&](auto np, auto nc) {
+            return with_bool(f.spec, [&](auto spec) { return with_bool(f.prog == PathProg::cornell, [&](auto cornell) {
+                return (const void*)k_path_views<R, decltype(spec)::value, decltype(np)::value, decltype(nc)::value, std::conditional_t<cornell, SigCornell, SigNone>>; }); });
+        });
+    }
     if (f.lean()) {
         // no roulette in the loop, no emitting scatterer (shard_plan: biased, f32, diffuse, lockstep): the headline's gradient form with the
         // reference's roles and the forward-only form, for the reference's kinds and the kind-sorted program; any other roles through hiprtc
@@ -501,14 +516,14 @@ void shard_plan(Shard<R>& s)
     // gradients: <= 8 parameters in registers / LDS columns; any number the kernels can stage (136: every analytic scene) through
     // the general form -- vertex history + per-wave tables (drt_path.h, DRT_NP_ANY); the gradient IMAGE (the lanes' own sums) in
     // analytic scenes too
-    const bool tangents = s.backward || s.gimg_param >= 0 || s.neq;
+    const bool tangents = s.backward || s.gimg_param >= 0 || s.neq || s.views_grad();
     const bool grads_ok = !tangents || ctx->n_params <= DRT_FAST_PARAMS || (s.n_dirs > 0 && ctx->n_params <= DRT_PATH_LDS_PARAMS) ||
                           (ctx->n_params <= DRT_PATH_LDS_PARAMS && tuning().path_general && (s.gimg_param < 0 || !ctx->has_mesh));
     s.use_path = ((s.can_fuse && ctx->prog_ok) || mesh_ok) && D > 0 && grads_ok &&
                  rp->bounces_per_launch <= 0 && tuning().shade_bounces <= 0 && tuning().dump_path == -1;
     s.mesh_path = s.use_path && ctx->has_mesh;
     PathForm& f = s.path;
-    const bool lane_is_pixel = (s.gimg_param >= 0 || s.neq || s.sets) && !s.mesh_path;   // the gradient image / the Jacobian is the lanes' own sums: lockstep form only
+    const bool lane_is_pixel = (s.gimg_param >= 0 || s.neq || s.sets || s.views) && !s.mesh_path;   // the gradient image / the Jacobian is the lanes' own sums: lockstep form only
     // (k_path_mesh: every lane on its own, always; k_path_unbiased walks its samples in lockstep)
     f.regen = (tuning().path_regen > 0 || s.mesh_path) && !s.unbiased && !lane_is_pixel;
     if (s.use_path && !s.mesh_path && !lane_is_pixel && tuning().path_regen < 0 && !s.unbiased) {
@@ -565,9 +580,10 @@ void shard_plan(Shard<R>& s)
             f.op = PathOp::param_sets_cross;
     }
     f.loss = s.loss_l2;
+    f.views = s.views != nullptr;   // (the forms above as one frame's plan picks them; no roles, not k_path_lean's facts: the shell has neither)
     // the slots' roles as the scene's records give them: for the form the headline runs -- diffuse, f32, lockstep, parameters in columns
     f.roles = 0;
-    if (tuning().path_roles && tangents && !gen && sizeof(R) == 4 && !f.spec && !f.regen && !f.loss && f.op == PathOp::biased && s.gimg_param < 0 && !s.neq &&
+    if (tuning().path_roles && !f.views && tangents && !gen && sizeof(R) == 4 && !f.spec && !f.regen && !f.loss && f.op == PathOp::biased && s.gimg_param < 0 && !s.neq &&
         ctx->colour_mask != 0 && ctx->emission_mask != 0)
         f.roles = (int)(ctx->colour_mask | ctx->emission_mask << 8);
     // ... and, for that form and the forward-only one, what else the host knows (k_path_lean, drt_path.h): the render has no roulette inside
@@ -575,7 +591,7 @@ void shard_plan(Shard<R>& s)
     // ... and, with both, which shapes are pure lights (upload_scene_one: an emitter, no BxDF), for the kernels whose program is compiled in
     f.fixed = f.no_lit_bxdf = false;
     f.lights = 0;
-    if (sizeof(R) == 4 && !f.spec && !f.regen && !f.loss && f.op == PathOp::biased && !s.pixel_sums() &&
+    if (sizeof(R) == 4 && !f.views && !f.spec && !f.regen && !f.loss && f.op == PathOp::biased && !s.pixel_sums() &&
         ((f.np == 4 && f.roles != 0) || (f.np == 0 && f.nc == 0)) &&
         rp->absorb >= 1.0 && rp->min_bounces == D && !ctx->emissive_bxdf) {
         f.fixed = f.no_lit_bxdf = true;
@@ -645,7 +661,7 @@ void shard_plan(Shard<R>& s)
         cap = s.total_paths;               // no per-path memory: one batch covers the frame
     if (tuning().batch_paths > 0)
         cap = (uint64_t)tuning().batch_paths;
-    if (s.neq || s.sets)
+    if (s.neq || s.sets || s.views)
         cap = s.total_paths;               // k_normal_eq / k_sets_finish reads every range of every pixel of the shard: one batch (render_impl refuses frames beyond 2^31 paths)
     if (cap > s.total_paths) cap = s.total_paths;
     if (cap < 1) cap = 1;
@@ -684,12 +700,12 @@ void shard_plan(Shard<R>& s)
     const int tail_bounces = tail_bounces_now();
     s.tail_nb = s.shade_tail && (tail_bounces > 1 || (tail_bounces == 0 && s.unbiased)) ? 2 : 1;
     s.tail_ring = s.tail_nb > 1 ? 3 : 2;
-    s.overlap_ok = ctx->overlap_next && s.use_path && !s.timing && !s.pixel_sums() && !s.sets && !s.sample_loss && ctx->path_stream[0] && ctx->ev_copied[0];
+    s.overlap_ok = ctx->overlap_next && s.use_path && !s.timing && !s.pixel_sums() && !s.sets && !s.views && !s.sample_loss && ctx->path_stream[0] && ctx->ev_copied[0];
     const bool odd = s.overlap_ok && (ctx->slot & 1);
     s.fpart_buf = odd ? &ctx->fpart2 : &ctx->fpart;
     s.gpart_buf = odd ? &ctx->gpart2 : &ctx->gpart;
     s.counts_buf = odd ? &ctx->counts2 : &ctx->counts;
-    s.cw = s.use_path ? (s.mesh_path ? 3 : 2) * s.path_waves      // [segments | capped paths (| rays the BVH walk took)] per wave
+    s.cw = s.use_path ? (s.mesh_path ? 3 : 2) * s.path_waves * s.n_views()     // [segments | capped paths (| rays the BVH walk took)] per wave
                       : (size_t)(D + 2) * s.max_regions;          // counts[depth][region] of one batch (row D: capped paths, D + 1: rays kept in registers)
     // a k_path launch that covers the whole frame is followed by ONE finishing launch that WRITES image, gradients and
     // totals (k_path_finish); every other route accumulates into zeroed buffers
@@ -730,7 +746,7 @@ int shard_buffers(Shard<R>& s)
     int rc;
     memset(&s.cs, 0, sizeof s.cs);
     if (s.use_path) {
-        if ((rc = ensure(ctx, *s.fpart_buf, (size_t)s.path_ranges * 3 * s.Pb * sizeof(double))) != DRT_OK) return rc;
+        if ((rc = ensure(ctx, *s.fpart_buf, s.n_views() * (size_t)s.path_ranges * 3 * s.Pb * sizeof(double))) != DRT_OK) return rc;
         if (s.pixel_sums())
             if ((rc = ensure(ctx, ctx->gpix, (size_t)s.path_ranges * (size_t)s.jac_rows() * s.Pb * sizeof(double))) != DRT_OK) return rc;
         if (s.neq) {
@@ -796,10 +812,10 @@ int shard_buffers(Shard<R>& s)
     }
     if ((rc = ensure(ctx, *s.counts_buf, s.cw * sizeof(uint32_t))) != DRT_OK) return rc;
     if ((rc = ensure(ctx, ctx->segtotal[ctx->slot], DRT_TOTAL_WORDS * sizeof(unsigned long long))) != DRT_OK) return rc;
-    if (s.backward || s.sets_grad()) {   // per-block partial sums: K6's persistent grid, the shade kernel's one block per 4 regions, or k_path's blocks
+    if (s.backward || s.sets_grad() || s.views_grad()) {   // per-block partial sums: K6's persistent grid, the shade kernel's one block per 4 regions, or k_path's blocks
         const size_t shade_blocks = (s.max_regions + DRT_BLOCK / DRT_WAVE - 1) / (DRT_BLOCK / DRT_WAVE);
         size_t blocks = std::max<size_t>(shade_blocks, (size_t)grid_for(ctx, N));
-        const size_t path_blocks = (s.path_waves + DRT_BLOCK / DRT_WAVE - 1) / (DRT_BLOCK / DRT_WAVE);
+        const size_t path_blocks = s.n_views() * ((s.path_waves + DRT_BLOCK / DRT_WAVE - 1) / (DRT_BLOCK / DRT_WAVE));   // (k_path_views: a frame's blocks per view)
         if (s.use_path && path_blocks > blocks)
             blocks = path_blocks;
         // rows per block: 24 for the register paths (<= 8 parameters), else one per parameter channel (LDS accumulators)
@@ -864,6 +880,24 @@ void shard_args(Shard<R>& s)
     a.aspect = (double)cam->width / (double)cam->height;
 }
 
+// One view's record of k_path_views' table: what shard_args and path_batch (below) put into the kernel's arguments for a camera and a seed, value
+// for value and cast for cast -- the kernel patches its arguments with it and must find the single call's bits there
+inline void fill_path_view(PathView& v, const drt_camera_desc& cam, uint32_t seed)
+{
+    memset(&v, 0, sizeof v);
+    for (int i = 0; i < 3; ++i) {
+        v.eye[i] = cam.eye[i]; v.fwd[i] = cam.forward[i]; v.right[i] = cam.right[i]; v.up[i] = cam.up[i];
+        v.eye_f[i] = (float)v.eye[i]; v.fwd_f[i] = (float)v.fwd[i]; v.right_f[i] = (float)v.right[i]; v.up_f[i] = (float)v.up[i];
+    }
+    v.tan_half = tan(cam.vfov / 2.);
+    v.aspect = (double)cam.width / (double)cam.height;
+    const double inv_W = 1.0 / (double)cam.width, inv_H = 1.0 / (double)cam.height;
+    v.cs_step_f = (float)(2. * v.aspect * v.tan_half * inv_W);
+    v.ct_step_f = (float)(2. * v.tan_half * inv_H);
+    v.seed = seed;
+    v.rng_stream = drt_rng_stream(seed, 0u);
+}
+
 // ---- route 1: the whole batch in ONE launch: camera -> path -> radiance sums + gradient partials (k_path) ----------------
 template <typename R>
 int path_batch(Shard<R>& s)
@@ -915,7 +949,7 @@ int path_batch(Shard<R>& s)
         pa.hist_lds = std::min<uint32_t>(hist_words, (uint32_t)tuning().gen_hist_lds);
     const unsigned hist_bytes = pa.hist_lds * DRT_BLOCK * (unsigned)sizeof(uint32_t);
     const uint32_t hist_ovf_words = hist_words - pa.hist_lds;
-    const unsigned short* slot_map = gen ? (const unsigned short*)((const char*)s.d_scene + offsetof(DevScene<R>, grad_slot)) : (const unsigned short*)nullptr;
+    const unsigned short* slot_map = (gen || s.views) ? (const unsigned short*)((const char*)s.d_scene + offsetof(DevScene<R>, grad_slot)) : (const unsigned short*)nullptr;
     const int g_rows = gen ? (int)s.gen_rows : s.n_fast * 3, g_stride = gen ? (int)s.gen_rows : DRT_FAST_PARAMS * 3;
     const size_t n_waves = (size_t)pa.n_groups * pa.n_ranges;
     const int gpath = (int)((n_waves + DRT_BLOCK / DRT_WAVE - 1) / (DRT_BLOCK / DRT_WAVE));
@@ -924,7 +958,11 @@ int path_batch(Shard<R>& s)
     const float* d_adjoint = s.d_adjoint;
     double* gpart = s.gpart;
     uint32_t* counts = s.counts;
-    double* fpart = s.film ? (double*)s.fpart_buf->p : (double*)nullptr;
+    double* fpart = (s.film || (s.views && s.views->d_images)) ? (double*)s.fpart_buf->p : (double*)nullptr;
+    // (k_path_views: the frame's grid once per view, every view on a block boundary)
+    const uint32_t view_blocks = (uint32_t)gpath;
+    const unsigned grid_blocks = (unsigned)((size_t)gpath * s.n_views());
+    const void* d_views = s.views ? s.views->d_table : nullptr;
     double* gpix = s.pixel_sums() ? (double*)ctx->gpix.p : (double*)nullptr;   // gradient image / derivative image partials
     unsigned long long* ptotal = s.path_finish ? s.totals : (unsigned long long*)nullptr;
     // (frames that overlap: this frame's grid goes to the lane's own stream, behind whoever still uses the lane's buffers, and
@@ -953,7 +991,7 @@ int path_batch(Shard<R>& s)
     // (the kind-sorted program gives way to a kernel of the scene's own once it has rendered enough for the compile to pay)
     PathForm form = s.path;
     hipFunction_t jit = s.loss_kernel;
-    ctx->scene_work += (uint64_t)a.n_paths * (uint64_t)(s.D > 0 ? s.D : 1);
+    ctx->scene_work += (uint64_t)a.n_paths * s.n_views() * (uint64_t)(s.D > 0 ? s.D : 1);
     if (form.prog == PathProg::sorted && form.op != PathOp::mesh && ctx->jit_mode > 0 && !form.f64 &&
         (ctx->jit_mode > 1 || ctx->scene_work >= DRT_JIT_AFTER_WORK) && (jit = jit_function(ctx, path_kernel_name(ctx, form), ctx->jit_mode > 1)))
         form.prog = PathProg::scene;
@@ -980,7 +1018,7 @@ int path_batch(Shard<R>& s)
     int rc;
     if ((rc = timing_begin(ctx, s.timing, DRT_K_PATH)) != DRT_OK) return rc;
     uint32_t* ovf = s.mesh_path ? (uint32_t*)ctx->mesh_ovf[(s.overlap_ok && lane2) ? 1 : 0].p : (uint32_t*)nullptr;
-    uint32_t ovf_stride = (uint32_t)gpath * DRT_BLOCK;
+    uint32_t ovf_stride = (uint32_t)grid_blocks * DRT_BLOCK;
     pa.hist_stride = ovf_stride;
     if (gen && hist_ovf_words > 0) {
         // the general form's history beyond its LDS words: a column per thread of the grid (one area per k_path stream); the
@@ -1013,12 +1051,13 @@ int path_batch(Shard<R>& s)
     void* args_path[] = {&pa, &d_scene, &d_params, &d_adjoint, &gpart, &fpart, &counts, &ptotal, &gpix, &loss_lv, &loss_part};
     void* args_unb[] = {&pa, &d_scene, &d_params, &d_adjoint, &gpart, &fpart, &counts, &ptotal};
     void* args_mesh[] = {&pa, &d_scene, &d_params, &d_adjoint, &s.bvh, &ovf, &ovf_stride, &gpart, &fpart, &counts, &ptotal, &gpix};
-    void** args = form.op == PathOp::unbiased ? args_unb : (form.op == PathOp::mesh ? args_mesh : args_path);
+    void* args_views[] = {&pa, &d_views, (void*)&view_blocks, &d_scene, &d_params, &d_adjoint, &gpart, &fpart, &counts, &ptotal};
+    void** args = form.views ? args_views : (form.op == PathOp::unbiased ? args_unb : (form.op == PathOp::mesh ? args_mesh : args_path));
     const unsigned lds_bytes = path_dynamic_lds<R>(form, ctx->n_params, hist_bytes);
     if (jit)
-        HIPCHK(ctx, hipModuleLaunchKernel(jit, (unsigned)gpath, 1, 1, DRT_BLOCK, 1, 1, lds_bytes, ks, args, nullptr));
+        HIPCHK(ctx, hipModuleLaunchKernel(jit, grid_blocks, 1, 1, DRT_BLOCK, 1, 1, lds_bytes, ks, args, nullptr));
     else
-        HIPCHK(ctx, hipLaunchKernel(fn, dim3(gpath), dim3(DRT_BLOCK), args, lds_bytes, ks));
+        HIPCHK(ctx, hipLaunchKernel(fn, dim3(grid_blocks), dim3(DRT_BLOCK), args, lds_bytes, ks));
     if ((rc = timing_end(ctx, s.timing)) != DRT_OK) return rc;
     if (overlap) {
         HIPCHK(ctx, hipEventRecord(ctx->ev_path[lane2], ks));
@@ -1027,8 +1066,24 @@ int path_batch(Shard<R>& s)
     st->launches[DRT_K_PATH]++;
     if (s.sample_loss)
         s.loss_parts += (uint32_t)n_waves;
-    st->path_bytes += (s.film ? (uint64_t)pa.n_ranges * a.Pb * 3 * sizeof(double) : 0) +
-                      (backward ? (uint64_t)gpath * (uint64_t)g_stride * sizeof(double) : 0) + (s.mesh_path ? 3 : 2) * n_waves * sizeof(uint32_t);
+    // (k_path_views: a frame's sums per view, whichever of them the call asked for)
+    st->path_bytes += s.n_views() * ((fpart ? (uint64_t)pa.n_ranges * a.Pb * 3 * sizeof(double) : 0) +
+                                     ((backward || s.views_grad()) ? (uint64_t)gpath * (uint64_t)g_stride * sizeof(double) : 0) +
+                                     (s.mesh_path ? 3 : 2) * n_waves * sizeof(uint32_t));
+    if (s.path_finish && s.views) {
+        // the views' images, their gradients, the gradients' sum in view order and the totals in one launch (timed in the film slot)
+        const ViewsRequest& q = *s.views;
+        const uint32_t film_blocks = q.d_images ? (uint32_t)grid_for(ctx, a.Pb) : 0u;
+        const uint32_t grad_words = q.backward ? (uint32_t)ctx->n_user_params * 3u : 0u;
+        const uint32_t count_blocks = (uint32_t)std::min<size_t>(64, (n_waves * s.n_views() + DRT_BLOCK - 1) / DRT_BLOCK);
+        DRT_TIMED(s, DRT_K_FILM,
+                  hipLaunchKernelGGL(k_views_finish, dim3((unsigned)s.n_views() * film_blocks + grad_words + count_blocks), dim3(DRT_BLOCK), 0, ctx->stream, pa,
+                                     (uint32_t)s.n_views(), (const double*)fpart, q.d_images, film_blocks, (const double*)gpart, gpath, g_rows, g_stride,
+                                     gen ? 1 : 0, slot_map, q.d_view_grads, q.d_grad, grad_words, (const uint32_t*)counts, (uint32_t)n_waves, s.totals));
+        st->units[DRT_K_FILM] += (uint64_t)a.n_paths * s.n_views();
+        s.path_finished = true;
+        return DRT_OK;
+    }
     if (s.path_finish) {
         // image, gradients and totals of the frame in one launch (timed in the film slot)
         const uint32_t film_blocks = s.film ? (uint32_t)grid_for(ctx, a.Pb) : 0u;
@@ -1469,6 +1524,11 @@ int render_impl(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_p
     s.n_dirs = directions ? tangent->n_dirs : (param_sets ? tangent->sets->n_sets : 0);
     if (sets_grad)
         s.d_adjoint = tangent->sets->d_adjoints;
+    const bool views = tangent && tangent->kind == Kind::views;
+    if (views) {
+        s.views = tangent->views;
+        s.d_adjoint = tangent->views->d_adjoints;
+    }
     s.d_params = forward || directions || param_sets ? (const R*)tangent->d_params
                                                      : (sizeof(R) == 4 ? (const R*)ctx->d_params_f : (const R*)ctx->d_params_d);
     s.sample_loss = ctx->sample_loss_render;
@@ -1506,6 +1566,10 @@ int render_impl(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_p
                                        "which this render does not take (a DRT_HIP_* setting that forces the queue wavefront or a batch size, paths "
                                        "that end at depth 0, or a scene its intersection program does not cover)");
     }
+    if (views && (!s.use_path || s.mesh_path || !s.path_finish || !s.path.views || s.path.op != PathOp::biased || s.path.regen))
+        return fail(ctx, DRT_ERR_UNSUPPORTED, "views: they come from the one-launch path kernel's lockstep forms over the whole shard in one batch, which "
+                                              "this render does not take (a DRT_HIP_* setting that forces the queue wavefront, paths that end at "
+                                              "depth 0, or a scene its intersection program does not cover)");
     if (!ctx->user_header.empty()) {
         // caller-defined shape kinds live in the one-launch path kernel hiprtc compiles for the scene, nowhere else
         if (ctx->jit_mode <= 0)
@@ -1581,7 +1645,7 @@ int render_impl(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_p
         DRT_TIMED(s, DRT_K_GRADREDUCE,
                   hipLaunchKernelGGL(k_loss_finish, dim3(1), dim3(DRT_BLOCK), 0, ctx->stream, (const double*)ctx->loss_part.p, s.loss_parts, (double*)ctx->loss_out.p));
     st->batches = batch;
-    st->paths = s.total_paths;
+    st->paths = s.total_paths * (uint64_t)s.n_views();
     if (film && d_out_rgb && !s.path_finished)
         hipLaunchKernelGGL(k_resolve, dim3(grid_for(ctx, n_local_pixels)), dim3(DRT_BLOCK), 0, ctx->stream, a, n_local_pixels, film, d_out_rgb);
     if (s.pixel_sums() && gfilm && d_out_gimg && !s.path_finished)

@@ -16,6 +16,7 @@
 //   drt::hip::render_param_sets(scene, cam, tracer, spp, {set, ...}, target, imgs, &losses [, options])      up to 8 parameter sets, one trace
 //   drt::hip::render_param_sets_along(scene, cam, tracer, spp, {set, ...}, target [, imgs, tangent_imgs, options])   up to 4 sets with a direction each: loss, slope, curvature
 //   drt::hip::render_param_sets_grad(scene, cam, tracer, spp, {set, ...} [, adjoints, options])     up to 8 sets with a summed gradient each, one trace
+//   drt::hip::render_views(scene, {cam, ...}, tracer, spp, imgs [, options, adjoints, seeds])       up to 64 cameras of one size, one trace
 //   drt::hip::normal_equations_along(scene, cam, tracer, spp, {direction, ...}, options, target_or_residual) Gauss-Newton in their span
 //   drt::hip::normal_equations_cross(scene, cam, tracer, spp, {direction, ...}, options, target)             ... unbiased from one render
 //   drt::hip::render(scene of Dual<U>, ...)
@@ -1267,6 +1268,54 @@ inline SetsGrad<T> render_param_sets_grad(const Scene<T>& scene, const Camera<T>
         for (std::size_t p = 0; p < n; ++p)
             r.grads[k].emplace_back(flat.handles[p], Vector<T, 3>{T(sums[(k * n + p) * 3]), T(sums[(k * n + p) * 3 + 1]), T(sums[(k * n + p) * 3 + 2])});
     return r;
+}
+
+// ---- one scene from several cameras in one trace (drt_hip_render_views) ----------------------------------------------------------------
+// render() for up to DRT_HIP_MAX_VIEWS cameras of one size at once: images[v * width * height + pixel] is what render() with cameras[v]
+// leaves in its img, bit for bit; with Options::backward the SUM over the views of what those calls add to the handles' grad() is added to
+// them (the views' gradients added in view order), adjoints + v * width * height view v's adjoint image (nullptr: all ones).  `seeds`
+// (one per view; empty: Options::seed for every view).  One device; the biased operator.  Throws what render() throws for a scene it
+// cannot flatten.
+template <typename T>
+inline Stats render_views(const Scene<T>& scene, const std::vector<Camera<T>>& cameras, const Pathtracer<T>& tracer, std::size_t spp,
+                          Vector<T, 3>* images, const Options& opt = Options(), const Vector<T, 3>* adjoints = nullptr,
+                          const std::vector<uint32_t>& seeds = std::vector<uint32_t>())
+{
+    const char* who = "drt::hip::render_views";
+    if (opt.unbiased || opt.sample_loss_l2)
+        throw std::runtime_error(std::string(who) + ": the biased operator (no unbiased, no sample_loss_l2)");
+    detail::one_device(who, opt);
+    if (cameras.empty() || cameras.size() > (std::size_t)DRT_HIP_MAX_VIEWS)
+        throw std::runtime_error(std::string(who) + ": 1 ... DRT_HIP_MAX_VIEWS = 64 cameras");
+    if (!seeds.empty() && seeds.size() != cameras.size())
+        throw std::runtime_error(std::string(who) + ": a seed per camera, or none");
+    FlatScene<T> flat = flatten(scene);
+    const std::size_t V = cameras.size(), npix = cameras[0].width() * cameras[0].height();
+    std::vector<drt_camera_desc> cds;
+    for (const Camera<T>& cam : cameras) {
+        if (cam.width() != cameras[0].width() || cam.height() != cameras[0].height())
+            throw std::runtime_error(std::string(who) + ": the cameras differ in width or height (all views share one size)");
+        cds.push_back(describe(cam));
+    }
+    const std::vector<float> adj = adjoints && opt.backward ? detail::to_floats(adjoints, npix * V) : std::vector<float>();
+    const drt_render_params rp = detail::render_params(tracer.absorb(), tracer.min_bounces(), spp, opt, detail::reverse_flags(opt));
+    std::vector<double> grads((flat.requires_grad.size() ? flat.requires_grad.size() : 1) * 3, 0.0);
+    std::vector<float> frames(images ? npix * 3 * V : 0, 0.f);
+    if (!images && !opt.backward)
+        throw std::runtime_error(std::string(who) + ": nothing to compute (no images, no backward)");
+    drt_hip_stats st{};
+    {
+        detail::Session s = detail::Session::on_first_device(opt, flat);
+        s.ctx.check(drt_hip_render_views(s.ctx.get(), cds.data(), (int32_t)V, &rp, seeds.empty() ? nullptr : seeds.data(),
+                                         adj.empty() ? nullptr : adj.data(), images ? frames.data() : nullptr,
+                                         opt.backward ? grads.data() : nullptr, nullptr, &st),
+                    "drt_hip_render_views");
+    }
+    if (images)
+        detail::from_buffer(frames.data(), npix * V, images);
+    if (opt.backward)
+        detail::accumulate_grads(flat.handles, flat.requires_grad, grads.data());
+    return detail::to_stats(st);
 }
 
 // ---- the per-sample loss from the caller's own source (drt_hip_set_sample_loss / drt_hip_render_sample_loss) ------------------------

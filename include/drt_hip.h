@@ -616,6 +616,38 @@ int drt_hip_render_param_sets_cross(drt_hip_ctx* ctx, const drt_camera_desc* cam
                                     float* out_images /* n_sets x H x W x 3, may be NULL */, double* out_loss /* n_sets x 3 */,
                                     double* out_bias /* n_sets x 3, may be NULL */, float* out_variance /* n_sets x H x W x 3, may be NULL */,
                                     drt_hip_stats* stats);
+/* ---- one scene from up to DRT_HIP_MAX_VIEWS cameras in ONE trace: what a fitting loop over several views of a scene renders per step.  For
+ * rp_v = *rp with seed = seeds ? seeds[v] : rp->seed, view v's results are what drt_hip_render(ctx, &cams[v], &rp_v, adjoints_rgb + v H W 3, ...)
+ * returns:
+ *   out_images[v]      that call's out_rgb, bit for bit, in f32 and under DRT_RENDER_F64
+ *   out_view_grads[v]  that call's out_param_grad, bit for bit -- the SUM over this shard's samples, zeros for requires_grad == 0 -- wherever
+ *                      drt_hip_render itself runs a lockstep form of the library's kernels: fixed-depth renders, through the built-in or the
+ *                      kind-sorted program.  (A roulette-terminated render runs in lockstep here, as in every derived form; drt_hip_render
+ *                      takes the regenerating form there, whose f32 sums are other sums of the same terms: equal within the stated f32 bound;
+ *                      in f64 the gradients within 1e-9 of the largest component, the images -- floats on both sides -- within 1e-9 of the
+ *                      largest value plus one float ulp of it.)
+ *   out_param_grad     the views' gradients added in view order in fp64
+ * stats->paths, ->segments and ->capped_paths are the sums over the views; launches[DRT_K_PATH] == 1 for any n_views.  The path kernel is a
+ * shell of its own (k_path_views): the single frame's grid once per view -- the same samples per wave, every view on a block boundary -- whose
+ * blocks take their view's camera constants, seed and stream from a table the host fills per call, and then run the single call's operations on
+ * the single call's operands; k_views_finish adds a view's partial sums in the single call's order, and no float is added by an atomic: the same
+ * call returns the same bits.  All cameras share width and height.  rp->shard / n_shards / band_rows apply to every view alike, and only the
+ * shard's rows of each image are written.  DRT_RENDER_BACKWARD is needed for either gradient output; _F64, _TIMING, _SYNC and _DEVICE_OUT as in
+ * drt_hip_render_param_sets_grad (with _DEVICE_OUT adjoints_rgb and the three outputs are device pointers; cams and seeds are host memory
+ * always).  One batch per shard, on the context's stream, in order.
+ * DRT_ERR_INVALID: n_views outside 1 ... DRT_HIP_MAX_VIEWS, NULL cams or rp, cameras of different sizes, no output requested, a gradient output
+ * without DRT_RENDER_BACKWARD (the flag without a gradient output renders forward only), an adjoint value that is not finite (host buffers),
+ * asynchronous frames in flight.  DRT_ERR_UNSUPPORTED: a scene that holds a triangle mesh, a group context, bounces_per_launch >= 1, DRT_RENDER_UNFUSED, _UNBIASED,
+ * _LOSS_L2 or _ALLREDUCE*, more parameters than the path kernels stage (136), more than 2^31 camera samples over all views, a render that a
+ * DRT_HIP_* setting forces onto the queue wavefront or whose paths end at depth 0 (batch_paths and DRT_HIP_BATCH_PATHS cannot force several
+ * batches: the shard renders in one whatever they say).  The message of either says "views"; the context stays usable. */
+#define DRT_HIP_MAX_VIEWS 64
+int drt_hip_render_views(drt_hip_ctx* ctx, const drt_camera_desc* cams /* n_views */, int32_t n_views, const drt_render_params* rp,
+                         const uint32_t* seeds /* n_views, NULL: rp->seed for every view */,
+                         const float* adjoints_rgb /* n_views x H x W x 3, NULL: all ones */,
+                         float* out_images /* n_views x H x W x 3, may be NULL */,
+                         double* out_param_grad /* n_params x 3, the sum over the views, may be NULL */,
+                         double* out_view_grads /* n_views x n_params x 3, may be NULL */, drt_hip_stats* stats);
 /* ---- the per-sample loss from the caller's own source, with the loss's value.  The reference's loop is
  *     auto radiance = tracer.trace(scene, orig, dir);  auto loss = loss_func(radiance);  loss.backward();       (README.md:93-98)
  * with loss_func the caller's code; DRT_RENDER_LOSS_L2 is the one loss_func the library carries, and returns no value.  Here the loss is the

@@ -16,6 +16,12 @@ the same thing for a loss that is linear in the radiance.
 
     python tools/fit_albedo.py [--size 128] [--spp 16] [--steps 60] [--async] [--oracle] [--gauss-newton [--one-render [--cross [--lambda-sets N]]] [--lambda-sets N]]
     python tools/fit_albedo.py --scene cornell_shapes --multi-start N [--oracle]
+    python tools/fit_albedo.py --views N [--size 32] [--spp 8] [--steps 60]
+
+--views N (N <= 64): the first loop above against N target views at once, cameras on an arc in front of the box: per step ONE
+drt_hip_render_views forward on seed A and ONE backward on seed B with the N adjoint images, whose summed gradient is the gradient of the mean
+squared error over all views; the loss is printed per step (fresh seeds: mostly noise at a few samples), and the loss on ONE fixed seed at
+128 spp before and after the fit, which decides the exit status.
 
 --async: the same loop through drt_hip_render_async / drt_hip_wait (frame i + 1 needs the parameters of step i, so frames
 cannot overlap: what is measured is the call overhead).  --oracle: the CPU restatement instead of the device (checker;
@@ -644,6 +650,56 @@ class OracleRender:
         return used_params(self.scene)
 
 
+def arc_cameras(pkg, n, size):
+    """n cameras on an arc in front of the box, looking at its middle"""
+    cams = []
+    for k in range(n):
+        t = (k + 0.5) / n - 0.5
+        cams.append(pkg.Camera(size, size).look_at((0.5 * np.sin(t), 0.1 * t, 0.15 * (1 - np.cos(t))), (0.0, -0.1, 1.0)))
+    return cams
+
+
+def fit_views(pkg, n_views, size, spp, depth, steps, lr=0.08, decay=0.96, log=None):
+    """--views N: fit()'s Adam loop on the red albedo against N target views at once -- per step ONE render_views forward on one seed and ONE
+    render_views backward on another, whose summed gradient is the loss's over all views.
+    -> (fitted rgb, loss per step, the loss on one fixed seed at 128 spp before and after)"""
+    r = pkg.HipRenderer(0)
+    scene = pkg.scene_by_name("cornell")
+    r.upload_scene(scene)
+    cams = arc_cameras(pkg, n_views, size)
+    params = np.array(scene.params, dtype=np.float64)
+    tracer = dict(min_bounces=depth, absorb=1.0)
+    target = r.render_views(cams, pkg.RenderParams(spp=256, seed=1, **tracer))[0].astype(np.float64)
+    params[0] = (0.2, 0.2, 0.2)
+
+    def fixed_seed_loss():
+        # (the per-step losses are taken on fresh seeds at `spp` and are mostly noise at a few samples: this one compares like with like)
+        r.update_params(params)
+        imgs = r.render_views(cams, pkg.RenderParams(spp=128, seed=9001, **tracer))[0]
+        return float(((imgs.astype(np.float64) - target) ** 2).mean())
+
+    fixed = [fixed_seed_loss()]
+    m = np.zeros(3); v = np.zeros(3)
+    b1, b2, eps = 0.8, 0.99, 1e-8
+    losses = []
+    for k in range(steps):
+        r.update_params(params)
+        imgs = r.render_views(cams, pkg.RenderParams(spp=spp, seed=1000 + 2 * k, **tracer))[0]
+        resid = imgs.astype(np.float64) - target
+        losses.append(float((resid ** 2).mean()))
+        adj = (2.0 * resid / resid.size).astype(np.float32)
+        _, gsum, _, _ = r.render_views(cams, pkg.RenderParams(spp=spp, seed=1001 + 2 * k, **tracer), backward=True, adjoints=adj)
+        g = gsum[0] / spp
+        m = b1 * m + (1 - b1) * g
+        v = b2 * v + (1 - b2) * g * g
+        params[0] = np.clip(params[0] - lr * decay ** k * (m / (1 - b1 ** (k + 1))) / (np.sqrt(v / (1 - b2 ** (k + 1))) + eps), 0.0, 1.0)
+        if log:
+            log(f"step {k:3d}  loss {losses[-1]:.6f}  red = ({params[0][0]:.4f}, {params[0][1]:.4f}, {params[0][2]:.4f})")
+    fixed.append(fixed_seed_loss())
+    r.close()
+    return params[0].copy(), losses, fixed
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=128)
@@ -662,6 +718,9 @@ def main():
     ap.add_argument("--multi-start", dest="multi_start", type=int, default=0,
                     help="with --scene: this many perturbed starts (<= 8) as Adam chains side by side, one render_param_sets and one "
                          "render_param_sets_grad call per step")
+    ap.add_argument("--views", type=int, default=0,
+                    help="fit the red albedo against this many views (<= 64) on an arc in front of the box: one render_views forward and one "
+                         "backward per step; prints the loss per step")
     ap.add_argument("--async", dest="use_async", action="store_true")
     ap.add_argument("--oracle", action="store_true")
     ap.add_argument("--quiet", action="store_true")
@@ -676,8 +735,18 @@ def main():
         ap.error("--line-search N (1 ... 4) goes with --gauss-newton --scene cornell_shapes on the device (not --oracle, not --lambda-sets)")
     if a.multi_start and (a.gauss_newton or a.use_async or a.lambda_sets or a.line_search or not 1 <= a.multi_start <= 8):
         ap.error("--multi-start N (1 ... 8) is the first-order loop (not --gauss-newton, --async, --lambda-sets, --line-search)")
+    if a.views and (a.gauss_newton or a.use_async or a.lambda_sets or a.line_search or a.multi_start or a.oracle or a.scene != "cornell" or
+                    not 1 <= a.views <= 64):
+        ap.error("--views N (1 ... 64) is the first-order loop on the device, --scene cornell (no other mode)")
     import __graft_entry__ as e
     pkg = e.load_package()
+    if a.views:
+        t0 = time.time()
+        steps = a.steps or 60
+        rgb, losses, fixed = fit_views(pkg, a.views, a.size, a.spp, a.depth, steps, log=print)
+        print(f"fitted red = ({rgb[0]:.4f}, {rgb[1]:.4f}, {rgb[2]:.4f})  {a.views} views, {steps} steps, {2 * steps} render_views calls in "
+              f"{time.time() - t0:.2f} s; loss {losses[0]:.6f} -> {losses[-1]:.6f}; fixed-seed loss {fixed[0]:.6f} -> {fixed[1]:.6f}")
+        return 0 if fixed[1] < fixed[0] else 1
     if a.oracle:
         render = OracleRender(pkg, e.load_oracle(), a.size, a.spp, a.depth, a.scene)
     else:
