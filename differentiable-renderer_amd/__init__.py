@@ -768,7 +768,7 @@ _ABI_SYMBOLS = ["drt_hip_abi_version", "drt_hip_device_count", "drt_hip_create",
                 "drt_hip_render_gradient_image", "drt_hip_render_tangent", "drt_hip_render_tangent_double", "drt_hip_render_normal_equations", "drt_hip_render_tangents",
                 "drt_hip_render_normal_equations_along", "drt_hip_render_normal_equations_cross", "drt_hip_render_param_sets", "drt_hip_render_param_sets_double",
                 "drt_hip_render_param_sets_along", "drt_hip_render_param_sets_along_double", "drt_hip_render_param_sets_grad", "drt_hip_render_param_sets_cross",
-                "drt_hip_render_views", "drt_hip_set_sample_loss", "drt_hip_render_sample_loss", "drt_hip_pin_host", "drt_hip_unpin_host", "drt_hip_stream",
+                "drt_hip_render_views", "drt_hip_render_pixels", "drt_hip_set_sample_loss", "drt_hip_render_sample_loss", "drt_hip_pin_host", "drt_hip_unpin_host", "drt_hip_stream",
                 "drt_hip_synchronize", "drt_hip_last_error", "drt_hip_kernel_name"]
 
 
@@ -829,6 +829,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(HipStats)]
     lib.drt_hip_render_views.argtypes = [C.c_void_p, C.POINTER(CameraDesc), C.c_int32, C.POINTER(RenderParamsDesc), C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(HipStats)]
+    lib.drt_hip_render_pixels.argtypes = [C.c_void_p, C.POINTER(CameraDesc), C.c_int32, C.POINTER(RenderParamsDesc), C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(HipStats)]
     lib.drt_hip_set_sample_loss.argtypes = [C.c_void_p, C.POINTER(SampleLossDesc)]
     lib.drt_hip_render_sample_loss.argtypes = [C.c_void_p, C.POINTER(CameraDesc), C.POINTER(RenderParamsDesc), C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_void_p, C.POINTER(HipStats)]
@@ -1442,14 +1444,14 @@ class HipRenderer:
         self._check(rc, "drt_hip_render_param_sets_cross")
         return stats.as_dict() if want_stats else {}
 
-    def _begin_views(self, cams: Sequence[Camera], rp: RenderParams, flags: int, seeds):
+    def _begin_views(self, cams: Sequence[Camera], rp: RenderParams, flags: int, seeds, who: str = "views"):
         """the cameras, the render parameters with `flags`, the seeds and a statistics record, as drt_hip_render_views takes them"""
         assert self.scene is not None
         cams = list(cams)
         if not 1 <= len(cams) <= MAX_VIEWS:
-            raise ValueError(f"views: n_views = {len(cams)} outside 1 ... MAX_VIEWS = {MAX_VIEWS}")
+            raise ValueError(f"{who}: n_views = {len(cams)} outside 1 ... MAX_VIEWS = {MAX_VIEWS}")
         if any((c.width, c.height) != (cams[0].width, cams[0].height) for c in cams):
-            raise ValueError("views: the cameras differ in width or height (all views share one size)")
+            raise ValueError(f"{who}: the cameras differ in width or height (all views share one size)")
         cds = (CameraDesc * len(cams))(*[c.to_desc() for c in cams])
         d = rp.to_desc()
         d.flags = flags
@@ -1457,7 +1459,7 @@ class HipRenderer:
         if seeds is not None:
             sd = np.ascontiguousarray(seeds, dtype=np.uint32)
             if sd.shape != (len(cams),):
-                raise ValueError(f"views: expected {len(cams)} seeds, got shape {list(sd.shape)}")
+                raise ValueError(f"{who}: expected {len(cams)} seeds, got shape {list(sd.shape)}")
         return cams, cds, d, sd, HipStats()
 
     def render_views(self, cams: Sequence[Camera], rp: RenderParams, backward: bool = False, adjoints: Optional[np.ndarray] = None,
@@ -1493,6 +1495,60 @@ class HipRenderer:
                                            C.c_void_p(adjoints_ptr or None), C.c_void_p(out_images_ptr or None), C.c_void_p(out_grad_ptr or None),
                                            C.c_void_p(out_view_grads_ptr or None), C.byref(stats) if want_stats else None)
         self._check(rc, "drt_hip_render_views")
+        return stats.as_dict() if want_stats else {}
+
+    def _begin_pixels(self, cams: Sequence[Camera], pixel_lists):
+        """the views' pixel lists (one sequence of y * W + x per camera) ->
+        (counts int32 [n], pixels uint32 [sum(counts)]); raises ValueError for what the library would refuse, said before the call"""
+        cams = list(cams)
+        lists = [np.asarray(l, dtype=np.int64).reshape(-1) for l in pixel_lists]
+        if len(lists) != len(cams):
+            raise ValueError(f"pixels: expected {len(cams)} pixel lists (one per camera), got {len(lists)}")
+        counts = np.array([len(l) for l in lists], dtype=np.int64)
+        pix = np.concatenate(lists) if lists else np.zeros(0, dtype=np.int64)
+        if pix.size == 0:
+            raise ValueError("pixels: an empty batch (no entries in any view)")
+        if cams and (pix.min() < 0 or pix.max() >= cams[0].width * cams[0].height):
+            raise ValueError("pixels: a pixel outside the frame (>= W * H)")
+        return counts.astype(np.int32), pix.astype(np.uint32)
+
+    def render_pixels(self, cams: Sequence[Camera], pixel_lists, rp: RenderParams, backward: bool = False, adjoints: Optional[np.ndarray] = None,
+                      seeds=None, f64: bool = False, timing: bool = False):
+        """drt_hip_render_pixels: a batch of pixels of the scene from the n <= MAX_VIEWS = 64 cameras `cams` (one size) in ONE trace.
+        `pixel_lists[v]` holds view v's pixels as y * W + x, in any order, repeats allowed, possibly none; view v is seeded with `seeds[v]`
+        (None: rp.seed) and, with `backward`, back-propagated from `adjoints` (float32 [E,3] for the E entries in list order; None: all ones).
+        -> (rgb float32 [E,3], grad_sum float64 [P,3] or None, view_grads float64 [n,P,3] or None, stats dict): an entry's radiance is that
+        pixel of render(cams[v], rp with seed seeds[v]), view v's gradient J_v^T w_v over its entries, grad_sum the views' added in view order."""
+        counts, pix = self._begin_pixels(cams, pixel_lists)
+        cams, cds, d, sd, stats = self._begin_views(cams, rp, self._host_flags(rp, f64, timing) | (RENDER_BACKWARD if backward else 0), seeds, "pixels")
+        n, E, P = len(cams), int(pix.size), self.scene.n_params
+        a_ptr = None
+        if adjoints is not None:
+            adjoints = np.ascontiguousarray(adjoints, dtype=np.float32)
+            if adjoints.shape != (E, 3):
+                raise ValueError(f"pixels: expected adjoints of shape {[E, 3]}, got {list(adjoints.shape)}")
+            a_ptr = adjoints.ctypes.data_as(C.c_void_p)
+        rgb = np.zeros((E, 3), dtype=np.float32)
+        gsum = np.zeros((max(P, 1), 3), dtype=np.float64) if backward else None
+        vg = np.zeros((n, max(P, 1), 3), dtype=np.float64) if backward else None
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+        rc = self.lib.drt_hip_render_pixels(self.ctx, cds, n, C.byref(d), ptr(sd), ptr(counts), ptr(pix), a_ptr, ptr(rgb), ptr(gsum), ptr(vg), C.byref(stats))
+        self._check(rc, "drt_hip_render_pixels")
+        return rgb, (gsum[:P] if backward else None), (vg[:, :P] if backward else None), stats.as_dict()
+
+    def render_pixels_device(self, cams: Sequence[Camera], pixel_lists, rp: RenderParams, out_rgb_ptr: int = 0, out_grad_ptr: int = 0,
+                             out_view_grads_ptr: int = 0, adjoints_ptr: int = 0, seeds=None, backward: bool = False, f64: bool = False,
+                             timing: bool = False, sync: bool = False, want_stats: Optional[bool] = None) -> dict:
+        """drt_hip_render_pixels on device pointers (radiance and adjoints float32 [E,3], the summed gradient float64 [P,3], the views'
+        gradients float64 [n,P,3]), enqueued on the context's stream; the cameras, the seeds and the pixel lists are host memory."""
+        want_stats = timing if want_stats is None else want_stats
+        counts, pix = self._begin_pixels(cams, pixel_lists)
+        cams, cds, d, sd, stats = self._begin_views(cams, rp, self._device_flags(rp, f64, timing, sync) | (RENDER_BACKWARD if backward else 0), seeds, "pixels")
+        rc = self.lib.drt_hip_render_pixels(self.ctx, cds, len(cams), C.byref(d), sd.ctypes.data_as(C.c_void_p) if sd is not None else None,
+                                            counts.ctypes.data_as(C.c_void_p), pix.ctypes.data_as(C.c_void_p),
+                                            C.c_void_p(adjoints_ptr or None), C.c_void_p(out_rgb_ptr or None), C.c_void_p(out_grad_ptr or None),
+                                            C.c_void_p(out_view_grads_ptr or None), C.byref(stats) if want_stats else None)
+        self._check(rc, "drt_hip_render_pixels")
         return stats.as_dict() if want_stats else {}
 
     def render_device(self, cam: Camera, rp: RenderParams, out_rgb_ptr: int, out_grad_ptr: int,

@@ -62,6 +62,24 @@ struct ViewsRequest {
     double* d_view_grads = nullptr;       // n_views x the caller's parameters x 3, or none
     double* d_grad = nullptr;             // the caller's parameters x 3: the views' gradients added in view order, or none
 };
+// ... and a caller's batch of pixels from several cameras (drt_hip_render_pixels): k_path_pixels over the views' lists -- a grid whose views
+// have different sizes, packed by drt_pixels.h once the plan has its sample ranges --, then k_pixels_finish.  The table is the host's copy
+// in the call's pinned block, its cameras, seeds and counts filled in; the plan adds every view's place in the grid and copies it to
+// d_table in stream order.  Every other pointer is the device's; the first camera is the one the pipeline is told about
+struct PixelsRequest {
+    int n_views = 0;
+    bool backward = false;                // gradients wanted: the kernel's gradient form, as drt_hip_render's plan picks it for one frame
+    const int32_t* counts = nullptr;      // n_views: entries of view v (host memory, checked: drt_pixels.h)
+    uint64_t n_entries = 0;               // their sum
+    void* h_table = nullptr;              // [PixelsHead | n_views PixelView records] (drt_path.h), pinned
+    void* d_table = nullptr;              // ... on the device
+    size_t table_bytes = 0;
+    const uint32_t* d_pixels = nullptr;   // n_entries: y W + x, the views' lists one behind the other
+    const float* d_adjoints = nullptr;    // n_entries x 3, or none (every seed (1, 1, 1))
+    float* d_rgb = nullptr;               // n_entries x 3, or none
+    double* d_view_grads = nullptr;       // n_views x the caller's parameters x 3, or none
+    double* d_grad = nullptr;             // the caller's parameters x 3: the views' gradients added in view order, or none
+};
 // A render on one of the path kernel's special forms, as render_common / render_launch / render_impl are told about it: which form, and what
 // that form reads.  render_impl decodes it, in one place
 struct TangentRequest {
@@ -72,6 +90,7 @@ struct TangentRequest {
         param_sets,                       // one frame under K parameter sets (drt_hip_render_param_sets; with sets->along each has a direction:
                                           // drt_hip_render_param_sets_along): d_params, sets
         views,                            // one scene from several cameras (drt_hip_render_views): views
+        pixels,                           // a batch of pixels from several cameras (drt_hip_render_pixels): pixels
     } kind = Kind::forward;
     const void* d_params = nullptr;       // the path kernel's `params`, in the render's compute type: [the scene's parameters | row_1 | ... | row_K],
                                           // the rows padded up to an instantiated width K (stage_rows, drt_hip.hip)
@@ -80,6 +99,7 @@ struct TangentRequest {
     int n_dirs = 0;                       // the rows k_normal_eq reduces are these directions instead of the parameters
     const ParamSetsRequest* sets = nullptr;
     const ViewsRequest* views = nullptr;
+    const PixelsRequest* pixels = nullptr;
 };
 
 // One render call between its phases: launch (everything enqueued, gradients in ctx->grad[ctx->slot]) -> reduce (the

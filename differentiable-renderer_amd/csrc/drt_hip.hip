@@ -38,6 +38,7 @@
 
 
 #include "drt_tuning.h"
+#include "drt_pixels.h"
 #include "drt_ctx.h"
 #include "drt_scene.h"
 #include "drt_render_impl.h"
@@ -1043,6 +1044,147 @@ int drt_hip_render_views(drt_hip_ctx* ctx, const drt_camera_desc* cams, int32_t 
                 memcpy((uint8_t*)out_images + at, block + off_img + at, (size_t)(y1 - y0) * row);
             });
     }
+    return DRT_OK;
+}
+
+} // extern "C"
+
+// ---- a caller's batch of pixels from several cameras in one trace (k_path_pixels, drt_path.h) -----------------------------------------
+// The call's pinned block, stage_views' buffers used the same way: [head | the views' records | the pixel lists], then `extra` bytes of the
+// caller's.  The records' cameras and seeds and the lists are filled here; the views' places in the grid need the plan's sample ranges, so
+// path_batch adds them and copies [head | records | lists] to ctx->tangent.p in stream order (the caller records the block's event behind it)
+static size_t pixels_list_offset(int n_views) { return (sizeof(PixelsHead) + (size_t)n_views * sizeof(PixelView) + 15) & ~(size_t)15; }
+static int stage_pixels(drt_hip_ctx* ctx, const drt_camera_desc* cams, int n_views, const drt_render_params* rp, const uint32_t* seeds,
+                        const uint32_t* pixels, size_t n_entries, size_t copy_bytes, size_t extra, int* which, uint8_t** block)
+{
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const int hb = (int)(ctx->tangent_calls++ & 1);
+    const size_t need = (copy_bytes + extra + sizeof(double) - 1) / sizeof(double);
+    if (!ctx->ev_tangent[hb])
+        HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_tangent[hb], hipEventDisableTiming));
+    else
+        HIPCHK(ctx, hipEventSynchronize(ctx->ev_tangent[hb]));
+    if (ctx->h_tangent_cap[hb] < need) {
+        if (ctx->h_tangent[hb])
+            (void)hipHostFree(ctx->h_tangent[hb]);
+        ctx->h_tangent[hb] = nullptr;
+        ctx->h_tangent_cap[hb] = 0;
+        HIPCHK(ctx, hipHostMalloc((void**)&ctx->h_tangent[hb], need * sizeof(double)));
+        ctx->h_tangent_cap[hb] = need;
+    }
+    uint8_t* b = reinterpret_cast<uint8_t*>(ctx->h_tangent[hb]);
+    PixelView* pv = const_cast<PixelView*>(pixel_views(reinterpret_cast<PixelsHead*>(b)));
+    for (int v = 0; v < n_views; ++v) {
+        memset(&pv[v], 0, sizeof pv[v]);
+        fill_path_view(pv[v].cam, cams[v], seeds ? seeds[v] : rp->seed);
+    }
+    memcpy(b + pixels_list_offset(n_views), pixels, n_entries * sizeof(uint32_t));
+    int rc;
+    if ((rc = ensure(ctx, ctx->tangent, copy_bytes)) != DRT_OK) return rc;
+    *which = hb;
+    *block = b;
+    return DRT_OK;
+}
+
+extern "C" {
+
+int drt_hip_render_pixels(drt_hip_ctx* ctx, const drt_camera_desc* cams, int32_t n_views, const drt_render_params* rp, const uint32_t* seeds,
+                          const int32_t* counts, const uint32_t* pixels, const float* adjoints_rgb, float* out_rgb, double* out_param_grad,
+                          double* out_view_grads, drt_hip_stats* stats)
+{
+    if (!ctx)
+        return DRT_ERR_INVALID;
+    static_assert(DRT_PIXELS_MAX_VIEWS == DRT_HIP_MAX_VIEWS && DRT_PIXELS_WAVE == DRT_WAVE && DRT_PIXELS_BLOCK_WAVES * DRT_WAVE == DRT_BLOCK,
+                  "drt_pixels.h packs for this grid");
+    static_assert(sizeof(PixelsHead) == DRT_HIP_MAX_VIEWS * sizeof(uint32_t) && sizeof(PixelView) % 8 == 0, "the table's layout");
+    static const PathFormCaller me = {"pixels", "render the lists on plain contexts", "the biased operator", DRT_PATH_LDS_PARAMS,
+                                      "more parameters than the path kernels stage (136)"};
+    int rc;
+    if ((rc = refuse_before(ctx, cams, rp, me)) != DRT_OK) return rc;
+    if (n_views < 1 || n_views > DRT_HIP_MAX_VIEWS)
+        return refuse(ctx, me, DRT_ERR_INVALID, pixels_refusal_text(DRT_PIXELS_N_VIEWS));
+    for (int v = 1; v < n_views; ++v)
+        if (cams[v].width != cams[0].width || cams[v].height != cams[0].height)
+            return refuse(ctx, me, DRT_ERR_INVALID, "the cameras differ in width or height (all views share one size)");
+    if (rp->n_shards > 1)
+        return refuse(ctx, me, DRT_ERR_INVALID, "not with n_shards > 1 (a list is the caller's own split of the work)");
+    if (!out_rgb && !out_param_grad && !out_view_grads)
+        return refuse(ctx, me, DRT_ERR_INVALID, "no output requested (out_rgb, out_param_grad and out_view_grads are all NULL)");
+    const bool backward = (out_param_grad || out_view_grads);
+    if (backward && !(rp->flags & DRT_RENDER_BACKWARD))
+        return refuse(ctx, me, DRT_ERR_INVALID, "out_param_grad and out_view_grads need DRT_RENDER_BACKWARD");
+    // the lists (drt_pixels.h): refused before anything is enqueued
+    uint64_t n_entries = 0;
+    const int why = pixels_check(counts, n_views, pixels, (uint64_t)cams[0].width * (uint64_t)cams[0].height, (uint64_t)(rp->spp > 0 ? rp->spp : 1), &n_entries);
+    if (why != DRT_PIXELS_OK && why != DRT_PIXELS_TOO_MANY)
+        return refuse(ctx, me, DRT_ERR_INVALID, pixels_refusal_text(why));
+    const bool dev = (rp->flags & DRT_RENDER_DEVICE_OUT) != 0;
+    if (why == DRT_PIXELS_OK && !dev && adjoints_rgb)
+        for (size_t i = 0; i < (size_t)n_entries * 3; ++i)
+            if (!std::isfinite(adjoints_rgb[i]))
+                return refuse(ctx, me, DRT_ERR_INVALID, "an adjoint holds a value that is not finite");
+    if ((rc = refuse_after(ctx, cams, rp, me)) != DRT_OK) return rc;
+    if (why == DRT_PIXELS_TOO_MANY)
+        return refuse(ctx, me, DRT_ERR_UNSUPPORTED, pixels_refusal_text(why));
+    // Host buffers: everything crosses in the call's pinned block, [table | pixels | gradients (the views', then their sum) | radiance |
+    // adjoints] -- the finishing kernel stores radiance and sums straight into it, and the path kernel reads its seeds from it where they
+    // are small (one 12-byte load per lane: render_impl's rule), from a copy in device memory else.  Device pointers: [table | pixels] alone
+    const size_t n_rgb = (size_t)n_entries * 3 * sizeof(float), ng = (size_t)ctx->n_user_params * 3;
+    const bool host_adj = !dev && backward && adjoints_rgb;
+    const size_t off_pix = pixels_list_offset(n_views), copy_bytes = off_pix + (size_t)n_entries * sizeof(uint32_t);
+    const size_t grad_bytes = (((size_t)(n_views + 1) * ng + 1) * sizeof(double) + 15) & ~(size_t)15, rgb_bytes = (n_rgb + 15) & ~(size_t)15;
+    const size_t off_grad = (copy_bytes + 15) & ~(size_t)15, off_rgb = off_grad + (backward ? grad_bytes : 0), off_adj = off_rgb + (out_rgb ? rgb_bytes : 0);
+    uint8_t* block = nullptr;
+    int hb = 0;
+    if ((rc = stage_pixels(ctx, cams, n_views, rp, seeds, pixels, (size_t)n_entries, copy_bytes,
+                           dev ? 0 : off_adj + (host_adj ? n_rgb : 0) - copy_bytes, &hb, &block)) != DRT_OK) return rc;
+    PixelsRequest q;
+    q.n_views = n_views;
+    q.backward = backward;
+    q.counts = counts;
+    q.n_entries = n_entries;
+    q.h_table = block;
+    q.d_table = ctx->tangent.p;
+    q.table_bytes = copy_bytes;
+    q.d_pixels = reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(ctx->tangent.p) + off_pix);
+    if (dev) {
+        q.d_adjoints = backward ? adjoints_rgb : nullptr;
+        q.d_rgb = out_rgb;
+        q.d_view_grads = out_view_grads;
+        q.d_grad = out_param_grad;
+    } else {
+        if (host_adj) {
+            memcpy(block + off_adj, adjoints_rgb, n_rgb);
+            q.d_adjoints = (const float*)(block + off_adj);
+            if (n_rgb > ((size_t)1 << 20)) {
+                if ((rc = ensure(ctx, ctx->neq_in, n_rgb)) != DRT_OK) return rc;
+                HIPCHK(ctx, hipMemcpyAsync(ctx->neq_in.p, block + off_adj, n_rgb, hipMemcpyHostToDevice, ctx->stream));
+                q.d_adjoints = (const float*)ctx->neq_in.p;
+            }
+        }
+        if (out_rgb)
+            q.d_rgb = (float*)(block + off_rgb);
+        if (backward) {
+            q.d_view_grads = (double*)(block + off_grad);
+            q.d_grad = q.d_view_grads + (size_t)n_views * ng;
+        }
+    }
+    TangentRequest req;
+    req.kind = TangentRequest::Kind::pixels;
+    req.pixels = &q;
+    // (the pipeline below is told a forward render of the first camera's whole frame -- the plan's sample ranges are that frame's --: this
+    //  form's seeds, radiance and sums go their own way)
+    drt_render_params r = *rp;
+    r.flags &= ~(uint32_t)DRT_RENDER_BACKWARD;
+    rc = render_common(ctx, &cams[0], &r, nullptr, nullptr, nullptr, stats, -1, nullptr, &req);
+    // (the block is free again once the table's copy -- and, host buffers, the adjoints' -- has been made)
+    (void)hipEventRecord(ctx->ev_tangent[hb], ctx->stream);
+    if (rc != DRT_OK || dev)
+        return rc;
+    // host buffers: the render has waited for its stream
+    if (out_view_grads && ng) memcpy(out_view_grads, q.d_view_grads, (size_t)n_views * ng * sizeof(double));
+    if (out_param_grad && ng) memcpy(out_param_grad, q.d_grad, ng * sizeof(double));
+    if (out_rgb) memcpy(out_rgb, block + off_rgb, n_rgb);
     return DRT_OK;
 }
 

@@ -2585,6 +2585,177 @@ k_path_views(PathArgs a0, const PathView* __restrict__ views, uint32_t view_bloc
         block_grad_sums<NP>(tg.acc, s_red, gpart, pl.lane);
 }
 
+// ---- k_path_pixels: a caller's batch of pixels from several cameras in one launch (drt_hip_render_pixels) -----------------------------
+// k_path_views with one indirection: a lane's pixel is the caller's, pixels[the view's first entry + the lane's place in the view's list].
+// View v's list is a "frame" of n_entries pixels -- n_groups = ceil(n_entries / 64) waves a sample range, every view on a block boundary, a
+// view without entries without blocks -- and the sample ranges are the ones the plan picks for a SINGLE W x H x spp frame (a0.spr,
+// a0.n_ranges), not re-tuned to the list's length: a lane then adds the samples the single call's lane of that pixel and range adds, in its
+// order, and the finishing kernel adds the ranges the single call's finishing launch adds -- that is what makes an entry's radiance the
+// single call's bits.  The RNG key of a sample is pixel spp + sample, so a pixel rendered alone draws what it draws inside its frame.
+// A block finds its view by a scalar search over the at most 64 first blocks at the head of the table (a view without blocks shares its
+// first block with its successor: the LAST view whose first block is not beyond the block's index is the one), takes the view's record
+// through that wave-uniform index -- scalar loads -- and patches its copy of the arguments: camera, seed, stream, Pb = n_entries, n_groups.
+// Partial sums: fpart per view [range][row][entry], counts per view [row][wave of the view], gpart[block of the grid][row], the general
+// form's global history columns over the threads of the whole grid.  k_pixels_finish (below) reduces them.
+template <typename SG> struct PixelsSig : SG {};
+struct PixelView {
+    PathView cam;
+    uint32_t first_block, n_blocks, first_entry, n_entries, n_groups, pad;
+    unsigned long long fpart_at, counts_at;               // doubles / words in front of the view's sums
+};
+struct PixelsHead {
+    uint32_t first_block[64];                             // per view (DRT_HIP_MAX_VIEWS); behind it, 16-byte aligned: PixelView[n_views]
+};
+__host__ __device__ inline const PixelView* pixel_views(const PixelsHead* head) { return reinterpret_cast<const PixelView*>(head + 1); }
+template <typename R, bool SPEC, int NP, int NCR, typename SG>
+__global__ void __launch_bounds__(DRT_BLOCK, (views_min_blocks<sizeof(R), SPEC, NP, SG::n, NCR>()))
+k_path_pixels(PathArgs a0, const PixelsHead* __restrict__ head, uint32_t n_views, const uint32_t* __restrict__ pixels, const DevScene<R>* __restrict__ sc,
+              const R* __restrict__ params, const float* __restrict__ adjoint, double* __restrict__ gpart, double* __restrict__ fpart,
+              uint32_t* __restrict__ counts, unsigned long long* __restrict__ total)
+{
+    static_assert(NP == 0 || NP == 4 || NP == 8 || NP == DRT_NP_ANY, "k_path_pixels: forward only, the gradient columns or the general form");
+    static_assert(!DRT_JACOBIAN_OF(NCR) && DRT_ROLES_OF(NCR) == 0, "k_path_pixels has no Jacobian form and no roles");
+    zero_totals(total);
+    typedef typename Q4<R>::T R4;
+    typedef typename Q2<R>::T R2;
+    constexpr int NC = DRT_NC_OF(NCR);
+    constexpr bool GEN = NP == DRT_NP_ANY;
+    static_assert(!GEN || NC == 0, "k_path_pixels: the general form without a gradient image");
+    // the block's view and its place among the view's blocks; the arguments as a single call's kernel over the list would have had them
+    uint32_t view = 0;
+    for (uint32_t i = 1; i < n_views; ++i)
+        view = head->first_block[i] <= blockIdx.x ? i : view;
+    view = __builtin_amdgcn_readfirstlane(view);
+    PathArgs a = a0;
+    uint32_t view_block, first_entry;
+    {
+        const PixelView& pv = pixel_views(head)[view];
+        const PathView& v = pv.cam;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            a.eye[i] = v.eye[i]; a.fwd[i] = v.fwd[i]; a.right[i] = v.right[i]; a.up[i] = v.up[i];
+            a.eye_f[i] = v.eye_f[i]; a.fwd_f[i] = v.fwd_f[i]; a.right_f[i] = v.right_f[i]; a.up_f[i] = v.up_f[i];
+        }
+        a.tan_half = v.tan_half; a.aspect = v.aspect;
+        a.cs_step_f = v.cs_step_f; a.ct_step_f = v.ct_step_f;
+        a.seed = v.seed; a.rng_stream = v.rng_stream;
+        a.Pb = pv.n_entries; a.n_groups = pv.n_groups; a.p0 = 0;
+        view_block = blockIdx.x - pv.first_block;
+        first_entry = pv.first_entry;
+        if (fpart)
+            fpart += pv.fpart_at;
+        counts += pv.counts_at;
+    }
+    pixels += first_entry;
+    if (adjoint)
+        adjoint += (size_t)first_entry * 3;
+
+    __shared__ PathSceneLds<R> lds;
+    __shared__ double s_red[DRT_BLOCK / DRT_WAVE][DRT_FAST_PARAMS * 3];
+    __shared__ TangentLds<R> s_tl;
+    __shared__ typename PickT<GEN, GenBlock<R>, NoLds>::T s_gen;
+    extern __shared__ uint32_t s_hist[];                  // GEN: [a.hist_lds][DRT_BLOCK] history words
+    if constexpr (GEN)
+        gen_zero(s_gen);
+    stage_path_scene(lds, sc, params);
+    const TangentLds<R>& tl = s_tl;
+    if (NC > 0 && !GEN)
+        stage_tangents(s_tl, lds);
+
+    const PathLane pl = path_lane_in_frame(a, __builtin_amdgcn_readfirstlane(view_block * (DRT_BLOCK / DRT_WAVE) + threadIdx.x / DRT_WAVE));
+
+    Tangents<R, NP, NC> tg;
+    __shared__ R s_acc[NP > 0 ? NP * 3 : 1][DRT_BLOCK];
+    tg.acc = &s_acc[0][threadIdx.x];
+    if constexpr (GEN)
+        gen_begin(s_gen, lds, sc, a, s_hist, reinterpret_cast<uint32_t*>(a.hist_ovf), tg);
+    else {
+#pragma unroll
+        for (int p = 0; p < NP; ++p)
+            tg.acc_set(p, mk<R>(R(0), R(0), R(0)));
+    }
+    double fx = 0, fy = 0, fz = 0;                        // radiance sum of this lane's entry over the range
+    uint32_t n_seg = 0, n_capped = 0;                     // wave-uniform counters
+
+    uint32_t gpix = 0, px = 0, py = 0;                    // (the pixel within its frame: the RNG key is the single call's)
+    V3<R> g = mk<R>(R(1), R(1), R(1));                    // render.cpp:80: radiance.backward(Vec3(1))
+    if (pl.have) {
+        gpix = pixels[pl.lp];                             // the one new line of the prologue: lane -> the caller's pixel
+        py = gpix / (uint32_t)a.W;
+        px = gpix - py * (uint32_t)a.W;
+        if (NP != 0 && adjoint)
+            g = mk<R>((R)adjoint[(size_t)pl.lp * 3], (R)adjoint[(size_t)pl.lp * 3 + 1], (R)adjoint[(size_t)pl.lp * 3 + 2]);
+    }
+    const CameraLane<R> cl = camera_lane<R>(a, px, py);
+    constexpr bool ARGS_F32 = path_args_f32<R, SG>();
+    const R pk_rr = ARGS_F32 ? (R)a.p_rr_f : (R)a.p_rr, inv_p_rr = ARGS_F32 ? (R)a.inv_p_rr_f : (R)a.inv_p_rr;
+    ProgRecs<SG::n, R> recs;
+    __shared__ typename PickT<(SG::n == 0), ProgLds, NoLds>::T s_prog;
+    recs.lds = reinterpret_cast<const ProgLds*>(&s_prog);
+    if (SG::n > 0)
+        recs.template load<SG>(sc);
+    if constexpr (sizeof(R) == 4 && SG::n == 0) {
+        const DevScene<float>* scf = reinterpret_cast<const DevScene<float>*>(sc);
+        if (threadIdx.x < DRT_PROG_SORTED_MAX) {
+            s_prog.rec[threadIdx.x] = *reinterpret_cast<const float4*>(scf->sorted[threadIdx.x]);
+            s_prog.shape[threadIdx.x] = scf->sorted_shape[threadIdx.x];
+        }
+        if (threadIdx.x < 8)
+            s_prog.kind_begin[threadIdx.x] = scf->kind_begin[threadIdx.x];
+        __syncthreads();
+    }
+
+    if (pl.range < a.n_ranges) {
+        for (uint32_t sl = pl.s_begin; sl < pl.s_end; ++sl) {
+            R4 ra;
+            R2 rb;
+            const uint32_t key = path_camera<R, ARGS_F32>(a, cl, gpix, px, py, sl, ra, rb);
+            // pathtracer.hpp:128 at depth 0
+            bool live = pl.have && a.depth_cap > 0 && !(a.min_bounces <= 0 && rng_draw(a.rng_stream, key, 2) < a.rr_threshold);
+            V3<R> T = mk<R>(R(1), R(1), R(1)), L = mk<R>(R(0), R(0), R(0));
+            uint32_t end_ids = DRT_ID_NONE;               // emission parameter of the light the path ended on
+            R end_inv_pk = R(1);
+            if (NC > 0 || GEN)
+                tg.new_path();
+            for (int kk = 0; kk < a.depth_cap; ++kk) {
+                const uint32_t n_live = (uint32_t)__popcll(wave_ballot(live));
+                if (n_live == 0)
+                    break;
+                n_seg += n_live;
+                const R pk = kk >= a.min_bounces ? pk_rr : R(1);                  // pathtracer.hpp:130
+                const R inv_pk = kk >= a.min_bounces ? inv_p_rr : R(1);
+                const uint32_t n_theta = draw_offset(kk, 0, a.min_bounces) + camera_draw_base(a.min_bounces);
+                const bool next_rr = (kk + 1) >= a.min_bounces;
+                const bool next_cap = (kk + 1) >= a.depth_cap;
+                bool alive, capped, on_light;
+                uint32_t light;
+                // (the program's type under the shell's own name -- PixelsSig --: the bounce is the shell's own instantiation, and neither
+                //  k_path's nor k_path_views' bounce gains a caller, which has moved a kernel's inlining before: HISTORY.md)
+                path_bounce<R, SPEC, NP, NC, PixelsSig<SG>, (DRT_FREEZE_BY_ROW != 0 && sizeof(R) == 4 && !SPEC && SG::n <= DRT_LEAN_MAX_SHAPES)>(a, lds, tl, sc, params, recs, key, pk, inv_pk, n_theta, next_rr, next_cap, live, g,
+                                                        ra, rb, T, L, tg, alive, capped, on_light, light, nullptr, next_cap);
+                // (a light without a BxDF ends the path; its emission is added once per sample, behind the loop)
+                end_ids = on_light ? light : end_ids;
+                end_inv_pk = on_light ? inv_pk : end_inv_pk;
+                if (next_cap && !a.cap_is_roulette)
+                    n_capped += (uint32_t)__popcll(wave_ballot(capped));
+                live = alive;
+            }
+            if (wave_any(end_ids != DRT_ID_NONE)) {
+                if (end_ids != DRT_ID_NONE)
+                    add_emission<R, NP, NC, false, PathSceneLds<R>, 0>(lds, tl, params, end_ids, end_inv_pk, T, g, L, tg);
+            }
+            fx += (double)L.x; fy += (double)L.y; fz += (double)L.z;
+        }
+        if (fpart && pl.have)
+            store_rows3(fpart + ((size_t)pl.range * 3) * a.Pb + pl.lp, a.Pb, fx, fy, fz);
+        store_counts(a, pl, counts, n_seg, n_capped);
+    }
+    if constexpr (GEN)
+        gen_finish(s_gen, a, gpart);
+    else if constexpr (NP > 0)
+        block_grad_sums<NP>(tg.acc, s_red, gpart, pl.lane);
+}
+
 // ---- the unbiased integration operator (integrate.hpp:11-24, 39-52; README.md:104-136) in one launch ------------------
 // The reference's IntegrateBackward does not reuse the forward samples: where a gradient arrives at a vertex it draws a
 // FRESH direction, evaluates forward(sample) -- a whole new suffix path -- back-propagates grad / pdf through
@@ -3381,6 +3552,98 @@ k_views_finish(PathArgs a, uint32_t n_views, const double* __restrict__ fpart, f
             const uint32_t* cv = counts + v * 2 * view_waves;
             seg += cv[w];
             cap += cv[(size_t)view_waves + w];
+        }
+        for (int off = DRT_WAVE / 2; off > 0; off >>= 1) {
+            seg += __shfl_down(seg, off);
+            cap += __shfl_down(cap, off);
+        }
+        if ((threadIdx.x & (DRT_WAVE - 1)) == 0) {
+            if (seg) atomicAdd(total, seg);
+            if (cap) atomicAdd(total + 3, cap);
+        }
+    }
+}
+
+// ---- everything behind a k_path_pixels launch, in ONE launch (drt_hip_render_pixels) --------------------------------------------------
+// k_views_finish over lists in place of frames:
+//   blocks [0, film_blocks):       out[entry] = float(sum over the sample ranges, in range order, in fp64, / spp) for the entries of all
+//                                  views, in the caller's order (an entry's view: the last one whose first entry is not beyond it)
+//   blocks [.., + grad_words):     word p of every view's gradient -- the sum over the VIEW's blocks of gpart[block][p] in k_views_finish's
+//                                  order: strided per thread, then the LDS tree; a view without blocks gives zero -- to view_grads[v][p], and
+//                                  their sum in view order, in fp64, to grad_sum[p]
+//   the rest:                      total[0] += segments, total[3] += capped paths over all views (integers; k_path_pixels zeroed them)
+// No atomics on a float: the same call gives the same bits.
+__global__ void __launch_bounds__(DRT_BLOCK)
+k_pixels_finish(PathArgs a, const PixelsHead* __restrict__ head, uint32_t n_views, uint32_t n_entries, const double* __restrict__ fpart,
+                float* __restrict__ out, uint32_t film_blocks, const double* __restrict__ gpart, int n_rows, int row_stride, int general,
+                const unsigned short* __restrict__ slot_map, double* __restrict__ view_grads, double* __restrict__ grad_sum, uint32_t grad_words,
+                const uint32_t* __restrict__ counts, unsigned long long* __restrict__ total)
+{
+    __shared__ double red[DRT_BLOCK];
+    const PixelView* views = pixel_views(head);
+    if (blockIdx.x < film_blocks) {
+        __shared__ uint32_t s_first[64];
+        if (threadIdx.x < 64)
+            s_first[threadIdx.x] = threadIdx.x < n_views ? views[threadIdx.x].first_entry : 0xFFFFFFFFu;
+        __syncthreads();
+        const double inv = 1.0 / (double)a.spp;
+        for (uint32_t e = blockIdx.x * DRT_BLOCK + threadIdx.x; e < n_entries; e += film_blocks * DRT_BLOCK) {
+            uint32_t v = 0;
+            for (uint32_t i = 1; i < n_views; ++i)
+                v = s_first[i] <= e ? i : v;
+            const uint32_t Pb = views[v].n_entries, j = e - views[v].first_entry;
+            const double* fv = fpart + views[v].fpart_at + j;
+            double r = 0, g = 0, b = 0;
+            for (uint32_t q = 0; q < a.n_ranges; ++q) {
+                const double* f = fv + ((size_t)q * 3) * Pb;
+                r += f[0]; g += f[(size_t)Pb]; b += f[(size_t)Pb * 2];
+            }
+            drt_f3 px;
+            px.x = (float)(r * inv); px.y = (float)(g * inv); px.z = (float)(b * inv);
+            *reinterpret_cast<drt_f3_u*>(out + (size_t)e * 3) = px;
+        }
+        return;
+    }
+    if (blockIdx.x < film_blocks + grad_words) {
+        const int p = (int)(blockIdx.x - film_blocks);
+        const int slot = slot_map[p / 3];
+        const int src = slot == (int)DRT_SLOT_NONE ? n_rows : (general ? slot * 3 + p % 3 : p);
+        double sum = 0;
+        for (uint32_t v = 0; v < n_views; ++v) {
+            const uint32_t first = views[v].first_block;
+            const int view_blocks = (int)views[v].n_blocks;
+            double x = 0;
+            if (src < n_rows)
+                for (int b = threadIdx.x; b < view_blocks; b += DRT_BLOCK)
+                    x += gpart[((size_t)first + b) * row_stride + src];
+            red[threadIdx.x] = x;
+            __syncthreads();
+            for (int off = DRT_BLOCK / 2; off > 0; off >>= 1) {
+                if ((int)threadIdx.x < off)
+                    red[threadIdx.x] += red[threadIdx.x + off];
+                __syncthreads();
+            }
+            if (threadIdx.x == 0) {
+                if (view_grads)
+                    view_grads[(size_t)v * grad_words + p] = red[0];
+                sum = v == 0 ? red[0] : sum + red[0];
+            }
+            __syncthreads();
+        }
+        if (threadIdx.x == 0 && grad_sum)
+            grad_sum[p] = sum;
+        return;
+    }
+    {
+        const uint32_t first = film_blocks + grad_words, nb = gridDim.x - first, me = blockIdx.x - first;
+        unsigned long long seg = 0, cap = 0;
+        for (uint32_t v = 0; v < n_views; ++v) {
+            const uint64_t view_waves = (uint64_t)views[v].n_groups * a.n_ranges;
+            const uint32_t* cv = counts + views[v].counts_at;
+            for (uint64_t w = (uint64_t)me * DRT_BLOCK + threadIdx.x; w < view_waves; w += (uint64_t)nb * DRT_BLOCK) {
+                seg += cv[w];
+                cap += cv[view_waves + w];
+            }
         }
         for (int off = DRT_WAVE / 2; off > 0; off >>= 1) {
             seg += __shfl_down(seg, off);

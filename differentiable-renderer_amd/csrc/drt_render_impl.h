@@ -216,6 +216,7 @@ struct PathForm {
                                     // order -- k_path_lean's last vertex asks only whether the path ended on one; 0: not known
     PathProg prog;
     bool views;                     // k_path_views: the biased lockstep forms -- forward only, columns, general -- over several frames (drt_hip_render_views)
+    bool pixels;                    // k_path_pixels: the same forms over the views' pixel lists (drt_hip_render_pixels)
     bool lean() const { return fixed && no_lit_bxdf; }
 };
 
@@ -250,7 +251,10 @@ struct Shard {
     bool sets_grad() const { return sets && sets->grad; }   // drt_hip_render_param_sets_grad: gradient tables, no per-pixel sums
     const ViewsRequest* views = nullptr;      // drt_hip_render_views: k_path_views, then k_views_finish
     size_t n_views() const { return views ? (size_t)views->n_views : 1; }   // frames in the one path launch: the partial sums' outermost dimension
-    bool views_grad() const { return views && views->backward; }
+    bool views_grad() const { return (views && views->backward) || (pixels && pixels->backward); }
+    const PixelsRequest* pixels = nullptr;    // drt_hip_render_pixels: k_path_pixels, then k_pixels_finish
+    PixelsGrid pixels_grid;                   // ... the views' places in its grid (shard_plan: drt_pixels.h)
+    bool multi() const { return views || pixels; }   // several cameras in the one path launch: the views plan
     bool pixel_sums() const { return gimg_param >= 0 || fwd_tangent || neq || (sets && !sets->grad); }   // the lanes' per-pixel sums leave the path kernel (gimg_part)
     // the scene in compute type R
     const DevScene<R>* d_scene;
@@ -352,6 +356,8 @@ inline std::string path_kernel_name(const drt_hip_ctx* ctx, const PathForm& f)
         snprintf(name, sizeof name, "k_path_sets_cross<%s, %s, %d, %s>", type, sp, f.nc, sg.c_str());
     else if (f.views)
         snprintf(name, sizeof name, "k_path_views<%s, %s, %d, %d, %s>", type, sp, f.np, DRT_NC_ROLES(f.nc, 0, 0), sg.c_str());
+    else if (f.pixels)
+        snprintf(name, sizeof name, "k_path_pixels<%s, %s, %d, %d, %s>", type, sp, f.np, DRT_NC_ROLES(f.nc, 0, 0), sg.c_str());
     else if (f.lean())
         snprintf(name, sizeof name, "k_path_lean<%s, %d, %d, %s, 0x%llxull>", type, f.np, DRT_NC_ROLES(f.nc, 0, 0) | f.roles << 8, sg.c_str(), f.lights);
     else
@@ -398,6 +404,15 @@ const void* library_path_kernel(const PathForm& f)
         return columns([&](auto np, auto nc) {
             return with_bool(f.spec, [&](auto spec) { return with_bool(f.prog == PathProg::cornell, [&](auto cornell) {
                 return (const void*)k_path_views<R, decltype(spec)::value, decltype(np)::value, decltype(nc)::value, std::conditional_t<cornell, SigCornell, SigNone>>; }); });
+        });
+    }
+    if (f.pixels) {
+        // ... and the same forms over pixel lists
+        if (f.op != PathOp::biased || f.regen || f.roles != 0 || f.nc == 1)
+            return nullptr;
+        return columns([&](auto np, auto nc) {
+            return with_bool(f.spec, [&](auto spec) { return with_bool(f.prog == PathProg::cornell, [&](auto cornell) {
+                return (const void*)k_path_pixels<R, decltype(spec)::value, decltype(np)::value, decltype(nc)::value, std::conditional_t<cornell, SigCornell, SigNone>>; }); });
         });
     }
     if (f.lean()) {
@@ -523,7 +538,7 @@ void shard_plan(Shard<R>& s)
                  rp->bounces_per_launch <= 0 && tuning().shade_bounces <= 0 && tuning().dump_path == -1;
     s.mesh_path = s.use_path && ctx->has_mesh;
     PathForm& f = s.path;
-    const bool lane_is_pixel = (s.gimg_param >= 0 || s.neq || s.sets || s.views) && !s.mesh_path;   // the gradient image / the Jacobian is the lanes' own sums: lockstep form only
+    const bool lane_is_pixel = (s.gimg_param >= 0 || s.neq || s.sets || s.multi()) && !s.mesh_path;   // the gradient image / the Jacobian is the lanes' own sums: lockstep form only
     // (k_path_mesh: every lane on its own, always; k_path_unbiased walks its samples in lockstep)
     f.regen = (tuning().path_regen > 0 || s.mesh_path) && !s.unbiased && !lane_is_pixel;
     if (s.use_path && !s.mesh_path && !lane_is_pixel && tuning().path_regen < 0 && !s.unbiased) {
@@ -581,9 +596,10 @@ void shard_plan(Shard<R>& s)
     }
     f.loss = s.loss_l2;
     f.views = s.views != nullptr;   // (the forms above as one frame's plan picks them; no roles, not k_path_lean's facts: the shell has neither)
+    f.pixels = s.pixels != nullptr; // (the views plan)
     // the slots' roles as the scene's records give them: for the form the headline runs -- diffuse, f32, lockstep, parameters in columns
     f.roles = 0;
-    if (tuning().path_roles && !f.views && tangents && !gen && sizeof(R) == 4 && !f.spec && !f.regen && !f.loss && f.op == PathOp::biased && s.gimg_param < 0 && !s.neq &&
+    if (tuning().path_roles && !f.views && !f.pixels && tangents && !gen && sizeof(R) == 4 && !f.spec && !f.regen && !f.loss && f.op == PathOp::biased && s.gimg_param < 0 && !s.neq &&
         ctx->colour_mask != 0 && ctx->emission_mask != 0)
         f.roles = (int)(ctx->colour_mask | ctx->emission_mask << 8);
     // ... and, for that form and the forward-only one, what else the host knows (k_path_lean, drt_path.h): the render has no roulette inside
@@ -591,7 +607,7 @@ void shard_plan(Shard<R>& s)
     // ... and, with both, which shapes are pure lights (upload_scene_one: an emitter, no BxDF), for the kernels whose program is compiled in
     f.fixed = f.no_lit_bxdf = false;
     f.lights = 0;
-    if (sizeof(R) == 4 && !f.views && !f.spec && !f.regen && !f.loss && f.op == PathOp::biased && !s.pixel_sums() &&
+    if (sizeof(R) == 4 && !f.views && !f.pixels && !f.spec && !f.regen && !f.loss && f.op == PathOp::biased && !s.pixel_sums() &&
         ((f.np == 4 && f.roles != 0) || (f.np == 0 && f.nc == 0)) &&
         rp->absorb >= 1.0 && rp->min_bounces == D && !ctx->emissive_bxdf) {
         f.fixed = f.no_lit_bxdf = true;
@@ -661,7 +677,7 @@ void shard_plan(Shard<R>& s)
         cap = s.total_paths;               // no per-path memory: one batch covers the frame
     if (tuning().batch_paths > 0)
         cap = (uint64_t)tuning().batch_paths;
-    if (s.neq || s.sets || s.views)
+    if (s.neq || s.sets || s.multi())
         cap = s.total_paths;               // k_normal_eq / k_sets_finish reads every range of every pixel of the shard: one batch (render_impl refuses frames beyond 2^31 paths)
     if (cap > s.total_paths) cap = s.total_paths;
     if (cap < 1) cap = 1;
@@ -692,6 +708,10 @@ void shard_plan(Shard<R>& s)
     }
     s.path_ranges = (s.Sb + s.path_spr - 1) / s.path_spr;
     s.path_waves = (size_t)path_groups * s.path_ranges;
+    // (a batch of pixel lists: the sample ranges above are the ones of a single W x H x spp frame, NOT re-tuned to the lists' lengths -- a
+    //  lane's sums and the sum over the ranges are then the single call's operations --; the grid and the partial sums are the packed lists')
+    if (s.pixels)
+        pixels_pack(s.pixels->counts, s.pixels->n_views, s.path_ranges, s.pixels_grid);
     s.shade_tail = ctx->has_mesh;
     // two-stage shade launches (measured, same process, alternating): config 4's share 5.90 -> 6.15 ms of shade launches (20 % fewer
     // bytes, 18 % more instructions, the second stage at two lanes in three), the unbiased operator's rounds 14.05 -> 13.25: on for those
@@ -700,12 +720,12 @@ void shard_plan(Shard<R>& s)
     const int tail_bounces = tail_bounces_now();
     s.tail_nb = s.shade_tail && (tail_bounces > 1 || (tail_bounces == 0 && s.unbiased)) ? 2 : 1;
     s.tail_ring = s.tail_nb > 1 ? 3 : 2;
-    s.overlap_ok = ctx->overlap_next && s.use_path && !s.timing && !s.pixel_sums() && !s.sets && !s.views && !s.sample_loss && ctx->path_stream[0] && ctx->ev_copied[0];
+    s.overlap_ok = ctx->overlap_next && s.use_path && !s.timing && !s.pixel_sums() && !s.sets && !s.multi() && !s.sample_loss && ctx->path_stream[0] && ctx->ev_copied[0];
     const bool odd = s.overlap_ok && (ctx->slot & 1);
     s.fpart_buf = odd ? &ctx->fpart2 : &ctx->fpart;
     s.gpart_buf = odd ? &ctx->gpart2 : &ctx->gpart;
     s.counts_buf = odd ? &ctx->counts2 : &ctx->counts;
-    s.cw = s.use_path ? (s.mesh_path ? 3 : 2) * s.path_waves * s.n_views()     // [segments | capped paths (| rays the BVH walk took)] per wave
+    s.cw = s.use_path ? (s.pixels ? (size_t)s.pixels_grid.count_words : (s.mesh_path ? 3 : 2) * s.path_waves * s.n_views())     // [segments | capped paths (| rays the BVH walk took)] per wave
                       : (size_t)(D + 2) * s.max_regions;          // counts[depth][region] of one batch (row D: capped paths, D + 1: rays kept in registers)
     // a k_path launch that covers the whole frame is followed by ONE finishing launch that WRITES image, gradients and
     // totals (k_path_finish); every other route accumulates into zeroed buffers
@@ -746,7 +766,7 @@ int shard_buffers(Shard<R>& s)
     int rc;
     memset(&s.cs, 0, sizeof s.cs);
     if (s.use_path) {
-        if ((rc = ensure(ctx, *s.fpart_buf, s.n_views() * (size_t)s.path_ranges * 3 * s.Pb * sizeof(double))) != DRT_OK) return rc;
+        if ((rc = ensure(ctx, *s.fpart_buf, (s.pixels ? (size_t)s.pixels_grid.fpart_doubles : s.n_views() * (size_t)s.path_ranges * 3 * s.Pb) * sizeof(double))) != DRT_OK) return rc;
         if (s.pixel_sums())
             if ((rc = ensure(ctx, ctx->gpix, (size_t)s.path_ranges * (size_t)s.jac_rows() * s.Pb * sizeof(double))) != DRT_OK) return rc;
         if (s.neq) {
@@ -815,7 +835,8 @@ int shard_buffers(Shard<R>& s)
     if (s.backward || s.sets_grad() || s.views_grad()) {   // per-block partial sums: K6's persistent grid, the shade kernel's one block per 4 regions, or k_path's blocks
         const size_t shade_blocks = (s.max_regions + DRT_BLOCK / DRT_WAVE - 1) / (DRT_BLOCK / DRT_WAVE);
         size_t blocks = std::max<size_t>(shade_blocks, (size_t)grid_for(ctx, N));
-        const size_t path_blocks = s.n_views() * ((s.path_waves + DRT_BLOCK / DRT_WAVE - 1) / (DRT_BLOCK / DRT_WAVE));   // (k_path_views: a frame's blocks per view)
+        const size_t path_blocks = s.pixels ? (size_t)s.pixels_grid.n_blocks    // (k_path_pixels: the packed grid)
+                                            : s.n_views() * ((s.path_waves + DRT_BLOCK / DRT_WAVE - 1) / (DRT_BLOCK / DRT_WAVE));   // (k_path_views: a frame's blocks per view)
         if (s.use_path && path_blocks > blocks)
             blocks = path_blocks;
         // rows per block: 24 for the register paths (<= 8 parameters), else one per parameter channel (LDS accumulators)
@@ -949,7 +970,7 @@ int path_batch(Shard<R>& s)
         pa.hist_lds = std::min<uint32_t>(hist_words, (uint32_t)tuning().gen_hist_lds);
     const unsigned hist_bytes = pa.hist_lds * DRT_BLOCK * (unsigned)sizeof(uint32_t);
     const uint32_t hist_ovf_words = hist_words - pa.hist_lds;
-    const unsigned short* slot_map = (gen || s.views) ? (const unsigned short*)((const char*)s.d_scene + offsetof(DevScene<R>, grad_slot)) : (const unsigned short*)nullptr;
+    const unsigned short* slot_map = (gen || s.multi()) ? (const unsigned short*)((const char*)s.d_scene + offsetof(DevScene<R>, grad_slot)) : (const unsigned short*)nullptr;
     const int g_rows = gen ? (int)s.gen_rows : s.n_fast * 3, g_stride = gen ? (int)s.gen_rows : DRT_FAST_PARAMS * 3;
     const size_t n_waves = (size_t)pa.n_groups * pa.n_ranges;
     const int gpath = (int)((n_waves + DRT_BLOCK / DRT_WAVE - 1) / (DRT_BLOCK / DRT_WAVE));
@@ -958,11 +979,27 @@ int path_batch(Shard<R>& s)
     const float* d_adjoint = s.d_adjoint;
     double* gpart = s.gpart;
     uint32_t* counts = s.counts;
-    double* fpart = (s.film || (s.views && s.views->d_images)) ? (double*)s.fpart_buf->p : (double*)nullptr;
+    double* fpart = (s.film || (s.views && s.views->d_images) || (s.pixels && s.pixels->d_rgb)) ? (double*)s.fpart_buf->p : (double*)nullptr;
     // (k_path_views: the frame's grid once per view, every view on a block boundary)
     const uint32_t view_blocks = (uint32_t)gpath;
-    const unsigned grid_blocks = (unsigned)((size_t)gpath * s.n_views());
+    const unsigned grid_blocks = s.pixels ? (unsigned)s.pixels_grid.n_blocks : (unsigned)((size_t)gpath * s.n_views());
     const void* d_views = s.views ? s.views->d_table : nullptr;
+    // (k_path_pixels: the views' places in the packed grid into the host's table, the table to the device in stream order)
+    const void* d_pixel_table = s.pixels ? s.pixels->d_table : nullptr;
+    const uint32_t* d_pixel_list = s.pixels ? s.pixels->d_pixels : nullptr;
+    const uint32_t n_pixel_views = s.pixels ? (uint32_t)s.pixels->n_views : 0u;
+    if (s.pixels) {
+        PixelsHead* head = reinterpret_cast<PixelsHead*>(s.pixels->h_table);
+        PixelView* pv = const_cast<PixelView*>(pixel_views(head));
+        for (uint32_t v = 0; v < 64; ++v)
+            head->first_block[v] = v < n_pixel_views ? s.pixels_grid.view[v].first_block : 0xFFFFFFFFu;
+        for (uint32_t v = 0; v < n_pixel_views; ++v) {
+            const PixelsViewGrid& g = s.pixels_grid.view[v];
+            pv[v].first_block = g.first_block; pv[v].n_blocks = g.n_blocks; pv[v].first_entry = g.first_entry; pv[v].n_entries = g.n_entries;
+            pv[v].n_groups = g.n_groups; pv[v].pad = 0; pv[v].fpart_at = g.fpart_at; pv[v].counts_at = g.counts_at;
+        }
+        HIPCHK(ctx, hipMemcpyAsync(s.pixels->d_table, s.pixels->h_table, s.pixels->table_bytes, hipMemcpyHostToDevice, ctx->stream));
+    }
     double* gpix = s.pixel_sums() ? (double*)ctx->gpix.p : (double*)nullptr;   // gradient image / derivative image partials
     unsigned long long* ptotal = s.path_finish ? s.totals : (unsigned long long*)nullptr;
     // (frames that overlap: this frame's grid goes to the lane's own stream, behind whoever still uses the lane's buffers, and
@@ -991,7 +1028,7 @@ int path_batch(Shard<R>& s)
     // (the kind-sorted program gives way to a kernel of the scene's own once it has rendered enough for the compile to pay)
     PathForm form = s.path;
     hipFunction_t jit = s.loss_kernel;
-    ctx->scene_work += (uint64_t)a.n_paths * s.n_views() * (uint64_t)(s.D > 0 ? s.D : 1);
+    ctx->scene_work += (s.pixels ? s.pixels->n_entries * (uint64_t)a.spp : (uint64_t)a.n_paths * s.n_views()) * (uint64_t)(s.D > 0 ? s.D : 1);
     if (form.prog == PathProg::sorted && form.op != PathOp::mesh && ctx->jit_mode > 0 && !form.f64 &&
         (ctx->jit_mode > 1 || ctx->scene_work >= DRT_JIT_AFTER_WORK) && (jit = jit_function(ctx, path_kernel_name(ctx, form), ctx->jit_mode > 1)))
         form.prog = PathProg::scene;
@@ -1052,7 +1089,8 @@ int path_batch(Shard<R>& s)
     void* args_unb[] = {&pa, &d_scene, &d_params, &d_adjoint, &gpart, &fpart, &counts, &ptotal};
     void* args_mesh[] = {&pa, &d_scene, &d_params, &d_adjoint, &s.bvh, &ovf, &ovf_stride, &gpart, &fpart, &counts, &ptotal, &gpix};
     void* args_views[] = {&pa, &d_views, (void*)&view_blocks, &d_scene, &d_params, &d_adjoint, &gpart, &fpart, &counts, &ptotal};
-    void** args = form.views ? args_views : (form.op == PathOp::unbiased ? args_unb : (form.op == PathOp::mesh ? args_mesh : args_path));
+    void* args_pixels[] = {&pa, &d_pixel_table, (void*)&n_pixel_views, &d_pixel_list, &d_scene, &d_params, &d_adjoint, &gpart, &fpart, &counts, &ptotal};
+    void** args = form.pixels ? args_pixels : form.views ? args_views : (form.op == PathOp::unbiased ? args_unb : (form.op == PathOp::mesh ? args_mesh : args_path));
     const unsigned lds_bytes = path_dynamic_lds<R>(form, ctx->n_params, hist_bytes);
     if (jit)
         HIPCHK(ctx, hipModuleLaunchKernel(jit, grid_blocks, 1, 1, DRT_BLOCK, 1, 1, lds_bytes, ks, args, nullptr));
@@ -1067,9 +1105,28 @@ int path_batch(Shard<R>& s)
     if (s.sample_loss)
         s.loss_parts += (uint32_t)n_waves;
     // (k_path_views: a frame's sums per view, whichever of them the call asked for)
-    st->path_bytes += s.n_views() * ((fpart ? (uint64_t)pa.n_ranges * a.Pb * 3 * sizeof(double) : 0) +
-                                     ((backward || s.views_grad()) ? (uint64_t)gpath * (uint64_t)g_stride * sizeof(double) : 0) +
-                                     (s.mesh_path ? 3 : 2) * n_waves * sizeof(uint32_t));
+    if (!s.pixels)      // (k_path_pixels: the packed lists' sums, below)
+        st->path_bytes += s.n_views() * ((fpart ? (uint64_t)pa.n_ranges * a.Pb * 3 * sizeof(double) : 0) +
+                                         ((backward || s.views_grad()) ? (uint64_t)gpath * (uint64_t)g_stride * sizeof(double) : 0) +
+                                         (s.mesh_path ? 3 : 2) * n_waves * sizeof(uint32_t));
+    if (s.path_finish && s.pixels) {
+        // the entries' radiance, the views' gradients, their sum in view order and the totals in one launch (timed in the film slot)
+        const PixelsRequest& q = *s.pixels;
+        const PixelsGrid& pg = s.pixels_grid;
+        st->path_bytes += (fpart ? pg.fpart_doubles * sizeof(double) : 0) + (q.backward ? (uint64_t)pg.n_blocks * (uint64_t)g_stride * sizeof(double) : 0) +
+                         pg.count_words * sizeof(uint32_t);
+        const uint32_t film_blocks = q.d_rgb ? (uint32_t)grid_for(ctx, (size_t)pg.n_entries) : 0u;
+        const uint32_t grad_words = q.backward ? (uint32_t)ctx->n_user_params * 3u : 0u;
+        const uint32_t count_blocks = (uint32_t)std::min<size_t>(64, ((size_t)pg.n_waves + DRT_BLOCK - 1) / DRT_BLOCK);
+        DRT_TIMED(s, DRT_K_FILM,
+                  hipLaunchKernelGGL(k_pixels_finish, dim3(film_blocks + grad_words + count_blocks), dim3(DRT_BLOCK), 0, ctx->stream, pa,
+                                     (const PixelsHead*)d_pixel_table, n_pixel_views, (uint32_t)pg.n_entries, (const double*)fpart, q.d_rgb, film_blocks,
+                                     (const double*)gpart, g_rows, g_stride, gen ? 1 : 0, slot_map, q.d_view_grads, q.d_grad, grad_words,
+                                     (const uint32_t*)counts, s.totals));
+        st->units[DRT_K_FILM] += pg.n_entries * (uint64_t)a.spp;
+        s.path_finished = true;
+        return DRT_OK;
+    }
     if (s.path_finish && s.views) {
         // the views' images, their gradients, the gradients' sum in view order and the totals in one launch (timed in the film slot)
         const ViewsRequest& q = *s.views;
@@ -1529,6 +1586,11 @@ int render_impl(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_p
         s.views = tangent->views;
         s.d_adjoint = tangent->views->d_adjoints;
     }
+    const bool pixels = tangent && tangent->kind == Kind::pixels;
+    if (pixels) {
+        s.pixels = tangent->pixels;
+        s.d_adjoint = tangent->pixels->d_adjoints;
+    }
     s.d_params = forward || directions || param_sets ? (const R*)tangent->d_params
                                                      : (sizeof(R) == 4 ? (const R*)ctx->d_params_f : (const R*)ctx->d_params_d);
     s.sample_loss = ctx->sample_loss_render;
@@ -1570,6 +1632,10 @@ int render_impl(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_p
         return fail(ctx, DRT_ERR_UNSUPPORTED, "views: they come from the one-launch path kernel's lockstep forms over the whole shard in one batch, which "
                                               "this render does not take (a DRT_HIP_* setting that forces the queue wavefront, paths that end at "
                                               "depth 0, or a scene its intersection program does not cover)");
+    if (pixels && (!s.use_path || s.mesh_path || !s.path_finish || !s.path.pixels || s.path.op != PathOp::biased || s.path.regen))
+        return fail(ctx, DRT_ERR_UNSUPPORTED, "pixels: they come from the one-launch path kernel's lockstep forms in one batch, which this render "
+                                              "does not take (a DRT_HIP_* setting that forces the queue wavefront, paths that end at depth 0, or "
+                                              "a scene its intersection program does not cover)");
     if (!ctx->user_header.empty()) {
         // caller-defined shape kinds live in the one-launch path kernel hiprtc compiles for the scene, nowhere else
         if (ctx->jit_mode <= 0)
@@ -1645,7 +1711,7 @@ int render_impl(drt_hip_ctx* ctx, const drt_camera_desc* cam, const drt_render_p
         DRT_TIMED(s, DRT_K_GRADREDUCE,
                   hipLaunchKernelGGL(k_loss_finish, dim3(1), dim3(DRT_BLOCK), 0, ctx->stream, (const double*)ctx->loss_part.p, s.loss_parts, (double*)ctx->loss_out.p));
     st->batches = batch;
-    st->paths = s.total_paths * (uint64_t)s.n_views();
+    st->paths = s.pixels ? s.pixels->n_entries * (uint64_t)s.spp : s.total_paths * (uint64_t)s.n_views();
     if (film && d_out_rgb && !s.path_finished)
         hipLaunchKernelGGL(k_resolve, dim3(grid_for(ctx, n_local_pixels)), dim3(DRT_BLOCK), 0, ctx->stream, a, n_local_pixels, film, d_out_rgb);
     if (s.pixel_sums() && gfilm && d_out_gimg && !s.path_finished)

@@ -17,6 +17,7 @@
 //   drt::hip::render_param_sets_along(scene, cam, tracer, spp, {set, ...}, target [, imgs, tangent_imgs, options])   up to 4 sets with a direction each: loss, slope, curvature
 //   drt::hip::render_param_sets_grad(scene, cam, tracer, spp, {set, ...} [, adjoints, options])     up to 8 sets with a summed gradient each, one trace
 //   drt::hip::render_views(scene, {cam, ...}, tracer, spp, imgs [, options, adjoints, seeds])       up to 64 cameras of one size, one trace
+//   drt::hip::render_pixels(scene, {cam, ...}, {{pixel, ...}, ...}, tracer, spp, out [, options, adjoints, seeds])   a batch of pixels of up to 64 cameras, one trace
 //   drt::hip::normal_equations_along(scene, cam, tracer, spp, {direction, ...}, options, target_or_residual) Gauss-Newton in their span
 //   drt::hip::normal_equations_cross(scene, cam, tracer, spp, {direction, ...}, options, target)             ... unbiased from one render
 //   drt::hip::render(scene of Dual<U>, ...)
@@ -1313,6 +1314,69 @@ inline Stats render_views(const Scene<T>& scene, const std::vector<Camera<T>>& c
     }
     if (images)
         detail::from_buffer(frames.data(), npix * V, images);
+    if (opt.backward)
+        detail::accumulate_grads(flat.handles, flat.requires_grad, grads.data());
+    return detail::to_stats(st);
+}
+
+// ---- a caller's batch of pixels from several cameras in one trace (drt_hip_render_pixels) ---------------------------------------------
+// render_views() for pixel lists: pixels[v] holds camera v's pixels as y * width + x, in any order, repeats allowed, possibly none; out gets
+// one value per entry in list order, the views' lists one behind the other -- that pixel of what render() with cameras[v] leaves in its
+// img, bit for bit; with Options::backward the SUM over all entries of what their samples add to the handles' grad() is added to them,
+// adjoints[e] entry e's adjoint (nullptr: all ones).  `seeds` (one per view; empty: Options::seed for every view).  One device; the biased
+// operator.  Throws where render_views() throws, and on an empty batch and on a pixel outside the frame.
+template <typename T>
+inline Stats render_pixels(const Scene<T>& scene, const std::vector<Camera<T>>& cameras, const std::vector<std::vector<uint32_t>>& pixels,
+                           const Pathtracer<T>& tracer, std::size_t spp, Vector<T, 3>* out, const Options& opt = Options(),
+                           const Vector<T, 3>* adjoints = nullptr, const std::vector<uint32_t>& seeds = std::vector<uint32_t>())
+{
+    const char* who = "drt::hip::render_pixels";
+    if (opt.unbiased || opt.sample_loss_l2)
+        throw std::runtime_error(std::string(who) + ": the biased operator (no unbiased, no sample_loss_l2)");
+    detail::one_device(who, opt);
+    if (cameras.empty() || cameras.size() > (std::size_t)DRT_HIP_MAX_VIEWS)
+        throw std::runtime_error(std::string(who) + ": 1 ... DRT_HIP_MAX_VIEWS = 64 cameras");
+    if (pixels.size() != cameras.size())
+        throw std::runtime_error(std::string(who) + ": a pixel list per camera");
+    if (!seeds.empty() && seeds.size() != cameras.size())
+        throw std::runtime_error(std::string(who) + ": a seed per camera, or none");
+    const std::size_t V = cameras.size(), npix = cameras[0].width() * cameras[0].height();
+    std::vector<int32_t> counts;
+    std::vector<uint32_t> list;
+    for (const std::vector<uint32_t>& l : pixels) {
+        counts.push_back((int32_t)l.size());
+        for (uint32_t p : l) {
+            if ((std::size_t)p >= npix)
+                throw std::runtime_error(std::string(who) + ": a pixel outside the frame (>= width * height)");
+            list.push_back(p);
+        }
+    }
+    if (list.empty())
+        throw std::runtime_error(std::string(who) + ": an empty batch (no entries in any view)");
+    FlatScene<T> flat = flatten(scene);
+    std::vector<drt_camera_desc> cds;
+    for (const Camera<T>& cam : cameras) {
+        if (cam.width() != cameras[0].width() || cam.height() != cameras[0].height())
+            throw std::runtime_error(std::string(who) + ": the cameras differ in width or height (all views share one size)");
+        cds.push_back(describe(cam));
+    }
+    const std::size_t E = list.size();
+    const std::vector<float> adj = adjoints && opt.backward ? detail::to_floats(adjoints, E) : std::vector<float>();
+    const drt_render_params rp = detail::render_params(tracer.absorb(), tracer.min_bounces(), spp, opt, detail::reverse_flags(opt));
+    std::vector<double> grads((flat.requires_grad.size() ? flat.requires_grad.size() : 1) * 3, 0.0);
+    std::vector<float> rgb(out ? E * 3 : 0, 0.f);
+    if (!out && !opt.backward)
+        throw std::runtime_error(std::string(who) + ": nothing to compute (no out, no backward)");
+    drt_hip_stats st{};
+    {
+        detail::Session s = detail::Session::on_first_device(opt, flat);
+        s.ctx.check(drt_hip_render_pixels(s.ctx.get(), cds.data(), (int32_t)V, &rp, seeds.empty() ? nullptr : seeds.data(), counts.data(), list.data(),
+                                          adj.empty() ? nullptr : adj.data(), out ? rgb.data() : nullptr,
+                                          opt.backward ? grads.data() : nullptr, nullptr, &st),
+                    "drt_hip_render_pixels");
+    }
+    if (out)
+        detail::from_buffer(rgb.data(), E, out);
     if (opt.backward)
         detail::accumulate_grads(flat.handles, flat.requires_grad, grads.data());
     return detail::to_stats(st);

@@ -648,6 +648,42 @@ int drt_hip_render_views(drt_hip_ctx* ctx, const drt_camera_desc* cams /* n_view
                          float* out_images /* n_views x H x W x 3, may be NULL */,
                          double* out_param_grad /* n_params x 3, the sum over the views, may be NULL */,
                          double* out_view_grads /* n_views x n_params x 3, may be NULL */, drt_hip_stats* stats);
+/* ---- a caller's batch of pixels from up to DRT_HIP_MAX_VIEWS cameras in ONE trace: what a stochastic fitting loop over several views renders
+ * per step (a few thousand pixels drawn across all views), and what an adaptive scheme re-renders (the pixels its variance image calls noisy).
+ * Entry e of view v is pixel pixels[e] = y W + x of camera v; the views' lists stand one behind the other, counts[v] entries each.  For
+ * rp_v = *rp with seed = seeds ? seeds[v] : rp->seed:
+ *   out_rgb[e]         that pixel of the image drt_hip_render(ctx, &cams[v], &rp_v, ...) returns, bit for bit, in f32 and under
+ *                      DRT_RENDER_F64, wherever drt_hip_render_views promises the same for a whole image (the RNG key of a camera sample is
+ *                      pixel spp + sample: a pixel rendered alone draws what it draws inside its frame); entries keep the caller's order
+ *   out_view_grads[v]  J_v^T w_v over view v's entries -- the SUM over the samples, w the entries' adjoints (adjoints_rgb, NULL: all ones) --,
+ *                      zeros for requires_grad == 0, all zeros for a view with counts[v] == 0.  A pixel may appear any number of times, in
+ *                      one view or in several: every occurrence gets the same radiance and counts once in the gradients, with its own
+ *                      adjoint.  Against drt_hip_render with the adjoint image that holds, per pixel, the sum of its entries' adjoints: the
+ *                      same paths and per-lane sums, another grouping into waves and blocks -- f64 within 1e-9 of the largest component,
+ *                      f32 within the stated bound; the full frame as a list (pixels 0 ... W H - 1 per view) is drt_hip_render_views' grid
+ *                      and gives its bits
+ *   out_param_grad     the views' vectors added in view order in fp64
+ * stats->paths = sum(counts) spp; ->segments and ->capped_paths are summed over all entries; launches[DRT_K_PATH] == 1 for any input.  The
+ * path kernel is a shell of its own (k_path_pixels): view v's list is a "frame" of counts[v] pixels -- ceil(counts[v] / 64) waves times the
+ * sample ranges the plan picks for a single W x H x spp frame (not re-tuned to the list's length: that is what keeps the single call's
+ * operations), every view on a block boundary, a view without entries without blocks.  k_pixels_finish adds the ranges and the views'
+ * blocks in fixed orders; no float is added by an atomic: the same call returns the same bits.  DRT_RENDER_BACKWARD is needed for either
+ * gradient output; _F64, _TIMING, _SYNC and _DEVICE_OUT as in drt_hip_render_views (with _DEVICE_OUT adjoints_rgb and the three outputs are
+ * device pointers; cams, seeds, counts and pixels are host memory always).  One batch, on the context's stream, in order.
+ * DRT_ERR_INVALID: n_views outside 1 ... DRT_HIP_MAX_VIEWS, NULL cams, rp, counts or pixels, a negative count, sum(counts) == 0, a pixel
+ * >= W H, cameras of different sizes, no output requested, a gradient output without DRT_RENDER_BACKWARD, an adjoint value that is not finite
+ * (host buffers), rp->n_shards > 1 (a list is the caller's own split), asynchronous frames in flight.  DRT_ERR_UNSUPPORTED: everything
+ * drt_hip_render_views refuses (a triangle mesh, a group context, bounces_per_launch >= 1, DRT_RENDER_UNFUSED, _UNBIASED, _LOSS_L2 or
+ * _ALLREDUCE*, more than 136 parameters, a DRT_HIP_* setting that forces the queue wavefront, paths that end at depth 0), and more than 2^31
+ * camera samples over all entries.  The message of either says "pixels"; the context stays usable. */
+int drt_hip_render_pixels(drt_hip_ctx* ctx, const drt_camera_desc* cams /* n_views, one size */, int32_t n_views, const drt_render_params* rp,
+                          const uint32_t* seeds /* n_views, NULL: rp->seed for every view */,
+                          const int32_t* counts /* n_views: entries of view v, >= 0 */,
+                          const uint32_t* pixels /* sum(counts): y * W + x, the views' lists one behind the other */,
+                          const float* adjoints_rgb /* sum(counts) x 3, NULL: all ones */,
+                          float* out_rgb /* sum(counts) x 3, may be NULL */,
+                          double* out_param_grad /* n_params x 3, the sum over all entries, may be NULL */,
+                          double* out_view_grads /* n_views x n_params x 3, may be NULL */, drt_hip_stats* stats);
 /* ---- the per-sample loss from the caller's own source, with the loss's value.  The reference's loop is
  *     auto radiance = tracer.trace(scene, orig, dir);  auto loss = loss_func(radiance);  loss.backward();       (README.md:93-98)
  * with loss_func the caller's code; DRT_RENDER_LOSS_L2 is the one loss_func the library carries, and returns no value.  Here the loss is the

@@ -17,6 +17,7 @@ the same thing for a loss that is linear in the radiance.
     python tools/fit_albedo.py [--size 128] [--spp 16] [--steps 60] [--async] [--oracle] [--gauss-newton [--one-render [--cross [--lambda-sets N]]] [--lambda-sets N]]
     python tools/fit_albedo.py --scene cornell_shapes --multi-start N [--oracle]
     python tools/fit_albedo.py --views N [--size 32] [--spp 8] [--steps 60]
+    python tools/fit_albedo.py --views N --pixels M [--size 32] [--spp 8] [--steps 60]
 
 --views N (N <= 64): the first loop above against N target views at once, cameras on an arc in front of the box: per step ONE
 drt_hip_render_views forward on seed A and ONE backward on seed B with the N adjoint images, whose summed gradient is the gradient of the mean
@@ -700,6 +701,54 @@ def fit_views(pkg, n_views, size, spp, depth, steps, lr=0.08, decay=0.96, log=No
     return params[0].copy(), losses, fixed
 
 
+def fit_pixels(pkg, n_views, n_pixels, size, spp, depth, steps, lr=0.08, decay=0.96, log=None, draw_seed=7):
+    """--views N --pixels M: fit_views' loop as the stochastic one -- each step draws M (view, pixel) pairs with a seeded generator and makes
+    ONE render_pixels forward on one seed and ONE render_pixels backward on another over those pixels alone; the loss of a step is the mean
+    squared error over its M entries.
+    -> (fitted rgb, loss per step, the loss over ALL views' frames on one fixed seed at 128 spp before and after)"""
+    r = pkg.HipRenderer(0)
+    scene = pkg.scene_by_name("cornell")
+    r.upload_scene(scene)
+    cams = arc_cameras(pkg, n_views, size)
+    params = np.array(scene.params, dtype=np.float64)
+    tracer = dict(min_bounces=depth, absorb=1.0)
+    target = r.render_views(cams, pkg.RenderParams(spp=256, seed=1, **tracer))[0].astype(np.float64)
+    flat_target = target.reshape(n_views, size * size, 3)
+    params[0] = (0.2, 0.2, 0.2)
+
+    def fixed_seed_loss():
+        r.update_params(params)
+        imgs = r.render_views(cams, pkg.RenderParams(spp=128, seed=9001, **tracer))[0]
+        return float(((imgs.astype(np.float64) - target) ** 2).mean())
+
+    fixed = [fixed_seed_loss()]
+    rs = np.random.RandomState(draw_seed)
+    m = np.zeros(3); v = np.zeros(3)
+    b1, b2, eps = 0.8, 0.99, 1e-8
+    losses = []
+    for k in range(steps):
+        r.update_params(params)
+        # M (view, pixel) pairs -> the views' lists, one behind the other, and the targets in that order
+        view = np.sort(rs.randint(0, n_views, n_pixels))
+        pix = rs.randint(0, size * size, n_pixels)
+        lists = [pix[view == i] for i in range(n_views)]
+        want = flat_target[view, pix]
+        rgb = r.render_pixels(cams, lists, pkg.RenderParams(spp=spp, seed=1000 + 2 * k, **tracer))[0]
+        resid = rgb.astype(np.float64) - want
+        losses.append(float((resid ** 2).mean()))
+        adj = (2.0 * resid / resid.size).astype(np.float32)
+        _, gsum, _, _ = r.render_pixels(cams, lists, pkg.RenderParams(spp=spp, seed=1001 + 2 * k, **tracer), backward=True, adjoints=adj)
+        g = gsum[0] / spp
+        m = b1 * m + (1 - b1) * g
+        v = b2 * v + (1 - b2) * g * g
+        params[0] = np.clip(params[0] - lr * decay ** k * (m / (1 - b1 ** (k + 1))) / (np.sqrt(v / (1 - b2 ** (k + 1))) + eps), 0.0, 1.0)
+        if log:
+            log(f"step {k:3d}  loss {losses[-1]:.6f}  red = ({params[0][0]:.4f}, {params[0][1]:.4f}, {params[0][2]:.4f})")
+    fixed.append(fixed_seed_loss())
+    r.close()
+    return params[0].copy(), losses, fixed
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=128)
@@ -721,6 +770,9 @@ def main():
     ap.add_argument("--views", type=int, default=0,
                     help="fit the red albedo against this many views (<= 64) on an arc in front of the box: one render_views forward and one "
                          "backward per step; prints the loss per step")
+    ap.add_argument("--pixels", type=int, default=0,
+                    help="with --views: the stochastic loop -- this many (view, pixel) pairs drawn per step with a seeded generator, one "
+                         "render_pixels forward and one backward over them alone")
     ap.add_argument("--async", dest="use_async", action="store_true")
     ap.add_argument("--oracle", action="store_true")
     ap.add_argument("--quiet", action="store_true")
@@ -738,8 +790,17 @@ def main():
     if a.views and (a.gauss_newton or a.use_async or a.lambda_sets or a.line_search or a.multi_start or a.oracle or a.scene != "cornell" or
                     not 1 <= a.views <= 64):
         ap.error("--views N (1 ... 64) is the first-order loop on the device, --scene cornell (no other mode)")
+    if a.pixels and (not a.views or a.pixels < 1):
+        ap.error("--pixels M (>= 1) goes with --views N")
     import __graft_entry__ as e
     pkg = e.load_package()
+    if a.views and a.pixels:
+        t0 = time.time()
+        steps = a.steps or 60
+        rgb, losses, fixed = fit_pixels(pkg, a.views, a.pixels, a.size, a.spp, a.depth, steps, log=print)
+        print(f"fitted red = ({rgb[0]:.4f}, {rgb[1]:.4f}, {rgb[2]:.4f})  {a.views} views, {a.pixels} pixels a step, {steps} steps, {2 * steps} "
+              f"render_pixels calls in {time.time() - t0:.2f} s; loss {losses[0]:.6f} -> {losses[-1]:.6f}; fixed-seed loss {fixed[0]:.6f} -> {fixed[1]:.6f}")
+        return 0 if fixed[1] < fixed[0] else 1
     if a.views:
         t0 = time.time()
         steps = a.steps or 60
