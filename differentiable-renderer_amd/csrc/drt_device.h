@@ -12,6 +12,7 @@
 #define INFINITY __builtin_huge_valf()
 #endif
 #include "drt_sincos.h"
+#include "drt_fold.h"
 
 #define DRT_MAX_SHAPES 64
 #define DRT_MAX_MATERIALS 64

@@ -125,6 +125,13 @@ typedef KindSig<DRT_SIG_CORNELL, 0ull, 0ull, 0ull, DRT_NSIG_CORNELL> SigCornell;
 #ifndef DRT_LEAN_LIVE_MASK
 #define DRT_LEAN_LIVE_MASK 1            // k_path_lean's gradient form carries "the lane's path goes on" round its loop as the wave's mask in a scalar pair (0: as a bool; profiles/r18_bounce_fusions.txt)
 #endif
+#ifndef DRT_LEAN_FOLD_DRAWS
+#ifdef DRT_USER_SHAPES
+#define DRT_LEAN_FOLD_DRAWS 0           // (caller-defined kinds: the loop's text stays, as above)
+#else
+#define DRT_LEAN_FOLD_DRAWS 1           // k_path_lean beside a compiled-in program folds the key once per sample and h(n) on the scalar unit (drt_fold.h; 0: the plain draw; profiles/r26_folded_draws.txt)
+#endif
+#endif
 
 // (DRT_PATH_LDS_PARAMS, drt_device.h: parameters staged in LDS; more: read from L2)
 
@@ -1223,14 +1230,22 @@ __device__ inline void path_bounce(const PathArgs& a, const PathSceneLds<R>& lds
                                    typename Q4<R>::T& ra, typename Q2<R>::T& rb, V3<R>& T, V3<R>& L, Tangents<R, NP, NC>& tg,
                                    bool& alive, bool& capped, bool& on_light, uint32_t& light, PathVertex<R>* vo = nullptr,
                                    bool last = false, const float* __restrict__ seed_px = nullptr, const uint32_t* ih = nullptr,
-                                   const LeanLds<SG::n, NC>* ll = nullptr, uint64_t* live_mask = nullptr)
+                                   const LeanLds<SG::n, NC>* ll = nullptr, uint64_t* live_mask = nullptr, uint32_t kf = 0u)
 {
     static_assert(LIGHTS == 0ull || (sizeof(R) == 4 && SG::n > 0 && FIXED && NO_LIT_BXDF), "LIGHTS: k_path_lean's compiled-in program");
+    // FOLDED (k_path_lean beside a compiled-in program): `kf` is the sample's folded key (path_camera) and a draw is combine_folded
+    // (drt_fold.h) of it and the folded h(n) -- the scalar unit's, as h(n) is: one exclusive-or a lane where the plain draw has two
+    constexpr bool FOLDED = DRT_LEAN_FOLD_DRAWS != 0 && FIXED && SG::n > 0;
     // LEAN_REC (k_path_lean's facts beside a compiled-in program): the hit's record and the colour's row come from `ll` (LeanLds)
     constexpr bool LEAN_REC = lean_rec<SG, NC, FREEZE_BY_ROW, FIXED, NO_LIT_BXDF, SPEC, R>();
     // (ih, the forms whose lanes stand at their own depths: the draw indices' hash rounds h(n) as a table in LDS -- where all
     //  lanes of a wave share the index, the lockstep kernel, the scalar unit computes h(n) and the table would only cost)
-    auto draw = [&](uint32_t n) { return ih ? drt_rng_combine(ih[n], key) : rng_draw(a.rng_stream, key, n); };
+    auto draw = [&](uint32_t n) {
+        if constexpr (FOLDED)
+            return combine_folded(fold16(drt_rng_index_hash(a.rng_stream, n)), kf);
+        else
+            return ih ? drt_rng_combine(ih[n], key) : rng_draw(a.rng_stream, key, n);
+    };
     // (seed_px, the regenerating form: where the pixel's adjoint seed stands in the caller's image -- read only where a vertex
     //  emits, instead of carrying it in registers for a lane that changes pixel with every path)
     // `last` (wave-uniform; the lockstep kernel at the deepest vertex a path can have): no lane's path goes on from here, so
@@ -1240,7 +1255,7 @@ __device__ inline void path_bounce(const PathArgs& a, const PathSceneLds<R>& lds
     // bounce's ~280 vector instructions less: 5 % of a depth-8 frame.
     if constexpr (LIGHTS != 0ull) if (last) {
         constexpr int l0 = __builtin_ctzll(LIGHTS);                   // (one light: its record's place is a constant)
-        const int il = light_end_sig<SG, LIGHTS>(recs, mk<R>(ra.x, ra.y, ra.z), mk<R>(ra.w, rb.x, rb.y));
+        const int il = light_end_sig<SG, LIGHTS>(recs, mk<R>(ra.x, ra.y, ra.z), mk<R>(ra.w, rb.x, rb.y), live);
         on_light = live && il >= 0;
         light = (uint32_t)lds.sc.shapes[(LIGHTS & (LIGHTS - 1ull)) == 0ull || il < 0 ? l0 : il].pad >> 16;
         alive = false;
@@ -1495,6 +1510,29 @@ __device__ inline uint32_t path_camera(const PathArgs& a, const CameraLane<R>& c
         px = gpix - py * (uint32_t)a.W;
     }
     return path_camera<R, false>(a, cl, gpix, px, py, sl, ra, rb);
+}
+// ... of k_path_lean beside a compiled-in program (f32; a twin, so that path_camera keeps its text for every other kernel): the same camera,
+// its two draws by the sample's folded key (drt_fold.h), which it makes here, once, and leaves in `kf` for the draws of the sample's bounces
+// (path_bounce: FOLDED).  The same draws bit for bit -- tests/cpp/fold_kat.cpp -- and so the same ray.
+template <bool ARGS_F32>
+__device__ inline uint32_t path_camera_folded(const PathArgs& a, const CameraLane<float>& cl, uint32_t gpix, uint32_t sl, float4& ra, float2& rb, uint32_t& kf)
+{
+    const uint64_t path = (uint64_t)gpix * (uint64_t)a.spp + (uint64_t)(a.s0 + sl);
+    const uint32_t key = (uint32_t)path;
+    kf = fold16(key);
+    const float cs_step = ARGS_F32 ? a.cs_step_f : (float)(2. * a.aspect * a.tan_half * a.inv_W);
+    const float ct_step = ARGS_F32 ? a.ct_step_f : (float)(2. * a.tan_half * a.inv_H);
+    const V3<float> eye = ARGS_F32 ? mk<float>(a.eye_f[0], a.eye_f[1], a.eye_f[2]) : mk<float>((float)a.eye[0], (float)a.eye[1], (float)a.eye[2]);
+    const V3<float> fw = ARGS_F32 ? mk<float>(a.fwd_f[0], a.fwd_f[1], a.fwd_f[2]) : mk<float>((float)a.fwd[0], (float)a.fwd[1], (float)a.fwd[2]);
+    const V3<float> rt = ARGS_F32 ? mk<float>(a.right_f[0], a.right_f[1], a.right_f[2]) : mk<float>((float)a.right[0], (float)a.right[1], (float)a.right[2]);
+    const V3<float> upv = ARGS_F32 ? mk<float>(a.up_f[0], a.up_f[1], a.up_f[2]) : mk<float>((float)a.up[0], (float)a.up[1], (float)a.up[2]);
+    const float cs = fmaf(u01(0.f, combine_folded(fold16(drt_rng_index_hash(a.rng_stream, 0)), kf)), cs_step, (float)cl.cs0);
+    const float ct = fmaf(u01(0.f, combine_folded(fold16(drt_rng_index_hash(a.rng_stream, 1)), kf)), ct_step, (float)cl.ct0);
+    const V3<float> dir = mk<float>(fw.x + cs * rt.x - ct * upv.x, fw.y + cs * rt.y - ct * upv.y, fw.z + cs * rt.z - ct * upv.z);
+    const V3<float> dn = normalize(dir);
+    ra.x = eye.x; ra.y = eye.y; ra.z = eye.z; ra.w = dn.x;
+    rb.x = dn.y; rb.y = dn.z;
+    return key;
 }
 
 // blocks per CU (= waves per SIMD) a k_path instantiation is compiled for (its register budget); the knobs are above.
@@ -2344,7 +2382,13 @@ k_path_lean(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict_
         for (uint32_t sl = pl.s_begin; sl < pl.s_end; ++sl) {
             R4 ra;
             R2 rb;
-            const uint32_t key = path_camera<R, ARGS_F32>(a, cl, gpix, px, py, sl, ra, rb);
+            // (FOLD: the sample's key folded once, here; the camera's draws and the bounces' take the folded key -- drt_fold.h, path_bounce: FOLDED)
+            constexpr bool FOLD = DRT_LEAN_FOLD_DRAWS != 0 && SG::n > 0;
+            uint32_t kf = 0u, key;
+            if constexpr (FOLD)
+                key = path_camera_folded<ARGS_F32>(a, cl, gpix, sl, ra, rb, kf);
+            else
+                key = path_camera<R, ARGS_F32>(a, cl, gpix, px, py, sl, ra, rb);
             bool live = pl.have;                             // (pathtracer.hpp:128 at depth 0: min_bounces = the cap > 0, no roulette there either)
             V3<R> T = mk<R>(R(1), R(1), R(1)), L = mk<R>(R(0), R(0), R(0));
             uint32_t end_ids = DRT_ID_NONE;               // emission parameter of the light the path ended on
@@ -2368,7 +2412,7 @@ k_path_lean(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict_
                         live = __builtin_amdgcn_inverse_ballot_w64(lm);
                     path_bounce<R, false, NP, NC, SG, BY_ROW, true, true, LIGHTS>(
                         a, lds, tl, sc, params, recs, key, R(1), R(1), n_theta, false, next_cap, live, g, ra, rb, T, L, tg, alive, capped, on_light, light, nullptr, next_cap,
-                        nullptr, nullptr, ll, LIVE_MASK ? &lm : nullptr);
+                        nullptr, nullptr, ll, LIVE_MASK ? &lm : nullptr, kf);
                     end_ids = on_light ? light : end_ids;
                     live = alive;
                 };
@@ -2397,7 +2441,7 @@ k_path_lean(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict_
                 uint32_t light;
                 path_bounce<R, false, NP, NC, SG, BY_ROW, true, true, LIGHTS>(
                     a, lds, tl, sc, params, recs, key, R(1), R(1), n_theta, false, next_cap, live, g, ra, rb, T, L, tg, alive, capped, on_light, light, nullptr, next_cap,
-                    nullptr, nullptr, ll);
+                    nullptr, nullptr, ll, nullptr, kf);
                 end_ids = on_light ? light : end_ids;     // (its emission: once per sample, below)
                 live = alive;
             }

@@ -244,14 +244,22 @@ __device__ inline void light_end_others(const ProgRecs<SG::n, float>& recs, V3<f
         light_end_others<SG, LM, S + 1>(recs, o, d, inv_d, tl, il, hidden);
     }
 }
+// `live`: the lane's path is still going.  Only a live lane whose ray reaches a light's front (il >= 0) has anything to ask the other shapes;
+// a wave without such a lane -- few paths left, or none of them looking at a light -- leaves them out: a compare's ballot and a scalar
+// branch, no vector instruction for the waves that go on.  The caller uses the result only as `live && il >= 0`.
+#ifndef DRT_LEAN_SKIP_UNLIT
+#define DRT_LEAN_SKIP_UNLIT 1           // (0: every wave asks the other shapes, as it was; profiles/r26_folded_draws.txt)
+#endif
 template <typename SG, unsigned long long LM>
-__device__ inline int light_end_sig(const ProgRecs<SG::n, float>& recs, V3<float> o, V3<float> d)
+__device__ inline int light_end_sig(const ProgRecs<SG::n, float>& recs, V3<float> o, V3<float> d, bool live)
 {
     static_assert(LM != 0 && SG::n > 0 && SG::n <= 64 && (SG::n == 64 || (LM >> (SG::n & 63)) == 0), "light_end_sig: a light set of the program's own shapes");
     const V3<float> inv_d = mk<float>(prog_rcp(d.x), prog_rcp(d.y), prog_rcp(d.z));
     float tl = INFINITY;
     int il = -1;
     light_end_lights<SG, LM>(recs, o, d, inv_d, tl, il);
+    if (DRT_LEAN_SKIP_UNLIT != 0 && __builtin_amdgcn_ballot_w64(live && il >= 0) == 0)
+        return -1;
     bool hidden = false;
     light_end_others<SG, LM>(recs, o, d, inv_d, tl, il, hidden);
     return hidden ? -1 : il;
