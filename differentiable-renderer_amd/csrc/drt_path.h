@@ -289,6 +289,25 @@ __device__ inline void stage_tangents(TangentLds<R>& tl, const SL& lds)
 //   col[r]   32 B per colour: (colnz.xyz, n_p increment low) -- one ds_read_b128 -- and (zc increment, n_p increment high).  Row 0 is
 //            TangentLds's rest row (1, 1, 1), zeros; colour p stands in row p + 1.  A lane that goes on selects its record's offset,
 //            any other lane 0: no shift, no add.  The same values as TangentLds's colnz / inc, copied, not recomputed.
+// Per-lane special cases of k_path_lean's bounce (LEAN_REC) under the lane mask instead of computed for all 64 lanes and kept by select
+// (profiles/r27_masked_lanes.txt).  Each switch: bit 0 the gradient forms (NP > 0), bit 1 the forward-only form; 0: the selects, as it was.
+//   DRT_LEAN_MASK_NORMAL  the sphere's normal only in the lanes that hit a sphere, behind a branch a wave of plane hits skips (71 % of
+//                         config 3's waves at the first vertex, 8 % at the second): both forms;
+//   DRT_LEAN_REC_OFFSET   the closest hit hands back the record's byte offset in LeanLds::rec (closest_hit_sig: SCALE), no shift: the
+//                         gradient form (forward only: no run-to-run gain over the masked normal alone);
+//   DRT_LEAN_MASK_REST    the colour's row, T, n_p and zc only in the lanes whose path goes on -- the rest row's factor is exactly 1
+//                         and its increments 0, so a lane that stops keeps the bits it had: the gradient form (forward only: three
+//                         instructions shorter and 0.4 % SLOWER, as a shorter loop was in r17 and r18).
+#ifndef DRT_LEAN_MASK_NORMAL
+#define DRT_LEAN_MASK_NORMAL 3
+#endif
+#ifndef DRT_LEAN_REC_OFFSET
+#define DRT_LEAN_REC_OFFSET 1
+#endif
+#ifndef DRT_LEAN_MASK_REST
+#define DRT_LEAN_MASK_REST 1
+#endif
+constexpr bool lean_part(int part, int np) { return ((part >> (np == 0 ? 1 : 0)) & 1) != 0; }
 #ifndef DRT_LEAN_REC
 #define DRT_LEAN_REC 1                  // 0: the bounce reads DevShape and TangentLds as before (the per-part A/B of profiles/r18_bounce_fusions.txt)
 #endif
@@ -1230,7 +1249,7 @@ __device__ inline void path_bounce(const PathArgs& a, const PathSceneLds<R>& lds
                                    typename Q4<R>::T& ra, typename Q2<R>::T& rb, V3<R>& T, V3<R>& L, Tangents<R, NP, NC>& tg,
                                    bool& alive, bool& capped, bool& on_light, uint32_t& light, PathVertex<R>* vo = nullptr,
                                    bool last = false, const float* __restrict__ seed_px = nullptr, const uint32_t* ih = nullptr,
-                                   const LeanLds<SG::n, NC>* ll = nullptr, uint64_t* live_mask = nullptr, uint32_t kf = 0u)
+                                   const LeanLds<SG::n, NC>* ll = nullptr, uint64_t* live_mask = nullptr, uint32_t kf = 0u, uint32_t* end_ids = nullptr)
 {
     static_assert(LIGHTS == 0ull || (sizeof(R) == 4 && SG::n > 0 && FIXED && NO_LIT_BXDF), "LIGHTS: k_path_lean's compiled-in program");
     // FOLDED (k_path_lean beside a compiled-in program): `kf` is the sample's folded key (path_camera) and a draw is combine_folded
@@ -1263,7 +1282,12 @@ __device__ inline void path_bounce(const PathArgs& a, const PathSceneLds<R>& lds
         return;
     }
     HitRec<R> h;
-    if constexpr (LEAN_REC)                                           // (a miss: the index of LeanLds's miss record)
+    // (REC_OFFSET: the hit comes back as its record's byte offset in LeanLds::rec, the miss record's included)
+    constexpr bool REC_OFFSET = LEAN_REC && lean_part(DRT_LEAN_REC_OFFSET, NP), MASK_NORMAL = LEAN_REC && lean_part(DRT_LEAN_MASK_NORMAL, NP),
+                   MASK_REST = LEAN_REC && lean_part(DRT_LEAN_MASK_REST, NP);
+    if constexpr (REC_OFFSET)
+        h = closest_hit_sig<SG, R, SG::n * (int)sizeof(LeanRec), (int)sizeof(LeanRec)>(recs, mk<R>(ra.x, ra.y, ra.z), mk<R>(ra.w, rb.x, rb.y));
+    else if constexpr (LEAN_REC)                                      // (a miss: the index of LeanLds's miss record)
         h = closest_hit_sig<SG, R, SG::n>(recs, mk<R>(ra.x, ra.y, ra.z), mk<R>(ra.w, rb.x, rb.y));
     else
         h = path_closest_hit<SG>(sc, recs, ra, rb);
@@ -1277,7 +1301,7 @@ __device__ inline void path_bounce(const PathArgs& a, const PathSceneLds<R>& lds
     uint32_t ids = 0, cid, eid, crow = 0;                             // colour | emission << 16 parameter ids
     float4 lean_a = make_float4(0.f, 0.f, 0.f, 0.f);
     if constexpr (LEAN_REC) {
-        const LeanRec& lr = ll->rec[prim];
+        const LeanRec& lr = REC_OFFSET ? *reinterpret_cast<const LeanRec*>(reinterpret_cast<const char*>(ll->rec) + prim) : ll->rec[prim];
         lean_a = lr.a;
         const uint2 b = lr.b;
         crow = cid = b.x;                                             // (with colour columns: the colour row's offset, not the id)
@@ -1310,9 +1334,21 @@ __device__ inline void path_bounce(const PathArgs& a, const PathSceneLds<R>& lds
     const V3<R> ctr = LEAN_REC ? mk<R>((R)lean_a.x, (R)lean_a.y, (R)lean_a.z) : mk<R>(sh.p[0], sh.p[1], sh.p[2]);
     // (f32: (P - c) / r with 1 / r from a table would save the rsq and the select -- and moves sphere normals by a few ulp,
     //  which flips one grazing path of the 64 x 48 x 8 smoke frame: measured, not kept; the literal form stays)
-    const V3<R> nsph = normalize(P - ctr);                            // shape.hpp:105-106
+    V3<R> nsph = ctr;
+    if constexpr (!MASK_NORMAL)
+        nsph = normalize(P - ctr);                                    // shape.hpp:105-106
     const bool is_plane = (LEAN_REC ? __float_as_int(lean_a.w) : sh.type) == DRT_SHAPE_PLANE;   // shape.hpp:58-59: the normal as stored
     V3<R> nrm = mk<R>(is_plane ? ctr.x : nsph.x, is_plane ? ctr.y : nsph.y, is_plane ? ctr.z : nsph.z);
+    if constexpr (MASK_NORMAL) {
+        // the sphere's normal in the sphere's lanes alone (nrm = ctr so far): the same normalize on the same operands, no select for the
+        // planes' lanes, and a wave that hit no sphere branches over it (the empty asm keeps the compiler from making selects of the
+        // branch again)
+        if (!is_plane) {
+            V3<R> n = normalize(P - ctr);                             // shape.hpp:105-106
+            asm volatile("" : "+v"(n.x), "+v"(n.y), "+v"(n.z));
+            nrm = n;
+        }
+    }
 #ifdef DRT_USER_SHAPES
     if (sh.type >= DRT_SHAPE_USER) {                                  // a caller-defined kind: its own normal(point) (shape.hpp:22)
         const R p8[8] = {sh.p[0], sh.p[1], sh.p[2], sh.p[3], lds.user_q[prim][0], lds.user_q[prim][1], lds.user_q[prim][2], lds.user_q[prim][3]};
@@ -1387,6 +1423,29 @@ __device__ inline void path_bounce(const PathArgs& a, const PathSceneLds<R>& lds
             tg.zc[k] += pid_unpack(rec[3]);
         }
         tg.h.template push<true>(live, alive ? cid : 0xFFu);
+    } else if constexpr (MASK_REST && REST) {
+        // the colour's row of LeanLds by its offset, in the lanes that go on alone: a lane that stops would read the rest row -- a factor
+        // of exactly 1, increments of 0 -- and keeps its bits without the read
+        // (live_mask: the wave's mask of `alive` stands in the scalar pair already)
+        // (end_ids: the caller's "which light the path ended on", moved on here, ahead of the block -- its select is the last use of the
+        //  mask of `live`, which would otherwise stay in a scalar pair of its own across the block)
+        if (end_ids) {
+            uint32_t e = on_light ? light : *end_ids;
+            asm volatile("" : "+v"(e));
+            *end_ids = e;
+        }
+        if (live_mask ? __builtin_amdgcn_inverse_ballot_w64(*live_mask) : alive) {
+            const LeanCol& lc = *reinterpret_cast<const LeanCol*>(reinterpret_cast<const char*>(ll->col) + crow);
+            const float4 c4 = lc.a;
+            T = T * (mk<R>((R)c4.x, (R)c4.y, (R)c4.z) * mk_);
+            tg.cnt[0] += __float_as_uint(c4.w);
+            if constexpr (NC > 4) {
+                const uint2 b = lc.b;
+                tg.cnt[NC > 4 ? 1 : 0] += b.y;
+                tg.zc += b.x;
+            } else
+                tg.zc += lc.b.x;
+        }
     } else if constexpr (LEAN_REC && REST) {
         // the colour's row of LeanLds by its offset (row 0: the rest row, for a lane that does not go on): one address, two reads
         const LeanCol& lc = *reinterpret_cast<const LeanCol*>(reinterpret_cast<const char*>(ll->col) + (alive ? crow : 0u));
@@ -1433,6 +1492,14 @@ __device__ inline void path_bounce(const PathArgs& a, const PathSceneLds<R>& lds
         } else
             col = NC > 0 ? mk<R>(tl.colnz[cidx][0], tl.colnz[cidx][1], tl.colnz[cidx][2]) : load_param<R, (NP > 0)>(lds, params, cidx);
         const V3<R> cmv = col * (BY_ROW ? (alive ? mk_ : R(1)) : mk_);
+        if constexpr (MASK_REST && NP == 0 && NC == 0) {
+            // (forward only: T moves on in the lanes that go on alone -- a factor of exactly 1 in the others, as below)
+            if (alive) {
+                V3<R> Tn = T * cmv;
+                asm volatile("" : "+v"(Tn.x), "+v"(Tn.y), "+v"(Tn.z));
+                T = Tn;
+            }
+        } else {
         const V3<R> cm = BY_ROW ? cmv : mk<R>(alive ? cmv.x : R(1), alive ? cmv.y : R(1), alive ? cmv.z : R(1));
         if constexpr (REST) {
             tg.cnt[0] += tl.inc[cidx][0];
@@ -1447,6 +1514,7 @@ __device__ inline void path_bounce(const PathArgs& a, const PathSceneLds<R>& lds
             tg.zc += alive ? tl.inc[cidx][2] : 0u;
         }
         T = T * cm;
+        }
     }
     const V3<R> no = P + wo * R(1e-3);                                // pathtracer.hpp:99
     ra.x = no.x; ra.y = no.y; ra.z = no.z; ra.w = wo.x;
@@ -2402,6 +2470,9 @@ k_path_lean(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict_
                 // register, v_cndmask + v_cmp at the top of every vertex.  The gradient form only: the forward-only kernel, two instructions
                 // shorter per vertex with it all the same, ran 1.7 % SLOWER than without (profiles/r18_bounce_fusions.txt)
                 constexpr bool LIVE_MASK = DRT_LEAN_LIVE_MASK != 0 && LEAN_REC && NP > 0;
+                // MASK_REST (path_bounce): the bounce itself moves end_ids on where it carries the mask, and the segment count is added where it
+                // stands -- left to sink behind the bounce, it too keeps the mask of `live` in a scalar pair across the masked block
+                constexpr bool MASK_REST = LEAN_REC && lean_part(DRT_LEAN_MASK_REST, NP), END_IN_BOUNCE = MASK_REST && LIVE_MASK;
                 uint64_t lm = LIVE_MASK ? wave_ballot(live) : 0ull;
                 const auto vertex = [&](int kk, auto is_last) {
                     const uint32_t n_theta = 2u * (uint32_t)kk + 2u;   // draw_offset + camera_draw_base below min_bounces
@@ -2412,8 +2483,9 @@ k_path_lean(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict_
                         live = __builtin_amdgcn_inverse_ballot_w64(lm);
                     path_bounce<R, false, NP, NC, SG, BY_ROW, true, true, LIGHTS>(
                         a, lds, tl, sc, params, recs, key, R(1), R(1), n_theta, false, next_cap, live, g, ra, rb, T, L, tg, alive, capped, on_light, light, nullptr, next_cap,
-                        nullptr, nullptr, ll, LIVE_MASK ? &lm : nullptr, kf);
-                    end_ids = on_light ? light : end_ids;
+                        nullptr, nullptr, ll, LIVE_MASK ? &lm : nullptr, kf, END_IN_BOUNCE && !next_cap ? &end_ids : nullptr);
+                    if (!(END_IN_BOUNCE && !next_cap))
+                        end_ids = on_light ? light : end_ids;
                     live = alive;
                 };
                 const auto n_alive = [&]() { return (uint32_t)__popcll(LIVE_MASK ? lm : wave_ballot(live)); };
@@ -2422,6 +2494,8 @@ k_path_lean(PathArgs a, const DevScene<R>* __restrict__ sc, const R* __restrict_
                     if (n_live == 0)
                         break;
                     n_seg += n_live;
+                    if constexpr (MASK_REST)
+                        asm volatile("" : "+s"(n_seg));
                     vertex(kk, BoolT<false>());
                 }
                 const uint32_t n_live = n_alive();

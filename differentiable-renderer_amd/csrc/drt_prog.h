@@ -169,7 +169,8 @@ struct ProgRecs {
 
 // the compiled-in form, f32 or f64: SG::n records in scalar registers, kinds from SG
 // (MISS: the index a ray that hits nothing comes back with -- k_path_lean's bounce hands in the place of its table's miss record)
-template <typename SG, typename R, int MISS = -1>
+// (SCALE: shape s comes back as s * SCALE -- k_path_lean's bounce takes its record's byte offset in the table, and MISS in the same unit)
+template <typename SG, typename R, int MISS = -1, int SCALE = 1>
 __device__ inline HitRec<R> closest_hit_sig(const ProgRecs<SG::n, R>& recs, V3<R> o, V3<R> d)
 {
     const V3<R> inv_d = mk<R>(prog_rcp(d.x), prog_rcp(d.y), prog_rcp(d.z));
@@ -179,20 +180,20 @@ __device__ inline HitRec<R> closest_hit_sig(const ProgRecs<SG::n, R>& recs, V3<R
     for (int s = 0; s < SG::n; ++s) {
         const int kind = SG::kind(s);
         const typename Q4<R>::T r = recs.r[s];
-        if (kind == DRT_PK_AX) prog_test<DRT_PK_AX, R>(r, s, o, d, inv_d, tmin, prim);
-        else if (kind == DRT_PK_AY) prog_test<DRT_PK_AY, R>(r, s, o, d, inv_d, tmin, prim);
-        else if (kind == DRT_PK_AZ) prog_test<DRT_PK_AZ, R>(r, s, o, d, inv_d, tmin, prim);
-        else if (kind == DRT_PK_PLANE) prog_test<DRT_PK_PLANE, R>(r, s, o, d, inv_d, tmin, prim);
+        if (kind == DRT_PK_AX) prog_test<DRT_PK_AX, R>(r, s * SCALE, o, d, inv_d, tmin, prim);
+        else if (kind == DRT_PK_AY) prog_test<DRT_PK_AY, R>(r, s * SCALE, o, d, inv_d, tmin, prim);
+        else if (kind == DRT_PK_AZ) prog_test<DRT_PK_AZ, R>(r, s * SCALE, o, d, inv_d, tmin, prim);
+        else if (kind == DRT_PK_PLANE) prog_test<DRT_PK_PLANE, R>(r, s * SCALE, o, d, inv_d, tmin, prim);
 #ifdef DRT_USER_SHAPES
         else if (kind >= DRT_PK_USER0 && kind < DRT_PK_USER0 + DRT_MAX_USER_KINDS) {
             const typename Q4<R>::T q = recs.q[s];
             const R p8[8] = {r.x, r.y, r.z, r.w, q.x, q.y, q.z, q.w};
             R t;
             if (kind == DRT_PK_USER0 ? user_intersect<0, R>(p8, o, d, t) : user_intersect<1, R>(p8, o, d, t))
-                prog_accept(t, s, tmin, prim);
+                prog_accept(t, s * SCALE, tmin, prim);
         }
 #endif
-        else prog_test<DRT_PK_SPHERE, R>(r, s, o, d, inv_d, tmin, prim);
+        else prog_test<DRT_PK_SPHERE, R>(r, s * SCALE, o, d, inv_d, tmin, prim);
     }
     HitRec<R> h;
     h.t = tmin;
